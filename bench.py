@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - rollout throughput of the MI355X engine on BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--workload tgv3d] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--workload tgv3d] [--batch B] [--dump-outputs DIR]
 
 A "step" is ONE rollout step (neighbor-list rebuild -> features -> GNS-10-128 -> integrator ->
 prediction store) over one batch of B synthetic trajectories per GPU.  Inputs are resident in
@@ -23,6 +23,10 @@ rounds 1 - 5 quoted `value` on are other_configs[tag = "tgv3d_drifting"].  Rank 
   cpu_baseline : the CPU restatement of the reference's algorithm (oracle/: torch-CPU network + NumPy
                  neighbor list, padded E_cap rows, unfused ops; kind "port", NOT JAX-CPU) timed on this
                  host's cores on a bounded sample after all GPU work (rank 0, N=1 only)
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed repeat of the K-step rollout returned as
+DIR/<name>.npy (float64, at most DUMP_BUDGET_BYTES in all, see dump_outputs); the inputs depend on the arguments only
+(seeded synthetic trajectories and weights), so two builds run with the same arguments compare output for output.
 
 Multi-GPU: launched by torch.distributed.run, one rank per GPU; trajectories are independent, so
 there is no data-path collective - RCCL only gathers the per-trajectory MSE vectors and the max
@@ -48,6 +52,7 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s
 MFMA_F32_PEAK_TF = 157.3   # MI355X_MICROARCH.md: fp32-input MFMA, dense
 MFMA_F16_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: bf16/fp16 MFMA, dense (2:1-sparse figure is 2x)
 D = 128
+DUMP_BUDGET_BYTES = 64 << 20
 
 
 def log(*a):
@@ -72,6 +77,23 @@ def pmc_traffic(kernel_substr: str, workload: str, batch: int, stationary: bool 
     except Exception:
         pass
     return None
+
+
+def dump_outputs(path, arrays):
+    """Write the (name, array) pairs to path/<name>.npy as float64, in order, within DUMP_BUDGET_BYTES in all.  An array
+    that does not fit into what is left is replaced by a fixed sample of its flattened elements (seed 0, ascending
+    index order), so that the same arguments always dump the same elements."""
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays:
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        cap = max(left - 4096, 0) // a.itemsize   # 4 KiB per file for the .npy header
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            log(f"[bench] --dump-outputs: {name} {a.shape} sampled to {cap} elements")
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes + 4096
 
 
 def hip_case(ds):
@@ -129,6 +151,10 @@ def main():
                     help="velocity scale of the synthetic trajectories: 0.03 (default, round 6) keeps the neighbour count of "
                          "the untrained rollout stationary (TGV3D ~14.4 per particle, SURVEY 8d: 13.1); 1.0 = the drifting "
                          "workload rounds 1-5 quoted `value` on (13.6 -> 18.5 -> 17.1, mean 16.2)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed rollout returned (rank 0) as DIR/<name>.npy: pred_last_step (B, N, dim) = "
+                         "the positions of the last timed step, mse (world*B, K) (GNS only), pred (B, K, N, dim); float64, "
+                         "<= 64 MB in all (a seeded sample of pred beyond that)")
     args = ap.parse_args()
     if args.cpu_baseline_only:   # legs one after the other in this process: they must not compete for the cores
         print(json.dumps({w: cpu_baseline_leg(w, args.mp_steps, args.vel_amp) for w in args.cpu_baseline_only.split(",")}), flush=True)
@@ -200,6 +226,10 @@ def main():
     tgt = traj[:, :, ds.input_seq_length:ds.input_seq_length + K].permute(0, 2, 1, 3).contiguous()
     mse = eng.metrics(pred, tgt, K, want=("mse",))["mse"]
     merged = lbdist.gather_metrics({mine[i]: mse[i] for i in range(B)}, world * B, K, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("pred_last_step", pred[:, -1].cpu().numpy()),
+                                         ("mse", np.stack([merged[i].cpu().numpy() for i in range(world * B)])),
+                                         ("pred", pred.cpu().numpy())])
 
     # second pass with per-kernel-class HIP events (same K steps) for the roofline objects
     eng.timers_enable(True)
@@ -741,6 +771,8 @@ def run_segnn(args, rank, world, device):
     lbdist.barrier(device)
     dt = lbdist.max_over_ranks(time.perf_counter() - t0, device)
     E_last = eng.stats()["n_edges_total"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("pred_last_step", pred[:, -1].cpu().numpy()), ("pred", pred.cpu().numpy())])
     eng.timers_enable(True)
     eng.timers_reset()
     eng.edge_accounting(reset=True)

@@ -8,6 +8,8 @@ stays "parity unpinned".  With the files present:
   * CPU (`-m "not gpu"`): oracle/lb_oracle.py vs the reference - neighbor list, features, GNS
     accelerations (1e-5 rel), integrator, 5-step rollout.
   * GPU (`-m gpu`): the HIP engine vs the reference on the same inputs.
+Without the files the GPU consumers still run, on a fixture in the generator's format whose expected values come from
+the CPU oracle (see "No JAX fixture committed" below): reader, engine and assertions are the same, the pin to JAX is not.
 """
 import glob
 import json
@@ -27,7 +29,10 @@ NO_FIXTURE = ("no JAX-reference fixture committed: run tests/golden/make_jax_gol
 
 
 def _load(path):
-    z = np.load(path, allow_pickle=False)
+    return _unpack(np.load(path, allow_pickle=False))
+
+
+def _unpack(z):
     md = json.loads(str(z["metadata_json"]))
     hk = {}
     for k in z.files:
@@ -96,12 +101,11 @@ def test_oracle_matches_jax_reference_gns(path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", GNS_FILES or [None])
 def test_engine_matches_jax_reference_gns(path):
-    if path is None:
-        pytest.skip(NO_FIXTURE)
+    """path None: no JAX fixture committed - the oracle-made fixture of the generator's 3D GNS case instead."""
     import torch
     from lagrangebench_amd.case_setup import case_builder
     from lagrangebench_amd.models import GNS
-    z, md, hk = _load(path)
+    z, md, hk = _load(path) if path is not None else _unpack(_oracle_gns_fixture())
     L = int(z["num_mp_steps"])
     pos, pt = z["position"], z["particle_type"]
     isl, dim, n = 6, md["dim"], len(pt)
@@ -256,13 +260,13 @@ def test_oracle_matches_jax_reference_extras(tmp_path):
 @pytest.mark.gpu
 def test_engine_matches_jax_reference_extras(tmp_path):
     """GPU side of jax_extras.npz: the engine's edge list (canonical order) and Sinkhorn kernels against the reference,
-    and the reference's checkpoint evaluated by the HIP engine."""
+    and the reference's checkpoint evaluated by the HIP engine.  Without jax_extras.npz: the oracle-made fixture."""
     import torch
     from lagrangebench_amd.case_setup import case_builder
     from lagrangebench_amd.evaluate.metrics import MetricsComputer
     from lagrangebench_amd.models import GNS
     from lagrangebench_amd.utils import gns_params_from_haiku, load_haiku
-    z = _extras()
+    z = np.load(EXTRAS, allow_pickle=False) if os.path.exists(EXTRAS) else _oracle_extras_fixture()
     pos = z["dense//position"]
     n = len(pos)
     pt = np.zeros(n, np.int32)
@@ -287,3 +291,130 @@ def test_engine_matches_jax_reference_extras(tmp_path):
     params = gns_params_from_haiku(params_hk, L, 2)
     acc = GNS(md["dim"], 128, 2, L, 16).apply(params, {}, (feats, pt))[0]["acc"].cpu().numpy()
     assert rel_err(acc, z["ckpt//acc"]) < 1e-5
+
+
+# ------------------------------------------------------------------------------------------ No JAX fixture committed
+# The GPU consumers above read the real reference's outputs, which only make_jax_golden.py on a machine with JAX can
+# write.  Until those files are committed they read fixtures built here in the generator's format: the generator's own
+# inputs (_cloud / _metadata, same cases and seeds), weights under Haiku module names (gns_params_to_haiku, and the files
+# of this package's save_haiku for the checkpoint), expected values from the CPU oracle.  The CPU consumers keep skipping:
+# the oracle against itself would check nothing.
+class _Fixture(dict):
+    """dict with the .files of an NpzFile."""
+    @property
+    def files(self):
+        return list(self)
+
+
+def _golden_generator():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_jax_golden", os.path.join(GOLD, "make_jax_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _oracle_params(box, md, isl, L, decoder_scale):
+    from types import SimpleNamespace
+    from tests._common import make_params
+    ds = SimpleNamespace(box=box, metadata=md, input_seq_length=isl, external_force_fn=None)
+    return make_params(ds, num_mp_steps=L, decoder_scale=decoder_scale)
+
+
+def _oracle_case(box, md, isl):
+    return O.case_builder(box, md, isl, cfg_neighbors={"multiplier": 1.25},
+                          cfg_model={"isotropic_norm": False, "magnitude_features": False}, noise_std=3e-4)
+
+
+def _oracle_gns_fixture():
+    """jax_gns_3d.npz's case (make_jax_golden.py main: dim 3, 8^3 particles, every 8th a wall, 2 MP steps, 5-step
+    rollout) with the oracle's neighbor list, accelerations and rollout."""
+    from lagrangebench_amd.utils import gns_params_to_haiku
+    G = _golden_generator()
+    dim, n_side, L, isl, n_extra, dx = 3, 8, 2, 6, 5, 0.05
+    pos, box = G._cloud(n_side, dim, dx, isl, n_extra, seed=dim)
+    n = len(pos)
+    pt = np.zeros(n, np.int32)
+    pt[: n // 8] = 1
+    md = G._metadata(dim, n, box, dx, 1.45 * dx, isl + n_extra)
+    case = _oracle_case(box, md, isl)
+    p64 = pos.astype(np.float64)
+    feats, nbrs = case.allocate_eval((p64[:, :isl], pt))
+    params = _oracle_params(box, md, isl, L, decoder_scale=0.01)
+
+    def apply(p, state, sample):
+        return O.gns_apply(p, sample[0], sample[1], num_mp_steps=L, skip_padding=True), state
+    roll, _, _ = O.eval_batched_rollout(apply, case, params, {}, (p64[None], pt[None]), nbrs, n_rollout_steps=n_extra,
+                                        t_window=isl)
+    z = _Fixture(position=pos, particle_type=pt, metadata_json=np.array(json.dumps(md)), idx=np.asarray(nbrs.idx),
+                 acc=O.gns_apply(params, feats, pt, num_mp_steps=L)["acc"], rollout=np.asarray(roll)[0],
+                 num_mp_steps=np.array(L))
+    for module, leaves in gns_params_to_haiku(params, L, 2).items():
+        for leaf, v in leaves.items():
+            z[f"param//{module}//{leaf}"] = np.asarray(v)
+    return z
+
+
+def _oracle_extras_fixture():
+    """jax_extras.npz's dense-cell case, Sinkhorn pair and checkpoint (make_jax_golden.py extras) with the oracle's
+    neighbor list, Sinkhorn divergences (OTT and POT formulations) and accelerations; the checkpoint files are written by
+    this package's save_haiku."""
+    import tempfile
+    from lagrangebench_amd.utils import gns_params_to_haiku, save_haiku
+    from oracle import sinkhorn_oracle as SK
+    from oracle import sinkhorn_pot_oracle as SP
+    G = _golden_generator()
+    dim, n_side, isl, n_extra, dx, L = 2, 18, 6, 21, 0.02, 2
+    pos, box = G._cloud(n_side, dim, dx, isl, n_extra, seed=11)
+    n = len(pos)
+    pt = np.zeros(n, np.int32)
+    md = G._metadata(dim, n, box, dx, 3.0 * dx, isl + n_extra)
+    case = _oracle_case(box, md, isl)
+    feats, nbrs = case.allocate_eval((pos[:, :isl].astype(np.float64), pt))
+    z = _Fixture()
+    z["dense//position"] = pos
+    z["dense//metadata_json"] = np.array(json.dumps(md))
+    z["dense//idx"] = np.asarray(nbrs.idx)
+    pred = np.transpose(pos[:, isl:], (1, 0, 2)).astype(np.float64)
+    targ = np.mod(pred + np.random.default_rng(5).normal(0, 0.4 * dx, pred.shape), box)
+    z["sinkhorn//pred"], z["sinkhorn//target"] = pred, targ
+    z["sinkhorn//ott"] = SK.sinkhorn_rollout(case.displacement, pred, targ, 10)
+    z["sinkhorn//pot"] = np.array([SP.sinkhorn_divergence_pot(case.displacement, p, t) for p, t in zip(pred[::10], targ[::10])])
+    params = _oracle_params(box, md, isl, L, decoder_scale=1.0)
+    with tempfile.TemporaryDirectory() as d:
+        save_haiku(d, gns_params_to_haiku(params, L, 2), {}, None, {"step": 7, "loss": 0.5})
+        for fn in sorted(os.listdir(d)):
+            fp = os.path.join(d, fn)
+            if os.path.isfile(fp):
+                with open(fp, "rb") as f:
+                    z[f"ckpt//{fn}"] = np.frombuffer(f.read(), dtype=np.uint8)
+    z["ckpt//acc"] = O.gns_apply(params, feats, pt, num_mp_steps=L)["acc"]
+    z["ckpt//num_mp_steps"] = np.array(L)
+    return z
+
+
+def test_oracle_fixtures_have_the_generators_layout():
+    """The oracle-made fixtures the GPU consumers fall back to carry every key the generator writes that those consumers
+    read, with the generator's shapes, and their weights / checkpoint read back through this package's readers."""
+    import tempfile
+    from lagrangebench_amd.utils import gns_params_from_haiku, load_haiku
+    z = _oracle_gns_fixture()
+    _, md, hk = _unpack(z)
+    n, L = len(z["particle_type"]), int(z["num_mp_steps"])
+    assert z["position"].shape == (n, 11, 3) and z["position"].dtype == np.float32 and md["dim"] == 3
+    assert z["acc"].shape == (n, 3) and z["rollout"].shape == (5, n, 3) and z["idx"].shape[0] == 2
+    assert np.isfinite(z["rollout"]).all() and np.abs(z["acc"]).max() > 0
+    back = gns_params_from_haiku(hk, L, 2)
+    ref = _oracle_params(np.array([b[1] - b[0] for b in md["bounds"]]), md, 6, L, 0.01)
+    assert sorted(back) == sorted(ref) and all(np.array_equal(back[k][q], ref[k][q]) for k in ref for q in ref[k])
+    x = _oracle_extras_fixture()
+    assert {"dense//position", "dense//metadata_json", "dense//idx", "sinkhorn//pred", "sinkhorn//target", "sinkhorn//ott",
+            "sinkhorn//pot", "ckpt//acc", "ckpt//num_mp_steps"} <= set(x.files)
+    assert x["sinkhorn//ott"].shape == x["sinkhorn//pot"].shape == (3,) and (x["sinkhorn//ott"] > 0).all()
+    with tempfile.TemporaryDirectory() as d:
+        for k in x.files:
+            if k.startswith("ckpt//") and k.count("//") == 1 and k.split("//")[1] not in ("acc", "num_mp_steps"):
+                with open(os.path.join(d, k.split("//")[1]), "wb") as f:
+                    f.write(x[k].tobytes())
+        params_hk, _, _, step = load_haiku(d)
+    assert step == 7 and len(gns_params_from_haiku(params_hk, int(x["ckpt//num_mp_steps"]), 2)) > 0
