@@ -5,30 +5,32 @@
 // feature_transform (lagrangebench/case_setup/features.py:110-124).
 //
 // Design (not a translation of jax-md's dense (N, 3^dim*cap) candidate matrix):
-//   1. k_cell_count / two-level scan / k_cell_fill : counting sort of the particles into cells
-//      (int atomics); k_cell_fill also writes the cell-sorted fp64 positions so that a cell's
-//      particles are one contiguous HBM range.
-//   2. stencil search, two kernels with identical results:
-//      k_nlw (3^3-cell stencils): one WAVE per receiver walks the particles of its stencil cells -
-//        short contiguous runs of the cell-sorted arrays, L2 resident - 64 candidates per sweep
-//        straight from global memory; no staging, 1.3 KiB of LDS per wave, full occupancy;
-//      k_nl (3^2-cell stencils and the all-pairs case): one workgroup per cell stages the stencil's
-//        particles (ids + fp64 positions) in LDS once (in 128-candidate capacity steps: the LDS
-//        footprint sets the occupancy) and each wave sweeps the tile for the receivers of the cell.
-//      In both the cutoff predicate is evaluated in fp64 exactly as the reference does
-//      (metric(pos[sender], pos[receiver]) < r_c^2), reduced with a wavefront ballot + popcount
-//      prefix; the row is compacted into LDS and rank-sorted by sender id with lane broadcasts.
-//        update path (capacities frozen): ONE sweep writes each receiver's sorted row + its edge
-//          features into fixed-stride per-node slots, then a two-level scan of the degrees gives the
-//          CSR offsets and k_nl_compact moves the rows into place (pure streaming copy);
+//   1. cell binning: a counting sort of the particles into cells (k_cell_count / two-level scan / k_cell_fill, or one launch:
+//      k_cells_small, k_cells_traj), or fixed-stride cell slots on the update path (k_cell_zero + k_cell_bin); the
+//      cell-sorted fp64 positions make a cell's particles one contiguous HBM range.
+//   2. stencil search, five kernels with identical results:
+//      k_nl  (workgroup per cell): stages the stencil's particles (ids + fp64 positions) in LDS once, in 128-candidate
+//            capacity steps (the LDS footprint sets the occupancy); each wave sweeps the tile for the receivers of the cell;
+//      k_nlw (wave per receiver): walks the particles of the stencil cells straight from global memory; its row buffer is
+//            dynamic LDS, sized from the largest degree seen - the dense fall-back;
+//      k_nlc (wave per cell): keeps the stencil candidates in registers and emits the edges of all the cell's receivers
+//            64 at a time;
+//      k_nl_small / k_nl_mid: one trajectory, the whole build (binning, search, CSR offsets, control block) in ONE launch.
+//      The input alone picks the kernel: one trajectory of <= NLM_N particles on the update path runs k_nl_small / k_nl_mid
+//      (lbk_nl_build); otherwise a cell list outside the dense fall-back in 3D or float32 geometry runs k_nlc, the dense
+//      fall-back or float32 geometry without a cell list runs k_nlw, and everything else (fp64 2D with a cell list, fp64
+//      all-pairs) runs k_nl (lb_nl_kernel_kind).
+//      Every kernel evaluates the cutoff predicate as the reference does (lb_pair_in_cutoff; k_nl_mid writes its arithmetic
+//      out) and writes the edge features with lb_write_edge; a row's hits come from a wavefront ballot + popcount prefix
+//      and are ordered by sender id.
+//        update path (capacities frozen): ONE sweep writes each receiver's sorted row + its edge features into fixed-stride
+//          per-node slots, then a scan of the degrees gives the CSR offsets and k_nl_compact moves the rows into place;
 //        allocate path (sizes unknown): count sweep -> scan -> host sizes the buffers -> fill sweep.
 //   3. k_row_finish : per-trajectory edge counts, did_buffer_overflow flags and the control block,
 //      all on the device (no host sync).
 // Output: CSR by receiver over the B*N nodes of the batch, senders ascending inside a row, i.e.
 // the edge list sorted by (receiver, sender) - deterministic, and directly consumable by the
 // atomic-free segmented aggregation.
-#include <cstdlib>
-
 #include "lb_features.h"
 
 #define SCAN_THREADS 256
@@ -465,6 +467,14 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 }
 
 // -------------------------------------------------------------------------- stencil search
+// output arrays of a search: CSR (receivers set: [E] ids, efeat [E][8]) or, NL_ROWS, per-node slots (receivers null:
+// senders [BN][maxd], efeat [BN][maxd][4]); efeat64: optional fp64 copy, same indexing with 4 doubles per edge
+struct lb_edge_out {
+  int32_t* senders;
+  int32_t* receivers;
+  float* efeat;
+  double* efeat64;
+};
 struct lb_nl_args {
   const int32_t* cell_of;   // [BN] global cell id of each particle
   const int32_t* cell_start;
@@ -478,24 +488,170 @@ struct lb_nl_args {
   int64_t cstride;
   int32_t* deg;             // [BN]
   const int32_t* row_ptr;   // NL_FILL
-  int32_t* senders;         // NL_FILL: CSR arrays; NL_ROWS: per-node slots [BN][maxd]
-  int32_t* receivers;       // NL_FILL
-  float* efeat;             // NL_FILL: [E][8]; NL_ROWS: [BN][maxd][4]
-  double* efeat64;          // optional fp64 copy, same indexing with 4 doubles per edge
+  lb_edge_out out;
   int64_t e_alloc;
   int32_t maxd;
   int32_t row_cap;          // k_nlw: LDS row-buffer entries per wave (>= LB_MAX_ROW)
   lb_feat_job feat;         // NL_ROWS in a rollout step: every search wave also writes the node-feature row of its
   const double* win;        //   receiver (lb_features.h; xnode == null: no job)
-  int32_t nb_search;        // k_nl: workgroups of the search proper; the ones behind them write feature rows (0: none)
+  int32_t nb_search;        // workgroups of the search proper; the ones behind them write feature rows (0: none)
 };
-#define NL_FEAT_ROWS 8      // feature rows per wave of a k_nl feature workgroup
+#define NL_FEAT_ROWS 8      // feature rows per wave of a feature workgroup
 __device__ __forceinline__ int lb_cell_begin(const lb_nl_args& a, int gc) { return a.cell_cap ? gc * a.cell_cap : a.cell_start[gc]; }
 __device__ __forceinline__ int lb_cell_size(const lb_nl_args& a, int gc, int begin) {
   return a.cell_cap ? min(a.cell_cnt[gc], a.cell_cap) : a.cell_start[gc + 1] - begin;
 }
 
-template <int MODE, int NL_THREADS, int MAXC, bool F32 = false>
+// The device helpers below take the dimension as an argument: the kernels with a DIM template parameter pass it (the loops
+// unroll), k_nl and k_nlw pass g.dim.  The per-dimension loops of lb_pair_in_cutoff and lb_write_edge stay rolled under a
+// run-time dim - the three-way unrolled, guarded form kept every component's fp64 division in flight at once and cost k_nlw
+// two waves per SIMD; their 3-entry register arrays stay in registers (no scratch in the kernel resource report).
+
+// fp64 position of slot i of a [dim][stride] array (components past dim: 0)
+__device__ __forceinline__ void lb_load_pos(double* p, const double* src, int64_t stride, int64_t i, int dim) {
+#pragma unroll
+  for (int d = 0; d < 3; ++d) p[d] = d < dim ? src[d * stride + i] : 0.0;
+}
+
+// metric_sq(position[sender], position[receiver]) < r_c^2 as the reference evaluates it: sum of squares in x, y, z order,
+// every operation rounded to the geometry dtype (lb_r), no FMA contraction, strict <.  ps(d): component d of the sender's
+// position (read where it is used: a component's load stays next to its arithmetic).  k_nl_mid writes the same arithmetic
+// out (see there): a change here must be made there too, bit for bit.
+template <bool F32, typename PS>
+__device__ __forceinline__ bool lb_pair_in_cutoff(const lb_geom& g, PS ps, const double* pr, int dim) {
+  double dd = lb_disp1(ps(0), pr[0], g.box[0], g.half_box[0], g.periodic, F32);
+  double d2 = lb_r(dd * dd, F32);
+  for (int d = 1; d < dim; ++d) {
+    dd = lb_disp1(ps(d), pr[d], g.box[d], g.half_box[d], g.periodic, F32);
+    d2 = lb_r(d2 + lb_r(dd * dd, F32), F32);
+  }
+  return d2 < g.rc2;
+}
+
+// Edge `slot`: sender id + features.py:115-124, disp(pos[receiver], pos[sender]) / r_c and its norm.  ROWS: the 4-wide row
+// of the per-node slots; otherwise the CSR arrays (receiver id, 8-wide feature row).  Plus the optional fp64 copy.  ps(d):
+// as in lb_pair_in_cutoff.
+template <bool F32, bool ROWS, typename PS>
+__device__ __forceinline__ void lb_write_edge(const lb_geom& g, const lb_edge_out& o, int64_t slot, int sender, int receiver,
+                                              const double* pr, PS ps, int dim) {
+  o.senders[slot] = sender;
+  double rd[3] = {0, 0, 0};
+  double s2 = 0.0;
+  for (int d = 0; d < dim; ++d) {
+    rd[d] = lb_r(lb_disp1(pr[d], ps(d), g.box[d], g.half_box[d], g.periodic, F32) / g.rc, F32);
+    s2 = (d == 0) ? lb_r(rd[d] * rd[d], F32) : lb_r(s2 + lb_r(rd[d] * rd[d], F32), F32);
+  }
+  const double dist = s2 > 0.0 ? lb_r(sqrt(s2), F32) : 0.0;
+  const f32x4 lo = (dim == 2) ? f32x4{(float)rd[0], (float)rd[1], (float)dist, 0.f}
+                              : f32x4{(float)rd[0], (float)rd[1], (float)rd[2], (float)dist};
+  if (ROWS) {
+    reinterpret_cast<f32x4*>(o.efeat)[slot] = lo;
+  } else {
+    o.receivers[slot] = receiver;
+    f32x4* ef = reinterpret_cast<f32x4*>(o.efeat + slot * 8);
+    ef[0] = lo;
+    ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  if (o.efeat64) {
+    double* e64 = o.efeat64 + slot * 4;
+    e64[0] = rd[0];
+    e64[1] = rd[1];
+    e64[2] = rd[2];
+    e64[3] = dist;
+  }
+}
+
+// Stencil table of cell gc, built by one wave: lane k < nstencil takes the k-th of the 3^dim neighbour cells, writes its first
+// slot to s_cstart[k] and the exclusive prefix of the cell sizes to s_coff[k]; s_coff[nstencil] = all candidates.
+__device__ __forceinline__ void lb_stencil_table(const lb_geom& g, const lb_nl_args& a, int gc, int lane, int dim,
+                                                 int* s_cstart, int* s_coff) {
+  const int b = gc / g.ncells, h = gc % g.ncells;
+  int cnt = 0;
+  if (lane < g.nstencil) {
+    int nh = h;
+    if (g.use_cell_list) {
+      const int c[3] = {h % g.ncell[0], (h / g.ncell[0]) % g.ncell[1], h / (g.ncell[0] * g.ncell[1])};
+      const int o[3] = {lane % 3 - 1, (lane / 3) % 3 - 1, lane / 9 - 1};
+      nh = 0;
+      int mult = 1;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        if (d < dim) {
+          int cc = c[d] + o[d];  // jax-md rolls the cell buffer: the stencil always wraps
+          cc = cc < 0 ? cc + g.ncell[d] : (cc >= g.ncell[d] ? cc - g.ncell[d] : cc);
+          nh += cc * mult;
+          mult *= g.ncell[d];
+        }
+      }
+    }
+    const int ngc = b * g.ncells + nh;
+    const int st = lb_cell_begin(a, ngc);
+    s_cstart[lane] = st;
+    cnt = lb_cell_size(a, ngc, st);
+  }
+  int incl = cnt;
+#pragma unroll
+  for (int off = 1; off < 32; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if (lane >= off) incl += v;
+  }
+  if (lane < g.nstencil) s_coff[lane] = incl - cnt;
+  if (lane == g.nstencil - 1) s_coff[g.nstencil] = incl;
+}
+
+// candidate j of a stencil table -> its slot in the cell-sorted arrays (k = the largest k with s_coff[k] <= j)
+__device__ __forceinline__ int lb_stencil_slot(const int* s_cstart, const int* s_coff, int nstencil, int j) {
+  int lo = 0, hi = nstencil;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (s_coff[mid] <= j) lo = mid; else hi = mid;
+  }
+  return s_cstart[lo] + (j - s_coff[lo]);
+}
+
+// Rollout step (NL_ROWS): the workgroups behind the search's (blockIdx.x >= nb_search) write the node-feature rows,
+// NL_FEAT_ROWS consecutive particles per wave, all their loads in flight together.  They run beside the search, which is a
+// latency chain (inside the receiver's own wave the row cost the batch search +19 us).  True for those workgroups.
+__device__ __forceinline__ bool lb_feature_rows(const lb_geom& g, int64_t BN, const lb_ctrl* ctrl, const lb_nl_args& a,
+                                                int waves) {
+  if (a.nb_search <= 0 || (int)blockIdx.x < a.nb_search) return false;
+  const int64_t first = ((int64_t)(blockIdx.x - a.nb_search) * waves + (threadIdx.x >> 6)) * NL_FEAT_ROWS;
+  const int cnt = (int)min((int64_t)NL_FEAT_ROWS, BN - first);
+  if (cnt > 0)
+    lb_node_features_wave_multi(g, BN, a.win, ctrl->step, a.feat, [&](int p) -> int64_t { return first + p; }, cnt);
+  return true;
+}
+
+// A row of `count` hits capped at the row buffer (row_cap entries) and, NL_ROWS, at the per-node slots.  Too long a row
+// asks the update path for a re-allocation (row_overflow) while the row buffer can still grow (can_grow; the allocation
+// switches to the dense fall-back) and is a density error otherwise.
+template <int MODE>
+__device__ __forceinline__ int lb_cap_row(lb_ctrl* ctrl, const lb_nl_args& a, int count, int lane, int row_cap, bool can_grow) {
+  if (count > row_cap) {
+    if (lane == 0) {
+      if (MODE == NL_ROWS && can_grow)
+        atomicExch(&ctrl->row_overflow, 1);
+      else
+        atomicExch(&ctrl->density_error, 2);
+    }
+    count = row_cap;
+  }
+  if (MODE == NL_ROWS && count > a.maxd) {
+    if (lane == 0) atomicExch(&ctrl->row_overflow, 1);  // per-node slots too small: re-allocate
+    count = a.maxd;
+  }
+  return count;
+}
+
+// rank of this lane's sender id in a row of count <= 64 ids held one per lane (ids are unique): lane broadcasts
+// (v_readlane), no LDS round trips
+__device__ __forceinline__ int lb_rank_in_row(int my, int count) {
+  int rank = 0;
+  for (int u = 0; u < count; ++u) rank += (__builtin_amdgcn_readlane(my, u) < my) ? 1 : 0;
+  return rank;
+}
+
+template <int MODE, int NL_THREADS, int MAXC>
 __global__ void __launch_bounds__(NL_THREADS)
     k_nl(lb_geom g, int64_t BN, lb_ctrl* __restrict__ ctrl, lb_nl_args a) {
   constexpr int NL_WAVES = NL_THREADS / 64;
@@ -505,53 +661,14 @@ __global__ void __launch_bounds__(NL_THREADS)
   __shared__ int s_cstart[28], s_coff[29];
 
   if (ctrl->overflow_step >= 0) return;
-  if (MODE == NL_ROWS && a.nb_search > 0 && (int)blockIdx.x >= a.nb_search) {
-    // rollout step: the workgroups behind the search's write the node-feature rows (NL_FEAT_ROWS consecutive particles
-    // per wave, all their loads in flight together; they run beside the per-cell search, which is a latency chain)
-    const int64_t first = ((int64_t)(blockIdx.x - a.nb_search) * NL_WAVES + (threadIdx.x >> 6)) * NL_FEAT_ROWS;
-    const int cnt = (int)min((int64_t)NL_FEAT_ROWS, BN - first);
-    if (cnt > 0)
-      lb_node_features_wave_multi(g, BN, a.win, ctrl->step, a.feat, [&](int p) -> int64_t { return first + p; }, cnt);
-    return;
-  }
+  if (MODE == NL_ROWS && lb_feature_rows(g, BN, ctrl, a, NL_WAVES)) return;
   const int tid = threadIdx.x;
   const int gc = blockIdx.x;
-  const int b = gc / g.ncells, h = gc % g.ncells;
   const int own_start = lb_cell_begin(a, gc);
   const int own_cnt = lb_cell_size(a, gc, own_start);
   if (own_cnt == 0) return;
 
-  // stencil cells: start + count, exclusive prefix of the counts with a wave scan
-  if (tid < 64) {
-    int cnt = 0;
-    if (tid < g.nstencil) {
-      int nh = h;
-      if (g.use_cell_list) {
-        int c[3] = {h % g.ncell[0], (h / g.ncell[0]) % g.ncell[1], h / (g.ncell[0] * g.ncell[1])};
-        int o[3] = {tid % 3 - 1, (tid / 3) % 3 - 1, tid / 9 - 1};
-        nh = 0;
-        int mult = 1;
-        for (int d = 0; d < g.dim; ++d) {
-          int cc = c[d] + o[d];  // jax-md rolls the cell buffer: the stencil always wraps
-          cc = cc < 0 ? cc + g.ncell[d] : (cc >= g.ncell[d] ? cc - g.ncell[d] : cc);
-          nh += cc * mult;
-          mult *= g.ncell[d];
-        }
-      }
-      const int ngc = b * g.ncells + nh;
-      const int st = lb_cell_begin(a, ngc);
-      s_cstart[tid] = st;
-      cnt = lb_cell_size(a, ngc, st);
-    }
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-      const int v = __shfl_up(incl, off);
-      if (tid >= off) incl += v;
-    }
-    if (tid < g.nstencil) s_coff[tid] = incl - cnt;
-    if (tid == g.nstencil - 1) s_coff[g.nstencil] = incl;
-  }
+  if (tid < 64) lb_stencil_table(g, a, gc, tid, g.dim, s_cstart, s_coff);
   __syncthreads();
   int M = s_coff[g.nstencil];
   if (M > MAXC) {
@@ -567,12 +684,7 @@ __global__ void __launch_bounds__(NL_THREADS)
   }
   // stage the stencil's particles (ids + fp64 positions, contiguous per cell in the sorted arrays)
   for (int j = tid; j < M; j += NL_THREADS) {
-    int lo = 0, hi = g.nstencil;  // largest k with s_coff[k] <= j
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_coff[mid] <= j) lo = mid; else hi = mid;
-    }
-    const int src = s_cstart[lo] + (j - s_coff[lo]);
+    const int src = lb_stencil_slot(s_cstart, s_coff, g.nstencil, j);
     s_id[j] = a.cell_part[src];
     for (int d = 0; d < g.dim; ++d) s_p[d][j] = a.cpos[(int64_t)d * a.cstride + src];
   }
@@ -586,23 +698,13 @@ __global__ void __launch_bounds__(NL_THREADS)
   for (int k = wave; k < own_cnt; k += NL_WAVES) {
     if (own_off + k >= M) break;  // truncated stencil (density error already flagged)
     const int gr = s_id[own_off + k];
-    double pr[3] = {0, 0, 0};
-    for (int d = 0; d < g.dim; ++d) pr[d] = s_p[d][own_off + k];
+    double pr[3];
+    lb_load_pos(pr, &s_p[0][0], MAXC, own_off + k, g.dim);
     int count = 0;
     for (int c0 = 0; c0 < M; c0 += 64) {
       const int j = c0 + lane;
       bool ok = false;
-      if (j < M) {
-        // metric_sq(position[sender], position[receiver]): sender = staged candidate,
-        // receiver = row owner; sum of squares in x,y,z order, no FMA contraction.
-        double dd = lb_disp1(s_p[0][j], pr[0], g.box[0], g.half_box[0], g.periodic, F32);
-        double d2 = lb_r(dd * dd, F32);
-        for (int d = 1; d < g.dim; ++d) {
-          dd = lb_disp1(s_p[d][j], pr[d], g.box[d], g.half_box[d], g.periodic, F32);
-          d2 = lb_r(d2 + lb_r(dd * dd, F32), F32);
-        }
-        ok = d2 < g.rc2;  // strict <
-      }
+      if (j < M) ok = lb_pair_in_cutoff<false>(g, [&](int d) { return s_p[d][j]; }, pr, g.dim);  // sender: staged candidate
       const unsigned long long mask = __ballot(ok);
       if (MODE != NL_COUNT && ok) {
         const int pos = count + __popcll(mask & lt_mask);
@@ -616,19 +718,7 @@ __global__ void __launch_bounds__(NL_THREADS)
       // serialises at its L2 channel - it was 150 of the 165 us of this kernel on 64 k receivers)
     }
     if (MODE == NL_COUNT) continue;
-    if (count > LB_MAX_ROW) {  // (update path: re-allocate - the allocation sizes the dense fall-back's row buffer)
-      if (lane == 0) {
-        if (MODE == NL_ROWS)
-          atomicExch(&ctrl->row_overflow, 1);
-        else
-          atomicExch(&ctrl->density_error, 2);
-      }
-      count = LB_MAX_ROW;
-    }
-    if (MODE == NL_ROWS && count > a.maxd) {
-      if (lane == 0) atomicExch(&ctrl->row_overflow, 1);  // per-node slots too small: re-allocate
-      count = a.maxd;
-    }
+    count = lb_cap_row<MODE>(ctrl, a, count, lane, LB_MAX_ROW, true);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     const int64_t base = (MODE == NL_ROWS) ? (int64_t)gr * a.maxd : (int64_t)a.row_ptr[gr];
     for (int t0 = 0; t0 < count; t0 += 64) {
@@ -636,44 +726,17 @@ __global__ void __launch_bounds__(NL_THREADS)
       const bool act = t < count;
       const int j = act ? s_row[wave][t] : 0;
       const int my = act ? s_id[j] : 0x7fffffff;
-      // rank of this sender id inside the row: rows of <= 64 neighbors (the normal case) compare
-      // against lane broadcasts (v_readlane, no LDS round trips), longer rows walk the LDS row
+      // rank of this sender id inside the row: longer rows than 64 walk the LDS row
       int rank = 0;
       if (count <= 64) {
-        for (int u = 0; u < count; ++u) rank += (__builtin_amdgcn_readlane(my, u) < my) ? 1 : 0;
+        rank = lb_rank_in_row(my, count);
       } else {
         for (int u = 0; u < count; ++u) rank += (s_id[s_row[wave][u]] < my) ? 1 : 0;
       }
       if (!act) continue;
       const int64_t slot = base + rank;
-      if (MODE == NL_ROWS || slot < a.e_alloc) {
-        a.senders[slot] = my;
-        // features.py:115-124: disp(pos[receiver], pos[sender]) / r_c and its norm
-        double rd[3] = {0, 0, 0};
-        double s2 = 0.0;
-        for (int d = 0; d < g.dim; ++d) {
-          rd[d] = lb_r(lb_disp1(pr[d], s_p[d][j], g.box[d], g.half_box[d], g.periodic, F32) / g.rc, F32);
-          s2 = (d == 0) ? lb_r(rd[d] * rd[d], F32) : lb_r(s2 + lb_r(rd[d] * rd[d], F32), F32);
-        }
-        const double dist = s2 > 0.0 ? lb_r(sqrt(s2), F32) : 0.0;
-        const f32x4 lo = (g.dim == 2) ? f32x4{(float)rd[0], (float)rd[1], (float)dist, 0.f}
-                                      : f32x4{(float)rd[0], (float)rd[1], (float)rd[2], (float)dist};
-        if (MODE == NL_ROWS) {
-          reinterpret_cast<f32x4*>(a.efeat)[slot] = lo;
-        } else {
-          a.receivers[slot] = gr;
-          f32x4* ef = reinterpret_cast<f32x4*>(a.efeat + slot * 8);
-          ef[0] = lo;
-          ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        if (a.efeat64) {
-          double* e64 = a.efeat64 + slot * 4;
-          e64[0] = rd[0];
-          e64[1] = rd[1];
-          e64[2] = rd[2];
-          e64[3] = dist;
-        }
-      }
+      if (MODE == NL_ROWS || slot < a.e_alloc)
+        lb_write_edge<false, MODE == NL_ROWS>(g, a.out, slot, my, gr, pr, [&](int d) { return s_p[d][j]; }, g.dim);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   }
@@ -687,7 +750,7 @@ __global__ void __launch_bounds__(NL_THREADS)
 // per receiver), and with one workgroup per CELL the staged stencil (28 B x cell_capacity x 3^dim of
 // LDS) capped the occupancy at a handful of waves per CU.  Same predicate, same operand order.
 #define NLW_WAVES 4
-template <int MODE, bool F32 = false>
+template <int MODE, bool F32>
 __global__ void __launch_bounds__(64 * NLW_WAVES)
     k_nlw(lb_geom g, int64_t BN, lb_ctrl* __restrict__ ctrl, lb_nl_args a) {
   // row buffers in DYNAMIC LDS: per wave row_cap candidate slots + row_cap sender ids (a.row_cap >= LB_MAX_ROW: the
@@ -696,81 +759,27 @@ __global__ void __launch_bounds__(64 * NLW_WAVES)
   const int row_cap = a.row_cap;
   __shared__ int s_cstart[NLW_WAVES][28], s_coff[NLW_WAVES][29];
   if (ctrl->overflow_step >= 0) return;
-  if (MODE == NL_ROWS && a.nb_search > 0 && (int)blockIdx.x >= a.nb_search) {
-    // rollout step: the workgroups behind the search's write the node-feature rows (as in k_nl; inside the receiver's
-    // own wave the row cost the batch search +19 us - one more round trip in a chain of five)
-    const int64_t first = ((int64_t)(blockIdx.x - a.nb_search) * NLW_WAVES + (threadIdx.x >> 6)) * NL_FEAT_ROWS;
-    const int cnt = (int)min((int64_t)NL_FEAT_ROWS, BN - first);
-    if (cnt > 0)
-      lb_node_features_wave_multi(g, BN, a.win, ctrl->step, a.feat, [&](int p) -> int64_t { return first + p; }, cnt);
-    return;
-  }
+  if (MODE == NL_ROWS && lb_feature_rows(g, BN, ctrl, a, NLW_WAVES)) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int* const s_row = s_dyn + (size_t)wave * 2 * row_cap;
   int* const s_id = s_row + row_cap;
   const int64_t r = (int64_t)blockIdx.x * NLW_WAVES + wave;  // receiver slot in cell-sorted order
   if (r >= BN) return;
   const int gr = a.cell_part[r];
-  const int gc = a.cell_of[gr];
-  const int b = gc / g.ncells, h = gc % g.ncells;
-  {
-    int cnt = 0;
-    if (lane < g.nstencil) {
-      int nh = h;
-      if (g.use_cell_list) {
-        int c[3] = {h % g.ncell[0], (h / g.ncell[0]) % g.ncell[1], h / (g.ncell[0] * g.ncell[1])};
-        int o[3] = {lane % 3 - 1, (lane / 3) % 3 - 1, lane / 9 - 1};
-        nh = 0;
-        int mult = 1;
-        for (int d = 0; d < g.dim; ++d) {
-          int cc = c[d] + o[d];  // jax-md rolls the cell buffer: the stencil always wraps
-          cc = cc < 0 ? cc + g.ncell[d] : (cc >= g.ncell[d] ? cc - g.ncell[d] : cc);
-          nh += cc * mult;
-          mult *= g.ncell[d];
-        }
-      }
-      const int ngc = b * g.ncells + nh;
-      const int st = lb_cell_begin(a, ngc);
-      s_cstart[wave][lane] = st;
-      cnt = lb_cell_size(a, ngc, st);
-    }
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-      const int v = __shfl_up(incl, off);
-      if (lane >= off) incl += v;
-    }
-    if (lane < g.nstencil) s_coff[wave][lane] = incl - cnt;
-    if (lane == g.nstencil - 1) s_coff[wave][g.nstencil] = incl;
-  }
+  lb_stencil_table(g, a, a.cell_of[gr], lane, g.dim, s_cstart[wave], s_coff[wave]);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   const int M = s_coff[wave][g.nstencil];
-  double pr[3] = {0, 0, 0};
-  for (int d = 0; d < g.dim; ++d) pr[d] = a.cpos[(int64_t)d * a.cstride + r];
+  double pr[3];
+  lb_load_pos(pr, a.cpos, a.cstride, r, g.dim);
   const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  auto slot_of = [&](int j) -> int {  // candidate j -> slot in the cell-sorted arrays
-    int lo = 0, hi = g.nstencil;      // largest k with s_coff[k] <= j
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (s_coff[wave][mid] <= j) lo = mid; else hi = mid;
-    }
-    return s_cstart[wave][lo] + (j - s_coff[wave][lo]);
-  };
   int count = 0;
   for (int c0 = 0; c0 < M; c0 += 64) {
     const int j = c0 + lane;
     bool ok = false;
     int src = 0;
     if (j < M) {
-      src = slot_of(j);
-      // metric_sq(position[sender], position[receiver]): sum of squares in x,y,z order, no FMA
-      double dd = lb_disp1(a.cpos[src], pr[0], g.box[0], g.half_box[0], g.periodic, F32);
-      double d2 = lb_r(dd * dd, F32);
-      for (int d = 1; d < g.dim; ++d) {
-        dd = lb_disp1(a.cpos[(int64_t)d * a.cstride + src], pr[d], g.box[d], g.half_box[d], g.periodic, F32);
-        d2 = lb_r(d2 + lb_r(dd * dd, F32), F32);
-      }
-      ok = d2 < g.rc2;  // strict <
+      src = lb_stencil_slot(s_cstart[wave], s_coff[wave], g.nstencil, j);
+      ok = lb_pair_in_cutoff<F32>(g, [&](int d) { return a.cpos[(int64_t)d * a.cstride + src]; }, pr, g.dim);
     }
     const unsigned long long mask = __ballot(ok);
     if (MODE != NL_COUNT && ok) {
@@ -784,19 +793,7 @@ __global__ void __launch_bounds__(64 * NLW_WAVES)
     // (ctrl->max_deg is reduced by the degree scan that follows, see k_nl)
   }
   if (MODE == NL_COUNT) return;
-  if (count > row_cap) {
-    if (lane == 0) {
-      if (MODE == NL_ROWS && row_cap < LB_MAX_ROW_DENSE)
-        atomicExch(&ctrl->row_overflow, 1);  // re-allocate with a longer row buffer
-      else
-        atomicExch(&ctrl->density_error, 2);
-    }
-    count = row_cap;
-  }
-  if (MODE == NL_ROWS && count > a.maxd) {
-    if (lane == 0) atomicExch(&ctrl->row_overflow, 1);  // per-node slots too small: re-allocate
-    count = a.maxd;
-  }
+  count = lb_cap_row<MODE>(ctrl, a, count, lane, row_cap, row_cap < LB_MAX_ROW_DENSE);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   const int64_t base = (MODE == NL_ROWS) ? (int64_t)gr * a.maxd : (int64_t)a.row_ptr[gr];
   if (count > 64) {  // long rows: the sender ids go to LDS once, the rank loop reads them as broadcasts
@@ -808,43 +805,17 @@ __global__ void __launch_bounds__(64 * NLW_WAVES)
     const bool act = t < count;
     const int src = act ? s_row[t] : 0;
     const int my = act ? a.cell_part[src] : 0x7fffffff;
-    // rank of this sender id inside the row (ids are unique): lane broadcasts for rows <= 64
     int rank = 0;
     if (count <= 64) {
-      for (int u = 0; u < count; ++u) rank += (__builtin_amdgcn_readlane(my, u) < my) ? 1 : 0;
+      rank = lb_rank_in_row(my, count);
     } else {
       for (int u = 0; u < count; ++u) rank += (s_id[u] < my) ? 1 : 0;
     }
     if (!act) continue;
     const int64_t slot = base + rank;
-    if (MODE == NL_ROWS || slot < a.e_alloc) {
-      a.senders[slot] = my;
-      // features.py:115-124: disp(pos[receiver], pos[sender]) / r_c and its norm
-      double rd[3] = {0, 0, 0};
-      double s2 = 0.0;
-      for (int d = 0; d < g.dim; ++d) {
-        rd[d] = lb_r(lb_disp1(pr[d], a.cpos[(int64_t)d * a.cstride + src], g.box[d], g.half_box[d], g.periodic, F32) / g.rc, F32);
-        s2 = (d == 0) ? lb_r(rd[d] * rd[d], F32) : lb_r(s2 + lb_r(rd[d] * rd[d], F32), F32);
-      }
-      const double dist = s2 > 0.0 ? lb_r(sqrt(s2), F32) : 0.0;
-      const f32x4 lo = (g.dim == 2) ? f32x4{(float)rd[0], (float)rd[1], (float)dist, 0.f}
-                                    : f32x4{(float)rd[0], (float)rd[1], (float)rd[2], (float)dist};
-      if (MODE == NL_ROWS) {
-        reinterpret_cast<f32x4*>(a.efeat)[slot] = lo;
-      } else {
-        a.receivers[slot] = gr;
-        f32x4* ef = reinterpret_cast<f32x4*>(a.efeat + slot * 8);
-        ef[0] = lo;
-        ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      if (a.efeat64) {
-        double* e64 = a.efeat64 + slot * 4;
-        e64[0] = rd[0];
-        e64[1] = rd[1];
-        e64[2] = rd[2];
-        e64[3] = dist;
-      }
-    }
+    if (MODE == NL_ROWS || slot < a.e_alloc)
+      lb_write_edge<F32, MODE == NL_ROWS>(g, a.out, slot, my, gr, pr, [&](int d) { return a.cpos[(int64_t)d * a.cstride + src]; },
+                                          g.dim);
   }
 }
 
@@ -869,14 +840,7 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
   __shared__ int s_src_[NLC_WAVES][NLC_LIST], s_id_[NLC_WAVES][NLC_LIST];
   __shared__ unsigned short s_kr_[NLC_WAVES][NLC_LIST];  // row of the batch << 8 | rank inside the row
   if (ctrl->overflow_step >= 0) return;
-  if (MODE == NL_ROWS && a.nb_search > 0 && (int)blockIdx.x >= a.nb_search) {
-    // rollout step: the workgroups behind the search's write the node-feature rows (as in k_nlw)
-    const int64_t first = ((int64_t)(blockIdx.x - a.nb_search) * NLC_WAVES + (threadIdx.x >> 6)) * NL_FEAT_ROWS;
-    const int cnt = (int)min((int64_t)NL_FEAT_ROWS, BN - first);
-    if (cnt > 0)
-      lb_node_features_wave_multi(g, BN, a.win, ctrl->step, a.feat, [&](int p) -> int64_t { return first + p; }, cnt);
-    return;
-  }
+  if (MODE == NL_ROWS && lb_feature_rows(g, BN, ctrl, a, NLC_WAVES)) return;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int gc = __builtin_amdgcn_readfirstlane((int)blockIdx.x * NLC_WAVES + wave);
   if (gc >= g.B * g.ncells) return;
@@ -888,38 +852,7 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
   int* const s_src = s_src_[wave];
   int* const s_id = s_id_[wave];
   unsigned short* const s_kr = s_kr_[wave];
-  const int b = gc / g.ncells, h = gc % g.ncells;
-  {
-    int cnt = 0;
-    if (lane < g.nstencil) {
-      int nh = h;
-      if (g.use_cell_list) {
-        int c[3] = {h % g.ncell[0], (h / g.ncell[0]) % g.ncell[1], h / (g.ncell[0] * g.ncell[1])};
-        int o[3] = {lane % 3 - 1, (lane / 3) % 3 - 1, lane / 9 - 1};
-        nh = 0;
-        int mult = 1;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) {
-          int cc = c[d] + o[d];  // jax-md rolls the cell buffer: the stencil always wraps
-          cc = cc < 0 ? cc + g.ncell[d] : (cc >= g.ncell[d] ? cc - g.ncell[d] : cc);
-          nh += cc * mult;
-          mult *= g.ncell[d];
-        }
-      }
-      const int ngc = b * g.ncells + nh;
-      const int st = lb_cell_begin(a, ngc);
-      s_cstart[lane] = st;
-      cnt = lb_cell_size(a, ngc, st);
-    }
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 32; off <<= 1) {
-      const int v = __shfl_up(incl, off);
-      if (lane >= off) incl += v;
-    }
-    if (lane < g.nstencil) s_coff[lane] = incl - cnt;
-    if (lane == g.nstencil - 1) s_coff[g.nstencil] = incl;
-  }
+  lb_stencil_table(g, a, gc, lane, DIM, s_cstart, s_coff);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   const int M = __builtin_amdgcn_readfirstlane(s_coff[g.nstencil]);
   const bool single = M <= 64 * NLC_S;
@@ -931,13 +864,7 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
 #pragma unroll
     for (int s = 0; s < NLC_S; ++s) {
       if (c0 + 64 * s >= M) continue;
-      const int j = min(c0 + 64 * s + lane, M - 1);
-      int lo = 0, hi = g.nstencil;  // largest k with s_coff[k] <= j
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (s_coff[mid] <= j) lo = mid; else hi = mid;
-      }
-      cj[s] = s_cstart[lo] + (j - s_coff[lo]);
+      cj[s] = lb_stencil_slot(s_cstart, s_coff, g.nstencil, min(c0 + 64 * s + lane, M - 1));
       cid[s] = a.cell_part[cj[s]];
     }
   };
@@ -962,35 +889,8 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
       if (!act) continue;
       const int64_t base = (MODE == NL_ROWS) ? (int64_t)gr * a.maxd : (int64_t)a.row_ptr[gr];
       const int64_t slot = base + rank;
-      if (MODE == NL_ROWS || slot < a.e_alloc) {
-        a.senders[slot] = my;
-        // features.py:115-124: disp(pos[receiver], pos[sender]) / r_c and its norm
-        double rd[3] = {0, 0, 0};
-        double s2 = 0.0;
-#pragma unroll
-        for (int d = 0; d < DIM; ++d) {
-          rd[d] = lb_r(lb_disp1(pr[d], sp[d], g.box[d], g.half_box[d], g.periodic, F32) / g.rc, F32);
-          s2 = (d == 0) ? lb_r(rd[d] * rd[d], F32) : lb_r(s2 + lb_r(rd[d] * rd[d], F32), F32);
-        }
-        const double dist = s2 > 0.0 ? lb_r(sqrt(s2), F32) : 0.0;
-        const f32x4 lo4 = (DIM == 2) ? f32x4{(float)rd[0], (float)rd[1], (float)dist, 0.f}
-                                     : f32x4{(float)rd[0], (float)rd[1], (float)rd[2], (float)dist};
-        if (MODE == NL_ROWS) {
-          reinterpret_cast<f32x4*>(a.efeat)[slot] = lo4;
-        } else {
-          a.receivers[slot] = gr;
-          f32x4* ef = reinterpret_cast<f32x4*>(a.efeat + slot * 8);
-          ef[0] = lo4;
-          ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        if (a.efeat64) {
-          double* e64 = a.efeat64 + slot * 4;
-          e64[0] = rd[0];
-          e64[1] = rd[1];
-          e64[2] = rd[2];
-          e64[3] = dist;
-        }
-      }
+      if (MODE == NL_ROWS || slot < a.e_alloc)
+        lb_write_edge<F32, MODE == NL_ROWS>(g, a.out, slot, my, gr, pr, [&](int d) { return sp[d]; }, DIM);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   };
@@ -1076,14 +976,9 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
 #pragma unroll
         for (int s = 0; s < NLC_S; ++s) {
           if (c0 + 64 * s >= M) continue;
-          // metric_sq(position[sender], position[receiver]): sum of squares in x,y,z order, no FMA
-          double dd = lb_disp1(a.cpos[cj[s]], pr[0], g.box[0], g.half_box[0], g.periodic, F32);
-          double d2 = lb_r(dd * dd, F32);
-          _Pragma("unroll") for (int d = 1; d < DIM; ++d) {
-            dd = lb_disp1(a.cpos[(int64_t)d * a.cstride + cj[s]], pr[d], g.box[d], g.half_box[d], g.periodic, F32);
-            d2 = lb_r(d2 + lb_r(dd * dd, F32), F32);
-          }
-          ok[s] = (c0 + 64 * s + lane < M) && (d2 < g.rc2);  // strict <
+          const int src = cj[s];
+          const bool hit = lb_pair_in_cutoff<F32>(g, [&](int d) { return a.cpos[(int64_t)d * a.cstride + src]; }, pr, DIM);
+          ok[s] = (c0 + 64 * s + lane < M) && hit;
         }
       }
 #pragma unroll
@@ -1102,25 +997,11 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
     }
     if (MODE != NL_FILL && lane == 0) a.deg[gr] = count;  // (ctrl->max_deg is reduced by the degree scan, see k_nl)
     if (MODE == NL_COUNT) continue;
-    if (count > LB_MAX_ROW) {
-      if (lane == 0) {
-        if (MODE == NL_ROWS)
-          atomicExch(&ctrl->row_overflow, 1);  // re-allocate (the allocation switches to the dense fall-back)
-        else
-          atomicExch(&ctrl->density_error, 2);
-      }
-      count = LB_MAX_ROW;
-    }
-    if (MODE == NL_ROWS && count > a.maxd) {
-      if (lane == 0) atomicExch(&ctrl->row_overflow, 1);  // per-node slots too small: re-allocate
-      count = a.maxd;
-    }
+    count = lb_cap_row<MODE>(ctrl, a, count, lane, LB_MAX_ROW, true);
     // rank of every hit inside its row (ids are unique): lane broadcasts for rows <= 64, the LDS row otherwise
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     if (count <= 64) {
-      const int my = s_id[list_len + min(lane, max(count - 1, 0))];
-      int rank = 0;
-      for (int u = 0; u < count; ++u) rank += (__builtin_amdgcn_readlane(my, u) < my) ? 1 : 0;
+      const int rank = lb_rank_in_row(s_id[list_len + min(lane, max(count - 1, 0))], count);
       if (lane < count) s_kr[list_len + lane] = (unsigned short)((kb << 8) | rank);
     } else {
       for (int t = lane; t < count; t += 64) {
@@ -1134,18 +1015,11 @@ __global__ void __launch_bounds__(64 * NLC_WAVES, 5)
   }
 }
 
-// NL_ROWS -> CSR: one 16-lane group per node copies its sorted row into place.
-__global__ void __launch_bounds__(256)
-    k_nl_compact(int64_t BN, const lb_ctrl* __restrict__ ctrl, const int32_t* __restrict__ deg,
-                 const int32_t* __restrict__ row_ptr, int32_t maxd, const int32_t* __restrict__ tsend,
-                 const float* __restrict__ tfeat, const double* __restrict__ tfeat64,
-                 int32_t* __restrict__ senders, int32_t* __restrict__ receivers,
-                 float* __restrict__ efeat, double* __restrict__ efeat64, int64_t e_alloc) {
-  if (ctrl->overflow_step >= 0) return;
-  const int64_t gnode = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (gnode >= BN) return;
-  const int d = min(deg[gnode], maxd);
-  const int64_t base = row_ptr[gnode];
+// NL_ROWS -> CSR: one 16-lane group copies node gnode's sorted row (d entries) from its per-node slots to CSR offset base
+__device__ __forceinline__ void lb_copy_row(int64_t gnode, int d, int64_t base, int32_t maxd, const int32_t* __restrict__ tsend,
+                                            const float* __restrict__ tfeat, const double* __restrict__ tfeat64,
+                                            int32_t* __restrict__ senders, int32_t* __restrict__ receivers,
+                                            float* __restrict__ efeat, double* __restrict__ efeat64, int64_t e_alloc) {
   for (int k = threadIdx.x & 15; k < d; k += 16) {
     const int64_t src = gnode * maxd + k, dst = base + k;
     if (dst >= e_alloc) break;
@@ -1157,6 +1031,40 @@ __global__ void __launch_bounds__(256)
     if (efeat64 && tfeat64)
       for (int c = 0; c < 4; ++c) efeat64[dst * 4 + c] = tfeat64[src * 4 + c];
   }
+}
+
+// did_buffer_overflow of one trajectory = cell list overflow | occupancy > max_occupancy (jax-md); a row that outgrew the
+// engine's per-node slots is reported the same way (the driver re-allocates)
+__device__ __forceinline__ int lb_did_overflow(const lb_geom& g, int eb, int e_cap, int max_occ, int cell_capacity,
+                                               int row_overflow) {
+  return (eb > e_cap) || (g.use_cell_list && max_occ > cell_capacity) || row_overflow;
+}
+
+// The control block after a build: edge counts and, on the update path (frozen), a did_buffer_overflow or an edge list longer
+// than the allocation poisons the step (overflow_step + the pinned host word, visible once the kernel retires)
+__device__ __forceinline__ void lb_ctrl_finish(lb_ctrl* __restrict__ ctrl, int total, int64_t e_alloc, bool frozen, bool ov,
+                                               int step, int32_t* host_flag) {
+  ctrl->n_edges_unclamped = total;
+  lb_acct_edges(ctrl, total);
+  ctrl->n_edges_total = (int)min((int64_t)total, e_alloc);
+  if (frozen && (ov || (int64_t)total > e_alloc) && ctrl->overflow_step < 0) {
+    ctrl->overflow_step = step;
+    if (host_flag) *host_flag = step;
+  }
+}
+
+// NL_ROWS -> CSR: one 16-lane group per node copies its sorted row into place.
+__global__ void __launch_bounds__(256)
+    k_nl_compact(int64_t BN, const lb_ctrl* __restrict__ ctrl, const int32_t* __restrict__ deg,
+                 const int32_t* __restrict__ row_ptr, int32_t maxd, const int32_t* __restrict__ tsend,
+                 const float* __restrict__ tfeat, const double* __restrict__ tfeat64,
+                 int32_t* __restrict__ senders, int32_t* __restrict__ receivers,
+                 float* __restrict__ efeat, double* __restrict__ efeat64, int64_t e_alloc) {
+  if (ctrl->overflow_step >= 0) return;
+  const int64_t gnode = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (gnode >= BN) return;
+  lb_copy_row(gnode, min(deg[gnode], maxd), row_ptr[gnode], maxd, tsend, tfeat, tfeat64, senders, receivers, efeat, efeat64,
+              e_alloc);
 }
 
 // NL_ROWS -> CSR for batches of at most LB_CSCAN_N nodes: degree scan, k_row_finish and the compaction in ONE launch
@@ -1195,18 +1103,7 @@ __global__ void __launch_bounds__(256)
   const int64_t gnode = (int64_t)node0 + q;
   if (gnode < BN) {
     if ((tid & 15) == 0) row_ptr[gnode] = base;
-    const int d = min(s_deg[q], maxd);
-    for (int k = tid & 15; k < d; k += 16) {
-      const int64_t src = gnode * maxd + k, dst = (int64_t)base + k;
-      if (dst >= e_alloc) break;
-      senders[dst] = tsend[src];
-      receivers[dst] = (int32_t)gnode;
-      f32x4* ef = reinterpret_cast<f32x4*>(efeat + dst * 8);
-      ef[0] = reinterpret_cast<const f32x4*>(tfeat)[src];
-      ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (efeat64 && tfeat64)
-        for (int c = 0; c < 4; ++c) efeat64[dst * 4 + c] = tfeat64[src * 4 + c];
-    }
+    lb_copy_row(gnode, min(s_deg[q], maxd), base, maxd, tsend, tfeat, tfeat64, senders, receivers, efeat, efeat64, e_alloc);
   }
   if (!last) return;
   // ---- k_row_finish's job: per-trajectory edge counts (B <= 64 here), overflow flags, the control block
@@ -1227,18 +1124,12 @@ __global__ void __launch_bounds__(256)
     for (int b = 0; b < g.B; ++b) {
       const int eb = s_b[b];
       nedges_b[b] = eb;
-      const int ov = (eb > e_cap) || (g.use_cell_list && ctrl->max_cell_occ > cell_capacity) || ctrl->row_overflow;
+      const int ov = lb_did_overflow(g, eb, e_cap, ctrl->max_cell_occ, cell_capacity, ctrl->row_overflow);
       overflow[b] = ov;
       any |= ov;
     }
     row_ptr[BN] = total;
-    ctrl->n_edges_unclamped = total;
-    lb_acct_edges(ctrl, total);
-    ctrl->n_edges_total = (int)min((int64_t)total, e_alloc);
-    if ((any || (int64_t)total > e_alloc) && ctrl->overflow_step < 0) {
-      ctrl->overflow_step = ctrl->step;
-      if (host_flag) *host_flag = ctrl->step;
-    }
+    lb_ctrl_finish(ctrl, total, e_alloc, true, any, ctrl->step, host_flag);
   }
 }
 
@@ -1256,25 +1147,12 @@ __device__ __forceinline__ void lb_row_finish_body(const lb_geom& g, const int32
   for (int b = threadIdx.x; b < g.B; b += blockDim.x) {
     const int eb = row_ptr[(b + 1) * g.N] - row_ptr[b * g.N];
     nedges_b[b] = eb;
-    // did_buffer_overflow = cell list overflow | occupancy > max_occupancy (jax-md); a row that
-    // outgrew the engine's per-node slots is reported the same way (the driver re-allocates)
-    int ov = 0;
-    if (frozen)
-      ov = (eb > e_cap) || (g.use_cell_list && ctrl->max_cell_occ > cell_capacity) || ctrl->row_overflow;
+    const int ov = frozen ? lb_did_overflow(g, eb, e_cap, ctrl->max_cell_occ, cell_capacity, ctrl->row_overflow) : 0;
     overflow[b] = ov;
     if (ov) atomicExch(s_any, 1);
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const int total = row_ptr[n];
-    ctrl->n_edges_unclamped = total;
-    lb_acct_edges(ctrl, total);
-    ctrl->n_edges_total = (int)min((int64_t)total, e_alloc);
-    if (frozen && (*s_any || (int64_t)total > e_alloc) && ctrl->overflow_step < 0) {
-      ctrl->overflow_step = ctrl->step;
-      if (host_flag) *host_flag = ctrl->step;  // pinned host memory: visible once this kernel retires
-    }
-  }
+  if (threadIdx.x == 0) lb_ctrl_finish(ctrl, row_ptr[n], e_alloc, frozen, *s_any, ctrl->step, host_flag);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1342,9 +1220,7 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 //     of its wave owns the 64 ids of word w - expanded in ascending id order into the wave's row buffer, and the
 //     fp64 predicate (same operand order as k_nl) runs on that short list only.  Same candidate set as the rolled
 //     3^dim stencil of k_nl (the masks wrap); the hits come out sorted by sender id, so the rank pass is gone;
-//   * rows go straight into the CSR arrays: a workgroup publishes the edge count of its NLS_WAVES receivers in one
-//     word (build epoch << 16 | count, agent-scope release store) and adds up the words of the workgroups before it
-//     (workgroups are dispatched in index order, so a predecessor is running or done; bounded spin);
+//   * rows go straight into the CSR arrays at offsets from a look-back over the earlier workgroups (lb_lookback);
 //   * the last workgroup also histograms the cells (max_cell_occ for the did_buffer_overflow flag) and does
 //     k_row_finish's job.
 // cell coordinate of a position: int(position / cell_size) clamped to the grid (k_cells_small's arithmetic).  The fp64
@@ -1357,32 +1233,85 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 #define NLS_CAND 512  // stencil candidates per receiver (row buffer entries; >= LB_MAX_ROW)
 struct lb_nls_args {
   const double* win;
-  int32_t *senders, *receivers;
-  float* efeat;
-  double* efeat64;
+  lb_edge_out out;
   int32_t *deg, *row_ptr, *overflow, *nedges_b;
   unsigned long long* wg_sum;  // [ceil(N / NLS_WAVES)]
   int64_t e_alloc;
   int32_t e_cap, cell_capacity, npad;
   int32_t* host_flag;
   lb_feat_job feat;  // node features of this step: every wave writes the row of its receiver (xnode == null: no job)
-  long long* dbg;  // -DLB_MS_STAMPS builds: [3 workgroups][8] wall-clock stamps (first, middle, last workgroup)
 };
-#define NLS_STAMP(k)                                                                                       \
-  do {                                                                                                     \
-    if (a.dbg && tid == 0) {                                                                               \
-      const int wsel = blockIdx.x == 0 ? 0 : ((int)blockIdx.x == (int)gridDim.x / 2 ? 1 : (last ? 2 : -1)); \
-      if (wsel >= 0) a.dbg[wsel * 8 + (k)] = wall_clock64();                                               \
-    }                                                                                                      \
-  } while (0)
+
+// Look-back of the single-launch builds: a workgroup's rows start after the edges of the workgroups before it.  Thread 0
+// publishes this workgroup's word (build epoch << 48 | largest cell occupancy << 32 | overflow << 31 | edge count, agent-scope
+// atomic store); every thread then adds up its share of the predecessors' words - workgroups are dispatched in index order,
+// so a predecessor is running or done.  The spin is bounded: a word that never arrives reports persist_error 2 at
+// persist_step, and the engine falls back to the multi-launch build (nl_one_off).  s_cnt[0 .. nrows): this workgroup's row
+// sizes; s_acc[1] / s_acc[2]: its overflow flag and largest occupancy, to which the predecessors' are added; s_acc[0]
+// receives the predecessors' edge total.  Every thread calls it, between two barriers.
+__device__ __forceinline__ void lb_lookback(lb_ctrl* __restrict__ ctrl, unsigned long long* wg_sum, unsigned long long epoch,
+                                            int step, const int* s_cnt, int nrows, int* s_acc) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  if (tid == 0) {
+    int tot = 0;
+    for (int w = 0; w < nrows; ++w) tot += s_cnt[w];
+    const unsigned long long word = (epoch << 48) | ((unsigned long long)(s_acc[2] & 0xffff) << 32) |
+                                    ((unsigned long long)(s_acc[1] & 1) << 31) | (unsigned long long)(tot & 0x7fffffff);
+    __hip_atomic_store(&wg_sum[blockIdx.x], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  int part = 0, occ = 0, ovf = 0;
+  bool timed_out = false;
+  for (int p = tid; p < (int)blockIdx.x; p += (int)blockDim.x) {
+    unsigned long long v = 0;
+    int spins = 0;
+    do {
+      v = __hip_atomic_load(&wg_sum[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if ((v >> 48) == epoch) break;
+      __builtin_amdgcn_s_sleep(1);
+    } while (++spins < (1 << 22));
+    if ((v >> 48) != epoch) timed_out = true;
+    part += (int)(v & 0x7fffffffu);
+    ovf |= (int)((v >> 31) & 1);
+    occ = max(occ, (int)((v >> 32) & 0xffff));
+  }
+  if (timed_out) {
+    atomicExch(&ctrl->persist_error, 2);
+    atomicMin(&ctrl->persist_step, step);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    part += __shfl_xor(part, off);
+    ovf |= __shfl_xor(ovf, off);
+    occ = max(occ, __shfl_xor(occ, off));
+  }
+  if (lane == 0 && (int)blockIdx.x > wave * 64) {
+    if (part) atomicAdd(&s_acc[0], part);
+    if (ovf) atomicOr(&s_acc[1], 1);
+    atomicMax(&s_acc[2], occ);
+  }
+}
+
+// k_row_finish's job in the single-launch builds, done by the last workgroup, which knows the total (s_cnt, s_acc: see
+// lb_lookback); then the next build's epoch
+__device__ __forceinline__ void lb_nls_finish(const lb_geom& g, lb_ctrl* __restrict__ ctrl, const lb_nls_args& a, const int* s_cnt,
+                                              int nrows, const int* s_acc, int step) {
+  int total = s_acc[0];
+  for (int w = 0; w < nrows; ++w) total += s_cnt[w];
+  a.row_ptr[g.N] = total;
+  a.nedges_b[0] = total;
+  const int ov = lb_did_overflow(g, total, a.e_cap, s_acc[2], a.cell_capacity, s_acc[1] & 1);
+  a.overflow[0] = ov;
+  ctrl->max_cell_occ = s_acc[2];
+  lb_ctrl_finish(ctrl, total, a.e_alloc, true, ov, step, a.host_flag);
+  int ne = ctrl->nl_epoch + 1;
+  if ((ne & 0xffff) == 0) ++ne;
+  ctrl->nl_epoch = ne;
+}
 
 // DIM is a template parameter: under a loop bounded by the run-time dimension the per-dimension register arrays are
 // indexed by a run-time value and land in scratch (144 B per lane, every access a memory round trip)
 template <bool F32, int DIM>
 __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __restrict__ ctrl, lb_nls_args a) {
   extern __shared__ double s_dynd[];
-  if (a.dbg && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))
-    a.dbg[24 + (blockIdx.x == 0 ? 0 : 1)] = wall_clock64();
   if (ctrl->overflow_step >= 0) return;
   const int N = g.N, npad = a.npad;
   const int nwv = blockDim.x >> 6, nwords = npad >> 6;
@@ -1397,7 +1326,6 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
   const int step = ctrl->step;
   const unsigned long long epoch = (unsigned long long)((uint32_t)ctrl->nl_epoch & 0xffffu);
   const bool last = blockIdx.x == gridDim.x - 1;
-  NLS_STAMP(0);
   if (tid < 32) s_cnt[tid] = 0;
   if (g.use_cell_list)
     for (int k = tid; k < tab_len; k += blockDim.x) s_tab[k] = 0ull;
@@ -1445,7 +1373,6 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
     }
   }
   __syncthreads();
-  NLS_STAMP(1);
   // ---- pass 1 (bit masks): the candidates of the receiver's 3^dim stencil cells, in id order, into the row buffer
   const int r = blockIdx.x * nwv + wave;
   const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -1454,7 +1381,7 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
   int* const row = s_row + wave * NLS_CAND;
   if (r < N) {
     if (a.feat.xnode) lb_node_features_wave(g, N, a.win, step, a.feat, r);
-    _Pragma("unroll") for (int d = 0; d < DIM; ++d) pr[d] = s_p[d * npad + r];
+    lb_load_pos(pr, s_p, npad, r, DIM);
     int ncand = N;  // (no cell list: every particle is a candidate, pass 2 walks the ids)
     if (g.use_cell_list) {
       const int pc = s_cell[r];
@@ -1499,14 +1426,7 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
       int j = 0;
       if (t < ncand) {
         j = g.use_cell_list ? row[t] : t;
-        // metric_sq(position[sender], position[receiver]) as in k_nl
-        double dd = lb_disp1(s_p[j], pr[0], g.box[0], g.half_box[0], g.periodic, F32);
-        double d2 = lb_r(dd * dd, F32);
-        _Pragma("unroll") for (int d = 1; d < DIM; ++d) {
-          dd = lb_disp1(s_p[d * npad + j], pr[d], g.box[d], g.half_box[d], g.periodic, F32);
-          d2 = lb_r(d2 + lb_r(dd * dd, F32), F32);
-        }
-        ok = d2 < g.rc2;
+        ok = lb_pair_in_cutoff<F32>(g, [&](int d) { return s_p[d * npad + j]; }, pr, DIM);
       }
       const unsigned long long mask = __ballot(ok);
       // (in place: hit k of this sweep lands at count + k <= c0 + lane's own index, and every lane has read its j)
@@ -1525,49 +1445,8 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
     }
   }
   __syncthreads();
-  NLS_STAMP(3);
-  // ---- this workgroup's word out (epoch | max occupancy seen | overflow | edge count), its predecessors' in
-  if (tid == 0) {
-    int tot = 0;
-    for (int w = 0; w < nwv; ++w) tot += s_cnt[w];
-    const unsigned long long word = (epoch << 48) | ((unsigned long long)(s_cnt[18] & 0xffff) << 32) |
-                                    ((unsigned long long)(s_cnt[17] & 1) << 31) | (unsigned long long)(tot & 0x7fffffff);
-    __hip_atomic_store(&a.wg_sum[blockIdx.x], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  NLS_STAMP(4);
-  {
-    int part = 0, occ = 0, ovf = 0;
-    bool timed_out = false;
-    for (int p = tid; p < (int)blockIdx.x; p += (int)blockDim.x) {
-      unsigned long long v = 0;
-      int spins = 0;
-      do {
-        v = __hip_atomic_load(&a.wg_sum[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((v >> 48) == epoch) break;
-        __builtin_amdgcn_s_sleep(1);
-      } while (++spins < (1 << 22));
-      if ((v >> 48) != epoch) timed_out = true;
-      part += (int)(v & 0x7fffffffu);
-      ovf |= (int)((v >> 31) & 1);
-      occ = max(occ, (int)((v >> 32) & 0xffff));
-    }
-    if (timed_out) {
-      atomicExch(&ctrl->persist_error, 2);
-      atomicMin(&ctrl->persist_step, step);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      part += __shfl_xor(part, off);
-      ovf |= __shfl_xor(ovf, off);
-      occ = max(occ, __shfl_xor(occ, off));
-    }
-    if (lane == 0 && (int)blockIdx.x > wave * 64) {
-      if (part) atomicAdd(&s_cnt[16], part);
-      if (ovf) atomicOr(&s_cnt[17], 1);
-      atomicMax(&s_cnt[18], occ);
-    }
-  }
+  lb_lookback(ctrl, a.wg_sum, epoch, step, s_cnt, nwv, s_cnt + 16);
   __syncthreads();
-  NLS_STAMP(5);
   int base = s_cnt[16];
   for (int w = 0; w < wave; ++w) base += s_cnt[w];
   // ---- rows straight into the CSR arrays (ascending sender id by construction)
@@ -1580,52 +1459,10 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
       const int j = row[t];
       const int64_t slot = (int64_t)base + t;
       if (slot >= a.e_alloc) break;
-      a.senders[slot] = j;
-      a.receivers[slot] = r;
-      // features.py:115-124: disp(pos[receiver], pos[sender]) / r_c and its norm
-      double rd[3] = {0, 0, 0};
-      double s2 = 0.0;
-      _Pragma("unroll") for (int d = 0; d < DIM; ++d) {
-        rd[d] = lb_r(lb_disp1(pr[d], s_p[d * npad + j], g.box[d], g.half_box[d], g.periodic, F32) / g.rc, F32);
-        s2 = (d == 0) ? lb_r(rd[d] * rd[d], F32) : lb_r(s2 + lb_r(rd[d] * rd[d], F32), F32);
-      }
-      const double dist = s2 > 0.0 ? lb_r(sqrt(s2), F32) : 0.0;
-      f32x4* ef = reinterpret_cast<f32x4*>(a.efeat + slot * 8);
-      ef[0] = (DIM == 2) ? f32x4{(float)rd[0], (float)rd[1], (float)dist, 0.f}
-                           : f32x4{(float)rd[0], (float)rd[1], (float)rd[2], (float)dist};
-      ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (a.efeat64) {
-        double* e64 = a.efeat64 + slot * 4;
-        e64[0] = rd[0];
-        e64[1] = rd[1];
-        e64[2] = rd[2];
-        e64[3] = dist;
-      }
+      lb_write_edge<F32, false>(g, a.out, slot, j, r, pr, [&](int d) { return s_p[d * npad + j]; }, DIM);
     }
   }
-  NLS_STAMP(6);
-  // ---- k_row_finish's job, by the workgroup that knows the total
-  if (last && tid == 0) {
-    int total = s_cnt[16];
-    for (int w = 0; w < nwv; ++w) total += s_cnt[w];
-    a.row_ptr[N] = total;
-    a.nedges_b[0] = total;
-    const int max_occ = s_cnt[18];
-    const int ov = (total > a.e_cap) || (g.use_cell_list && max_occ > a.cell_capacity) || (s_cnt[17] & 1);
-    a.overflow[0] = ov;
-    ctrl->max_cell_occ = max_occ;
-    ctrl->n_edges_unclamped = total;
-    lb_acct_edges(ctrl, total);
-    ctrl->n_edges_total = (int)min((int64_t)total, a.e_alloc);
-    if ((ov || (int64_t)total > a.e_alloc) && ctrl->overflow_step < 0) {
-      ctrl->overflow_step = step;
-      if (a.host_flag) *a.host_flag = step;
-    }
-    int ne = ctrl->nl_epoch + 1;
-    if ((ne & 0xffff) == 0) ++ne;
-    ctrl->nl_epoch = ne;
-  }
-  NLS_STAMP(7);
+  if (last && tid == 0) lb_nls_finish(g, ctrl, a, s_cnt, nwv, s_cnt + 16, step);
 }
 
 // ----------------------------------------------- one trajectory, 4096 < N <= 8192 particles (3D: 8 k): k_nl_mid
@@ -1710,8 +1547,8 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
     hit_base[i + 1] = hit_base[i];
     if (r >= N) continue;
     if (a.feat.xnode) lb_node_features_wave(g, N, a.win, step, a.feat, r);
-    double pr[3] = {0, 0, 0};
-    _Pragma("unroll") for (int d = 0; d < DIM; ++d) pr[d] = w0[d * N + r];
+    double pr[3];
+    lb_load_pos(pr, w0, N, r, DIM);
     const int pc = s_cell[r];
     unsigned long long m[2], ms[2];
 #pragma unroll
@@ -1781,6 +1618,8 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int t = c0 + 64 * u + lane;
+        // lb_pair_in_cutoff's arithmetic written out - keep the two bit-identical: through the helper the 3D instances'
+        // register allocation spills 16 more SGPRs, and k_nl_mid<true, 3> needs scratch (kernel resource report)
         bool ok = false;
         if (t < ncand) {
           double dd = lb_disp1(pj[u][0], pr[0], g.box[0], g.half_box[0], g.periodic, F32);
@@ -1810,44 +1649,7 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
     atomicMax(&s_cnt[34], same_max);
   }
   __syncthreads();
-  if (tid == 0) {
-    int tot = 0;
-    for (int w = 0; w < NLM_WAVES * NLM_RPW; ++w) tot += s_cnt[w];
-    const unsigned long long word = (epoch << 48) | ((unsigned long long)(s_cnt[34] & 0xffff) << 32) |
-                                    ((unsigned long long)(s_cnt[33] & 1) << 31) | (unsigned long long)(tot & 0x7fffffff);
-    __hip_atomic_store(&a.wg_sum[blockIdx.x], word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  {
-    int part = 0, occ = 0, ovf = 0;
-    bool timed_out = false;
-    for (int p = tid; p < (int)blockIdx.x; p += (int)blockDim.x) {
-      unsigned long long v = 0;
-      int spins = 0;
-      do {
-        v = __hip_atomic_load(&a.wg_sum[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((v >> 48) == epoch) break;
-        __builtin_amdgcn_s_sleep(1);
-      } while (++spins < (1 << 22));
-      if ((v >> 48) != epoch) timed_out = true;
-      part += (int)(v & 0x7fffffffu);
-      ovf |= (int)((v >> 31) & 1);
-      occ = max(occ, (int)((v >> 32) & 0xffff));
-    }
-    if (timed_out) {
-      atomicExch(&ctrl->persist_error, 2);
-      atomicMin(&ctrl->persist_step, step);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      part += __shfl_xor(part, off);
-      ovf |= __shfl_xor(ovf, off);
-      occ = max(occ, __shfl_xor(occ, off));
-    }
-    if (lane == 0 && (int)blockIdx.x > wave * 64) {
-      if (part) atomicAdd(&s_cnt[32], part);
-      if (ovf) atomicOr(&s_cnt[33], 1);
-      atomicMax(&s_cnt[34], occ);
-    }
-  }
+  lb_lookback(ctrl, a.wg_sum, epoch, step, s_cnt, NLM_WAVES * NLM_RPW, s_cnt + 32);
   __syncthreads();
   int base = s_cnt[32];
   for (int w = 0; w < wave * NLM_RPW; ++w) base += s_cnt[w];
@@ -1856,8 +1658,8 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
     const int r = r0 + i;
     if (r >= N) continue;
     if (lane == 0) a.row_ptr[r] = base;
-    double pr[3] = {0, 0, 0};
-    _Pragma("unroll") for (int d = 0; d < DIM; ++d) pr[d] = w0[d * N + r];
+    double pr[3];
+    lb_load_pos(pr, w0, N, r, DIM);
     const int cnt = min(cnt_i[i], LB_MAX_ROW);
     for (int t0 = 0; t0 < cnt; t0 += 64) {
       const int t = t0 + lane;
@@ -1865,133 +1667,73 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
       const int j = row[hit_base[i] + t];
       const int64_t slot_e = (int64_t)base + t;
       if (slot_e >= a.e_alloc) break;
-      a.senders[slot_e] = j;
-      a.receivers[slot_e] = r;
-      double rd[3] = {0, 0, 0};
-      double s2 = 0.0;
-      _Pragma("unroll") for (int d = 0; d < DIM; ++d) {
-        rd[d] = lb_r(lb_disp1(pr[d], w0[d * N + j], g.box[d], g.half_box[d], g.periodic, F32) / g.rc, F32);
-        s2 = (d == 0) ? lb_r(rd[d] * rd[d], F32) : lb_r(s2 + lb_r(rd[d] * rd[d], F32), F32);
-      }
-      const double dist = s2 > 0.0 ? lb_r(sqrt(s2), F32) : 0.0;
-      f32x4* ef = reinterpret_cast<f32x4*>(a.efeat + slot_e * 8);
-      ef[0] = (DIM == 2) ? f32x4{(float)rd[0], (float)rd[1], (float)dist, 0.f}
-                         : f32x4{(float)rd[0], (float)rd[1], (float)rd[2], (float)dist};
-      ef[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (a.efeat64) {
-        double* e64 = a.efeat64 + slot_e * 4;
-        e64[0] = rd[0];
-        e64[1] = rd[1];
-        e64[2] = rd[2];
-        e64[3] = dist;
-      }
+      lb_write_edge<F32, false>(g, a.out, slot_e, j, r, pr, [&](int d) { return w0[d * N + j]; }, DIM);
     }
     base += cnt_i[i];
   }
-  if (last && tid == 0) {
-    int total = s_cnt[32];
-    for (int w = 0; w < NLM_WAVES * NLM_RPW; ++w) total += s_cnt[w];
-    a.row_ptr[N] = total;
-    a.nedges_b[0] = total;
-    const int max_occ = s_cnt[34];
-    const int ov = (total > a.e_cap) || (max_occ > a.cell_capacity) || (s_cnt[33] & 1);
-    a.overflow[0] = ov;
-    ctrl->max_cell_occ = max_occ;
-    ctrl->n_edges_unclamped = total;
-    lb_acct_edges(ctrl, total);
-    ctrl->n_edges_total = (int)min((int64_t)total, a.e_alloc);
-    if ((ov || (int64_t)total > a.e_alloc) && ctrl->overflow_step < 0) {
-      ctrl->overflow_step = step;
-      if (a.host_flag) *a.host_flag = step;
-    }
-    int ne = ctrl->nl_epoch + 1;
-    if ((ne & 0xffff) == 0) ++ne;
-    ctrl->nl_epoch = ne;
-  }
+  if (last && tid == 0) lb_nls_finish(g, ctrl, a, s_cnt, NLM_WAVES * NLM_RPW, s_cnt + 32, step);
 }
 
 // ----------------------------------------------------------------------------------- host
-// `small` = staged-candidate capacity of the one-wave variant to use (a multiple of 128 up to
-// NL_SMALL_MAXC), or 0 for the 256-thread / 2048-candidate variant.  The LDS footprint of the
-// staged stencil (28 B per candidate) sets how many cells a CU keeps in flight - the search is
-// latency bound, so the smallest variant that holds cell_capacity * 3^dim candidates is used.
-// which search kernel a build uses: 0 = k_nl (workgroup per cell, staged stencil), 1 = k_nlw (wave per receiver), 2 = k_nlc
-// (wave per cell).  Measured (MI355X, B = 8): 3^3-cell stencils favour the per-wave kernels (TGV3D 0.28 -> 0.18 -> 0.12 ms per
-// step), 3^2-cell stencils the staged per-cell kernel (DAM2D 0.11 vs 0.15 ms).  LB_NL_KERNEL=cell|wave|nlc overrides.
+// Which search kernel a build uses, from the input alone: 0 = k_nl (workgroup per cell, staged stencil), 1 = k_nlw (wave per
+// receiver), 2 = k_nlc (wave per cell).  Measured (MI355X, B = 8): 3^3-cell stencils favour the per-wave kernels (TGV3D 0.28
+// -> 0.18 -> 0.12 ms per step), 3^2-cell stencils the staged per-cell kernel (DAM2D 0.11 vs 0.15 ms).  The dense fall-back
+// (e->nl_dense, sticky) exceeds the staged kernels' LB_MAX_STENCIL_CAND candidates or LB_MAX_ROW neighbors: k_nlw with a row
+// buffer sized from the largest degree runs (the reference re-allocates for ANY occupancy, rollout.py:134-151).
 static int lb_nl_kernel_kind(const lb_engine* e) {
-  static const char* force = getenv("LB_NL_KERNEL");
-  // dense fall-back (e->nl_dense, sticky): the staged per-cell kernel is bounded by LB_MAX_STENCIL_CAND candidates and
-  // LB_MAX_ROW neighbors; beyond that the wave-per-receiver kernel with a row buffer sized from the largest degree runs
-  // (the reference re-allocates for ANY occupancy, rollout.py:134-151)
-  const bool per_wave = e->nl_dense || e->g.f32 || (force ? force[0] == 'w' : e->g.nstencil == 27);
-  const bool cell_wave = e->g.use_cell_list && !e->nl_dense && (e->g.dim == 2 || e->g.dim == 3) && (force ? force[0] == 'n' : per_wave);
-  return cell_wave ? 2 : (per_wave ? 1 : 0);
+  if (e->g.use_cell_list && !e->nl_dense && (e->g.dim == 3 || e->g.f32)) return 2;
+  return e->nl_dense || e->g.f32 ? 1 : 0;
 }
+
+// Launches kernel K with `lds` bytes of dynamic LDS.  Its dynamic-LDS limit is raised to `limit` ONCE, at its first launch,
+// which follows an allocation and so never runs inside a hipGraph capture.
+template <auto K, typename... Args>
+static void lb_launch_lds(int limit, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static bool raised = false;
+  if (!raised) {
+    (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    raised = true;
+  }
+  hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+}
+
+// `small` = staged-candidate capacity of the one-wave k_nl variant to use (a multiple of 128 up to NL_SMALL_MAXC), or 0 for the
+// 256-thread / 2048-candidate variant.  The LDS footprint of the staged stencil (28 B per candidate) sets how many cells a CU
+// keeps in flight - the search is latency bound, so the smallest variant that holds cell_capacity * 3^dim candidates is used.
 template <int MODE>
 static void lb_launch_nl(lb_engine* e, int small, const lb_nl_args& a) {
   const int kind = lb_nl_kernel_kind(e);
-  const bool per_wave = kind == 1;
-  // NL_ROWS in a rollout step: every search wave also writes the node-feature row of its receiver
-  const bool ride = MODE == NL_ROWS && e->feat_job.xnode && !a.efeat64;
+  // NL_ROWS in a rollout step: workgroups behind the search's write the node-feature rows
+  const bool ride = MODE == NL_ROWS && e->feat_job.xnode && !a.out.efeat64;
   if (ride) e->feat_done = true;
-  const bool cell_wave = kind == 2;   // round 6: one wave per CELL
-  if (cell_wave) {
-    const int ncell_all = e->g.B * e->g.ncells;
-    const int nb_s = (ncell_all + NLC_WAVES - 1) / NLC_WAVES;
-    int nb = nb_s;
-    lb_nl_args aw = a;
-    if (ride) {
-      aw.feat = e->feat_job;
-      aw.win = e->win;
-      aw.nb_search = nb_s;
-      nb = nb_s + (int)((e->BN + NLC_WAVES * NL_FEAT_ROWS - 1) / (NLC_WAVES * NL_FEAT_ROWS));
-    }
-#define LB_NLC_LAUNCH(F, D) \
-  hipLaunchKernelGGL((k_nlc<MODE, F, D>), dim3(nb), dim3(64 * NLC_WAVES), 0, e->stream, e->g, e->BN, e->ctrl, aw)
-    if (e->g.f32) {
-      if (e->g.dim == 3) LB_NLC_LAUNCH(true, 3); else LB_NLC_LAUNCH(true, 2);
-    } else {
-      if (e->g.dim == 3) LB_NLC_LAUNCH(false, 3); else LB_NLC_LAUNCH(false, 2);
-    }
-#undef LB_NLC_LAUNCH
+  lb_nl_args aw = a;
+  // the grid: nb_s search workgroups of `waves` waves, plus the feature workgroups behind them
+  auto grid = [&](int64_t nb_s, int waves) -> dim3 {
+    if (!ride) return dim3((unsigned)nb_s);
+    aw.feat = e->feat_job;
+    aw.win = e->win;
+    aw.nb_search = (int)nb_s;
+    return dim3((unsigned)(nb_s + (e->BN + waves * NL_FEAT_ROWS - 1) / (waves * NL_FEAT_ROWS)));
+  };
+  if (kind == 2) {  // round 6: one wave per CELL
+    const dim3 nb = grid((e->g.B * e->g.ncells + NLC_WAVES - 1) / NLC_WAVES, NLC_WAVES);
+    const auto k = e->g.f32 ? (e->g.dim == 3 ? k_nlc<MODE, true, 3> : k_nlc<MODE, true, 2>) : k_nlc<MODE, false, 3>;
+    hipLaunchKernelGGL(k, nb, dim3(64 * NLC_WAVES), 0, e->stream, e->g, e->BN, e->ctrl, aw);
     return;
   }
-  if (per_wave) {
-    const int nb_s = (int)((e->BN + NLW_WAVES - 1) / NLW_WAVES);
-    int nb = nb_s;
-    lb_nl_args aw = a;
-    if (ride) {
-      aw.feat = e->feat_job;
-      aw.win = e->win;
-      aw.nb_search = nb_s;
-      nb = nb_s + (int)((e->BN + NLW_WAVES * NL_FEAT_ROWS - 1) / (NLW_WAVES * NL_FEAT_ROWS));
-    }
+  if (kind == 1) {
+    const dim3 nb = grid((e->BN + NLW_WAVES - 1) / NLW_WAVES, NLW_WAVES);
     aw.row_cap = e->row_cap > LB_MAX_ROW ? e->row_cap : LB_MAX_ROW;
     const size_t lds = sizeof(int) * 2 * NLW_WAVES * (size_t)aw.row_cap;
-    if (e->g.f32) {  // dtype=float32 geometry: every result rounded to float
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)k_nlw<MODE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_nlw<MODE, true>), dim3(nb), dim3(64 * NLW_WAVES), lds, e->stream, e->g, e->BN, e->ctrl, aw);
-    } else {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute((const void*)k_nlw<MODE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((k_nlw<MODE>), dim3(nb), dim3(64 * NLW_WAVES), lds, e->stream, e->g, e->BN, e->ctrl, aw);
-    }
+    const auto k = e->g.f32 ? k_nlw<MODE, true> : k_nlw<MODE, false>;  // dtype=float32 geometry: every result rounded to float
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k, nb, dim3(64 * NLW_WAVES), lds, e->stream, e->g, e->BN, e->ctrl, aw);
     return;
   }
-  const int ncell_tot = e->g.B * e->g.ncells;
-  lb_nl_args ac = a;
-  if (ride) {
-    ac.feat = e->feat_job;
-    ac.win = e->win;
-    ac.nb_search = ncell_tot;
-  }
-  const int ride64 = ride ? (int)((e->BN + NL_FEAT_ROWS - 1) / NL_FEAT_ROWS) : 0;
-  const int ride256 = ride ? (int)((e->BN + 4 * NL_FEAT_ROWS - 1) / (4 * NL_FEAT_ROWS)) : 0;
-#define LB_NL_CASE(C)                                                                                       \
-  case C:                                                                                                   \
-    hipLaunchKernelGGL((k_nl<MODE, 64, C>), dim3(ncell_tot + ride64), dim3(64), 0, e->stream, e->g, e->BN,  \
-                       e->ctrl, ac);                                                                        \
+  const dim3 nb = grid(e->g.B * e->g.ncells, small ? 1 : 4);
+#define LB_NL_CASE(C)                                                                                         \
+  case C:                                                                                                     \
+    hipLaunchKernelGGL((k_nl<MODE, 64, C>), nb, dim3(64), 0, e->stream, e->g, e->BN, e->ctrl, aw);           \
     break;
   switch (small) {
     LB_NL_CASE(128)
@@ -2003,10 +1745,40 @@ static void lb_launch_nl(lb_engine* e, int small, const lb_nl_args& a) {
     LB_NL_CASE(896)
     LB_NL_CASE(1024)
     default:
-      hipLaunchKernelGGL((k_nl<MODE, 256, LB_MAX_STENCIL_CAND>), dim3(ncell_tot + ride256), dim3(256), 0,
-                         e->stream, e->g, e->BN, e->ctrl, ac);
+      hipLaunchKernelGGL((k_nl<MODE, 256, LB_MAX_STENCIL_CAND>), nb, dim3(256), 0, e->stream, e->g, e->BN, e->ctrl, aw);
   }
 #undef LB_NL_CASE
+}
+
+// arguments of the single-launch builds (k_nl_small, k_nl_mid)
+static lb_nls_args lb_nls_setup(lb_engine* e, bool want_efeat64, int npad) {
+  lb_nls_args a{};
+  a.win = e->win;
+  a.out = {e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : nullptr};
+  a.deg = e->deg;
+  a.row_ptr = e->row_ptr;
+  a.overflow = e->overflow;
+  a.nedges_b = e->nedges_b;
+  a.wg_sum = e->nl_wg_sum;
+  a.e_alloc = e->e_alloc;
+  a.e_cap = e->e_cap;
+  a.cell_capacity = e->cell_capacity;
+  a.npad = npad;
+  a.host_flag = e->host_flag_dev;
+  if (e->feat_job.xnode && !want_efeat64) {
+    a.feat = e->feat_job;
+    e->feat_done = true;
+  }
+  return a;
+}
+
+#define LB_NLS_MAX_LDS (150 * 1024)  // dynamic LDS the single-launch builds may use
+template <bool F32, int DIM>
+static void lb_launch_one_traj(lb_engine* e, bool mid, int nb, int threads, size_t lds, const lb_nls_args& a) {
+  if (mid)
+    lb_launch_lds<k_nl_mid<F32, DIM>>(LB_NLS_MAX_LDS, dim3(nb), dim3(threads), lds, e->stream, e->g, e->ctrl, a);
+  else
+    lb_launch_lds<k_nl_small<F32, DIM>>(LB_NLS_MAX_LDS, dim3(nb), dim3(threads), lds, e->stream, e->g, e->ctrl, a);
 }
 
 int lbk_nl_build(lb_engine* e, bool want_efeat64) {
@@ -2020,141 +1792,40 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   const bool small_ok = lb_fused_launches();
   const bool small_rows = small_ok && BN <= LB_SMALL_N;
   const bool small_cells = small_rows && ncell_tot <= LB_SMALL_N;
-  // one trajectory of <= 4096 particles on the update path: the whole build is ONE launch (k_nl_small)
-  const bool one_ok = small_ok;
-  const int nls_npad = (int)((BN + 63) / 64 * 64);
+  // one trajectory on the update path: the whole build is ONE launch - k_nl_small up to LB_SMALL_N particles, k_nl_mid with
+  // a cell list whose masks fit LDS up to NLM_N
+  static_assert(NLS_CAND >= LB_MAX_ROW, "k_nl_small's row buffer holds a full row");
+  const bool one_traj = small_ok && frozen && g.B == 1 && !e->nl_dense && !e->nl_one_off && e->nl_wg_sum &&
+                        g.ncell[0] < 2048 && g.ncell[1] < 2048 && g.ncell[2] < 1024;
+  const int npad = (int)((BN + 63) / 64 * 64);
+  const int64_t tab = g.use_cell_list ? (int64_t)(g.ncell[0] + g.ncell[1] + (g.dim == 3 ? g.ncell[2] : 0)) * (npad / 64) : 0;
   const int nls_waves = (int)std::min<int64_t>(NLS_WAVES, std::max<int64_t>(1, (BN + 255) / 256));
-  const int64_t nls_tab = g.use_cell_list ? (int64_t)(g.ncell[0] + g.ncell[1] + (g.dim == 3 ? g.ncell[2] : 0)) * (nls_npad / 64) : 0;
-  const size_t nls_lds = (size_t)nls_npad * (8 * g.dim + 4) + 8 * (size_t)nls_tab + sizeof(int) * ((size_t)nls_waves * NLS_CAND + 32);
-  if (one_ok && small_ok && frozen && g.B == 1 && (g.dim == 2 || g.dim == 3) && BN <= LB_SMALL_N && !e->nl_dense && !e->nl_one_off && nls_lds <= 150 * 1024 &&
-      (!g.use_cell_list || (int64_t)e->cell_capacity * g.nstencil <= NLS_CAND) &&
-      e->nl_wg_sum && g.ncell[0] < 2048 && g.ncell[1] < 2048 && g.ncell[2] < 1024 && NLS_CAND >= LB_MAX_ROW) {
+  const size_t nls_lds = (size_t)npad * (8 * g.dim + 4) + 8 * (size_t)tab + sizeof(int) * ((size_t)nls_waves * NLS_CAND + 32);
+  const bool nls = one_traj && BN <= LB_SMALL_N && nls_lds <= LB_NLS_MAX_LDS &&
+                   (!g.use_cell_list || (int64_t)e->cell_capacity * g.nstencil <= NLS_CAND);
+  const size_t nlm_lds = 8 * (size_t)tab + sizeof(int) * ((size_t)npad + NLM_WAVES * NLM_ROWBUF + 48);
+  const bool nlm = one_traj && BN > LB_SMALL_N && BN <= NLM_N && g.use_cell_list && nlm_lds <= LB_NLS_MAX_LDS &&
+                   (int64_t)e->cell_capacity * g.nstencil <= NLM_ROWBUF - LB_MAX_ROW * (NLM_RPW - 1);
+  if (nls || nlm) {
     lb_tic(e, LB_T_NEIGH);
-    lb_nls_args a{};
-    a.win = e->win;
-    a.senders = e->senders;
-    a.receivers = e->receivers;
-    a.efeat = e->efeat;
-    a.efeat64 = want_efeat64 ? e->efeat64 : nullptr;
-    a.deg = e->deg;
-    a.row_ptr = e->row_ptr;
-    a.overflow = e->overflow;
-    a.nedges_b = e->nedges_b;
-    a.wg_sum = e->nl_wg_sum;
-    a.e_alloc = e->e_alloc;
-    a.e_cap = e->e_cap;
-    a.cell_capacity = e->cell_capacity;
-    a.npad = nls_npad;
-    a.host_flag = e->host_flag_dev;
-#ifdef LB_MS_STAMPS  // debug builds only: wall-clock stamps of three workgroups
-    static const bool nls_dbg = true;
-#else
-    static const bool nls_dbg = false;
-#endif
-    static long long* dbg_dev = nullptr;
-    if (nls_dbg && !dbg_dev) LB_HIP(hipMalloc((void**)&dbg_dev, sizeof(long long) * 32));
-    a.dbg = nls_dbg ? dbg_dev : nullptr;
-    const int nwv = nls_waves;
-    const size_t lds = nls_lds;
-    const int nb = (int)((BN + nwv - 1) / nwv);
-    if (e->feat_job.xnode && !want_efeat64) {
-      a.feat = e->feat_job;
-      e->feat_done = true;
-    }
-  // (the dynamic-LDS limit is raised ONCE per kernel instance - the first launch after an allocation runs outside a
-  // hipGraph capture - to the 150 KiB the routing above admits)
-#define LB_NLS_LAUNCH(F, D)                                                                                      \
-  do {                                                                                                          \
-    static bool raised = false;                                                                                 \
-    if (!raised) {                                                                                              \
-      (void)hipFuncSetAttribute((const void*)k_nl_small<F, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-      raised = true;                                                                                            \
-    }                                                                                                           \
-    hipLaunchKernelGGL((k_nl_small<F, D>), dim3(nb), dim3(64 * nwv), lds, s, g, e->ctrl, a);                    \
-  } while (0)
-    if (g.f32) {
-      if (g.dim == 3) LB_NLS_LAUNCH(true, 3); else LB_NLS_LAUNCH(true, 2);
-    } else {
-      if (g.dim == 3) LB_NLS_LAUNCH(false, 3); else LB_NLS_LAUNCH(false, 2);
-    }
-#undef LB_NLS_LAUNCH
-    if (nls_dbg) {
-      long long h[32];
-      LB_HIP(hipStreamSynchronize(s));
-      LB_HIP(hipMemcpy(h, dbg_dev, sizeof(h), hipMemcpyDeviceToHost));
-      static int n_print = 0;
-      if (n_print++ % 16 == 8)
-        for (int w = 0; w < 3; ++w) {
-          fprintf(stderr, "k_nl_small wg%d (10 ns ticks from wg0 start):", w);
-          for (int k = 0; k < 8; ++k) fprintf(stderr, " %lld", h[w * 8 + k] - h[0]);
-          fprintf(stderr, "  | entry wg0 %lld, last wg %lld\n", h[24] - h[0], h[25] - h[0]);
-        }
-    }
+    const lb_nls_args a = lb_nls_setup(e, want_efeat64, npad);
+    const auto launch = g.f32 ? (g.dim == 3 ? lb_launch_one_traj<true, 3> : lb_launch_one_traj<true, 2>)
+                              : (g.dim == 3 ? lb_launch_one_traj<false, 3> : lb_launch_one_traj<false, 2>);
+    if (nls)
+      launch(e, false, (int)((BN + nls_waves - 1) / nls_waves), 64 * nls_waves, nls_lds, a);
+    else
+      launch(e, true, (int)((BN + NLM_WAVES * NLM_RPW - 1) / (NLM_WAVES * NLM_RPW)), 64 * NLM_WAVES, nlm_lds, a);
     lb_toc(e);
     LB_HIP(hipGetLastError());
     return LB_OK;
   }
-  // one trajectory of up to 8192 particles with a cell list whose masks fit LDS: k_nl_mid (one launch)
-  {
-    const int npad_m = (int)((BN + 63) / 64 * 64);
-    const int64_t tab_m = (int64_t)(g.ncell[0] + g.ncell[1] + (g.dim == 3 ? g.ncell[2] : 0)) * (npad_m / 64);
-    const size_t lds_m = 8 * (size_t)tab_m + sizeof(int) * ((size_t)npad_m + NLM_WAVES * NLM_ROWBUF + 48);
-    const bool mid_ok = small_ok;
-    if (mid_ok && one_ok && small_ok && frozen && g.B == 1 && BN > LB_SMALL_N && BN <= NLM_N && g.use_cell_list &&
-        (g.dim == 2 || g.dim == 3) && !e->nl_dense && !e->nl_one_off && lds_m <= 150 * 1024 &&
-        (int64_t)e->cell_capacity * g.nstencil <= NLM_ROWBUF - LB_MAX_ROW * (NLM_RPW - 1) && e->nl_wg_sum && g.ncell[0] < 2048 &&
-        g.ncell[1] < 2048 && g.ncell[2] < 1024) {
-      lb_tic(e, LB_T_NEIGH);
-      lb_nls_args a{};
-      a.win = e->win;
-      a.senders = e->senders;
-      a.receivers = e->receivers;
-      a.efeat = e->efeat;
-      a.efeat64 = want_efeat64 ? e->efeat64 : nullptr;
-      a.deg = e->deg;
-      a.row_ptr = e->row_ptr;
-      a.overflow = e->overflow;
-      a.nedges_b = e->nedges_b;
-      a.wg_sum = e->nl_wg_sum;
-      a.e_alloc = e->e_alloc;
-      a.e_cap = e->e_cap;
-      a.cell_capacity = e->cell_capacity;
-      a.npad = npad_m;
-      a.host_flag = e->host_flag_dev;
-      if (e->feat_job.xnode && !want_efeat64) {
-        a.feat = e->feat_job;
-        e->feat_done = true;
-      }
-      const int nb = (int)((BN + NLM_WAVES * NLM_RPW - 1) / (NLM_WAVES * NLM_RPW));
-#define LB_NLM_LAUNCH(F, D)                                                                                     \
-  do {                                                                                                          \
-    static bool raised = false;                                                                                 \
-    if (!raised) {                                                                                              \
-      (void)hipFuncSetAttribute((const void*)k_nl_mid<F, D>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); \
-      raised = true;                                                                                            \
-    }                                                                                                           \
-    hipLaunchKernelGGL((k_nl_mid<F, D>), dim3(nb), dim3(64 * NLM_WAVES), lds_m, s, g, e->ctrl, a);             \
-  } while (0)
-      if (g.f32) {
-        if (g.dim == 3) LB_NLM_LAUNCH(true, 3); else LB_NLM_LAUNCH(true, 2);
-      } else {
-        if (g.dim == 3) LB_NLM_LAUNCH(false, 3); else LB_NLM_LAUNCH(false, 2);
-      }
-#undef LB_NLM_LAUNCH
-      lb_toc(e);
-      LB_HIP(hipGetLastError());
-      return LB_OK;
-    }
-  }
   lb_tic(e, LB_T_CELLS);
   // (one mid-size trajectory that the single-launch builds above refused, e.g. DAM2D: binning still in one launch)
-  const bool cells1_ok = small_ok;
-  const bool mid_cells = cells1_ok && small_ok && frozen && g.B == 1 && BN <= LB_CELLS1_N && ncell_tot <= LB_CELLS1_NCELL;
+  const bool mid_cells = small_ok && frozen && g.B == 1 && BN <= LB_CELLS1_N && ncell_tot <= LB_CELLS1_NCELL;
   // batches: one workgroup per trajectory, one launch (LB_SMALL_FUSED=0: the five-launch counting sort)
-  const bool cells_traj_ok = small_ok;
   // (measured, profiles/r04_ab_cells_traj.txt: 2.5 k particles x 8 23.1 -> 17.5 us, 5.7 k x 8 27.7 -> 22.7 us, 8 k x 8 30.8 -> 32.5 us -
   // one workgroup per trajectory is bound by its scattered stores from ONE CU; above 6 k particles the five launches stay)
-  const bool traj_cells = cells_traj_ok && frozen && !small_cells && g.B > 1 && g.use_cell_list && g.N <= 6144 &&
+  const bool traj_cells = small_ok && frozen && !small_cells && g.B > 1 && g.use_cell_list && g.N <= 6144 &&
                           g.ncells <= LB_CELLS1_NCELL;
   // frozen capacities + a search kernel that walks CELLS: fixed-stride slots, two launches (k_cell_zero, k_cell_bin)
   const int64_t strided_slots = (int64_t)ncell_tot * e->cell_capacity;
@@ -2164,7 +1835,6 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   const bool strided = small_ok && frozen && g.use_cell_list && e->cell_capacity > 0 && lb_nl_kernel_kind(e) != 1 &&
                        strided_slots < ((int64_t)1 << 30);
 #endif
-  e->cells_strided = strided;
   if (strided) {
     if (strided_slots > e->cell_slots) {   // (first build after an allocation: never inside a graph capture)
       LB_HIP(hipStreamSynchronize(s));
@@ -2184,27 +1854,17 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
     hipLaunchKernelGGL((k_cells_small<LB_SMALL_N / LB_SMALL_T>), dim3(1), dim3(LB_SMALL_T), sizeof(int) * (size_t)ncell_tot, s, g,
                        BN, e->win, e->ctrl, e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
   } else if (traj_cells) {
-    static bool raised_t = false;
-    if (!raised_t) {
-      (void)hipFuncSetAttribute((const void*)k_cells_traj<LB_CELLS1_PER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                sizeof(int) * LB_CELLS1_NCELL);
-      raised_t = true;
-    }
     if (!e->cells_traj_ready) {  // occ[0 .. B] (max occupancy per trajectory, arrival ticket) live in the unused cell_count
       LB_HIP(hipMemsetAsync(e->cell_count, 0, sizeof(int32_t) * (size_t)(g.B + 1), s));
       e->cells_traj_ready = true;
     }
-    hipLaunchKernelGGL((k_cells_traj<LB_CELLS1_PER>), dim3(g.B), dim3(LB_SMALL_T), sizeof(int) * (size_t)g.ncells, s, g, BN,
-                       e->win, e->ctrl, e->cell_of, e->cell_start, e->cell_part, e->cpos, e->cell_count);
+    lb_launch_lds<k_cells_traj<LB_CELLS1_PER>>(sizeof(int) * LB_CELLS1_NCELL, dim3(g.B), dim3(LB_SMALL_T),
+                                               sizeof(int) * (size_t)g.ncells, s, g, BN, e->win, e->ctrl, e->cell_of,
+                                               e->cell_start, e->cell_part, e->cpos, e->cell_count);
   } else if (mid_cells) {
-    static bool raised = false;
-    if (!raised) {
-      (void)hipFuncSetAttribute((const void*)k_cells_small<LB_CELLS1_PER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                sizeof(int) * LB_CELLS1_NCELL);
-      raised = true;
-    }
-    hipLaunchKernelGGL((k_cells_small<LB_CELLS1_PER>), dim3(1), dim3(LB_SMALL_T), sizeof(int) * (size_t)ncell_tot, s, g, BN,
-                       e->win, e->ctrl, e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
+    lb_launch_lds<k_cells_small<LB_CELLS1_PER>>(sizeof(int) * LB_CELLS1_NCELL, dim3(1), dim3(LB_SMALL_T),
+                                                sizeof(int) * (size_t)ncell_tot, s, g, BN, e->win, e->ctrl, e->cell_of,
+                                                e->cell_start, e->cell_part, e->cpos, ncell_tot);
   } else {
     e->cells_traj_ready = false;  // (the counting sort uses cell_count: k_cells_traj's occ[] must be zeroed again after it)
     LB_HIP(hipMemsetAsync(e->cell_count, 0, sizeof(int32_t) * 2 * (size_t)ncell_tot, s));
@@ -2243,16 +1903,13 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   a.e_alloc = e->e_alloc;
   a.maxd = e->maxd;
   if (rows) {
-    a.senders = e->tmp_send;
-    a.efeat = e->tmp_feat;
-    a.efeat64 = want_efeat64 ? e->tmp_feat64 : nullptr;
+    a.out = {e->tmp_send, nullptr, e->tmp_feat, want_efeat64 ? e->tmp_feat64 : nullptr};
     lb_launch_nl<NL_ROWS>(e, small, a);
   } else {
     lb_launch_nl<NL_COUNT>(e, small, a);
   }
   // update path of a small batch: scan + finish + compaction in one launch (LB_SMALL_FUSED=0: the separate launches)
-  const bool cscan_ok = small_ok;
-  if (rows && cscan_ok && small_ok && BN <= LB_CSCAN_N && g.B <= 64) {
+  if (rows && small_ok && BN <= LB_CSCAN_N && g.B <= 64) {
     hipLaunchKernelGGL(k_nl_compact_scan, dim3((int)((BN + 15) / 16)), dim3(256), 0, s, g, BN, e->ctrl, e->deg, e->row_ptr,
                        e->maxd, e->tmp_send, e->tmp_feat, want_efeat64 ? e->tmp_feat64 : (const double*)nullptr,
                        e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : (double*)nullptr, e->e_alloc,
@@ -2319,10 +1976,7 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
                           hipMemcpyHostToDevice, s));
     a.e_alloc = e->e_alloc;
   }
-  a.senders = e->senders;
-  a.receivers = e->receivers;
-  a.efeat = e->efeat;
-  a.efeat64 = want_efeat64 ? e->efeat64 : nullptr;
+  a.out = {e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : nullptr};
   lb_launch_nl<NL_FILL>(e, small, a);
   lb_toc(e);
   LB_HIP(hipGetLastError());

@@ -1,4 +1,4 @@
-"""Every environment switch that selects another kernel family or schedule and SURVIVED the round-6 clean-up (11 left in the
+"""Every environment switch that selects another kernel family or schedule and SURVIVED the round-6 clean-up (10 left in the
 library; INTEGRATION.md section 3 lists them) must stay correct: the forward / rollout parity subset of
 tests/test_gpu_parity.py is re-run in a subprocess under each GROUP of compatible switches (the switches are read once per
 process).  LB_TRAIN_MATH / LB_TRAIN_SORT are covered by tests/test_train.py, LB_GUARD_MAX_FALLBACKS by the guard-loop tests."""
@@ -17,13 +17,12 @@ SWITCHES = [
                                                           # of every tile range-tested)
     {"LB_MSPLIT": "0"},                                   # ... k_edge16w + k_node16s on small graphs
     {"LB_MSPLIT": "1"},                                   # M-split kernels also on large graphs
-    {"LB_NL_KERNEL": "cell", "LB_GRAPH": "1"},            # workgroup-per-cell search; hipGraph replay of the step
-    {"LB_NL_KERNEL": "nlc"},                              # wave-per-cell search (round 6) also for 3^2-cell stencils
+    {"LB_GRAPH": "1"},                                    # hipGraph replay of the step
     {"LB_GUARD": "sampled"},                              # rounds 2-3 guard: first tile of every wave only
     # every launch-fusion of rounds 2-4 switched off together (each unfused path is also the default at larger sizes):
-    # multi-launch cell binning / neighbor build / degree scan + compaction, wave-per-receiver search, decoder and
-    # node features / integrator as launches of their own
-    {"LB_SMALL_FUSED": "0", "LB_NL_KERNEL": "wave"},
+    # multi-launch cell binning / neighbor build / degree scan + compaction, decoder and node features / integrator as
+    # launches of their own
+    {"LB_SMALL_FUSED": "0"},
 ]
 
 SEGNN_SWITCHES = [
