@@ -1,17 +1,22 @@
 #!/usr/bin/env python
 """bench.py - rollout throughput of the MI355X engine on BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W [--workload tgv3d] [--batch B] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload tgv3d] [--batch B] [--dump-outputs DIR] [--full]
 
 A "step" is ONE rollout step (neighbor-list rebuild -> features -> GNS-10-128 -> integrator ->
 prediction store) over one batch of B synthetic trajectories per GPU.  Inputs are resident in
 HBM before the timed region.  Workload of `value` (config.workload): TGV3D-8k x 8 trajectories whose
 neighbour count is stationary over the rollout (--vel-amp 0.03, round 6); the drifting trajectories
-rounds 1 - 5 quoted `value` on are other_configs[tag = "tgv3d_drifting"].  Rank 0 prints ONE JSON line:
+rounds 1 - 5 quoted `value` on are other_configs[tag = "tgv3d_drifting"].  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set-up, allocation pass, warm-up, the timed repeats, the MSE
+gather, --dump-outputs, and a line with metric / value / unit / higher_is_better / dtype / ms_per_step, the
+repeats, dist and config objects and mse20_mean.  --full appends everything below; each object takes runs of
+its own after the timed region (--no-f32, --no-other-configs, --no-cpu-baseline trim them, --pmc adds to them):
 
   metric/value : rollout particle-steps/s, whole job = n_gpus * B * N_particles * K / max-rank time
                  (median of --repeats timed regions of exactly K steps)
-  roofline     : the dominant kernel (processor edge MLP with the fused aggregation), timed with HIP
+  roofline     : (--full) the dominant kernel (processor edge MLP with the fused aggregation), timed with HIP
                  events bound to its dispatches inside this run; algorithmic bytes from the mean real
                  edge count of the timed steps.  `bound` "hbm" in the default f16x2 arithmetic (edge
                  latents stream once in, once out per layer), `limiter` says what actually holds the
@@ -20,9 +25,12 @@ rounds 1 - 5 quoted `value` on are other_configs[tag = "tgv3d_drifting"].  Rank 
                  (profiles/pmc_traffic.json; --pmc re-measures with two nested passes).
                  With LB_MATH=f32 the kernel is bound by the fp32 MFMA pipe and the object says so.
   roofline_aggregate : the stand-alone jraph.segment_sum kernel (HBM bound) north_star singles out
+  breakdown_ms_per_step, power : per-kernel-class HIP-event times of the same K steps; hwmon clock / power
+  f32_exact    : the same K steps in exact-fp32 MFMA arithmetic (N=1, unless --no-f32)
+  other_configs, stationary, train_step : short runs of the other BASELINE.json configs (N=1, unless --no-other-configs)
   cpu_baseline : the CPU restatement of the reference's algorithm (oracle/: torch-CPU network + NumPy
                  neighbor list, padded E_cap rows, unfused ops; kind "port", NOT JAX-CPU) timed on this
-                 host's cores on a bounded sample after all GPU work (rank 0, N=1 only)
+                 host's cores on a bounded sample after all GPU work (rank 0, N=1 only, unless --no-cpu-baseline)
 
 --dump-outputs DIR: after the timed region, rank 0 writes what the last timed repeat of the K-step rollout returned as
 DIR/<name>.npy (float64, at most DUMP_BUDGET_BYTES in all, see dump_outputs); the inputs depend on the arguments only
@@ -132,11 +140,14 @@ def main():
     ap.add_argument("--mp-steps", type=int, default=10)
     ap.add_argument("--model", default="gns", choices=["gns", "segnn"],
                     help="gns: BASELINE.json's headline config; segnn: configs[4] (SEGNN-10-64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: roofline objects and per-kernel "
+                         "breakdown, power, the fp32 sub-run, the other configs, training steps and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short sub-runs of the other BASELINE.json configs appended as `other_configs`")
+                    help="(--full) skip the short sub-runs of the other BASELINE.json configs appended as `other_configs`")
     ap.add_argument("--pmc", action="store_true",
-                    help="re-measure roofline.traffic with two nested rocprofv3 PMC passes of this command (FETCH_SIZE, WRITE_SIZE; "
+                    help="(--full) re-measure roofline.traffic with two nested rocprofv3 PMC passes of this command (FETCH_SIZE, WRITE_SIZE; "
                          "~10 s); default (round 6): the committed profiles/pmc_traffic.json value, `traffic_source` names it")
     ap.add_argument("--no-pmc", action="store_true", help="(accepted for older scripts; the nested passes are opt-in now: --pmc)")
     ap.add_argument("--shuffle", action="store_true",
@@ -146,7 +157,7 @@ def main():
                     help="the K-step timed region is repeated this many times; value / ms_per_step = the median")
     ap.add_argument("--cpu-baseline-only", default=None, metavar="WORKLOAD",
                     help="(internal) run only the CPU baseline leg of WORKLOAD and print its JSON object")
-    ap.add_argument("--no-f32", action="store_true", help="skip the exact-fp32 (LB_MATH=f32 arithmetic) sub-run")
+    ap.add_argument("--no-f32", action="store_true", help="(--full) skip the exact-fp32 (LB_MATH=f32 arithmetic) sub-run")
     ap.add_argument("--vel-amp", type=float, default=STATIONARY_VEL_AMP,
                     help="velocity scale of the synthetic trajectories: 0.03 (default, round 6) keeps the neighbour count of "
                          "the untrained rollout stationary (TGV3D ~14.4 per particle, SURVEY 8d: 13.1); 1.0 = the drifting "
@@ -156,6 +167,8 @@ def main():
                          "the positions of the last timed step, mse (world*B, K) (GNS only), pred (B, K, N, dim); float64, "
                          "<= 64 MB in all (a seeded sample of pred beyond that)")
     args = ap.parse_args()
+    if args.pmc and not args.full:
+        ap.error("--pmc re-measures the roofline objects of --full: give both")
     if args.cpu_baseline_only:   # legs one after the other in this process: they must not compete for the cores
         print(json.dumps({w: cpu_baseline_leg(w, args.mp_steps, args.vel_amp) for w in args.cpu_baseline_only.split(",")}), flush=True)
         return
@@ -231,6 +244,54 @@ def main():
                                          ("mse", np.stack([merged[i].cpu().numpy() for i in range(world * B)])),
                                          ("pred", pred.cpu().numpy())])
 
+    def headline(a):
+        """The line of a plain run; `a`: the edge accounting its edge figures come from (--full: the HIP-event pass)."""
+        return {
+            "metric": "rollout particle-steps/sec",
+            "value": world * B * N * K / dt,
+            "unit": "particle-steps/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "ms_per_step": 1e3 * dt / K,
+            "repeats": {"n": len(dts), "ms_per_step_all": [round(1e3 * x / K, 4) for x in dts],
+                        "ms_per_step_min": 1e3 * min(dts) / K, "ms_per_step_max": 1e3 * max(dts) / K,
+                        "note": "value / ms_per_step = the median repeat of the K-step timed region"},
+            "dist": dist_info,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32" if math_mode == "f32" else "f32 (GEMMs as fp16 hi/lo split products, fp32 accumulate)",
+            "data": "synthetic",
+            "config": {
+                "workload": f"{args.workload} GNS-{L}-{D} inference rollout, neighbor list rebuilt every step",
+                "n_particles": int(N), "batch_per_gpu": B, "edges_per_traj": int(round(a["mean"] / B)),
+                "edges_per_traj_first": int(a["first"] // B), "edges_per_traj_mean": round(a["mean"] / B, 1),
+                "edges_per_traj_last": int(E_last // B), "edges_per_traj_mean_timed_repeats": round(acct["mean"] / B, 1),
+                "vel_amp": args.vel_amp,
+                "edges_note": ("per-launch bytes / flops of every roofline object use the MEAN real E of the K steps the HIP-event "
+                               "timers cover (device-side sum over the neighbor-list builds, lb_edge_accounting); round 6: `value` "
+                               "is quoted on trajectories whose neighbour count is stationary (vel_amp 0.03, ~14.4 per particle; "
+                               "SURVEY 8d: 13.1) - the drifting workload of rounds 1 - 5 is other_configs[tag = tgv3d_drifting]"),
+                "math_fallbacks": int(fallbacks_timed),
+                "input_seq_length": ds.input_seq_length, "geometry_dtype": "f64", "network_math": math_mode,
+                "weights": "haiku-default init (seed 1234), decoder x0.01", "n_realloc": int(n_realloc),
+            },
+            "steps_per_s_per_traj": K / dt,
+            "mse20_mean": float(np.mean([float(v.mean()) for v in merged.values()])),
+            "mse_note": ("untrained (random-init) weights against synthetic trajectories: exercises the metric kernel "
+                         "and the RCCL gather, NOT an accuracy figure; parity of the rollout with the reference "
+                         "arithmetic (MSE within 1e-5 of the oracle) is asserted by tests/test_gpu_parity.py"),
+        }
+
+    if not args.full:
+        if rank == 0:
+            out = headline(acct)
+            out["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
+            log(f"[bench] done at {out['bench_wall_s']} s (--full for roofline, breakdown, sub-runs and CPU baseline)")
+            print(json.dumps(out), flush=True)
+        return
+
     # second pass with per-kernel-class HIP events (same K steps) for the roofline objects
     eng.timers_enable(True)
     eng.timers_reset()
@@ -279,7 +340,6 @@ def main():
                 power["steps_in_window"] = n_pw
         except Exception as exc:
             power = {"error": repr(exc)[:200]}
-    value = world * B * N * K / dt
     ms_edge, n_edge = tm["edge_mlp"]
     ms_last, n_last = tm.get("edge_mlp_last", (0.0, 0))   # last layer: no edge-latent store (its own timer class)
     if n_edge == 0 and n_last > 0:                         # (one MP layer: the no-store variant is the only launch)
@@ -345,42 +405,8 @@ def main():
     gbs_agg = agg_bytes / (us_agg * 1e-6) / 1e9
     breakdown = {k: round(v[0] / K, 4) for k, v in tm.items() if v[1] > 0 and not (fused and k == "aggregate")}
 
-    out = {
-        "metric": "rollout particle-steps/sec",
-        "value": value,
-        "unit": "particle-steps/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": 1e3 * dt / K,
-        "repeats": {"n": len(dts), "ms_per_step_all": [round(1e3 * x / K, 4) for x in dts],
-                    "ms_per_step_min": 1e3 * min(dts) / K, "ms_per_step_max": 1e3 * max(dts) / K,
-                    "note": "value / ms_per_step = the median repeat of the K-step timed region"},
-        "dist": dist_info,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32" if math_mode == "f32" else "f32 (GEMMs as fp16 hi/lo split products, fp32 accumulate)",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{args.workload} GNS-{L}-{D} inference rollout, neighbor list rebuilt every step",
-            "n_particles": int(N), "batch_per_gpu": B, "edges_per_traj": int(round(E_tot / B)),
-            "edges_per_traj_first": int(acct_tm["first"] // B), "edges_per_traj_mean": round(E_tot / B, 1),
-            "edges_per_traj_last": int(E_last // B), "edges_per_traj_mean_timed_repeats": round(acct["mean"] / B, 1),
-            "vel_amp": args.vel_amp,
-            "edges_note": ("per-launch bytes / flops of every roofline object use the MEAN real E of the K steps the HIP-event "
-                           "timers cover (device-side sum over the neighbor-list builds, lb_edge_accounting); round 6: `value` "
-                           "is quoted on trajectories whose neighbour count is stationary (vel_amp 0.03, ~14.4 per particle; "
-                           "SURVEY 8d: 13.1) - the drifting workload of rounds 1 - 5 is other_configs[tag = tgv3d_drifting]"),
-            "math_fallbacks": int(fallbacks_timed),
-            "input_seq_length": ds.input_seq_length, "geometry_dtype": "f64", "network_math": math_mode,
-            "weights": "haiku-default init (seed 1234), decoder x0.01", "n_realloc": int(n_realloc),
-        },
-        "steps_per_s_per_traj": K / dt,
-        "mse20_mean": float(np.mean([float(v.mean()) for v in merged.values()])),
-        "mse_note": ("untrained (random-init) weights against synthetic trajectories: exercises the metric kernel "
-                     "and the RCCL gather, NOT an accuracy figure; parity of the rollout with the reference "
-                     "arithmetic (MSE within 1e-5 of the oracle) is asserted by tests/test_gpu_parity.py"),
+    out = headline(acct_tm)
+    out.update({
         "roofline": roof,
         "roofline_aggregate": {
             "kernel": "k_segment_sum", "bound": "hbm", "achieved": gbs_agg, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -392,7 +418,7 @@ def main():
         },
         "breakdown_ms_per_step": breakdown,
         "power": power,
-    }
+    })
     if power and power.get("power_w_mean") and power.get("power_cap_w"):
         at_cap = power["power_w_mean"] >= 0.93 * power["power_cap_w"]
         roof["sclk_mhz"] = power["sclk_mhz_mean"]
@@ -481,7 +507,7 @@ def measure_traffic(args, timeout_s=240):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             d = tempfile.mkdtemp(prefix="lbpmc_", dir="/tmp")
             cmd = ["rocprofv3", "--kernel-trace", "--pmc", ctr, "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--no-cpu-baseline", "--no-other-configs", "--no-pmc", "--no-f32", "--repeats", "1",
+                   "--full", "--no-cpu-baseline", "--no-other-configs", "--no-pmc", "--no-f32", "--repeats", "1",
                    "--steps", str(args.steps), "--warmup", str(args.warmup),   # the SAME steps as the timed region: same mean E
                    "--workload", args.workload, "--batch", str(args.batch), "--mp-steps", str(args.mp_steps),
                    "--model", args.model, "--vel-amp", str(args.vel_amp)]
@@ -773,6 +799,24 @@ def run_segnn(args, rank, world, device):
     E_last = eng.stats()["n_edges_total"]
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, [("pred_last_step", pred[:, -1].cpu().numpy()), ("pred", pred.cpu().numpy())])
+
+    def headline(edges):
+        """The line of a plain run; `edges`: the config's edge figures (--full: those of the HIP-event pass)."""
+        return {
+            "metric": "rollout particle-steps/sec", "value": world * B * N * K / dt, "unit": "particle-steps/s",
+            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * dt / K, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.workload} SEGNN-{L}-64 (lmax 1) inference rollout, neighbor list rebuilt every step",
+                       "n_particles": int(N), "batch_per_gpu": B, **edges,
+                       "input_seq_length": isl, "geometry_dtype": "f64", "network_math": "f32",
+                       "weights": "U(-1,1) e3nn-style init (seed 1234), output x0.01", "n_realloc": int(n_realloc)},
+            "steps_per_s_per_traj": K / dt,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline({"edges_per_traj_last": int(E_last // B)})), flush=True)
+        return
     eng.timers_enable(True)
     eng.timers_reset()
     eng.edge_accounting(reset=True)
@@ -801,17 +845,9 @@ def run_segnn(args, rank, world, device):
         peak, kname = MFMA_F32_PEAK_TF, "k_sg_tp<GATE> x2 (message blocks of one layer, fp32 MFMA)"
         msg_bytes = int(round(E_tot * (2 * 512 + 512 + 512 + 512 + 16 + 64 + 8)))
     tf = flop_exec / (us_msg * 1e-6) / 1e12
-    out = {
-        "metric": "rollout particle-steps/sec", "value": world * B * N * K / dt, "unit": "particle-steps/s",
-        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * dt / K, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.workload} SEGNN-{L}-64 (lmax 1) inference rollout, neighbor list rebuilt every step",
-                   "n_particles": int(N), "batch_per_gpu": B, "edges_per_traj": int(round(E_tot / B)),
-                   "edges_per_traj_first": int(acct_tm["first"] // B), "edges_per_traj_mean": round(E_tot / B, 1),
-                   "edges_per_traj_last": int(E_last // B),
-                   "input_seq_length": isl, "geometry_dtype": "f64", "network_math": "f32",
-                   "weights": "U(-1,1) e3nn-style init (seed 1234), output x0.01", "n_realloc": int(n_realloc)},
-        "steps_per_s_per_traj": K / dt,
+    out = headline({"edges_per_traj": int(round(E_tot / B)), "edges_per_traj_first": int(acct_tm["first"] // B),
+                    "edges_per_traj_mean": round(E_tot / B, 1), "edges_per_traj_last": int(E_last // B)})
+    out.update({
         "roofline": {"kernel": kname, "bound": "mfma", "achieved": tf,
                      "peak": peak, "unit": "TFLOP/s", "frac": tf / peak,
                      "traffic": pmc_traffic("k_sg_msg", "segnn_" + args.workload, B),
@@ -821,7 +857,7 @@ def run_segnn(args, rank, world, device):
                      "gather": {"achieved": msg_bytes / (us_msg * 1e-6) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                 "note": "node rows gathered per edge (mostly L2/MALL hits) + rows written"}},
         "breakdown_ms_per_step": {k: round(v[0] / K, 4) for k, v in tm.items() if v[1] > 0},
-    }
+    })
     print(json.dumps(out), flush=True)
 
 

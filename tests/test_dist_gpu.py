@@ -91,7 +91,7 @@ def test_bench_two_ranks_on_this_box():
     """`bench.py --gpus 2` as the driver launches it (python -m torch.distributed.run, one rank per GPU).  With
     one GPU visible the two ranks share it and the metric gather / max-over-ranks travel over gloo
     (LB_DIST_BACKEND); with two GPUs it is the RCCL path itself.  Checks the contract fields of the JSON line
-    and that the aggregate counts both ranks' trajectories."""
+    and that the aggregate counts both ranks' trajectories; --full, so that the roofline pass runs on both ranks."""
     import json
     import torch
     if not torch.cuda.is_available():
@@ -102,7 +102,7 @@ def test_bench_two_ranks_on_this_box():
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-           "--warmup", "3", "--batch", "2", "--workload", "tgv2d", "--no-cpu-baseline", "--no-other-configs"]
+           "--warmup", "3", "--batch", "2", "--workload", "tgv2d", "--full", "--no-cpu-baseline", "--no-other-configs"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

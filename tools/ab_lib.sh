@@ -9,7 +9,7 @@ pick() { if [ "$1" = product ]; then cp /tmp/liblbhip_product.so $L; else cp too
 for i in 1 2; do
   for V in $A $B; do
     pick $V
-    python bench.py --no-cpu-baseline --no-other-configs --no-pmc --no-f32 --repeats 3 "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-other-configs --no-pmc --no-f32 --repeats 3 "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$V', round(d['ms_per_step'],4), round(d['value']/1e6,2), d['breakdown_ms_per_step'])"
   done

@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06p
 mkdir -p $O
-python bench.py > $O/r06_bench_tgv3d_b8.json 2> $O/bench_default.err
-B="python bench.py --no-cpu-baseline --no-other-configs --no-f32 --repeats 1 --steps 20 --warmup 20"
+python bench.py --full > $O/r06_bench_tgv3d_b8.json 2> $O/bench_default.err
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-f32 --repeats 1 --steps 20 --warmup 20"
 rm -rf /tmp/p_kt /tmp/p_f /tmp/p_w /tmp/p_sq /tmp/p_sq2
 rocprofv3 --kernel-trace --stats -d /tmp/p_kt -- $B > $O/kt.json 2> $O/kt.log
 python tools/rocpd_summary.py $(find /tmp/p_kt -name "*.db" | head -1) > $O/r06_kernel_trace_stats.txt 2>&1

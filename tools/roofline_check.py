@@ -3,7 +3,7 @@
 
     python tools/roofline_check.py <bench line of the profiled command (json)> <kernel trace summary> <pmc_traffic.json> <pmc sq summary>
 
-Inputs: the JSON line the profiled `bench.py --steps K --warmup W` printed (mean real E of the timed steps:
+Inputs: the JSON line the profiled `bench.py --full --steps K --warmup W` printed (mean real E of the timed steps:
 config.edges_per_traj_mean, lb_edge_accounting), tools/rocpd_summary.py's table of the same run (avg_real_us of the edge
 kernel), the FETCH_SIZE / WRITE_SIZE table and the SQ_INSTS_* table.  Checks:
   1. algorithmic bytes (E_mean * 1032 + B*N * 1024) / rocprofv3's average launch time  vs  the bench line's roofline.frac
