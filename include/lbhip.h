@@ -277,6 +277,46 @@ void lb_segnn_destroy(lb_segnn* segnn);
 /* SEGNN.__call__ -> {"acc": (B,N,dim) fp32} (segnn.py:595-610) on the current window + list. */
 int lb_segnn_forward(lb_engine* eng, lb_segnn* segnn, float* acc_out_dev);
 
+/* ---- EGNN (models/egnn.py:209-400) --------------------------------------------------------------
+ * Construction by runner.py:246-268: hidden_size = latent_dim, dt = metadata dt * write_every, n_vels = isl - 1,
+ * residual = 1, homogeneous_particles left at its default 1, attention / normalize / tanh 0, act_fn silu.  Runs in fp32
+ * throughout (runner.py:71-72), positions included; sums in a fixed order (bit-reproducible). */
+typedef struct lb_egnn lb_egnn;
+typedef struct lb_egnn_desc {
+  int32_t hidden;        /* hidden_size: a multiple of 16, <= 128 */
+  int32_t num_mp_steps;  /* >= 1 */
+  int32_t n_vels;        /* input_seq_length - 1 (1 .. 9) */
+  int32_t homogeneous;   /* homogeneous_particles: 1 = no one-hot of the 9 particle types in the node input */
+  int32_t residual;      /* h' = h + node_mlp(..) */
+  int32_t normalize;     /* coord_diff /= sqrt(radial) + 1e-8 */
+  int32_t tanh_pos;      /* tanh on the position net's output */
+} lb_egnn_desc;
+
+/* EGNN(...) + params.  weights_host, with H = hidden, I = n_vels (+ 9 when !homogeneous), A = 1 when the engine has an
+ * external force (node attribute |force|) else 0; every matrix (fan_in, fan_out) row-major:
+ *   scalar_emb w (I, H), b (H)
+ *   per layer n (module names egnn/~/layer_{n}/~/...):
+ *     mlp_xav/~/linear_0   w (2H + 2, H), b (H)   rows [h_sender | h_receiver | radial | rel_dist]
+ *     mlp_xav/~/linear_1   w (H, H), b (H)
+ *     mlp_xav_1/~/linear_0 w (2H + A, H), b (H)   rows [h | aggregated messages | |force|]
+ *     mlp_xav_1/~/linear_1 w (H, H), b (H)
+ *     linear_xav   w (H, H), b (H);  linear_xav_1 w (H, 1)     position net
+ *     linear_xav_2 w (H, H), b (H);  linear_xav_3 w (H, 1)     velocity net
+ * n_floats must match exactly. */
+int lb_egnn_create(lb_engine* eng, const lb_egnn_desc* desc, const float* weights_host, int64_t n_floats,
+                   lb_egnn** out);
+void lb_egnn_destroy(lb_egnn* egnn);
+/* EGNN.__call__ -> {"pos"} on the current window + list: (B,N,dim) fp64 holding the fp32 positions (fp64 so that
+ * rollout.py's window keeps its dtype, as the reference's promotion does).  LB_ERR_STATE if an edge of the list has no
+ * transposed edge (the position update sums over senders through the transpose).  Host-synchronous. */
+int lb_egnn_forward(lb_engine* eng, lb_egnn* egnn, double* pos_out_dev);
+/* Debug/parity taps: h after the embedding and after every layer ((L+1), B*N, hidden) fp32 and the positions at the same
+ * points ((L+1), B*N, dim) fp32; NULL = off. */
+int lb_egnn_set_tap(lb_egnn* egnn, float* h_out_dev, float* pos_out_dev);
+/* lb_rollout for an EGNN: the whole step loop on the device (the predicted positions are the new frame). */
+int lb_egnn_rollout(lb_engine* eng, lb_egnn* egnn, const double* traj_dev, int32_t T, int32_t n_steps,
+                    double* pred_out_dev, int32_t* n_realloc_out);
+
 /* Arithmetic of the GNS GEMMs.  Default (LB_MATH unset) = mode 1: every fp32 operand is carried as an fp16
  * hi/lo pair on the fp16 MFMA (fp32-class accuracy, ~5x fewer matrix-pipe cycles than the fp32 MFMA) WITH a
  * range guard: operands >= 2^15 (sampled), operand ROWS whose values all sit below 2^-11 (tested on every tile of the

@@ -56,6 +56,15 @@ class SegnnDesc(C.Structure):
             self.lmax_attributes = 1
 
 
+class EgnnDesc(C.Structure):
+    """lb_egnn_desc (include/lbhip.h)."""
+
+    _fields_ = [
+        ("hidden", C.c_int32), ("num_mp_steps", C.c_int32), ("n_vels", C.c_int32), ("homogeneous", C.c_int32),
+        ("residual", C.c_int32), ("normalize", C.c_int32), ("tanh_pos", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes).  Every symbol include/lbhip.h declares must be listed here;
 # tests/test_abi.py checks the two against each other.
 _P = C.c_void_p
@@ -119,6 +128,11 @@ _SIGS = {
     "lb_segnn_row_floats": (C.c_int32, [_P]),
     "lb_segnn_set_tap": (C.c_int, [_P, _P]),
     "lb_segnn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "lb_egnn_create": (C.c_int, [_P, C.POINTER(EgnnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "lb_egnn_destroy": (None, [_P]),
+    "lb_egnn_forward": (C.c_int, [_P, _P, _P]),
+    "lb_egnn_set_tap": (C.c_int, [_P, _P, _P]),
+    "lb_egnn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CaseDesc, GnsDesc, LbHipError, SegnnDesc, check, ptr
+from ._lib import CaseDesc, EgnnDesc, GnsDesc, LbHipError, SegnnDesc, check, ptr
 
 
 def _d3(v, fill=0.0):
@@ -293,6 +293,21 @@ class RolloutEngine:
         check(self.lib.lb_segnn_forward(self._h, segnn._h, ptr(out)), "lb_segnn_forward")
         return out
 
+    def egnn_create(self, desc: EgnnDesc, blob: np.ndarray) -> "EgnnHandle":
+        """One EGNN on this engine (csrc/lb_egnn.hip); blob in EGNN.flatten order (include/lbhip.h: lb_egnn_create)."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        h = C.c_void_p()
+        check(self.lib.lb_egnn_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
+                                      C.c_int64(blob.size), C.byref(h)), "lb_egnn_create")
+        return EgnnHandle(self, h, desc)
+
+    def egnn_forward(self, egnn: "EgnnHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """EGNN positions (B, N, dim) fp64 holding the fp32 values of the network."""
+        if out is None:
+            out = torch.empty((self.B, self.N, self.dim), dtype=torch.float64, device=self.device)
+        check(self.lib.lb_egnn_forward(self._h, egnn._h, ptr(out)), "lb_egnn_forward")
+        return out
+
     def math_mode(self, set_mode: int = -1) -> Tuple[int, int]:
         """(mode, guard flags): 0 exact fp32 MFMA, 1 guarded f16x2 (default), 2 unguarded f16x2; flags: 1
         large operand, 2 tiny operand tile, 4 non-finite acceleration (include/lbhip.h: lb_math_mode)."""
@@ -332,12 +347,16 @@ class RolloutEngine:
         return out
 
     def rollout(self, model, traj: torch.Tensor, n_steps: int) -> Tuple[torch.Tensor, int]:
-        """model: a GnsHandle (lb_rollout) or a SegnnHandle (lb_segnn_rollout)."""
+        """model: a GnsHandle (lb_rollout), a SegnnHandle (lb_segnn_rollout) or an EgnnHandle (lb_egnn_rollout)."""
         traj = self.prepare_traj(traj)
         pred = torch.zeros((self.B, n_steps, self.N, self.dim), dtype=torch.float64, device=self.device)
         nre = C.c_int32(0)
-        fn, name = ((self.lib.lb_segnn_rollout, "lb_segnn_rollout") if isinstance(model, SegnnHandle)
-                    else (self.lib.lb_rollout, "lb_rollout"))
+        if isinstance(model, SegnnHandle):
+            fn, name = self.lib.lb_segnn_rollout, "lb_segnn_rollout"
+        elif isinstance(model, EgnnHandle):
+            fn, name = self.lib.lb_egnn_rollout, "lb_egnn_rollout"
+        else:
+            fn, name = self.lib.lb_rollout, "lb_rollout"
         check(fn(self._h, model._h, ptr(traj), traj.shape[2], n_steps, ptr(pred), C.byref(nre)), name)
         self.version += 1
         st = self.stats()
@@ -534,6 +553,38 @@ class SegnnHandle:
             if self.engine._h:
                 torch.cuda.synchronize(self.engine.device)
             self.engine.lib.lb_segnn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EgnnHandle:
+    def __init__(self, engine: RolloutEngine, h, desc: EgnnDesc):
+        self.engine, self._h, self.desc = engine, h, desc
+        self._tap = None
+
+    def set_tap(self, on: bool = True) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """Per-layer taps: (h (L+1, B*N, hidden), positions (L+1, B*N, dim)) fp32, filled by every forward."""
+        e = self.engine
+        if on:
+            L = self.desc.num_mp_steps
+            self._tap = (torch.zeros((L + 1, e.B * e.N, self.desc.hidden), dtype=torch.float32, device=e.device),
+                         torch.zeros((L + 1, e.B * e.N, e.dim), dtype=torch.float32, device=e.device))
+            check(e.lib.lb_egnn_set_tap(self._h, ptr(self._tap[0]), ptr(self._tap[1])), "lb_egnn_set_tap")
+        else:
+            self._tap = None
+            check(e.lib.lb_egnn_set_tap(self._h, None, None), "lb_egnn_set_tap")
+        return self._tap
+
+    def close(self):
+        if self._h:
+            if self.engine._h:
+                torch.cuda.synchronize(self.engine.device)
+            self.engine.lib.lb_egnn_destroy(self._h)
             self._h = None
 
     def __del__(self):

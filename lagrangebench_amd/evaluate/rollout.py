@@ -26,6 +26,7 @@ import torch
 from ..case_setup.features import FeatureDict, NeighborList
 from .._lib import LB_FORCE_BUFFER
 from ..defaults import defaults, merge
+from ..models.egnn import EGNN
 from ..models.gns import GNS
 from ..models.segnn import SEGNN
 from ..utils import broadcast_from_batch, broadcast_to_batch, get_kinematic_mask
@@ -53,7 +54,7 @@ def _gns_of(model_apply) -> Optional[GNS]:
     while isinstance(fn, partial):
         fn = fn.func
     owner = getattr(fn, "__self__", None)
-    return owner if isinstance(owner, (GNS, SEGNN)) else None
+    return owner if isinstance(owner, (GNS, SEGNN, EGNN)) else None
 
 
 def _eval_batched_rollout(forward_eval_vmap: Callable, preprocess_eval_vmap: Callable, case, params, state,
@@ -235,6 +236,9 @@ def infer(model, case, data_test, params=None, state=None, load_ckp: Optional[st
         if isinstance(model, SEGNN) and "embedding_nodes" not in params:
             from ..utils import segnn_params_from_haiku
             params = segnn_params_from_haiku(params, model)
+        if isinstance(model, EGNN) and "scalar_emb" not in params:
+            from ..utils import egnn_params_from_haiku
+            params = egnn_params_from_haiku(params, model)
     if state is None:
         state = {}
     loader_test = _Loader(data_test, cfg.batch_size)

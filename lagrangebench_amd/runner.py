@@ -75,7 +75,15 @@ def setup_model(cfg, metadata: Dict, homogeneous_particles: bool = False, has_ex
             velocity_aggregate=cfg.model.velocity_aggregate, homogeneous_particles=homogeneous_particles,
             blocks_per_step=cfg.model.num_mlp_layers, norm=cfg.model.segnn_norm)
         return model, models.SEGNN
-    raise NotImplementedError(f"model {cfg.model.name!r}: 'gns' and 'segnn' are built (egnn/painn/linear are not)")
+    if name == "egnn":
+        # runner.py:246-268: homogeneous_particles is NOT passed (the model's default True holds for every dataset);
+        # attention / normalize / tanh keep their defaults; displacement / shift: the case's space (models/egnn.py)
+        model = models.EGNN(
+            hidden_size=cfg.model.latent_dim, output_size=1, dt=metadata["dt"] * metadata["write_every"],
+            displacement_fn=None, shift_fn=None, normalization_stats=normalization_stats,
+            num_mp_steps=cfg.model.num_mp_steps, n_vels=cfg.model.input_seq_length - 1, residual=True)
+        return model, models.EGNN
+    raise NotImplementedError(f"model {cfg.model.name!r}: 'gns', 'segnn' and 'egnn' are built (painn/linear are not built)")
 
 
 def train_or_infer(cfg):

@@ -467,3 +467,47 @@ def segnn_params_to_haiku(params, model, module: str = "segnn"):
         leaves[f"w[1,{1 if ms else 0}] {K}x1o,{mv}x1o"] = np.asarray(blk["wv"], np.float32)[inv]
         out[f"{module}/{hk_name}/linear"] = leaves
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# EGNN checkpoints (models/egnn.py:24-206, 209-400 of the reference).  Haiku module names follow from module creation
+# order: egnn/~/scalar_emb, then per layer egnn/~/layer_{n}/~/ mlp_xav (edge MLP, linear_0 / linear_1), mlp_xav_1 (node
+# MLP), linear_xav / linear_xav_1 (position net), linear_xav_2 / linear_xav_3 (velocity net).  Derived from Haiku's
+# naming rules, not checked against a real checkpoint (Haiku cannot be imported here).
+_EGNN_MODULES = (("edge_0", "mlp_xav/~/linear_0"), ("edge_1", "mlp_xav/~/linear_1"),
+                 ("node_0", "mlp_xav_1/~/linear_0"), ("node_1", "mlp_xav_1/~/linear_1"),
+                 ("pos_0", "linear_xav"), ("pos_1", "linear_xav_1"), ("vel_0", "linear_xav_2"), ("vel_1", "linear_xav_3"))
+
+
+def egnn_params_to_haiku(params, model=None, module: str = "egnn"):
+    """This package's EGNN parameter tree (models/egnn.py) -> Haiku module names."""
+    out = {f"{module}/~/scalar_emb": {k: np.asarray(v, np.float32) for k, v in params["scalar_emb"].items()}}
+    layers = sorted({int(k.split("/")[0][len("layer_"):]) for k in params if k.startswith("layer_")})
+    for n in layers:
+        for ours, theirs in _EGNN_MODULES:
+            out[f"{module}/~/layer_{n}/~/{theirs}"] = {k: np.asarray(v, np.float32)
+                                                        for k, v in params[f"layer_{n}/{ours}"].items()}
+    return out
+
+
+def egnn_params_from_haiku(hk_params, model=None):
+    """Haiku EGNN parameter dict -> this package's layout (inverse of egnn_params_to_haiku).  The top-level module name
+    is whatever precedes "/~/scalar_emb"."""
+    emb = [k for k in hk_params if k.endswith("/~/scalar_emb") or k == "scalar_emb"]
+    if len(emb) != 1:
+        raise ValueError(f"EGNN checkpoint: expected one scalar_emb module, found {emb}")
+    prefix = emb[0][: -len("scalar_emb")]
+    out = {"scalar_emb": {k: np.asarray(v, np.float32) for k, v in hk_params[emb[0]].items()}}
+    n = 0
+    while f"{prefix}layer_{n}/~/mlp_xav/~/linear_0" in hk_params:
+        for ours, theirs in _EGNN_MODULES:
+            key = f"{prefix}layer_{n}/~/{theirs}"
+            if key not in hk_params:
+                raise ValueError(f"EGNN checkpoint: module {key!r} missing")
+            out[f"layer_{n}/{ours}"] = {k: np.asarray(v, np.float32) for k, v in hk_params[key].items()}
+        n += 1
+    if n == 0:
+        raise ValueError("EGNN checkpoint: no layer_0 modules")
+    if model is not None and n != model._num_mp_steps:
+        raise ValueError(f"EGNN checkpoint has {n} layers, the model {model._num_mp_steps}")
+    return out
