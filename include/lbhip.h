@@ -317,6 +317,52 @@ int lb_egnn_set_tap(lb_egnn* egnn, float* h_out_dev, float* pos_out_dev);
 int lb_egnn_rollout(lb_engine* eng, lb_egnn* egnn, const double* traj_dev, int32_t T, int32_t n_steps,
                     double* pred_out_dev, int32_t* n_realloc_out);
 
+/* ---- PaiNN (models/painn.py:372-510) -----------------------------------------------------------
+ * Construction by runner.py:270-284: hidden_size = latent_dim, output_size 1, n_vels = isl - 1, gaussian_rbf(20,
+ * 1.5 r_c, trainable) and cosine_cutoff(1.5 r_c) with the PHYSICAL radius (the network's norms are in units of r_c),
+ * homogeneous_particles left at its default 1, activation silu.  The output is the normalised acceleration, integrated
+ * like GNS's.  Runs in fp32 throughout (runner.py:71-72); sums in a fixed order (bit-reproducible).  The case must
+ * carry the velocity magnitudes (magnitude_features), the model's scalars. */
+typedef struct lb_painn lb_painn;
+typedef struct lb_painn_desc {
+  int32_t hidden;               /* hidden_size: a multiple of 16, <= 128 */
+  int32_t num_mp_steps;         /* >= 1 */
+  int32_t n_vels;               /* input_seq_length - 1 (1 .. 9) */
+  int32_t homogeneous;          /* homogeneous_particles: 1 = no one-hot of the 9 particle types in the scalars */
+  int32_t shared_filters;       /* one 3H filter block for all layers */
+  int32_t shared_interactions;  /* one set of layer weights (layer_0) for all layers */
+  int32_t n_rbf;                /* Gaussian radial basis functions (1 .. 64) */
+  int32_t has_cutoff;           /* 1: cosine_cutoff(cutoff); 0: cutoff_fn None (the filters are scaled by the norm) */
+  float cutoff;                 /* cosine cutoff radius in the units of rel_disp's norm */
+} lb_painn_desc;
+
+/* PaiNN(...) + params.  weights_host, with H = hidden, Hh = H / 2, R = n_rbf, S = n_vels (+ 9 when !homogeneous),
+ * C = n_vels (+ 1 with an external force) (+ 2 with boundary features) vector channels in the order [v_0 .. v_{K-1} |
+ * force | bound_lo | bound_hi], F = 1 if shared_filters else num_mp_steps, P = 1 if shared_interactions else
+ * num_mp_steps; every matrix (fan_in, fan_out) row-major (Haiku names painn/~/...):
+ *   scalar_embedding w (S, H), b (H);  vector_embedding w (C, H)
+ *   filter_net w (R, F 3H), b (F 3H)                    layer n takes columns [3H n, 3H (n + 1)) as [ds | dv1 | dv2]
+ *   per parameter set p < P (layer_{p}/~/...):
+ *     linear_xav   w (H, H), b (H);  linear_xav_1 w (H, 3H), b (3H)     interaction block
+ *     linear_xav_2 w (2H, H), b (H); linear_xav_3 w (H, 3H), b (3H)     mixing block, rows [s | |v_r|]
+ *     vector_mixing_block w (H, 2H)                                      columns [v_l | v_r]
+ *   readout_block_0/~/:   vector_mix_net w (H, H); linear_xav w (H + Hh, H), b (H); linear_xav_1 w (H, H), b (H)
+ *   readout_block_out/~/: vector_mix_net w (Hh, 2); linear_xav w (Hh + 1, Hh), b (Hh); linear_xav_1 w (Hh, 2), b (2)
+ *   ~/widths (R), ~/offset (R)                          the radial basis (parameters, or state when not trainable)
+ * n_floats must match exactly. */
+int lb_painn_create(lb_engine* eng, const lb_painn_desc* desc, const float* weights_host, int64_t n_floats,
+                    lb_painn** out);
+void lb_painn_destroy(lb_painn* painn);
+/* PaiNN.__call__ -> {"acc": (B,N,dim) fp32} on the current window + list.  LB_ERR_STATE if an edge of the list has no
+ * transposed edge (the messages are summed over senders through the transpose).  Host-synchronous. */
+int lb_painn_forward(lb_engine* eng, lb_painn* painn, float* acc_out_dev);
+/* Debug/parity taps: s after the embedding and after every layer ((L+1), B*N, hidden) fp32 and v at the same points
+ * ((L+1), B*N, dim, hidden) fp32; NULL = off. */
+int lb_painn_set_tap(lb_painn* painn, float* s_out_dev, float* v_out_dev);
+/* lb_rollout for a PaiNN: the whole step loop on the device, the acceleration integrated as GNS's. */
+int lb_painn_rollout(lb_engine* eng, lb_painn* painn, const double* traj_dev, int32_t T, int32_t n_steps,
+                     double* pred_out_dev, int32_t* n_realloc_out);
+
 /* Arithmetic of the GNS GEMMs.  Default (LB_MATH unset) = mode 1: every fp32 operand is carried as an fp16
  * hi/lo pair on the fp16 MFMA (fp32-class accuracy, ~5x fewer matrix-pipe cycles than the fp32 MFMA) WITH a
  * range guard: operands >= 2^15 (sampled), operand ROWS whose values all sit below 2^-11 (tested on every tile of the

@@ -65,6 +65,16 @@ class EgnnDesc(C.Structure):
     ]
 
 
+class PainnDesc(C.Structure):
+    """lb_painn_desc (include/lbhip.h)."""
+
+    _fields_ = [
+        ("hidden", C.c_int32), ("num_mp_steps", C.c_int32), ("n_vels", C.c_int32), ("homogeneous", C.c_int32),
+        ("shared_filters", C.c_int32), ("shared_interactions", C.c_int32), ("n_rbf", C.c_int32),
+        ("has_cutoff", C.c_int32), ("cutoff", C.c_float),
+    ]
+
+
 # name -> (restype, argtypes).  Every symbol include/lbhip.h declares must be listed here;
 # tests/test_abi.py checks the two against each other.
 _P = C.c_void_p
@@ -133,6 +143,11 @@ _SIGS = {
     "lb_egnn_forward": (C.c_int, [_P, _P, _P]),
     "lb_egnn_set_tap": (C.c_int, [_P, _P, _P]),
     "lb_egnn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "lb_painn_create": (C.c_int, [_P, C.POINTER(PainnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "lb_painn_destroy": (None, [_P]),
+    "lb_painn_forward": (C.c_int, [_P, _P, _P]),
+    "lb_painn_set_tap": (C.c_int, [_P, _P, _P]),
+    "lb_painn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -199,6 +199,15 @@ __global__ void k_eg_rev(const lb_ctrl* __restrict__ ctrl, int64_t cap, const in
   rev[e] = found;
 }
 
+int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err) {
+  const int64_t ecap = (int64_t)e->e_cap * e->g.B;
+  const unsigned nb = (unsigned)((ecap + 255) / 256);
+  hipLaunchKernelGGL(k_eg_rev, dim3(nb ? nb : 1), dim3(256), 0, e->stream, e->ctrl, ecap, e->row_ptr, e->senders,
+                     e->receivers, rev, err);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+
 // -------------------------------------------------------------------- node projection
 // P[i] = [h_i W0[0:H] | h_i W0[H:2H]]: the sender and receiver blocks of the first edge Linear, once per node.
 __global__ void __launch_bounds__(EG_THREADS)
@@ -650,7 +659,7 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
   LB_TRY(eg_ensure_edges(m));
   const int64_t ecap = (int64_t)e->e_cap * e->g.B;
   const unsigned nb_t = (unsigned)((BN + EG_TN - 1) / EG_TN), nb_n = (unsigned)((BN + 255) / 256);
-  const unsigned nb_e = (unsigned)((ecap + 255) / 256), nb_te = (unsigned)((ecap + EG_TE - 1) / EG_TE);
+  const unsigned nb_te = (unsigned)((ecap + EG_TE - 1) / EG_TE);
   auto tap = [&](int slot) -> int {
     if (m->tap_h)
       LB_HIP(hipMemcpyAsync(m->tap_h + (size_t)slot * BN * H, m->h, sizeof(float) * BN * H, hipMemcpyDeviceToDevice, s));
@@ -661,8 +670,7 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
   LB_TRY(lbk_node_features_raw(e, m->xnode, EG_KPAD));
   hipLaunchKernelGGL(k_eg_prologue, dim3(nb_t), dim3(EG_THREADS), 0, s, e->g, BN, e->ctrl, e->win, m->xnode, e->ptype, H,
                      m->desc.n_vels, m->desc.homogeneous, m->n_attr, m->w_emb, m->b_emb, m->h, m->x32, m->vel, m->nattr);
-  hipLaunchKernelGGL(k_eg_rev, dim3(nb_e ? nb_e : 1), dim3(256), 0, s, e->ctrl, ecap, e->row_ptr, e->senders, e->receivers,
-                     m->rev, m->err);
+  LB_TRY(lbk_edge_rev(e, m->rev, m->err));
   lb_toc(e);
   LB_HIP(hipGetLastError());
   LB_TRY(tap(0));

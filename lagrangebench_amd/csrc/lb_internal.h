@@ -394,6 +394,10 @@ int lbk_sinkhorn_pot(lb_engine* e, const double* pred, int pred_T, const double*
 
 int lbk_node_features_raw(lb_engine* e, float* xnode, int kpad);
 
+// lb_egnn.hip: rev[e] = the slot of edge e's transpose for the first n_edges_total slots of the list (binary search in
+// the sender-sorted row); every edge without one adds 1 to *err and gets rev[e] = e.  rev: [e_cap * B] slots.
+int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err);
+
 // lb_api.hip: the device-resident step loop shared by the models
 int lb_rollout_generic(lb_engine* e, int (*forward)(lb_engine*, void*), void* model,
                        const double* traj_dev, int32_t T, int32_t n_steps, double* pred_out_dev,

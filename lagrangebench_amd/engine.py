@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CaseDesc, EgnnDesc, GnsDesc, LbHipError, SegnnDesc, check, ptr
+from ._lib import CaseDesc, EgnnDesc, GnsDesc, LbHipError, PainnDesc, SegnnDesc, check, ptr
 
 
 def _d3(v, fill=0.0):
@@ -308,6 +308,21 @@ class RolloutEngine:
         check(self.lib.lb_egnn_forward(self._h, egnn._h, ptr(out)), "lb_egnn_forward")
         return out
 
+    def painn_create(self, desc: PainnDesc, blob: np.ndarray) -> "PainnHandle":
+        """One PaiNN on this engine (csrc/lb_painn.hip); blob in PaiNN.flatten order (include/lbhip.h: lb_painn_create)."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        h = C.c_void_p()
+        check(self.lib.lb_painn_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
+                                       C.c_int64(blob.size), C.byref(h)), "lb_painn_create")
+        return PainnHandle(self, h, desc)
+
+    def painn_forward(self, painn: "PainnHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """PaiNN normalised accelerations (B, N, dim) fp32."""
+        if out is None:
+            out = torch.empty((self.B, self.N, self.dim), dtype=torch.float32, device=self.device)
+        check(self.lib.lb_painn_forward(self._h, painn._h, ptr(out)), "lb_painn_forward")
+        return out
+
     def math_mode(self, set_mode: int = -1) -> Tuple[int, int]:
         """(mode, guard flags): 0 exact fp32 MFMA, 1 guarded f16x2 (default), 2 unguarded f16x2; flags: 1
         large operand, 2 tiny operand tile, 4 non-finite acceleration (include/lbhip.h: lb_math_mode)."""
@@ -347,7 +362,8 @@ class RolloutEngine:
         return out
 
     def rollout(self, model, traj: torch.Tensor, n_steps: int) -> Tuple[torch.Tensor, int]:
-        """model: a GnsHandle (lb_rollout), a SegnnHandle (lb_segnn_rollout) or an EgnnHandle (lb_egnn_rollout)."""
+        """model: a GnsHandle (lb_rollout), a SegnnHandle (lb_segnn_rollout), an EgnnHandle (lb_egnn_rollout) or a
+        PainnHandle (lb_painn_rollout)."""
         traj = self.prepare_traj(traj)
         pred = torch.zeros((self.B, n_steps, self.N, self.dim), dtype=torch.float64, device=self.device)
         nre = C.c_int32(0)
@@ -355,6 +371,8 @@ class RolloutEngine:
             fn, name = self.lib.lb_segnn_rollout, "lb_segnn_rollout"
         elif isinstance(model, EgnnHandle):
             fn, name = self.lib.lb_egnn_rollout, "lb_egnn_rollout"
+        elif isinstance(model, PainnHandle):
+            fn, name = self.lib.lb_painn_rollout, "lb_painn_rollout"
         else:
             fn, name = self.lib.lb_rollout, "lb_rollout"
         check(fn(self._h, model._h, ptr(traj), traj.shape[2], n_steps, ptr(pred), C.byref(nre)), name)
@@ -585,6 +603,38 @@ class EgnnHandle:
             if self.engine._h:
                 torch.cuda.synchronize(self.engine.device)
             self.engine.lib.lb_egnn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PainnHandle:
+    def __init__(self, engine: RolloutEngine, h, desc: PainnDesc):
+        self.engine, self._h, self.desc = engine, h, desc
+        self._tap = None
+
+    def set_tap(self, on: bool = True) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
+        """Per-layer taps: (s (L+1, B*N, hidden), v (L+1, B*N, dim, hidden)) fp32, filled by every forward."""
+        e = self.engine
+        if on:
+            L, H = self.desc.num_mp_steps, self.desc.hidden
+            self._tap = (torch.zeros((L + 1, e.B * e.N, H), dtype=torch.float32, device=e.device),
+                         torch.zeros((L + 1, e.B * e.N, e.dim, H), dtype=torch.float32, device=e.device))
+            check(e.lib.lb_painn_set_tap(self._h, ptr(self._tap[0]), ptr(self._tap[1])), "lb_painn_set_tap")
+        else:
+            self._tap = None
+            check(e.lib.lb_painn_set_tap(self._h, None, None), "lb_painn_set_tap")
+        return self._tap
+
+    def close(self):
+        if self._h:
+            if self.engine._h:
+                torch.cuda.synchronize(self.engine.device)
+            self.engine.lib.lb_painn_destroy(self._h)
             self._h = None
 
     def __del__(self):

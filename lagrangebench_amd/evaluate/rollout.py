@@ -28,6 +28,7 @@ from .._lib import LB_FORCE_BUFFER
 from ..defaults import defaults, merge
 from ..models.egnn import EGNN
 from ..models.gns import GNS
+from ..models.painn import PaiNN
 from ..models.segnn import SEGNN
 from ..utils import broadcast_from_batch, broadcast_to_batch, get_kinematic_mask
 from .metrics import MetricsComputer, MetricsDict
@@ -54,7 +55,7 @@ def _gns_of(model_apply) -> Optional[GNS]:
     while isinstance(fn, partial):
         fn = fn.func
     owner = getattr(fn, "__self__", None)
-    return owner if isinstance(owner, (GNS, SEGNN, EGNN)) else None
+    return owner if isinstance(owner, (GNS, SEGNN, EGNN, PaiNN)) else None
 
 
 def _eval_batched_rollout(forward_eval_vmap: Callable, preprocess_eval_vmap: Callable, case, params, state,
@@ -88,7 +89,8 @@ def _eval_batched_rollout(forward_eval_vmap: Callable, preprocess_eval_vmap: Cal
         eng.set_particle_type(ptype)
         if neighbors is not None and (eng.e_cap, eng.cell_capacity) != (neighbors.max_occupancy, neighbors.cell_capacity):
             eng.nl_set_capacity(neighbors.cell_capacity, neighbors.max_occupancy)
-        predictions_batch, n_realloc = eng.rollout(gns.handle(eng, params), traj, traj_len)
+        h = gns.handle(eng, params, state) if isinstance(gns, PaiNN) else gns.handle(eng, params)
+        predictions_batch, n_realloc = eng.rollout(h, traj, traj_len)
         if n_realloc:
             print(f"(eval) Reallocated the neighbors list {n_realloc}x; capacity now (2, {eng.e_cap})")
         eng.load_window(traj, t0=0, step=0)  # leave a defined state behind for the returned list
@@ -239,6 +241,9 @@ def infer(model, case, data_test, params=None, state=None, load_ckp: Optional[st
         if isinstance(model, EGNN) and "scalar_emb" not in params:
             from ..utils import egnn_params_from_haiku
             params = egnn_params_from_haiku(params, model)
+        if isinstance(model, PaiNN) and "scalar_embedding" not in params:
+            from ..utils import painn_params_from_haiku
+            params = painn_params_from_haiku(params, model)
     if state is None:
         state = {}
     loader_test = _Loader(data_test, cfg.batch_size)

@@ -511,3 +511,71 @@ def egnn_params_from_haiku(hk_params, model=None):
     if model is not None and n != model._num_mp_steps:
         raise ValueError(f"EGNN checkpoint has {n} layers, the model {model._num_mp_steps}")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PaiNN checkpoints (models/painn.py of the reference).  Haiku module names follow from module creation order:
+# painn/~/scalar_embedding, vector_embedding, filter_net (PaiNN.__init__); per layer painn/~/layer_{n}/~/ linear_xav,
+# linear_xav_1 (interaction block), linear_xav_2, linear_xav_3 (mixing block), vector_mixing_block - the Linears are made
+# in the layer's __init__ before their hk.Sequential, so they belong to the layer's scope; the readout blocks are made
+# inside PaiNN.__call__, hence painn/readout_block_{0,out}/~/ vector_mix_net, linear_xav, linear_xav_1 (no "~" before
+# the block); the trainable radial basis is ~/widths, ~/offset (gaussian_rbf runs outside any module).  The state
+# (non-trainable radial basis, cutoff) already has Haiku's names.  Derived from Haiku's naming rules, not checked
+# against a real checkpoint (Haiku cannot be imported here).
+_PAINN_TOP = (("scalar_embedding", "scalar_embedding"), ("vector_embedding", "vector_embedding"),
+              ("filter_net", "filter_net"))
+_PAINN_LAYER = (("interaction_0", "linear_xav"), ("interaction_1", "linear_xav_1"), ("mixing_0", "linear_xav_2"),
+                ("mixing_1", "linear_xav_3"), ("vector_mixing", "vector_mixing_block"))
+_PAINN_READOUT = (("vector_mix", "vector_mix_net"), ("gate_0", "linear_xav"), ("gate_1", "linear_xav_1"))
+
+
+def _f32_leaves(d):
+    return {k: np.asarray(v, np.float32) for k, v in d.items()}
+
+
+def painn_params_to_haiku(params, model=None, module: str = "painn"):
+    """This package's PaiNN parameter tree (models/painn.py) -> Haiku module names."""
+    out = {f"{module}/~/{theirs}": _f32_leaves(params[ours]) for ours, theirs in _PAINN_TOP}
+    layers = sorted({int(k.split("/")[0][len("layer_"):]) for k in params if k.startswith("layer_")})
+    for n in layers:
+        for ours, theirs in _PAINN_LAYER:
+            out[f"{module}/~/layer_{n}/~/{theirs}"] = _f32_leaves(params[f"layer_{n}/{ours}"])
+    for blk in ("0", "out"):
+        for ours, theirs in _PAINN_READOUT:
+            out[f"{module}/readout_block_{blk}/~/{theirs}"] = _f32_leaves(params[f"readout_{blk}/{ours}"])
+    if "~" in params:
+        out["~"] = _f32_leaves(params["~"])
+    return out
+
+
+def painn_params_from_haiku(hk_params, model=None):
+    """Haiku PaiNN parameter dict -> this package's layout (inverse of painn_params_to_haiku).  The top-level module
+    name is whatever precedes "/~/scalar_embedding"."""
+    emb = [k for k in hk_params if k.endswith("/~/scalar_embedding")]
+    if len(emb) != 1:
+        raise ValueError(f"PaiNN checkpoint: expected one scalar_embedding module, found {emb}")
+    top = emb[0][: -len("/~/scalar_embedding")]
+
+    def get(key):
+        if key not in hk_params:
+            raise ValueError(f"PaiNN checkpoint: module {key!r} missing")
+        return _f32_leaves(hk_params[key])
+
+    out = {ours: get(f"{top}/~/{theirs}") for ours, theirs in _PAINN_TOP}
+    n = 0
+    while f"{top}/~/layer_{n}/~/linear_xav" in hk_params:
+        for ours, theirs in _PAINN_LAYER:
+            out[f"layer_{n}/{ours}"] = get(f"{top}/~/layer_{n}/~/{theirs}")
+        n += 1
+    if n == 0:
+        raise ValueError("PaiNN checkpoint: no layer_0 modules")
+    for blk in ("0", "out"):
+        for ours, theirs in _PAINN_READOUT:
+            out[f"readout_{blk}/{ours}"] = get(f"{top}/readout_block_{blk}/~/{theirs}")
+    if "~" in hk_params:
+        out["~"] = _f32_leaves(hk_params["~"])
+    if model is not None:
+        want = 1 if model._shared_interactions else model._num_mp_steps
+        if n != want:
+            raise ValueError(f"PaiNN checkpoint has {n} layer parameter sets, the model {want}")
+    return out
