@@ -317,6 +317,25 @@ int lb_egnn_set_tap(lb_egnn* egnn, float* h_out_dev, float* pos_out_dev);
 int lb_egnn_rollout(lb_engine* eng, lb_egnn* egnn, const double* traj_dev, int32_t T, int32_t n_steps,
                     double* pred_out_dev, int32_t* n_realloc_out);
 
+/* The training step for EGNN (reference: train/trainer.py:35-89 with EGNN's three outputs, models/egnn.py:361-369).  The
+ * handle type is lb_gns_train: lb_gns_train_zero_grad, lb_adamw_step, lb_gns_train_read / _write (flat blob in EGNN.flatten
+ * order = lb_egnn_create's), lb_gns_train_step_count and lb_gns_train_destroy work on it unchanged; lb_gns_train_loss_grad
+ * on it returns LB_ERR_ARG (the loss needs three targets).  desc->normalize = 1 is refused (LB_ERR_ARG): every radius graph
+ * here holds self-edges, and d/d radial of coord_diff / (sqrt(radial) + 1e-8) at radial = 0 is 0 * inf, so the
+ * reference's own gradient is NaN for num_mp_steps >= 2.  num_mp_steps <= 40.  Exact fp32 arithmetic, sums in a fixed
+ * order: gradients bit-reproducible. */
+int lb_egnn_train_create(lb_engine* eng, const lb_egnn_desc* desc, const float* weights_host, int64_t n_floats,
+                         lb_gns_train** out);
+/* value_and_grad of _mse on the engine's CURRENT window / neighbor list: predictions pos = the network's fp32 positions,
+ * vel = displacement(pos, newest input position), acc = vel - the normalised last velocity feature (all fp32); loss =
+ * sum over the outputs of w_k |pred_k - target_k|^2 (fp64 residuals), summed over dim, masked to the non-kinematic
+ * particles, / their number; mean over the batch, gradients summed and ACCUMULATED (lb_gns_train_zero_grad).  Targets: device
+ * (B*N, dim) fp64, the case's {pos, vel, acc}; a target may be NULL when its weight is 0.  pred_pos_out_dev (B*N, dim) fp32
+ * or NULL: the prediction, bit-identical to lb_egnn_forward's.  LB_ERR_STATE (nothing accumulated) if an edge has no
+ * transpose.  Host-synchronous. */
+int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
+                            float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev);
+
 /* ---- PaiNN (models/painn.py:372-510) -----------------------------------------------------------
  * Construction by runner.py:270-284: hidden_size = latent_dim, output_size 1, n_vels = isl - 1, gaussian_rbf(20,
  * 1.5 r_c, trainable) and cosine_cutoff(1.5 r_c) with the PHYSICAL radius (the network's norms are in units of r_c),

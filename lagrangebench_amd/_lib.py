@@ -143,6 +143,8 @@ _SIGS = {
     "lb_egnn_forward": (C.c_int, [_P, _P, _P]),
     "lb_egnn_set_tap": (C.c_int, [_P, _P, _P]),
     "lb_egnn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "lb_egnn_train_create": (C.c_int, [_P, C.POINTER(EgnnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "lb_egnn_train_loss_grad": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _P]),
     "lb_painn_create": (C.c_int, [_P, C.POINTER(PainnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_painn_destroy": (None, [_P]),
     "lb_painn_forward": (C.c_int, [_P, _P, _P]),

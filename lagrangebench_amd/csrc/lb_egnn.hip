@@ -574,6 +574,35 @@ static int64_t eg_n_floats(const lb_egnn_desc* d, int node_in, int n_attr) {
   return (int64_t)node_in * H + H + d->num_mp_steps * layer;
 }
 
+// the layer pointers into a weight blob in lb_egnn_create's layout (include/lbhip.h)
+static void eg_carve(lb_egnn* m, const float* q) {
+  const int64_t H = m->desc.hidden, node_in = m->node_in, n_attr = m->n_attr;
+  auto take = [&](int64_t n) {
+    const float* r = q;
+    q += n;
+    return r;
+  };
+  m->w_emb = take(node_in * H);
+  m->b_emb = take(H);
+  m->layers.resize(m->desc.num_mp_steps);
+  for (auto& l : m->layers) {
+    l.w0 = take((2 * H + 2) * H);
+    l.b0 = take(H);
+    l.w1 = take(H * H);
+    l.b1 = take(H);
+    l.wn0 = take((2 * H + n_attr) * H);
+    l.bn0 = take(H);
+    l.wn1 = take(H * H);
+    l.bn1 = take(H);
+    l.wx0 = take(H * H);
+    l.bx0 = take(H);
+    l.wx1 = take(H);
+    l.wv0 = take(H * H);
+    l.bv0 = take(H);
+    l.wv1 = take(H);
+  }
+}
+
 extern "C" int lb_egnn_create(lb_engine* e, const lb_egnn_desc* d, const float* w, int64_t n_floats, lb_egnn** out) {
   if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
   *out = nullptr;
@@ -615,32 +644,40 @@ extern "C" int lb_egnn_create(lb_engine* e, const lb_egnn_desc* d, const float* 
     lb_egnn_destroy(m);
     return rc;
   }
-  // carve the blob (include/lbhip.h: lb_egnn_create)
-  const float* q = m->blob;
-  auto take = [&](int64_t n) {
-    const float* r = q;
-    q += n;
-    return r;
+  eg_carve(m, m->blob);
+  *out = m;
+  return LB_OK;
+}
+
+// Training (lb_train_egnn.h): a model that runs on a weight blob the caller owns and keeps in lb_egnn_create's layout (the
+// training handle's device weights, which AdamW updates in place).  Nothing is copied; lb_egnn_destroy leaves the blob alone.
+int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev, lb_egnn** out) {
+  *out = nullptr;
+  const int node_in = d->n_vels + (d->homogeneous ? 0 : 9);
+  lb_egnn* m = new lb_egnn();
+  m->desc = *d;
+  m->eng = e;
+  m->node_in = node_in;
+  m->n_attr = e->g.force_kind != LB_FORCE_NONE ? 1 : 0;
+  const int64_t BN = e->BN, H = d->hidden;
+  int rc = LB_OK;
+  auto step = [&](int r) {
+    if (!rc) rc = r;
   };
-  m->w_emb = take(node_in * H);
-  m->b_emb = take(H);
-  m->layers.resize(d->num_mp_steps);
-  for (auto& l : m->layers) {
-    l.w0 = take((2 * H + 2) * H);
-    l.b0 = take(H);
-    l.w1 = take(H * H);
-    l.b1 = take(H);
-    l.wn0 = take((2 * H + n_attr) * H);
-    l.bn0 = take(H);
-    l.wn1 = take(H * H);
-    l.bn1 = take(H);
-    l.wx0 = take(H * H);
-    l.bx0 = take(H);
-    l.wx1 = take(H);
-    l.wv0 = take(H * H);
-    l.bv0 = take(H);
-    l.wv1 = take(H);
+  step(lb_alloc(&m->xnode, (size_t)BN * EG_KPAD));
+  step(lb_alloc(&m->h, (size_t)BN * H));
+  step(lb_alloc(&m->p, (size_t)BN * 2 * H));
+  step(lb_alloc(&m->x32, (size_t)BN * 4));
+  step(lb_alloc(&m->vel, (size_t)BN * 4));
+  step(lb_alloc(&m->nattr, (size_t)BN));
+  step(lb_alloc(&m->err, 1));
+  if (!rc && hipHostMalloc((void**)&m->err_host, sizeof(int32_t)) != hipSuccess)
+    rc = lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
+  if (rc) {
+    lb_egnn_destroy(m);
+    return rc;
   }
+  eg_carve(m, w_dev);
   *out = m;
   return LB_OK;
 }
@@ -787,4 +824,18 @@ extern "C" int lb_egnn_rollout(lb_engine* e, lb_egnn* m, const double* traj_dev,
   LB_TRY(eg_reset_err(e, m));
   LB_TRY(lb_rollout_generic(e, eg_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out));
   return eg_check_err(e, m);
+}
+
+// one forward as lb_egnn_forward runs it (no export); LB_ERR_STATE for an edge without a transpose.  Host-synchronous.
+int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st) {
+  if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
+    return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
+  LB_TRY(eg_reset_err(e, m));
+  LB_TRY(lbk_egnn_forward(e, m));
+  LB_TRY(eg_check_err(e, m));
+  st->xnode = m->xnode;
+  st->vel = m->vel;
+  st->nattr = m->nattr;
+  st->rev = m->rev;
+  return LB_OK;
 }

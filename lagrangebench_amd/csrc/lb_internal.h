@@ -397,6 +397,16 @@ int lbk_node_features_raw(lb_engine* e, float* xnode, int kpad);
 // lb_egnn.hip: rev[e] = the slot of edge e's transpose for the first n_edges_total slots of the list (binary search in
 // the sender-sorted row); every edge without one adds 1 to *err and gets rev[e] = e.  rev: [e_cap * B] slots.
 int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err);
+// ... and for the EGNN training step (lb_train_egnn.h): a model on a caller-owned device blob in lb_egnn_create's layout,
+// and one forward on it (taps through lb_egnn_set_tap) that hands back the state the backward reads
+struct lb_egnn_state {
+  const float* xnode;    // [BN][64] raw node features (normalised velocities first)
+  const float* vel;      // [BN][4] un-normalised last velocity
+  const float* nattr;    // [BN] |force|
+  const int32_t* rev;    // [n_edges_total] slot of each edge's transpose
+};
+int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev, lb_egnn** out);
+int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st);
 
 // lb_api.hip: the device-resident step loop shared by the models
 int lb_rollout_generic(lb_engine* e, int (*forward)(lb_engine*, void*), void* model,

@@ -67,9 +67,11 @@ static bool lb_train_f16x2_default() {
 }
 
 struct lb_sgt;  // SEGNN-specific state of a training handle (lb_train_segnn.h)
+struct lb_egt;  // EGNN-specific state of a training handle (lb_train_egnn.h)
 
 struct lb_gns_train {
   lb_sgt* sg = nullptr;   // non-null: this handle trains a SEGNN (created by lb_segnn_train_create)
+  lb_egt* eg = nullptr;   // non-null: this handle trains an EGNN (created by lb_egnn_train_create)
   lb_gns_desc desc;
   lb_engine* eng;
   int64_t n_floats = 0;   // floats of the DEVICE blobs (latent padded to 128)
@@ -1636,9 +1638,11 @@ extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const flo
 }
 
 static void sgt_free(lb_gns_train* t);
+static void egt_free(lb_gns_train* t);
 extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   if (!t) return;
   sgt_free(t);
+  egt_free(t);
   std::vector<void*> bufs = {t->w, t->g, t->m, t->v, t->xnode, t->a_en, t->z_en, t->a_ee, t->z_ee, t->a_d, t->pred,
                              t->dn, t->de, t->dy, t->dz, t->da, t->dx, t->dagg, t->agg, t->dwpart, t->red_dev, t->proj, t->node_w,
                              t->loss_dev, t->dw_flag, t->da2, t->loss_part, t->cnt_dev, t->snd_key, t->snd_perm, t->iota, t->snd_ptr, t->sort_tmp,
@@ -1715,6 +1719,7 @@ extern "C" int32_t lb_gns_train_math_fallbacks(lb_gns_train* t) { return t ? t->
 extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                       float* pred_out_dev) {
   if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
   return train_loss_grad_guarded(t, target_dev, loss_weight, loss_out, pred_out_dev);
 }
 static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
@@ -1829,3 +1834,6 @@ extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* i
 
 // ------------------------------------------------------------------------------------------------ SEGNN
 #include "lb_train_segnn.h"
+
+// ------------------------------------------------------------------------------------------------ EGNN
+#include "lb_train_egnn.h"

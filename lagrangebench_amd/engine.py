@@ -274,6 +274,15 @@ class RolloutEngine:
                                              C.c_int64(blob.size), C.byref(h)), "lb_segnn_train_create")
         return GnsTrainHandle(self, h, desc, blob.size)
 
+    def egnn_train_create(self, desc: EgnnDesc, blob: np.ndarray) -> "EgnnTrainHandle":
+        """Device-resident training state of one EGNN (csrc/lb_train_egnn.h); blob in EGNN.flatten order.  zero_grad /
+        adamw_step / read / write are the GNS handle's; loss_grad takes the case's {pos, vel, acc} targets."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32)
+        h = C.c_void_p()
+        check(self.lib.lb_egnn_train_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
+                                            C.c_int64(blob.size), C.byref(h)), "lb_egnn_train_create")
+        return EgnnTrainHandle(self, h, desc, blob.size)
+
     def gns_forward(self, gns: "GnsHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:
             out = torch.empty((self.B, self.N, self.dim), dtype=torch.float32, device=self.device)
@@ -547,6 +556,29 @@ class GnsTrainHandle:
             self.close()
         except Exception:
             pass
+
+
+class EgnnTrainHandle(GnsTrainHandle):
+    """trainer.py:35-89 for EGNN: _mse over the model's three outputs pos / vel / acc (models/egnn.py:361-369)."""
+
+    def loss_grad(self, targets: Dict[str, torch.Tensor], loss_weight: Dict[str, float], want_pred: bool = False):
+        """targets: the case's {"pos", "vel", "acc"} (B, N, dim) (a missing one needs weight 0); loss_weight: {"pos", "vel",
+        "acc"} -> mean per-trajectory loss (float); gradients accumulate.  want_pred: also the fp32 positions (B, N, dim)."""
+        e = self.engine
+        w = {k: float(loss_weight.get(k, 0.0)) for k in ("pos", "vel", "acc")}
+        tg = {}
+        for k in ("pos", "vel", "acc"):
+            if w[k] != 0.0:
+                if k not in targets or targets[k] is None:
+                    raise ValueError(f"EGNN loss: loss_weight[{k!r}] = {w[k]} but there is no {k!r} target")
+                tg[k] = torch.as_tensor(targets[k]).to(device=e.device, dtype=torch.float64).reshape(e.B * e.N, e.dim).contiguous()
+        loss = C.c_double()
+        pred = torch.empty((e.B, e.N, e.dim), dtype=torch.float32, device=e.device) if want_pred else None
+        check(e.lib.lb_egnn_train_loss_grad(self._h, ptr(tg["pos"]) if "pos" in tg else None,
+                                            ptr(tg["vel"]) if "vel" in tg else None, ptr(tg["acc"]) if "acc" in tg else None,
+                                            C.c_float(w["pos"]), C.c_float(w["vel"]), C.c_float(w["acc"]), C.byref(loss),
+                                            ptr(pred) if want_pred else None), "lb_egnn_train_loss_grad")
+        return (loss.value, pred) if want_pred else loss.value
 
 
 class SegnnHandle:

@@ -11,7 +11,8 @@ runner.py:71-72, and ``jnp.concatenate`` promotes the prediction back into the f
 * ``normalization_stats`` likewise: the velocity is un-normalised with the case's statistics, the ones the
   runner passes (runner.py:264).
 * Not built (``NotImplementedError``): ``attention=True`` (no config uses it), an activation other than
-  SiLU, and a hidden size that is not a multiple of 16 or exceeds 128.
+  SiLU, and a hidden size that is not a multiple of 16 or exceeds 128; training (``train_handle``,
+  csrc/lb_train_egnn.h) with ``normalize=True``.
 
 Parameters: ``{"scalar_emb": {"w", "b"}, "layer_{n}/edge_{0,1}", "layer_{n}/node_{0,1}", "layer_{n}/pos_0",
 "layer_{n}/vel_0": {"w", "b"}, "layer_{n}/pos_1", "layer_{n}/vel_1": {"w"}}`` with ``w`` of shape
@@ -149,6 +150,18 @@ class EGNN(BaseModel):
         d.homogeneous = int(bool(self._homogeneous_particles))
         d.residual, d.normalize, d.tanh_pos = int(bool(self._residual)), int(bool(self._normalize)), int(bool(self._tanh))
         return d
+
+    # ------------------------------------------------------------------ training
+    def train_handle(self, engine, params):
+        """Device-resident training state for `params` on `engine` (csrc/lb_train_egnn.h): ``loss_grad(targets,
+        loss_weight, want_pred=False)`` takes the case's {"pos", "vel", "acc"} targets and the loss weights."""
+        if self._normalize:
+            raise NotImplementedError(self.NORMALIZE_REFUSAL)
+        return engine.egnn_train_create(self._desc(), self.flatten(params))
+
+    NORMALIZE_REFUSAL = ("EGNN training with normalize=True is not built: every radius graph holds self-edges, and the "
+                         "derivative of coord_diff / (sqrt(radial) + 1e-8) at radial = 0 is 0 * inf - the reference's own "
+                         "gradient is NaN for num_mp_steps >= 2 (inference runs it)")
 
     # ------------------------------------------------------------------ engine binding
     @staticmethod

@@ -17,8 +17,11 @@ block's scale; gradients within 1e-4 per leaf of float64 autograd), with a range
 activation operand that repeats a step on the exact-fp32 MFMA kernels; ``LB_TRAIN_MATH=f32`` in the environment when the
 handle is created selects the exact kernels throughout (1.7x slower).
 torch is used for the noise / sampling random streams and as the tensor container only.  Trainable: GNS (latent <= 128,
-two to eight Linears per MLP) and, since round 5, SEGNN (lmax 1, hidden <= 32x0e+32x1o: ``lb_segnn_train_loss_grad``,
-csrc/lb_train_segnn.h - the loop below is the reference's model-agnostic one); wandb logging is not wired (stdout).
+two to eight Linears per MLP), since round 5 SEGNN (lmax 1, hidden <= 32x0e+32x1o: ``lb_segnn_train_loss_grad``,
+csrc/lb_train_segnn.h) and EGNN (``lb_egnn_train_loss_grad``, csrc/lb_train_egnn.h: the inference forward, a hand-written
+backward on the exact-fp32 MFMA products; the loss covers every output the model predicts - pos, vel, acc - weighted by
+``loss_weight`` against the case's targets, as _mse does; ``normalize=True`` is refused) - the loop below is the
+reference's model-agnostic one; wandb logging is not wired (stdout).
 """
 from __future__ import annotations
 
@@ -31,9 +34,11 @@ import torch
 from ..defaults import defaults, merge
 from ..evaluate import MetricsComputer, averaged_metrics, eval_rollout
 from ..evaluate.rollout import _Loader
+from ..models.egnn import EGNN
 from ..models.gns import GNS
-from ..utils import (broadcast_from_batch, get_kinematic_mask, gns_params_from_haiku, gns_params_to_haiku,
-                     load_haiku, save_haiku, segnn_params_from_haiku, segnn_params_to_haiku)
+from ..utils import (broadcast_from_batch, egnn_params_from_haiku, egnn_params_to_haiku, get_kinematic_mask,
+                     gns_params_from_haiku, gns_params_to_haiku, load_haiku, save_haiku, segnn_params_from_haiku,
+                     segnn_params_to_haiku)
 from .strats import push_forward_build, push_forward_sample_steps
 
 
@@ -72,10 +77,13 @@ class Trainer:
             raise NotImplementedError("training is built for SEGNN in the shipped configuration (scalar_units 64, lmax_hidden = "
                                       "lmax_attributes = 1, norm None); the other switches are inference-only "
                                       "(csrc/lb_segnn_gen.hip)")
+        if isinstance(model, EGNN) and model._normalize:
+            raise NotImplementedError(EGNN.NORMALIZE_REFUSAL)
         if not hasattr(model, "train_handle"):
             raise NotImplementedError("Trainer: the model has no device training step (GNS: csrc/lb_train.hip, SEGNN: "
-                                      "csrc/lb_train_segnn.h)")
+                                      "csrc/lb_train_segnn.h, EGNN: csrc/lb_train_egnn.h)")
         self._is_gns = isinstance(model, GNS)
+        self._is_egnn = isinstance(model, EGNN)
         self.model, self.case, self.input_seq_length = model, case, input_seq_length
         self.cfg_train = merge(defaults.train, cfg_train)
         self.cfg_eval = merge(defaults.eval, cfg_eval)
@@ -123,7 +131,9 @@ class Trainer:
             params, state, opt_state, step = load_haiku(load_ckp)
             if self._is_gns and "enc_node/linear_0" not in params:
                 params = gns_params_from_haiku(params, model._mp_steps, model._blocks_per_step)
-            elif not self._is_gns and "embedding_nodes" not in params:
+            elif self._is_egnn and "scalar_emb" not in params:
+                params = egnn_params_from_haiku(params, model)
+            elif not self._is_gns and not self._is_egnn and "embedding_nodes" not in params:
                 params = segnn_params_from_haiku(params, model)
         else:
             params, state = model.init(torch.randint(0, 2**31 - 1, (1,), generator=key).numpy(), (features, raw_sample[1]))
@@ -176,7 +186,10 @@ class Trainer:
                 # value_and_grad of _mse vmapped over the batch, gradients summed, loss averaged (trainer.py:63-89) +
                 # optax.adamw(lr(step), weight_decay 1e-8): on the engine's current window / neighbor list
                 th.zero_grad()
-                loss = th.loss_grad(target_batch["acc"], lw)
+                if self._is_egnn:   # _mse over every output the model predicts (pos, vel, acc)
+                    loss = th.loss_grad(target_batch, self.loss_weight)
+                else:
+                    loss = th.loss_grad(target_batch["acc"], lw)
                 th.adamw_step(self._lr(step), 0.9, 0.999, 1e-8, float(getattr(o, "weight_decay", 1e-8)))
 
                 if step % cfg_logging.log_steps == 0:
@@ -193,6 +206,7 @@ class Trainer:
                     metrics = averaged_metrics(eval_metrics)
                     if store_ckp is not None:
                         hk = (gns_params_to_haiku(params_np, model._mp_steps, model._blocks_per_step) if self._is_gns
+                              else egnn_params_to_haiku(params_np, model) if self._is_egnn
                               else segnn_params_to_haiku(params_np, model))
                         save_haiku(store_ckp, hk, state, opt_state_dict(), {"step": step, "loss": metrics.get("val/loss", None)})
                     print(metrics)
