@@ -929,12 +929,37 @@ extern "C" int lb_gns_set_tap(lb_gns* g, float* tap) {
   return LB_OK;
 }
 
-__global__ void k_acc_export(int64_t BN, int dim, const float* __restrict__ acc4,
-                             float* __restrict__ out) {
-  int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= BN) return;
-  for (int d = 0; d < dim; ++d) out[gi * dim + d] = acc4[gi * 4 + d];
+int lb_model_check(const lb_engine* e, const lb_engine* model_eng) {
+  if (!e || !model_eng) return lb_fail(LB_ERR_ARG, "null argument");
+  if (model_eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
+  return LB_OK;
 }
+
+int lb_forward_check(const lb_engine* e, const char* name) {
+  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "%s before lb_nl_allocate", name);
+  if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
+    return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
+  return LB_OK;
+}
+
+template <typename T>
+__global__ void k_row_export(int64_t BN, int dim, const lb_ctrl* __restrict__ ctrl, const float* __restrict__ rows4,
+                             T* __restrict__ out) {
+  if (ctrl && ctrl->overflow_step >= 0) return;
+  const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= BN) return;
+  for (int d = 0; d < dim; ++d) out[gi * dim + d] = (T)rows4[gi * 4 + d];
+}
+
+template <typename T>
+int lb_export_rows(lb_engine* e, const float* rows4, T* out, bool gated) {
+  hipLaunchKernelGGL(k_row_export<T>, dim3((unsigned)((e->BN + 255) / 256)), dim3(256), 0, e->stream, e->BN, e->g.dim,
+                     gated ? e->ctrl : nullptr, rows4, out);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+template int lb_export_rows<float>(lb_engine*, const float*, float*, bool);
+template int lb_export_rows<double>(lb_engine*, const float*, double*, bool);
 
 // f16x2 range guard, host side: read (and clear) the flags the kernels raised since the last check.
 // *switched = 1 when the engine was in guarded f16x2 mode and has just been put on exact fp32 - the caller then
@@ -999,11 +1024,8 @@ extern "C" int lb_debug_inject_guard(lb_engine* e, int32_t flags, int32_t step) 
 }
 
 extern "C" int lb_gns_forward(lb_engine* e, lb_gns* g, float* acc_out_dev) {
-  if (!e || !g) return lb_fail(LB_ERR_ARG, "null argument");
-  if (g->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_gns_forward before lb_nl_allocate");
-  if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
-    return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
+  LB_TRY(lb_model_check(e, g ? g->eng : nullptr));
+  LB_TRY(lb_forward_check(e, "lb_gns_forward"));
   LB_TRY(lbk_gns_forward(e, g));
   if (e->f16x2 && e->math_auto) {  // guarded mode: one host sync per stand-alone forward (not the rollout path)
     int switched = 0;
@@ -1017,12 +1039,7 @@ extern "C" int lb_gns_forward(lb_engine* e, lb_gns* g, float* acc_out_dev) {
       if (rc) return rc;
     }
   }
-  if (acc_out_dev) {
-    const int nb = (int)((e->BN + 255) / 256);
-    hipLaunchKernelGGL(k_acc_export, dim3(nb), dim3(256), 0, e->stream, e->BN, e->g.dim, e->acc,
-                       acc_out_dev);
-    LB_HIP(hipGetLastError());
-  }
+  if (acc_out_dev) LB_TRY(lb_export_rows(e, e->acc, acc_out_dev, false));
   return LB_OK;
 }
 
@@ -1047,8 +1064,8 @@ static int gns_forward_thunk(lb_engine* e, void* model) { return lbk_gns_forward
 
 extern "C" int lb_rollout(lb_engine* e, lb_gns* g, const double* traj_dev, int32_t T,
                           int32_t n_steps, double* pred_out_dev, int32_t* n_realloc_out) {
-  if (!e || !g || !traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (g->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
+  if (!traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  LB_TRY(lb_model_check(e, g ? g->eng : nullptr));
   // the node-feature rows of every step ride along with its neighbor search
   struct FeatJob {
     lb_engine* e;

@@ -55,8 +55,7 @@ struct lb_egnn {
   float* x32 = nullptr;    // [BN][4]
   float* vel = nullptr;    // [BN][4]
   float* nattr = nullptr;  // [BN]
-  int32_t* err = nullptr;  // device: edges without a transpose
-  int32_t* err_host = nullptr;
+  lb_rev_err err;          // edges without a transpose
   int64_t e_alloc = 0;
   float* msg = nullptr;    // [e_alloc][H]
   float* trans = nullptr;  // [e_alloc][4]
@@ -205,6 +204,32 @@ int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err) {
   hipLaunchKernelGGL(k_eg_rev, dim3(nb ? nb : 1), dim3(256), 0, e->stream, e->ctrl, ecap, e->row_ptr, e->senders,
                      e->receivers, rev, err);
   LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+
+int lb_rev_err_alloc(lb_rev_err* w) {
+  LB_TRY(lb_alloc(&w->dev, 1));
+  if (hipHostMalloc((void**)&w->host, sizeof(int32_t)) != hipSuccess) return lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
+  return LB_OK;
+}
+
+void lb_rev_err_free(lb_rev_err* w) {
+  if (w->dev) (void)hipFree(w->dev);
+  if (w->host) (void)hipHostFree(w->host);
+  *w = lb_rev_err{};
+}
+
+int lb_rev_err_reset(lb_engine* e, const lb_rev_err& w) {
+  LB_HIP(hipMemsetAsync(w.dev, 0, sizeof(int32_t), e->stream));
+  return LB_OK;
+}
+
+int lb_rev_err_check(lb_engine* e, const lb_rev_err& w, const char* model) {
+  LB_HIP(hipMemcpyAsync(w.host, w.dev, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipStreamSynchronize(e->stream));
+  if (*w.host)
+    return lb_fail(LB_ERR_STATE, "%s: %d edges of the neighbor list have no transposed edge (the sender sum needs a "
+                   "symmetric list)", model, *w.host);
   return LB_OK;
 }
 
@@ -526,20 +551,6 @@ __global__ void k_eg_integrate(lb_geom g, int64_t BN, double* __restrict__ win, 
   }
 }
 
-__global__ void k_eg_export(int64_t BN, int dim, const lb_ctrl* __restrict__ ctrl, const float* __restrict__ x32,
-                            double* __restrict__ out) {
-  if (ctrl->overflow_step >= 0) return;
-  const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= BN) return;
-  for (int d = 0; d < dim; ++d) out[gi * dim + d] = (double)x32[gi * 4 + d];
-}
-
-__global__ void k_eg_tap_pos(int64_t BN, int dim, const float* __restrict__ x32, float* __restrict__ out) {
-  const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= BN) return;
-  for (int d = 0; d < dim; ++d) out[gi * dim + d] = x32[gi * 4 + d];
-}
-
 // ------------------------------------------------------------------------------- model
 static int eg_ensure_edges(lb_egnn* m) {
   lb_engine* e = m->eng;
@@ -560,9 +571,9 @@ static int eg_ensure_edges(lb_egnn* m) {
 extern "C" void lb_egnn_destroy(lb_egnn* m) {
   if (!m) return;
   for (void* b : {(void*)m->blob, (void*)m->xnode, (void*)m->h, (void*)m->p, (void*)m->x32, (void*)m->vel,
-                  (void*)m->nattr, (void*)m->err, (void*)m->msg, (void*)m->trans, (void*)m->rev})
+                  (void*)m->nattr, (void*)m->msg, (void*)m->trans, (void*)m->rev})
     if (b) (void)hipFree(b);
-  if (m->err_host) (void)hipHostFree(m->err_host);
+  lb_rev_err_free(&m->err);
   delete m;
 }
 
@@ -637,9 +648,7 @@ extern "C" int lb_egnn_create(lb_engine* e, const lb_egnn_desc* d, const float* 
   step(lb_alloc(&m->x32, (size_t)BN * 4));
   step(lb_alloc(&m->vel, (size_t)BN * 4));
   step(lb_alloc(&m->nattr, (size_t)BN));
-  step(lb_alloc(&m->err, 1));
-  if (!rc && hipHostMalloc((void**)&m->err_host, sizeof(int32_t)) != hipSuccess)
-    rc = lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
+  step(lb_rev_err_alloc(&m->err));
   if (rc) {
     lb_egnn_destroy(m);
     return rc;
@@ -670,9 +679,7 @@ int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev
   step(lb_alloc(&m->x32, (size_t)BN * 4));
   step(lb_alloc(&m->vel, (size_t)BN * 4));
   step(lb_alloc(&m->nattr, (size_t)BN));
-  step(lb_alloc(&m->err, 1));
-  if (!rc && hipHostMalloc((void**)&m->err_host, sizeof(int32_t)) != hipSuccess)
-    rc = lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
+  step(lb_rev_err_alloc(&m->err));
   if (rc) {
     lb_egnn_destroy(m);
     return rc;
@@ -695,19 +702,19 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
   const int H = m->desc.hidden, dim = e->g.dim;
   LB_TRY(eg_ensure_edges(m));
   const int64_t ecap = (int64_t)e->e_cap * e->g.B;
-  const unsigned nb_t = (unsigned)((BN + EG_TN - 1) / EG_TN), nb_n = (unsigned)((BN + 255) / 256);
+  const unsigned nb_t = (unsigned)((BN + EG_TN - 1) / EG_TN);
   const unsigned nb_te = (unsigned)((ecap + EG_TE - 1) / EG_TE);
   auto tap = [&](int slot) -> int {
     if (m->tap_h)
       LB_HIP(hipMemcpyAsync(m->tap_h + (size_t)slot * BN * H, m->h, sizeof(float) * BN * H, hipMemcpyDeviceToDevice, s));
-    if (m->tap_x) hipLaunchKernelGGL(k_eg_tap_pos, dim3(nb_n), dim3(256), 0, s, BN, dim, m->x32, m->tap_x + (size_t)slot * BN * dim);
+    if (m->tap_x) LB_TRY(lb_export_rows(e, m->x32, m->tap_x + (size_t)slot * BN * dim, false));
     return LB_OK;
   };
   lb_tic(e, LB_T_NODEFEAT);
   LB_TRY(lbk_node_features_raw(e, m->xnode, EG_KPAD));
   hipLaunchKernelGGL(k_eg_prologue, dim3(nb_t), dim3(EG_THREADS), 0, s, e->g, BN, e->ctrl, e->win, m->xnode, e->ptype, H,
                      m->desc.n_vels, m->desc.homogeneous, m->n_attr, m->w_emb, m->b_emb, m->h, m->x32, m->vel, m->nattr);
-  LB_TRY(lbk_edge_rev(e, m->rev, m->err));
+  LB_TRY(lbk_edge_rev(e, m->rev, m->err.dev));
   lb_toc(e);
   LB_HIP(hipGetLastError());
   LB_TRY(tap(0));
@@ -774,33 +781,13 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
   return LB_OK;
 }
 
-static int eg_reset_err(lb_engine* e, lb_egnn* m) {
-  LB_HIP(hipMemsetAsync(m->err, 0, sizeof(int32_t), e->stream));
-  return LB_OK;
-}
-static int eg_check_err(lb_engine* e, lb_egnn* m) {
-  LB_HIP(hipMemcpyAsync(m->err_host, m->err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipStreamSynchronize(e->stream));
-  if (*m->err_host)
-    return lb_fail(LB_ERR_STATE, "EGNN: %d edges of the neighbor list have no transposed edge (the sender sum needs a "
-                   "symmetric list)", *m->err_host);
-  return LB_OK;
-}
-
 extern "C" int lb_egnn_forward(lb_engine* e, lb_egnn* m, double* pos_out_dev) {
-  if (!e || !m) return lb_fail(LB_ERR_ARG, "null argument");
-  if (m->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_egnn_forward before lb_nl_allocate");
-  if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
-    return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
-  LB_TRY(eg_reset_err(e, m));
+  LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
+  LB_TRY(lb_forward_check(e, "lb_egnn_forward"));
+  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lbk_egnn_forward(e, m));
-  if (pos_out_dev) {
-    hipLaunchKernelGGL(k_eg_export, dim3((unsigned)((e->BN + 255) / 256)), dim3(256), 0, e->stream, e->BN, e->g.dim,
-                       e->ctrl, m->x32, pos_out_dev);
-    LB_HIP(hipGetLastError());
-  }
-  return eg_check_err(e, m);
+  if (pos_out_dev) LB_TRY(lb_export_rows(e, m->x32, pos_out_dev, true));
+  return lb_rev_err_check(e, m->err, "EGNN");
 }
 
 // one rollout step's model + integrator (lb_enqueue_step has set e->integ_job)
@@ -819,20 +806,20 @@ static int eg_forward_thunk(lb_engine* e, void* model) {
 
 extern "C" int lb_egnn_rollout(lb_engine* e, lb_egnn* m, const double* traj_dev, int32_t T, int32_t n_steps,
                                double* pred_out_dev, int32_t* n_realloc_out) {
-  if (!e || !m || !traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (m->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
-  LB_TRY(eg_reset_err(e, m));
+  if (!traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
+  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lb_rollout_generic(e, eg_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out));
-  return eg_check_err(e, m);
+  return lb_rev_err_check(e, m->err, "EGNN");
 }
 
 // one forward as lb_egnn_forward runs it (no export); LB_ERR_STATE for an edge without a transpose.  Host-synchronous.
 int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st) {
   if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
     return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
-  LB_TRY(eg_reset_err(e, m));
+  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lbk_egnn_forward(e, m));
-  LB_TRY(eg_check_err(e, m));
+  LB_TRY(lb_rev_err_check(e, m->err, "EGNN"));
   st->xnode = m->xnode;
   st->vel = m->vel;
   st->nattr = m->nattr;

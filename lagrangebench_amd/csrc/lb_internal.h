@@ -397,6 +397,16 @@ int lbk_node_features_raw(lb_engine* e, float* xnode, int kpad);
 // lb_egnn.hip: rev[e] = the slot of edge e's transpose for the first n_edges_total slots of the list (binary search in
 // the sender-sorted row); every edge without one adds 1 to *err and gets rev[e] = e.  rev: [e_cap * B] slots.
 int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err);
+// ... the count it raises: a device word and its pinned host copy.  check: host-synchronous; a nonzero count is
+// LB_ERR_STATE "<model>: <count> edges of the neighbor list have no transposed edge ...".
+struct lb_rev_err {
+  int32_t* dev = nullptr;
+  int32_t* host = nullptr;
+};
+int lb_rev_err_alloc(lb_rev_err* w);
+void lb_rev_err_free(lb_rev_err* w);
+int lb_rev_err_reset(lb_engine* e, const lb_rev_err& w);
+int lb_rev_err_check(lb_engine* e, const lb_rev_err& w, const char* model);
 // ... and for the EGNN training step (lb_train_egnn.h): a model on a caller-owned device blob in lb_egnn_create's layout,
 // and one forward on it (taps through lb_egnn_set_tap) that hands back the state the backward reads
 struct lb_egnn_state {
@@ -407,6 +417,16 @@ struct lb_egnn_state {
 };
 int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev, lb_egnn** out);
 int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st);
+
+// lb_api.hip: the checks every model entry point makes.  lb_model_check: a null engine or model (model_eng = null), or a
+// model created for another engine -> LB_ERR_ARG.  lb_forward_check: the stand-alone forward `name` before
+// lb_nl_allocate, or an LB_FORCE_BUFFER engine without its force -> LB_ERR_STATE.
+int lb_model_check(const lb_engine* e, const lb_engine* model_eng);
+int lb_forward_check(const lb_engine* e, const char* name);
+// lb_api.hip: out[i][0:dim] = rows4[i][0:dim] (T = float or double) for the B*N rows of 4 floats of a model's output.
+// gated: nothing is written once the rollout's neighbor list has overflowed (ctrl->overflow_step >= 0).
+template <typename T>
+int lb_export_rows(lb_engine* e, const float* rows4, T* out, bool gated);
 
 // lb_api.hip: the device-resident step loop shared by the models
 int lb_rollout_generic(lb_engine* e, int (*forward)(lb_engine*, void*), void* model,

@@ -78,8 +78,7 @@ struct lb_painn {
   float* h1 = nullptr;     // [BN][H]
   float* ts = nullptr;     // [BN][2H]
   float* vm = nullptr;     // [BN][dim][2H]
-  int32_t* err = nullptr;
-  int32_t* err_host = nullptr;
+  lb_rev_err err;          // edges without a transpose
   int64_t e_alloc = 0;
   int32_t* rev = nullptr;  // [e_alloc]
   f32x4* geo = nullptr;    // [e_alloc]: dir (3), filter scale (0 on a dead edge)
@@ -392,14 +391,6 @@ __global__ void __launch_bounds__(64) k_pn_readout(const lb_ctrl* __restrict__ c
   o[3] = 0.f;
 }
 
-__global__ void k_pn_export(int64_t BN, int dim, const lb_ctrl* __restrict__ ctrl, const float* __restrict__ acc4,
-                            float* __restrict__ out) {
-  if (ctrl->overflow_step >= 0) return;
-  const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= BN) return;
-  for (int d = 0; d < dim; ++d) out[gi * dim + d] = acc4[gi * 4 + d];
-}
-
 // ------------------------------------------------------------------------------- model
 static int64_t pn_frag_floats(int K, int NO) {
   const int NJ = (K + 15) / 16, NOB = (NO + 63) / 64 * 4;
@@ -438,10 +429,10 @@ static int pn_ensure_edges(lb_painn* m) {
 extern "C" void lb_painn_destroy(lb_painn* m) {
   if (!m) return;
   for (void* b : {(void*)m->blob, (void*)m->packed, (void*)m->xnode, (void*)m->s, (void*)m->va, (void*)m->vb,
-                  (void*)m->x3, (void*)m->h1, (void*)m->ts, (void*)m->vm, (void*)m->err, (void*)m->rev, (void*)m->geo,
+                  (void*)m->x3, (void*)m->h1, (void*)m->ts, (void*)m->vm, (void*)m->rev, (void*)m->geo,
                   (void*)m->nrm})
     if (b) (void)hipFree(b);
-  if (m->err_host) (void)hipHostFree(m->err_host);
+  lb_rev_err_free(&m->err);
   delete m;
 }
 
@@ -503,9 +494,7 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
   step(lb_alloc(&m->h1, (size_t)BN * H));
   step(lb_alloc(&m->ts, (size_t)BN * 2 * H));
   step(lb_alloc(&m->vm, (size_t)BN * dim * 2 * H));
-  step(lb_alloc(&m->err, 1));
-  if (!rc && hipHostMalloc((void**)&m->err_host, sizeof(int32_t)) != hipSuccess)
-    rc = lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
+  step(lb_rev_err_alloc(&m->err));
   if (rc) {
     lb_painn_destroy(m);
     return rc;
@@ -646,7 +635,7 @@ static int lbk_painn_forward(lb_engine* e, lb_painn* m) {
   hipLaunchKernelGGL(k_pn_embed, dim3(nb_t), dim3(128), 0, st, ea);
   hipLaunchKernelGGL(k_pn_edge, dim3(nb_e ? nb_e : 1), dim3(256), 0, st, e->ctrl, ecap, dim, m->desc.has_cutoff,
                      m->desc.cutoff, e->efeat, m->geo, m->nrm);
-  LB_TRY(lbk_edge_rev(e, m->rev, m->err));
+  LB_TRY(lbk_edge_rev(e, m->rev, m->err.dev));
   lb_toc(e);
   LB_HIP(hipGetLastError());
   LB_TRY(tap(0));
@@ -704,33 +693,13 @@ static int lbk_painn_forward(lb_engine* e, lb_painn* m) {
   return LB_OK;
 }
 
-static int pn_reset_err(lb_engine* e, lb_painn* m) {
-  LB_HIP(hipMemsetAsync(m->err, 0, sizeof(int32_t), e->stream));
-  return LB_OK;
-}
-static int pn_check_err(lb_engine* e, lb_painn* m) {
-  LB_HIP(hipMemcpyAsync(m->err_host, m->err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipStreamSynchronize(e->stream));
-  if (*m->err_host)
-    return lb_fail(LB_ERR_STATE, "PaiNN: %d edges of the neighbor list have no transposed edge (the sender sum needs a "
-                   "symmetric list)", *m->err_host);
-  return LB_OK;
-}
-
 extern "C" int lb_painn_forward(lb_engine* e, lb_painn* m, float* acc_out_dev) {
-  if (!e || !m) return lb_fail(LB_ERR_ARG, "null argument");
-  if (m->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_painn_forward before lb_nl_allocate");
-  if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
-    return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
-  LB_TRY(pn_reset_err(e, m));
+  LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
+  LB_TRY(lb_forward_check(e, "lb_painn_forward"));
+  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lbk_painn_forward(e, m));
-  if (acc_out_dev) {
-    hipLaunchKernelGGL(k_pn_export, dim3((unsigned)((e->BN + 255) / 256)), dim3(256), 0, e->stream, e->BN, e->g.dim,
-                       e->ctrl, e->acc, acc_out_dev);
-    LB_HIP(hipGetLastError());
-  }
-  return pn_check_err(e, m);
+  if (acc_out_dev) LB_TRY(lb_export_rows(e, e->acc, acc_out_dev, true));
+  return lb_rev_err_check(e, m->err, "PaiNN");
 }
 
 // one rollout step's model; lb_rollout_generic integrates e->acc with the GNS integrator
@@ -738,9 +707,9 @@ static int pn_forward_thunk(lb_engine* e, void* model) { return lbk_painn_forwar
 
 extern "C" int lb_painn_rollout(lb_engine* e, lb_painn* m, const double* traj_dev, int32_t T, int32_t n_steps,
                                 double* pred_out_dev, int32_t* n_realloc_out) {
-  if (!e || !m || !traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (m->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
-  LB_TRY(pn_reset_err(e, m));
+  if (!traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
+  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lb_rollout_generic(e, pn_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out));
-  return pn_check_err(e, m);
+  return lb_rev_err_check(e, m->err, "PaiNN");
 }

@@ -695,26 +695,11 @@ int lbk_segnn_forward(lb_engine* e, lb_segnn* m) {
   return LB_OK;
 }
 
-__global__ void k_sg_acc_export(int64_t BN, int dim, const float* __restrict__ acc4,
-                                float* __restrict__ out) {
-  int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gi >= BN) return;
-  for (int d = 0; d < dim; ++d) out[gi * dim + d] = acc4[gi * 4 + d];
-}
-
 extern "C" int lb_segnn_forward(lb_engine* e, lb_segnn* m, float* acc_out_dev) {
-  if (!e || !m) return lb_fail(LB_ERR_ARG, "null argument");
-  if (m->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_segnn_forward before lb_nl_allocate");
-  if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
-    return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
+  LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
+  LB_TRY(lb_forward_check(e, "lb_segnn_forward"));
   LB_TRY(lbk_segnn_forward(e, m));
-  if (acc_out_dev) {
-    const int nb = (int)((e->BN + 255) / 256);
-    hipLaunchKernelGGL(k_sg_acc_export, dim3(nb), dim3(256), 0, e->stream, e->BN, e->g.dim, e->acc,
-                       acc_out_dev);
-    LB_HIP(hipGetLastError());
-  }
+  if (acc_out_dev) LB_TRY(lb_export_rows(e, e->acc, acc_out_dev, false));
   return LB_OK;
 }
 
@@ -722,8 +707,8 @@ static int sg_forward_thunk(lb_engine* e, void* model) { return lbk_segnn_forwar
 
 extern "C" int lb_segnn_rollout(lb_engine* e, lb_segnn* m, const double* traj_dev, int32_t T,
                                 int32_t n_steps, double* pred_out_dev, int32_t* n_realloc_out) {
-  if (!e || !m || !traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (m->eng != e) return lb_fail(LB_ERR_ARG, "model was created for another engine");
+  if (!traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
   if (!m->gen) e->feat_job = lb_feat_job{m->xnode, nullptr, 0, 1, 32, e->ptype, e->force};  // node-feature rows ride along with the search
   const int rc = lb_rollout_generic(e, sg_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out);
   e->feat_job = lb_feat_job{};

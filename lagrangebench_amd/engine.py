@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CaseDesc, EgnnDesc, GnsDesc, LbHipError, PainnDesc, SegnnDesc, check, ptr
+from ._lib import CaseDesc, LbHipError, check, ptr
 
 
 def _d3(v, fill=0.0):
@@ -250,87 +250,34 @@ class RolloutEngine:
         return {"rel_disp": rd, "rel_dist": rr}
 
     # ------------------------------------------------------------------ model
-    def gns_create(self, desc: GnsDesc, blob: np.ndarray) -> "GnsHandle":
+    def _new_handle(self, cls, symbol: str, desc, blob: np.ndarray):
+        """A new `cls` handle from the C entry point `symbol`(engine, desc, blob, n_floats, &handle): one model
+        (models/*.py `_create`) or its training state (`_train_create`) on this engine."""
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         h = C.c_void_p()
-        check(self.lib.lb_gns_create(self._h, C.byref(desc), blob.ctypes.data_as(C.c_void_p),
-                                     C.c_int64(blob.size), C.byref(h)), "lb_gns_create")
-        return GnsHandle(self, h, desc)
+        check(getattr(self.lib, symbol)(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
+                                        C.c_int64(blob.size), C.byref(h)), symbol)
+        return cls(self, h, desc, blob.size)
 
-    def gns_train_create(self, desc: GnsDesc, blob: np.ndarray) -> "GnsTrainHandle":
-        """Device-resident training state (weights, gradients, AdamW moments) of one GNS: csrc/lb_train.hip."""
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        h = C.c_void_p()
-        check(self.lib.lb_gns_train_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                           C.c_int64(blob.size), C.byref(h)), "lb_gns_train_create")
-        return GnsTrainHandle(self, h, desc, blob.size)
-
-    def segnn_train_create(self, desc: SegnnDesc, blob: np.ndarray) -> "GnsTrainHandle":
-        """Device-resident training state of one SEGNN (csrc/lb_train_segnn.h); the handle type and its zero_grad /
-        loss_grad / adamw_step / read / write are the GNS ones (lb_gns_train_loss_grad dispatches on the handle)."""
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        h = C.c_void_p()
-        check(self.lib.lb_segnn_train_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                             C.c_int64(blob.size), C.byref(h)), "lb_segnn_train_create")
-        return GnsTrainHandle(self, h, desc, blob.size)
-
-    def egnn_train_create(self, desc: EgnnDesc, blob: np.ndarray) -> "EgnnTrainHandle":
-        """Device-resident training state of one EGNN (csrc/lb_train_egnn.h); blob in EGNN.flatten order.  zero_grad /
-        adamw_step / read / write are the GNS handle's; loss_grad takes the case's {pos, vel, acc} targets."""
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        h = C.c_void_p()
-        check(self.lib.lb_egnn_train_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                            C.c_int64(blob.size), C.byref(h)), "lb_egnn_train_create")
-        return EgnnTrainHandle(self, h, desc, blob.size)
+    def _forward(self, symbol: str, model, out: Optional[torch.Tensor], dtype) -> torch.Tensor:
+        if out is None:
+            out = torch.empty((self.B, self.N, self.dim), dtype=dtype, device=self.device)
+        check(getattr(self.lib, symbol)(self._h, model._h, ptr(out)), symbol)
+        return out
 
     def gns_forward(self, gns: "GnsHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if out is None:
-            out = torch.empty((self.B, self.N, self.dim), dtype=torch.float32, device=self.device)
-        check(self.lib.lb_gns_forward(self._h, gns._h, ptr(out)), "lb_gns_forward")
-        return out
-
-    def segnn_create(self, desc: SegnnDesc, blob: np.ndarray) -> "SegnnHandle":
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        h = C.c_void_p()
-        check(self.lib.lb_segnn_create(self._h, C.byref(desc), blob.ctypes.data_as(C.c_void_p),
-                                       C.c_int64(blob.size), C.byref(h)), "lb_segnn_create")
-        return SegnnHandle(self, h, desc)
+        return self._forward("lb_gns_forward", gns, out, torch.float32)
 
     def segnn_forward(self, segnn: "SegnnHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if out is None:
-            out = torch.empty((self.B, self.N, self.dim), dtype=torch.float32, device=self.device)
-        check(self.lib.lb_segnn_forward(self._h, segnn._h, ptr(out)), "lb_segnn_forward")
-        return out
-
-    def egnn_create(self, desc: EgnnDesc, blob: np.ndarray) -> "EgnnHandle":
-        """One EGNN on this engine (csrc/lb_egnn.hip); blob in EGNN.flatten order (include/lbhip.h: lb_egnn_create)."""
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        h = C.c_void_p()
-        check(self.lib.lb_egnn_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                      C.c_int64(blob.size), C.byref(h)), "lb_egnn_create")
-        return EgnnHandle(self, h, desc)
+        return self._forward("lb_segnn_forward", segnn, out, torch.float32)
 
     def egnn_forward(self, egnn: "EgnnHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """EGNN positions (B, N, dim) fp64 holding the fp32 values of the network."""
-        if out is None:
-            out = torch.empty((self.B, self.N, self.dim), dtype=torch.float64, device=self.device)
-        check(self.lib.lb_egnn_forward(self._h, egnn._h, ptr(out)), "lb_egnn_forward")
-        return out
-
-    def painn_create(self, desc: PainnDesc, blob: np.ndarray) -> "PainnHandle":
-        """One PaiNN on this engine (csrc/lb_painn.hip); blob in PaiNN.flatten order (include/lbhip.h: lb_painn_create)."""
-        blob = np.ascontiguousarray(blob, dtype=np.float32)
-        h = C.c_void_p()
-        check(self.lib.lb_painn_create(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                       C.c_int64(blob.size), C.byref(h)), "lb_painn_create")
-        return PainnHandle(self, h, desc)
+        return self._forward("lb_egnn_forward", egnn, out, torch.float64)
 
     def painn_forward(self, painn: "PainnHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """PaiNN normalised accelerations (B, N, dim) fp32."""
-        if out is None:
-            out = torch.empty((self.B, self.N, self.dim), dtype=torch.float32, device=self.device)
-        check(self.lib.lb_painn_forward(self._h, painn._h, ptr(out)), "lb_painn_forward")
-        return out
+        return self._forward("lb_painn_forward", painn, out, torch.float32)
 
     def math_mode(self, set_mode: int = -1) -> Tuple[int, int]:
         """(mode, guard flags): 0 exact fp32 MFMA, 1 guarded f16x2 (default), 2 unguarded f16x2; flags: 1
@@ -371,20 +318,13 @@ class RolloutEngine:
         return out
 
     def rollout(self, model, traj: torch.Tensor, n_steps: int) -> Tuple[torch.Tensor, int]:
-        """model: a GnsHandle (lb_rollout), a SegnnHandle (lb_segnn_rollout), an EgnnHandle (lb_egnn_rollout) or a
-        PainnHandle (lb_painn_rollout)."""
+        """model: a model handle; its class names the C rollout (GnsHandle: lb_rollout, SegnnHandle: lb_segnn_rollout,
+        ...)."""
         traj = self.prepare_traj(traj)
         pred = torch.zeros((self.B, n_steps, self.N, self.dim), dtype=torch.float64, device=self.device)
         nre = C.c_int32(0)
-        if isinstance(model, SegnnHandle):
-            fn, name = self.lib.lb_segnn_rollout, "lb_segnn_rollout"
-        elif isinstance(model, EgnnHandle):
-            fn, name = self.lib.lb_egnn_rollout, "lb_egnn_rollout"
-        elif isinstance(model, PainnHandle):
-            fn, name = self.lib.lb_painn_rollout, "lb_painn_rollout"
-        else:
-            fn, name = self.lib.lb_rollout, "lb_rollout"
-        check(fn(self._h, model._h, ptr(traj), traj.shape[2], n_steps, ptr(pred), C.byref(nre)), name)
+        check(getattr(self.lib, model._ROLLOUT)(self._h, model._h, ptr(traj), traj.shape[2], n_steps, ptr(pred),
+                                                C.byref(nre)), model._ROLLOUT)
         self.version += 1
         st = self.stats()
         self.e_cap, self.cell_capacity = st["e_cap"], st["cell_capacity"]
@@ -468,10 +408,31 @@ class RolloutEngine:
         return out
 
 
-class GnsHandle:
-    def __init__(self, engine: RolloutEngine, h, desc: GnsDesc):
-        self.engine, self._h, self.desc = engine, h, desc
-        self._tap = None
+class _Handle:
+    """An engine-side object (a model or its training state) made from a blob of n_floats weights on `engine`; the
+    subclass names its destroy symbol (and a model handle its rollout symbol)."""
+    _DESTROY = ""
+
+    def __init__(self, engine: RolloutEngine, h, desc, n_floats: int):
+        self.engine, self._h, self.desc, self.n_floats = engine, h, desc, int(n_floats)
+
+    def close(self):
+        if self._h:
+            if self.engine._h:
+                torch.cuda.synchronize(self.engine.device)
+            getattr(self.engine.lib, self._DESTROY)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GnsHandle(_Handle):
+    _DESTROY, _ROLLOUT = "lb_gns_destroy", "lb_rollout"
+    _tap = None
 
     def set_tap(self, on: bool = True) -> Optional[torch.Tensor]:
         e = self.engine
@@ -486,25 +447,10 @@ class GnsHandle:
         check(e.lib.lb_gns_set_tap(self._h, None))
         return None
 
-    def close(self):
-        if self._h:
-            if self.engine._h:
-                torch.cuda.synchronize(self.engine.device)
-            self.engine.lib.lb_gns_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GnsTrainHandle:
+class GnsTrainHandle(_Handle):
     """trainer.py:35-89 on the device: value_and_grad of _mse summed over the batch + optax.adamw."""
-
-    def __init__(self, engine: RolloutEngine, h, desc: GnsDesc, n_floats: int):
-        self.engine, self._h, self.desc, self.n_floats = engine, h, desc, int(n_floats)
+    _DESTROY = "lb_gns_train_destroy"
 
     def loss_grad(self, target: torch.Tensor, loss_weight: float = 1.0, want_pred: bool = False):
         """target (B, N, dim) normalised accelerations -> mean per-trajectory loss (float); gradients accumulate."""
@@ -544,19 +490,6 @@ class GnsTrainHandle:
         check(self.engine.lib.lb_gns_train_write(self._h, idx, blob.ctypes.data_as(C.POINTER(C.c_float)),
                                                  C.c_int64(blob.size), C.c_int64(step)), "lb_gns_train_write")
 
-    def close(self):
-        if self._h:
-            if self.engine._h:
-                torch.cuda.synchronize(self.engine.device)
-            self.engine.lib.lb_gns_train_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class EgnnTrainHandle(GnsTrainHandle):
     """trainer.py:35-89 for EGNN: _mse over the model's three outputs pos / vel / acc (models/egnn.py:361-369)."""
@@ -581,10 +514,9 @@ class EgnnTrainHandle(GnsTrainHandle):
         return (loss.value, pred) if want_pred else loss.value
 
 
-class SegnnHandle:
-    def __init__(self, engine: RolloutEngine, h, desc: SegnnDesc):
-        self.engine, self._h, self.desc = engine, h, desc
-        self._tap = None
+class SegnnHandle(_Handle):
+    _DESTROY, _ROLLOUT = "lb_segnn_destroy", "lb_segnn_rollout"
+    _tap = None
 
     def set_tap(self, on: bool = True) -> Optional[torch.Tensor]:
         e = self.engine
@@ -598,24 +530,10 @@ class SegnnHandle:
             check(e.lib.lb_segnn_set_tap(self._h, None))
         return self._tap
 
-    def close(self):
-        if self._h:
-            if self.engine._h:
-                torch.cuda.synchronize(self.engine.device)
-            self.engine.lib.lb_segnn_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class EgnnHandle:
-    def __init__(self, engine: RolloutEngine, h, desc: EgnnDesc):
-        self.engine, self._h, self.desc = engine, h, desc
-        self._tap = None
+class EgnnHandle(_Handle):
+    _DESTROY, _ROLLOUT = "lb_egnn_destroy", "lb_egnn_rollout"
+    _tap = None
 
     def set_tap(self, on: bool = True) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
         """Per-layer taps: (h (L+1, B*N, hidden), positions (L+1, B*N, dim)) fp32, filled by every forward."""
@@ -630,24 +548,10 @@ class EgnnHandle:
             check(e.lib.lb_egnn_set_tap(self._h, None, None), "lb_egnn_set_tap")
         return self._tap
 
-    def close(self):
-        if self._h:
-            if self.engine._h:
-                torch.cuda.synchronize(self.engine.device)
-            self.engine.lib.lb_egnn_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PainnHandle:
-    def __init__(self, engine: RolloutEngine, h, desc: PainnDesc):
-        self.engine, self._h, self.desc = engine, h, desc
-        self._tap = None
+class PainnHandle(_Handle):
+    _DESTROY, _ROLLOUT = "lb_painn_destroy", "lb_painn_rollout"
+    _tap = None
 
     def set_tap(self, on: bool = True) -> Optional[Tuple[torch.Tensor, torch.Tensor]]:
         """Per-layer taps: (s (L+1, B*N, hidden), v (L+1, B*N, dim, hidden)) fp32, filled by every forward."""
@@ -661,16 +565,3 @@ class PainnHandle:
             self._tap = None
             check(e.lib.lb_painn_set_tap(self._h, None, None), "lb_painn_set_tap")
         return self._tap
-
-    def close(self):
-        if self._h:
-            if self.engine._h:
-                torch.cuda.synchronize(self.engine.device)
-            self.engine.lib.lb_painn_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -26,10 +26,7 @@ import torch
 from ..case_setup.features import FeatureDict, NeighborList
 from .._lib import LB_FORCE_BUFFER
 from ..defaults import defaults, merge
-from ..models.egnn import EGNN
-from ..models.gns import GNS
-from ..models.painn import PaiNN
-from ..models.segnn import SEGNN
+from ..models.base import BaseModel
 from ..utils import broadcast_from_batch, broadcast_to_batch, get_kinematic_mask
 from .metrics import MetricsComputer, MetricsDict
 from .utils import write_vtk
@@ -50,12 +47,13 @@ def _forward_eval(params, state, sample, current_positions, target_positions, mo
     return current_positions, state
 
 
-def _gns_of(model_apply) -> Optional[GNS]:
+def _gns_of(model_apply) -> Optional[BaseModel]:
+    """The device model whose apply `model_apply` is (the fused path rolls its handle out), or None."""
     fn = model_apply
     while isinstance(fn, partial):
         fn = fn.func
     owner = getattr(fn, "__self__", None)
-    return owner if isinstance(owner, (GNS, SEGNN, EGNN, PaiNN)) else None
+    return owner if isinstance(owner, BaseModel) else None
 
 
 def _eval_batched_rollout(forward_eval_vmap: Callable, preprocess_eval_vmap: Callable, case, params, state,
@@ -89,8 +87,7 @@ def _eval_batched_rollout(forward_eval_vmap: Callable, preprocess_eval_vmap: Cal
         eng.set_particle_type(ptype)
         if neighbors is not None and (eng.e_cap, eng.cell_capacity) != (neighbors.max_occupancy, neighbors.cell_capacity):
             eng.nl_set_capacity(neighbors.cell_capacity, neighbors.max_occupancy)
-        h = gns.handle(eng, params, state) if isinstance(gns, PaiNN) else gns.handle(eng, params)
-        predictions_batch, n_realloc = eng.rollout(h, traj, traj_len)
+        predictions_batch, n_realloc = eng.rollout(gns.handle(eng, params, state), traj, traj_len)
         if n_realloc:
             print(f"(eval) Reallocated the neighbors list {n_realloc}x; capacity now (2, {eng.e_cap})")
         eng.load_window(traj, t0=0, step=0)  # leave a defined state behind for the returned list
@@ -230,20 +227,10 @@ def infer(model, case, data_test, params=None, state=None, load_ckp: Optional[st
     if n_trajs == -1:
         n_trajs = data_test.num_samples
     if params is None:
-        # rollout.py:359 load_haiku(load_ckp); a Haiku-named GNS tree is mapped onto the engine's layout
-        from ..utils import gns_params_from_haiku, load_haiku
+        # rollout.py:359 load_haiku(load_ckp); a Haiku-named tree is mapped onto the engine's layout
+        from ..utils import load_haiku
         params, state, _, _ = load_haiku(load_ckp)
-        if isinstance(model, GNS) and "enc_node/linear_0" not in params:
-            params = gns_params_from_haiku(params, model._mp_steps, model._blocks_per_step)
-        if isinstance(model, SEGNN) and "embedding_nodes" not in params:
-            from ..utils import segnn_params_from_haiku
-            params = segnn_params_from_haiku(params, model)
-        if isinstance(model, EGNN) and "scalar_emb" not in params:
-            from ..utils import egnn_params_from_haiku
-            params = egnn_params_from_haiku(params, model)
-        if isinstance(model, PaiNN) and "scalar_embedding" not in params:
-            from ..utils import painn_params_from_haiku
-            params = painn_params_from_haiku(params, model)
+        params = model.params_from_haiku(params)
     if state is None:
         state = {}
     loader_test = _Loader(data_test, cfg.batch_size)

@@ -26,7 +26,8 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .._lib import EgnnDesc
-from ..utils import NodeType
+from ..engine import EgnnHandle, EgnnTrainHandle
+from ..utils import NodeType, egnn_params_from_haiku, egnn_params_to_haiku
 from .base import BaseModel
 
 
@@ -70,7 +71,7 @@ class EGNN(BaseModel):
         self._normalization_stats = normalization_stats
         self._n_vels = n_vels
         self._homogeneous_particles = homogeneous_particles
-        self._handles: Dict[Tuple[int, int], Tuple[object, object, tuple]] = {}
+        self._handles: Dict[Tuple[int, int], tuple] = {}
 
     # ------------------------------------------------------------------ parameters
     def node_in(self) -> int:
@@ -151,57 +152,32 @@ class EGNN(BaseModel):
         d.residual, d.normalize, d.tanh_pos = int(bool(self._residual)), int(bool(self._normalize)), int(bool(self._tanh))
         return d
 
-    # ------------------------------------------------------------------ training
-    def train_handle(self, engine, params):
-        """Device-resident training state for `params` on `engine` (csrc/lb_train_egnn.h): ``loss_grad(targets,
-        loss_weight, want_pred=False)`` takes the case's {"pos", "vel", "acc"} targets and the loss weights."""
-        if self._normalize:
-            raise NotImplementedError(self.NORMALIZE_REFUSAL)
-        return engine.egnn_train_create(self._desc(), self.flatten(params))
+    # ------------------------------------------------------------------ engine binding (models/base.py)
+    _FORWARD, _OUTPUT, _HAIKU_KEY = "egnn_forward", "pos", "scalar_emb"
 
+    def _create(self, engine, params, state):
+        return engine._new_handle(EgnnHandle, "lb_egnn_create", self._desc(), self.flatten(params))
+
+    def _from_haiku(self, hk_params):
+        return egnn_params_from_haiku(hk_params, self)
+
+    def _to_haiku(self, params):
+        return egnn_params_to_haiku(params, self)
+
+    # ------------------------------------------------------------------ training
     NORMALIZE_REFUSAL = ("EGNN training with normalize=True is not built: every radius graph holds self-edges, and the "
                          "derivative of coord_diff / (sqrt(radial) + 1e-8) at radial = 0 is 0 * inf - the reference's own "
                          "gradient is NaN for num_mp_steps >= 2 (inference runs it)")
 
-    # ------------------------------------------------------------------ engine binding
-    @staticmethod
-    def _fingerprint(params) -> tuple:
-        """Content stamp of a parameter tree (models/gns.py): an in-place edit must not reuse a stale device copy."""
-        out = []
-        for mod in sorted(params):
-            for leaf in sorted(params[mod]):
-                a = np.asarray(params[mod][leaf])
-                flat = a.reshape(-1)
-                out.append((mod, leaf, a.shape, float(flat.sum(dtype=np.float64)),
-                            float(flat[:: max(1, flat.size // 7)].astype(np.float64).sum())))
-        return tuple(out)
+    def check_trainable(self) -> None:
+        if self._normalize:
+            raise NotImplementedError(self.NORMALIZE_REFUSAL)
 
-    _MAX_HANDLES = 4  # device copies kept per model object (LRU), as models/gns.py
+    def _train_create(self, engine, params):
+        """csrc/lb_train_egnn.h: ``loss_grad(targets, loss_weight, want_pred=False)`` takes the case's {"pos", "vel",
+        "acc"} targets and the loss weights."""
+        return engine._new_handle(EgnnTrainHandle, "lb_egnn_train_create", self._desc(), self.flatten(params))
 
-    def handle(self, engine, params):
-        key = (id(engine), id(params))
-        hit = self._handles.get(key)
-        stamp = self._fingerprint(params)
-        if hit is not None and hit[1] is params and hit[2] == stamp and hit[0].engine is engine:
-            self._handles[key] = self._handles.pop(key)  # most recently used last
-            return hit[0]
-        self._handles.pop(key, None)
-        while len(self._handles) >= self._MAX_HANDLES:
-            self._handles.pop(next(iter(self._handles)))
-        h = engine.egnn_create(self._desc(), self.flatten(params))
-        self._handles[key] = (h, params, stamp)
-        return h
-
-    def apply(self, params, state, sample):
-        features, particle_type = sample
-        engine = getattr(features, "engine", None)
-        if engine is None:
-            raise TypeError("EGNN.apply needs the FeatureDict returned by case.preprocess_eval/"
-                            "allocate_eval (it names the engine state to run on)")
-        if features.version != engine.version:
-            raise RuntimeError("features are stale: the engine state changed since they were produced")
-        pos = engine.egnn_forward(self.handle(engine, params))
-        return {"pos": pos if features.batched else pos[0]}, state
-
-    def __call__(self, params, state, sample):
-        return self.apply(params, state, sample)
+    def loss_grad(self, th, target, loss_weight) -> float:
+        """_mse over every output the model predicts (pos, vel, acc)."""
+        return th.loss_grad(target, loss_weight)

@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from .._lib import GnsDesc
-from ..utils import NodeType
+from ..engine import GnsHandle, GnsTrainHandle
+from ..utils import NodeType, gns_params_from_haiku, gns_params_to_haiku
 from .base import BaseModel
 
 
@@ -44,7 +45,7 @@ class GNS(BaseModel):
         self._mp_steps = num_mp_steps
         self._num_particle_types = num_particle_types
         self._embedding_size = particle_type_embedding_size
-        self._handles: Dict[Tuple[int, int], Tuple[object, object]] = {}
+        self._handles: Dict[Tuple[int, int], tuple] = {}
 
     # ------------------------------------------------------------------ parameters
     def _widths(self, features) -> Tuple[int, int]:
@@ -129,62 +130,34 @@ class GNS(BaseModel):
         assert o == blob.size, (o, blob.size)
         return out
 
-    def train_handle(self, engine, params):
-        """Device-resident training state for `params` on `engine` (csrc/lb_train.hip)."""
+    # ------------------------------------------------------------------ engine binding (models/base.py)
+    _FORWARD, _OUTPUT, _HAIKU_KEY = "gns_forward", "acc", "enc_node/linear_0"
+
+    def _desc(self, engine) -> GnsDesc:
         d = GnsDesc()
         d.latent_size, d.blocks_per_step, d.num_mp_steps = self._latent_size, self._blocks_per_step, self._mp_steps
         d.embedding_size, d.num_particle_types = self._embedding_size, self._num_particle_types
         d.node_in, d.edge_in, d.out_dim = engine.node_in, engine.dim + 1, self._output_size
-        return engine.gns_train_create(d, self.flatten(params))
+        return d
 
-    # ------------------------------------------------------------------ engine binding
-    @staticmethod
-    def _fingerprint(params) -> tuple:
-        """Cheap content stamp of a parameter tree (a few strided samples + the sum of every leaf): an
-        in-place update of the weights (an optimiser step, a test editing one bias) must not reuse the
-        device copy made for the old values."""
-        out = []
-        for mod in sorted(params):
-            for leaf in sorted(params[mod]):
-                a = np.asarray(params[mod][leaf])
-                flat = a.reshape(-1)
-                out.append((mod, leaf, a.shape, float(flat.sum(dtype=np.float64)),
-                            float(flat[:: max(1, flat.size // 7)].astype(np.float64).sum())))
-        return tuple(out)
+    def _create(self, engine, params, state):
+        return engine._new_handle(GnsHandle, "lb_gns_create", self._desc(engine), self.flatten(params))
 
-    _MAX_HANDLES = 4  # device copies kept per model object (LRU): a training loop that hands over a fresh
-    #                   parameter tree every step must not accumulate one packed weight blob per step
+    def _from_haiku(self, hk_params):
+        return gns_params_from_haiku(hk_params, self._mp_steps, self._blocks_per_step)
 
-    def handle(self, engine, params):
-        key = (id(engine), id(params))
-        hit = self._handles.get(key)
-        stamp = self._fingerprint(params)
-        if hit is not None and hit[1] is params and hit[2] == stamp and hit[0].engine is engine:
-            self._handles[key] = self._handles.pop(key)  # most recently used last
-            return hit[0]
-        self._handles.pop(key, None)
-        while len(self._handles) >= self._MAX_HANDLES:
-            # drop OUR reference to the least recently used handle: GnsHandle.__del__ frees the device blob
-            # once no caller holds it any more
-            self._handles.pop(next(iter(self._handles)))
-        d = GnsDesc()
-        d.latent_size, d.blocks_per_step, d.num_mp_steps = self._latent_size, self._blocks_per_step, self._mp_steps
-        d.embedding_size, d.num_particle_types = self._embedding_size, self._num_particle_types
-        d.node_in, d.edge_in, d.out_dim = engine.node_in, engine.dim + 1, self._output_size
-        h = engine.gns_create(d, self.flatten(params))
-        self._handles[key] = (h, params, stamp)
-        return h
+    def _to_haiku(self, params):
+        return gns_params_to_haiku(params, self._mp_steps, self._blocks_per_step)
 
-    def apply(self, params, state, sample):
-        features, particle_type = sample
-        engine = getattr(features, "engine", None)
-        if engine is None:
-            raise TypeError("GNS.apply needs the FeatureDict returned by case.preprocess_eval/"
-                            "allocate_eval (it names the engine state to run on)")
-        if features.version != engine.version:
-            raise RuntimeError("features are stale: the engine state changed since they were produced")
-        acc = engine.gns_forward(self.handle(engine, params))
-        return {"acc": acc if features.batched else acc[0]}, state
+    # ------------------------------------------------------------------ training
+    def check_trainable(self) -> None:
+        if not 4 <= self._latent_size <= 128 or not 2 <= self._blocks_per_step <= 8:
+            # csrc/lb_train.hip: the training step runs on 128-wide rows (narrower latents are zero-padded) with two to
+            # eight Linears per MLP
+            raise NotImplementedError(
+                f"training is built for GNS with latent_size <= 128 and 2 <= num_mlp_layers <= 8 (got latent_size "
+                f"{self._latent_size}, num_mlp_layers {self._blocks_per_step}); inference runs every size")
 
-    def __call__(self, params, state, sample):
-        return self.apply(params, state, sample)
+    def _train_create(self, engine, params):
+        """csrc/lb_train.hip."""
+        return engine._new_handle(GnsTrainHandle, "lb_gns_train_create", self._desc(engine), self.flatten(params))

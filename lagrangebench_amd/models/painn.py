@@ -30,7 +30,8 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .._lib import PainnDesc
-from ..utils import NodeType
+from ..engine import PainnHandle
+from ..utils import NodeType, painn_params_from_haiku, painn_params_to_haiku
 from .base import BaseModel
 from .egnn import _is_silu
 
@@ -96,7 +97,7 @@ class PaiNN(BaseModel):
         self._shared_interactions = shared_interactions
         self._shared_filters = shared_filters
         self._eps = eps
-        self._handles: Dict[Tuple[int, int], Tuple[object, object, tuple]] = {}
+        self._handles: Dict[Tuple[int, int], tuple] = {}
 
     # ------------------------------------------------------------------ parameters
     def n_scalars(self) -> int:
@@ -217,45 +218,14 @@ class PaiNN(BaseModel):
         d.cutoff = self.cutoff_fn.cutoff if self.cutoff_fn is not None else 0.0
         return d
 
-    # ------------------------------------------------------------------ engine binding
-    @staticmethod
-    def _fingerprint(tree) -> tuple:
-        """Content stamp of a parameter tree (models/gns.py): an in-place edit must not reuse a stale device copy."""
-        out = []
-        for mod in sorted(tree or {}):
-            for leaf in sorted(tree[mod]):
-                a = np.asarray(tree[mod][leaf])
-                flat = a.reshape(-1)
-                out.append((mod, leaf, a.shape, float(flat.sum(dtype=np.float64)),
-                            float(flat[:: max(1, flat.size // 7)].astype(np.float64).sum())))
-        return tuple(out)
+    # ------------------------------------------------------------------ engine binding (models/base.py)
+    _FORWARD, _OUTPUT, _HAIKU_KEY = "painn_forward", "acc", "scalar_embedding"
 
-    _MAX_HANDLES = 4  # device copies kept per model object (LRU), as models/gns.py
+    def _create(self, engine, params, state):
+        return engine._new_handle(PainnHandle, "lb_painn_create", self._desc(), self.flatten(params, state))
 
-    def handle(self, engine, params, state=None):
-        key = (id(engine), id(params))
-        hit = self._handles.get(key)
-        stamp = (self._fingerprint(params), self._fingerprint(state))
-        if hit is not None and hit[1] is params and hit[2] == stamp and hit[0].engine is engine:
-            self._handles[key] = self._handles.pop(key)  # most recently used last
-            return hit[0]
-        self._handles.pop(key, None)
-        while len(self._handles) >= self._MAX_HANDLES:
-            self._handles.pop(next(iter(self._handles)))
-        h = engine.painn_create(self._desc(), self.flatten(params, state))
-        self._handles[key] = (h, params, stamp)
-        return h
+    def _from_haiku(self, hk_params):
+        return painn_params_from_haiku(hk_params, self)
 
-    def apply(self, params, state, sample):
-        features, particle_type = sample
-        engine = getattr(features, "engine", None)
-        if engine is None:
-            raise TypeError("PaiNN.apply needs the FeatureDict returned by case.preprocess_eval/"
-                            "allocate_eval (it names the engine state to run on)")
-        if features.version != engine.version:
-            raise RuntimeError("features are stale: the engine state changed since they were produced")
-        acc = engine.painn_forward(self.handle(engine, params, state))
-        return {"acc": acc if features.batched else acc[0]}, state
-
-    def __call__(self, params, state, sample):
-        return self.apply(params, state, sample)
+    def _to_haiku(self, params):
+        return painn_params_to_haiku(params, self)

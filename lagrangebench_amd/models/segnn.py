@@ -28,6 +28,8 @@ from typing import Dict, List, Tuple
 import numpy as np
 
 from .._lib import SegnnDesc
+from ..engine import GnsTrainHandle, SegnnHandle
+from ..utils import segnn_params_from_haiku, segnn_params_to_haiku
 from .base import BaseModel
 
 
@@ -130,7 +132,7 @@ class SEGNN(BaseModel):
         self._n_vels = n_vels
         self._velocity_aggregate = velocity_aggregate
         self._homogeneous_particles = homogeneous_particles
-        self._handles: Dict[Tuple[int, int], Tuple[object, object]] = {}
+        self._handles: Dict[Tuple[int, int], tuple] = {}
 
     # ------------------------------------------------------------------ parameters
     def block_shapes(self) -> List[Tuple[str, int, int, int]]:
@@ -259,36 +261,25 @@ class SEGNN(BaseModel):
                                                                 float(self.norm_eps))
         return d
 
-    def train_handle(self, engine, params):
-        """Device-resident training state for `params` on `engine` (csrc/lb_train_segnn.h, round 5)."""
+    # ------------------------------------------------------------------ engine binding (models/base.py)
+    _FORWARD, _OUTPUT, _HAIKU_KEY = "segnn_forward", "acc", "embedding_nodes"
+
+    def _create(self, engine, params, state):
+        return engine._new_handle(SegnnHandle, "lb_segnn_create", self._desc(), self.flatten(params))
+
+    def _from_haiku(self, hk_params):
+        return segnn_params_from_haiku(hk_params, self)
+
+    def _to_haiku(self, params):
+        return segnn_params_to_haiku(params, self)
+
+    # ------------------------------------------------------------------ training
+    def check_trainable(self) -> None:
         if self.generic:
-            raise NotImplementedError("SEGNN training is built for the shipped configuration (scalar_units 64, lmax 1, norm None)")
-        return engine.segnn_train_create(self._desc(), self.flatten(params))
+            raise NotImplementedError("training is built for SEGNN in the shipped configuration (scalar_units 64, "
+                                      "lmax_hidden = lmax_attributes = 1, norm None); the other switches are "
+                                      "inference-only (csrc/lb_segnn_gen.hip)")
 
-    # ------------------------------------------------------------------ engine binding
-    def handle(self, engine, params):
-        key = (id(engine), id(params))
-        hit = self._handles.get(key)
-        if hit is not None and hit[1] is params and hit[0].engine is engine:
-            self._handles[key] = self._handles.pop(key)
-            return hit[0]
-        self._handles.pop(key, None)
-        while len(self._handles) >= 4:  # LRU: at most four device copies per model object (models/gns.py)
-            self._handles.pop(next(iter(self._handles)))
-        h = engine.segnn_create(self._desc(), self.flatten(params))
-        self._handles[key] = (h, params)
-        return h
-
-    def apply(self, params, state, sample):
-        features, particle_type = sample
-        engine = getattr(features, "engine", None)
-        if engine is None:
-            raise TypeError("SEGNN.apply needs the FeatureDict returned by case.preprocess_eval/"
-                            "allocate_eval (it names the engine state to run on)")
-        if features.version != engine.version:
-            raise RuntimeError("features are stale: the engine state changed since they were produced")
-        acc = engine.segnn_forward(self.handle(engine, params))
-        return {"acc": acc if features.batched else acc[0]}, state
-
-    def __call__(self, params, state, sample):
-        return self.apply(params, state, sample)
+    def _train_create(self, engine, params):
+        """csrc/lb_train_segnn.h: the handle is the GNS one (lb_gns_train_loss_grad dispatches on it)."""
+        return engine._new_handle(GnsTrainHandle, "lb_segnn_train_create", self._desc(), self.flatten(params))

@@ -34,11 +34,8 @@ import torch
 from ..defaults import defaults, merge
 from ..evaluate import MetricsComputer, averaged_metrics, eval_rollout
 from ..evaluate.rollout import _Loader
-from ..models.egnn import EGNN
-from ..models.gns import GNS
-from ..utils import (broadcast_from_batch, egnn_params_from_haiku, egnn_params_to_haiku, get_kinematic_mask,
-                     gns_params_from_haiku, gns_params_to_haiku, load_haiku, save_haiku, segnn_params_from_haiku,
-                     segnn_params_to_haiku)
+from ..models.base import BaseModel
+from ..utils import broadcast_from_batch, get_kinematic_mask, load_haiku, save_haiku
 from .strats import push_forward_build, push_forward_sample_steps
 
 
@@ -65,25 +62,9 @@ class _ShuffledLoader:
 
 
 class Trainer:
-    def __init__(self, model: GNS, case, data_train, data_valid, cfg_train=None, cfg_eval=None, cfg_logging=None,
+    def __init__(self, model: BaseModel, case, data_train, data_valid, cfg_train=None, cfg_eval=None, cfg_logging=None,
                  input_seq_length: int = defaults.model.input_seq_length, seed: int = defaults.seed):
-        if isinstance(model, GNS) and (not 4 <= model._latent_size <= 128 or not 2 <= model._blocks_per_step <= 8):
-            # fail HERE, before datasets and neighbor lists are set up (csrc/lb_train.hip: the training step runs on
-            # 128-wide rows - narrower latents are zero-padded - with two to eight Linears per MLP)
-            raise NotImplementedError(
-                f"training is built for GNS with latent_size <= 128 and 2 <= num_mlp_layers <= 8 (got latent_size "
-                f"{model._latent_size}, num_mlp_layers {model._blocks_per_step}); inference runs every size")
-        if getattr(model, "generic", False):
-            raise NotImplementedError("training is built for SEGNN in the shipped configuration (scalar_units 64, lmax_hidden = "
-                                      "lmax_attributes = 1, norm None); the other switches are inference-only "
-                                      "(csrc/lb_segnn_gen.hip)")
-        if isinstance(model, EGNN) and model._normalize:
-            raise NotImplementedError(EGNN.NORMALIZE_REFUSAL)
-        if not hasattr(model, "train_handle"):
-            raise NotImplementedError("Trainer: the model has no device training step (GNS: csrc/lb_train.hip, SEGNN: "
-                                      "csrc/lb_train_segnn.h, EGNN: csrc/lb_train_egnn.h)")
-        self._is_gns = isinstance(model, GNS)
-        self._is_egnn = isinstance(model, EGNN)
+        model.check_trainable()   # fail HERE, before datasets and neighbor lists are set up
         self.model, self.case, self.input_seq_length = model, case, input_seq_length
         self.cfg_train = merge(defaults.train, cfg_train)
         self.cfg_eval = merge(defaults.eval, cfg_eval)
@@ -129,12 +110,7 @@ class Trainer:
             state = {} if state is None else state
         elif load_ckp:
             params, state, opt_state, step = load_haiku(load_ckp)
-            if self._is_gns and "enc_node/linear_0" not in params:
-                params = gns_params_from_haiku(params, model._mp_steps, model._blocks_per_step)
-            elif self._is_egnn and "scalar_emb" not in params:
-                params = egnn_params_from_haiku(params, model)
-            elif not self._is_gns and not self._is_egnn and "embedding_nodes" not in params:
-                params = segnn_params_from_haiku(params, model)
+            params = model.params_from_haiku(params)
         else:
             params, state = model.init(torch.randint(0, 2**31 - 1, (1,), generator=key).numpy(), (features, raw_sample[1]))
         B = self.loader_train.batch_size
@@ -144,7 +120,6 @@ class Trainer:
             # `count` = AdamW steps taken (optax's count); checkpoints of round 3 only carried the loop index `step`
             th.write("v", np.asarray(opt_state["v"], np.float32), step=int(opt_state.get("count", opt_state.get("step", step))))
         o = cfg_train.optimizer
-        lw = float(self.loss_weight.get("acc", 1.0))
 
         def current_params():
             return model.unflatten(th.read("weights"), params)
@@ -186,10 +161,7 @@ class Trainer:
                 # value_and_grad of _mse vmapped over the batch, gradients summed, loss averaged (trainer.py:63-89) +
                 # optax.adamw(lr(step), weight_decay 1e-8): on the engine's current window / neighbor list
                 th.zero_grad()
-                if self._is_egnn:   # _mse over every output the model predicts (pos, vel, acc)
-                    loss = th.loss_grad(target_batch, self.loss_weight)
-                else:
-                    loss = th.loss_grad(target_batch["acc"], lw)
+                loss = model.loss_grad(th, target_batch, self.loss_weight)
                 th.adamw_step(self._lr(step), 0.9, 0.999, 1e-8, float(getattr(o, "weight_decay", 1e-8)))
 
                 if step % cfg_logging.log_steps == 0:
@@ -205,10 +177,7 @@ class Trainer:
                                                 rollout_dir=cfg_eval.rollout_dir, out_type=cfg_eval.train.out_type)
                     metrics = averaged_metrics(eval_metrics)
                     if store_ckp is not None:
-                        hk = (gns_params_to_haiku(params_np, model._mp_steps, model._blocks_per_step) if self._is_gns
-                              else egnn_params_to_haiku(params_np, model) if self._is_egnn
-                              else segnn_params_to_haiku(params_np, model))
-                        save_haiku(store_ckp, hk, state, opt_state_dict(), {"step": step, "loss": metrics.get("val/loss", None)})
+                        save_haiku(store_ckp, model.params_to_haiku(params_np), state, opt_state_dict(), {"step": step, "loss": metrics.get("val/loss", None)})
                     print(metrics)
                     # the validation rollouts re-sized / re-used the engine: the training list is rebuilt
                     key, _, _, neighbors = case.allocate(key, raw_sample)
