@@ -229,6 +229,11 @@ int64_t lb_gns_train_step_count(lb_gns_train* t);
  * (tests/test_train.py).  LB_TRAIN_MATH=f32 in the environment at handle creation selects the exact-fp32 MFMA kernels
  * throughout (1.7x slower).  This returns how many steps were repeated so far. */
 int32_t lb_gns_train_math_fallbacks(lb_gns_train* t);
+/* Training steps repeated with a radix sort of the senders: the sender-sorted view of a step is built by transposing the
+ * receiver rows, which needs every edge's transpose; a list with an edge in one direction only (a pair within one rounding
+ * of the cutoff: the periodic displacement is not exactly antisymmetric) sends the step to the sort.  Gradients are the
+ * same either way. */
+int32_t lb_gns_train_sort_fallbacks(lb_gns_train* t);
 
 typedef struct lb_segnn lb_segnn;
 
@@ -307,8 +312,9 @@ int lb_egnn_create(lb_engine* eng, const lb_egnn_desc* desc, const float* weight
                    lb_egnn** out);
 void lb_egnn_destroy(lb_egnn* egnn);
 /* EGNN.__call__ -> {"pos"} on the current window + list: (B,N,dim) fp64 holding the fp32 positions (fp64 so that
- * rollout.py's window keeps its dtype, as the reference's promotion does).  LB_ERR_STATE if an edge of the list has no
- * transposed edge (the position update sums over senders through the transpose).  Host-synchronous. */
+ * rollout.py's window keeps its dtype, as the reference's promotion does).  The position update sums over senders: an
+ * edge held in one direction only (a pair within one rounding of the cutoff) is summed at its sender as the reference's
+ * segment_sum does.  Host-synchronous. */
 int lb_egnn_forward(lb_engine* eng, lb_egnn* egnn, double* pos_out_dev);
 /* Debug/parity taps: h after the embedding and after every layer ((L+1), B*N, hidden) fp32 and the positions at the same
  * points ((L+1), B*N, dim) fp32; NULL = off. */
@@ -331,8 +337,7 @@ int lb_egnn_train_create(lb_engine* eng, const lb_egnn_desc* desc, const float* 
  * sum over the outputs of w_k |pred_k - target_k|^2 (fp64 residuals), summed over dim, masked to the non-kinematic
  * particles, / their number; mean over the batch, gradients summed and ACCUMULATED (lb_gns_train_zero_grad).  Targets: device
  * (B*N, dim) fp64, the case's {pos, vel, acc}; a target may be NULL when its weight is 0.  pred_pos_out_dev (B*N, dim) fp32
- * or NULL: the prediction, bit-identical to lb_egnn_forward's.  LB_ERR_STATE (nothing accumulated) if an edge has no
- * transpose.  Host-synchronous. */
+ * or NULL: the prediction, bit-identical to lb_egnn_forward's.  Host-synchronous. */
 int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
                             float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev);
 
@@ -372,8 +377,8 @@ typedef struct lb_painn_desc {
 int lb_painn_create(lb_engine* eng, const lb_painn_desc* desc, const float* weights_host, int64_t n_floats,
                     lb_painn** out);
 void lb_painn_destroy(lb_painn* painn);
-/* PaiNN.__call__ -> {"acc": (B,N,dim) fp32} on the current window + list.  LB_ERR_STATE if an edge of the list has no
- * transposed edge (the messages are summed over senders through the transpose).  Host-synchronous. */
+/* PaiNN.__call__ -> {"acc": (B,N,dim) fp32} on the current window + list.  The messages are summed over senders, edges
+ * held in one direction only included.  Host-synchronous. */
 int lb_painn_forward(lb_engine* eng, lb_painn* painn, float* acc_out_dev);
 /* Debug/parity taps: s after the embedding and after every layer ((L+1), B*N, hidden) fp32 and v at the same points
  * ((L+1), B*N, dim, hidden) fp32; NULL = off. */

@@ -52,6 +52,27 @@ __device__ __forceinline__ double lb_pos(const double* __restrict__ win, const l
 
 __device__ __forceinline__ int lb_lane() { return threadIdx.x & 63; }
 
+// The orphans of a neighbor list (lbk_edge_rev): edges held in one direction only, whose sender has no row slot for
+// them.  f(e) for every orphan e sent by node i, in ascending slot order whatever order they were appended in (a
+// selection over the whole list per orphan found: the list is empty on a symmetric list and a handful of slots
+// otherwise), so a sum over them is deterministic.
+template <class F>
+__device__ __forceinline__ void lb_for_orphans(const int32_t* __restrict__ orph, const int32_t* __restrict__ senders,
+                                               int64_t i, F&& f) {
+  const int n = orph[0];
+  int last = -1;
+  while (n > 0) {
+    int best = 0x7fffffff;
+    for (int o = 0; o < n; ++o) {
+      const int e = orph[1 + o];
+      if (e > last && e < best && senders[e] == i) best = e;
+    }
+    if (best == 0x7fffffff) break;
+    f(best);
+    last = best;
+  }
+}
+
 // range guard: raise flag bits and remember the first rollout step they were raised in
 __device__ __forceinline__ void lb_raise_math(const lb_ctrl* ctrl, int flags) {
   lb_ctrl* c = const_cast<lb_ctrl*>(ctrl);

@@ -15,13 +15,14 @@
 //   k_eg_prologue  node inputs |v_k| (+ one-hot), h0 = x W_emb + b, x32 (newest positions), vel (un-normalised last
 //                  velocity), node attribute |force|
 //   k_eg_rev       rev[e]: the slot of the transposed edge (r=s(e), s=r(e)), binary search in the sender-sorted row;
-//                  a missing transpose raises m->err (the host turns it into LB_ERR_STATE)
+//                  an edge without one gets rev = -1 and goes on the orphan list (lb_internal.h: lbk_edge_rev)
 //   per layer:
 //   k_eg_proj      [P_s | P_r] = h [W0[0:H] | W0[H:2H]]  (the first edge Linear split by input block)
 //   k_eg_edge      coord_diff = disp(x_s, x_r), radial; a = silu(P_s[s] + P_r[r] + radial w_rad + rel_dist w_ea + b0);
 //                  m = silu(a W1 + b1) -> msg; phi = silu(m Wx0 + bx0) . wx1 (+ tanh); trans = coord_diff phi
 //   k_eg_node      agg = sum of msg over the receiver row (row order); h' = [h +] silu([h|agg|attr] Wn0 + bn0) Wn1 + bn1;
-//                  psi = silu(h' Wv0 + bv0) . wv1; x <- shift(x, sum_{sender = i} trans) (through rev, row order);
+//                  psi = silu(h' Wv0 + bv0) . wv1; x <- shift(x, sum_{sender = i} trans) (through rev, row order,
+//                  then the orphans sent by i in slot order);
 //                  x <- shift(x, psi vel)
 //   k_eg_integrate (rollout step) kinematic select, window advance, prediction store, step counter
 #include <cmath>
@@ -55,11 +56,11 @@ struct lb_egnn {
   float* x32 = nullptr;    // [BN][4]
   float* vel = nullptr;    // [BN][4]
   float* nattr = nullptr;  // [BN]
-  lb_rev_err err;          // edges without a transpose
   int64_t e_alloc = 0;
   float* msg = nullptr;    // [e_alloc][H]
   float* trans = nullptr;  // [e_alloc][4]
   int32_t* rev = nullptr;  // [e_alloc]
+  int32_t* orph = nullptr; // [e_alloc + 1] edges without a transpose (count first)
   float* tap_h = nullptr;
   float* tap_x = nullptr;
 };
@@ -167,11 +168,13 @@ __global__ void __launch_bounds__(EG_THREADS)
 }
 
 // ------------------------------------------------------------------------ reverse edges
-// The radius graph is symmetric: edge e = (r, s) has a transpose (s, r), found by binary search in row s (senders
-// ascending inside a row: lb_neighbor.hip).
+// Edge e = (r, s) almost always has a transpose (s, r), found by binary search in row s (senders ascending inside a row:
+// lb_neighbor.hip).  A pair within one rounding of the cutoff can be an edge in one direction only (lb_internal.h:
+// lbk_edge_rev): e gets rev = -1 - row r's slot k = (r, s) has no edge sent by r to s - and goes on the orphan list,
+// since s does send e.  orph[0] is zero on entry.
 __global__ void k_eg_rev(const lb_ctrl* __restrict__ ctrl, int64_t cap, const int32_t* __restrict__ row_ptr,
                          const int32_t* __restrict__ senders, const int32_t* __restrict__ receivers,
-                         int32_t* __restrict__ rev, int32_t* __restrict__ err) {
+                         int32_t* __restrict__ rev, int32_t* __restrict__ orph) {
   if (ctrl->overflow_step >= 0) return;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int E = ctrl->n_edges_total;
@@ -191,45 +194,17 @@ __global__ void k_eg_rev(const lb_ctrl* __restrict__ ctrl, int64_t cap, const in
     if (v < r) lo = mid + 1;
     else hi = mid;
   }
-  if (found < 0) {
-    atomicAdd(err, 1);
-    found = (int)e;
-  }
+  if (found < 0) orph[1 + atomicAdd(orph, 1)] = (int32_t)e;   // at most E < cap appends
   rev[e] = found;
 }
 
-int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err) {
+int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* orph) {
   const int64_t ecap = (int64_t)e->e_cap * e->g.B;
   const unsigned nb = (unsigned)((ecap + 255) / 256);
+  LB_HIP(hipMemsetAsync(orph, 0, sizeof(int32_t), e->stream));
   hipLaunchKernelGGL(k_eg_rev, dim3(nb ? nb : 1), dim3(256), 0, e->stream, e->ctrl, ecap, e->row_ptr, e->senders,
-                     e->receivers, rev, err);
+                     e->receivers, rev, orph);
   LB_HIP(hipGetLastError());
-  return LB_OK;
-}
-
-int lb_rev_err_alloc(lb_rev_err* w) {
-  LB_TRY(lb_alloc(&w->dev, 1));
-  if (hipHostMalloc((void**)&w->host, sizeof(int32_t)) != hipSuccess) return lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
-  return LB_OK;
-}
-
-void lb_rev_err_free(lb_rev_err* w) {
-  if (w->dev) (void)hipFree(w->dev);
-  if (w->host) (void)hipHostFree(w->host);
-  *w = lb_rev_err{};
-}
-
-int lb_rev_err_reset(lb_engine* e, const lb_rev_err& w) {
-  LB_HIP(hipMemsetAsync(w.dev, 0, sizeof(int32_t), e->stream));
-  return LB_OK;
-}
-
-int lb_rev_err_check(lb_engine* e, const lb_rev_err& w, const char* model) {
-  LB_HIP(hipMemcpyAsync(w.host, w.dev, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipStreamSynchronize(e->stream));
-  if (*w.host)
-    return lb_fail(LB_ERR_STATE, "%s: %d edges of the neighbor list have no transposed edge (the sender sum needs a "
-                   "symmetric list)", model, *w.host);
   return LB_OK;
 }
 
@@ -390,6 +365,8 @@ struct lb_eg_node_args {
   float box[3];
   const int32_t* row_ptr;
   const int32_t* rev;
+  const int32_t* orph;
+  const int32_t* senders;
   const float* msg;
   const float* trans;
   const float* nattr;
@@ -495,7 +472,8 @@ __global__ void __launch_bounds__(EG_THREADS) k_eg_node(lb_eg_node_args a) {
     for (int t = 0; t < EG_TN; ++t) s_u[t][j] = j < H ? eg_silu(acc[t] + b) * w1 : 0.f;
   }
   eg_rowsum<EG_TN>(s_u, s_part, s_psi);
-  // positions: shift by the sender sum of trans (rev[k] over row i = the edges whose sender is i), then by psi * vel
+  // positions: shift by the sender sum of trans (rev[k] over row i, then the orphans sent by i = the edges whose sender
+  // is i), then by psi * vel
   if (j < EG_TN) {
     const int64_t i = base + j;
     if (i < a.BN) {
@@ -504,11 +482,19 @@ __global__ void __launch_bounds__(EG_THREADS) k_eg_node(lb_eg_node_args a) {
       k1 = k1 < E ? k1 : E;
       float d0 = 0.f, d1 = 0.f, d2 = 0.f;
       for (int k = k0; k < k1; ++k) {
-        const f32x4 tr = reinterpret_cast<const f32x4*>(a.trans)[a.rev[k]];
+        const int e = a.rev[k];
+        if (e < 0) continue;   // i does not send to the sender of slot k
+        const f32x4 tr = reinterpret_cast<const f32x4*>(a.trans)[e];
         d0 += tr[0];
         d1 += tr[1];
         d2 += tr[2];
       }
+      lb_for_orphans(a.orph, a.senders, i, [&](int e) {
+        const f32x4 tr = reinterpret_cast<const f32x4*>(a.trans)[e];
+        d0 += tr[0];
+        d1 += tr[1];
+        d2 += tr[2];
+      });
       const float psi = s_psi[j];
       float* x = a.x32 + i * 4;
       const float* v = a.vel + i * 4;
@@ -556,14 +542,15 @@ static int eg_ensure_edges(lb_egnn* m) {
   lb_engine* e = m->eng;
   if (m->e_alloc >= e->e_alloc && m->msg) return LB_OK;
   LB_HIP(hipStreamSynchronize(e->stream));
-  for (void* b : {(void*)m->msg, (void*)m->trans, (void*)m->rev})
+  for (void* b : {(void*)m->msg, (void*)m->trans, (void*)m->rev, (void*)m->orph})
     if (b) (void)hipFree(b);
   m->msg = m->trans = nullptr;
-  m->rev = nullptr;
+  m->rev = m->orph = nullptr;
   const size_t n = (size_t)e->e_alloc;
   LB_TRY(lb_alloc(&m->msg, n * m->desc.hidden));
   LB_TRY(lb_alloc(&m->trans, n * 4));
   LB_TRY(lb_alloc(&m->rev, n));
+  LB_TRY(lb_alloc(&m->orph, n + 1));
   m->e_alloc = e->e_alloc;
   return LB_OK;
 }
@@ -571,9 +558,8 @@ static int eg_ensure_edges(lb_egnn* m) {
 extern "C" void lb_egnn_destroy(lb_egnn* m) {
   if (!m) return;
   for (void* b : {(void*)m->blob, (void*)m->xnode, (void*)m->h, (void*)m->p, (void*)m->x32, (void*)m->vel,
-                  (void*)m->nattr, (void*)m->msg, (void*)m->trans, (void*)m->rev})
+                  (void*)m->nattr, (void*)m->msg, (void*)m->trans, (void*)m->rev, (void*)m->orph})
     if (b) (void)hipFree(b);
-  lb_rev_err_free(&m->err);
   delete m;
 }
 
@@ -648,7 +634,6 @@ extern "C" int lb_egnn_create(lb_engine* e, const lb_egnn_desc* d, const float* 
   step(lb_alloc(&m->x32, (size_t)BN * 4));
   step(lb_alloc(&m->vel, (size_t)BN * 4));
   step(lb_alloc(&m->nattr, (size_t)BN));
-  step(lb_rev_err_alloc(&m->err));
   if (rc) {
     lb_egnn_destroy(m);
     return rc;
@@ -679,7 +664,6 @@ int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev
   step(lb_alloc(&m->x32, (size_t)BN * 4));
   step(lb_alloc(&m->vel, (size_t)BN * 4));
   step(lb_alloc(&m->nattr, (size_t)BN));
-  step(lb_rev_err_alloc(&m->err));
   if (rc) {
     lb_egnn_destroy(m);
     return rc;
@@ -714,7 +698,7 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
   LB_TRY(lbk_node_features_raw(e, m->xnode, EG_KPAD));
   hipLaunchKernelGGL(k_eg_prologue, dim3(nb_t), dim3(EG_THREADS), 0, s, e->g, BN, e->ctrl, e->win, m->xnode, e->ptype, H,
                      m->desc.n_vels, m->desc.homogeneous, m->n_attr, m->w_emb, m->b_emb, m->h, m->x32, m->vel, m->nattr);
-  LB_TRY(lbk_edge_rev(e, m->rev, m->err.dev));
+  LB_TRY(lbk_edge_rev(e, m->rev, m->orph));
   lb_toc(e);
   LB_HIP(hipGetLastError());
   LB_TRY(tap(0));
@@ -760,6 +744,8 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
     for (int d = 0; d < 3; ++d) na.box[d] = box[d];
     na.row_ptr = e->row_ptr;
     na.rev = m->rev;
+    na.orph = m->orph;
+    na.senders = e->senders;
     na.msg = m->msg;
     na.trans = m->trans;
     na.nattr = m->nattr;
@@ -784,10 +770,10 @@ static int lbk_egnn_forward(lb_engine* e, lb_egnn* m) {
 extern "C" int lb_egnn_forward(lb_engine* e, lb_egnn* m, double* pos_out_dev) {
   LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
   LB_TRY(lb_forward_check(e, "lb_egnn_forward"));
-  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lbk_egnn_forward(e, m));
   if (pos_out_dev) LB_TRY(lb_export_rows(e, m->x32, pos_out_dev, true));
-  return lb_rev_err_check(e, m->err, "EGNN");
+  LB_HIP(hipStreamSynchronize(e->stream));
+  return LB_OK;
 }
 
 // one rollout step's model + integrator (lb_enqueue_step has set e->integ_job)
@@ -808,21 +794,19 @@ extern "C" int lb_egnn_rollout(lb_engine* e, lb_egnn* m, const double* traj_dev,
                                double* pred_out_dev, int32_t* n_realloc_out) {
   if (!traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
-  LB_TRY(lb_rev_err_reset(e, m->err));
-  LB_TRY(lb_rollout_generic(e, eg_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out));
-  return lb_rev_err_check(e, m->err, "EGNN");
+  return lb_rollout_generic(e, eg_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out);
 }
 
-// one forward as lb_egnn_forward runs it (no export); LB_ERR_STATE for an edge without a transpose.  Host-synchronous.
+// one forward as lb_egnn_forward runs it (no export).  Host-synchronous.
 int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st) {
   if (e->g.force_kind == LB_FORCE_BUFFER && !e->force)
     return lb_fail(LB_ERR_STATE, "LB_FORCE_BUFFER engine: call lb_set_force first");
-  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lbk_egnn_forward(e, m));
-  LB_TRY(lb_rev_err_check(e, m->err, "EGNN"));
+  LB_HIP(hipStreamSynchronize(e->stream));
   st->xnode = m->xnode;
   st->vel = m->vel;
   st->nattr = m->nattr;
   st->rev = m->rev;
+  st->orph = m->orph;
   return LB_OK;
 }

@@ -394,26 +394,22 @@ int lbk_sinkhorn_pot(lb_engine* e, const double* pred, int pred_T, const double*
 
 int lbk_node_features_raw(lb_engine* e, float* xnode, int kpad);
 
-// lb_egnn.hip: rev[e] = the slot of edge e's transpose for the first n_edges_total slots of the list (binary search in
-// the sender-sorted row); every edge without one adds 1 to *err and gets rev[e] = e.  rev: [e_cap * B] slots.
-int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* err);
-// ... the count it raises: a device word and its pinned host copy.  check: host-synchronous; a nonzero count is
-// LB_ERR_STATE "<model>: <count> edges of the neighbor list have no transposed edge ...".
-struct lb_rev_err {
-  int32_t* dev = nullptr;
-  int32_t* host = nullptr;
-};
-int lb_rev_err_alloc(lb_rev_err* w);
-void lb_rev_err_free(lb_rev_err* w);
-int lb_rev_err_reset(lb_engine* e, const lb_rev_err& w);
-int lb_rev_err_check(lb_engine* e, const lb_rev_err& w, const char* model);
+// lb_egnn.hip: the sum over the edges a node SENDS, through the receiver CSR.  For the first n_edges_total slots of the
+// list, rev[e] = the slot of edge e's transpose (binary search in the sender-sorted row), or -1 when the list holds e in
+// one direction only: a pair within one rounding of the cutoff (the periodic displacement is antisymmetric only up to
+// one rounding of x + L/2).  Such an edge e = (r, s) is an ORPHAN: s sends it, but row s has no slot for it.  orph[0] =
+// the number of orphans, orph[1 ..] their slots in append order (visit them with lb_for_orphans).  A sender sum is then
+// the row of i through rev[] (slots with rev = -1 skipped), then the orphans sent by i.  No host synchronisation; the
+// count is reset on the stream first.  rev: [e_cap * B] slots, orph: [e_cap * B + 1].
+int lbk_edge_rev(lb_engine* e, int32_t* rev, int32_t* orph);
 // ... and for the EGNN training step (lb_train_egnn.h): a model on a caller-owned device blob in lb_egnn_create's layout,
 // and one forward on it (taps through lb_egnn_set_tap) that hands back the state the backward reads
 struct lb_egnn_state {
   const float* xnode;    // [BN][64] raw node features (normalised velocities first)
   const float* vel;      // [BN][4] un-normalised last velocity
   const float* nattr;    // [BN] |force|
-  const int32_t* rev;    // [n_edges_total] slot of each edge's transpose
+  const int32_t* rev;    // [n_edges_total] slot of each edge's transpose, -1 if none
+  const int32_t* orph;   // orphan count and slots (lbk_edge_rev)
 };
 int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev, lb_egnn** out);
 int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st);

@@ -16,10 +16,11 @@
 //   k_pn_embed    s0 = [vel_mag (| one-hot)] W_se + b, v0[d] = [v_0 .. v_{K-1} | force | bound_lo | bound_hi][d] W_ve
 //   k_pn_edge     per edge: norm = sqrt(|rel_disp|^2 + eps), dir = rel_disp / (norm + eps), the filter scale (cosine
 //                 cutoff or norm itself) and whether the edge is live (norm < cutoff; every edge without a cutoff)
-//   lbk_edge_rev  (lb_egnn.hip) the transposed edge of every edge: the sum over senders runs through the receiver CSR
+//   lbk_edge_rev  (lb_egnn.hip) the transposed edge of every edge: the sum over senders runs through the receiver CSR,
+//                 then over the few edges that have no transpose (orphans, lb_internal.h)
 //   per layer:
 //   k_pn_lin x2   x = silu(s Wi0 + bi0) Wi1 + bi1                              interaction block  (N x H -> N x 3H)
-//   k_pn_msg      per node i, the row of i in order, e = rev[e']: live edges only, W = (rbf(norm_e) Wf + bf) * scale_e
+//   k_pn_msg      per node i, the row of i in order, e = rev[e'], then i's orphans: live edges only, W = (rbf(norm_e) Wf + bf) * scale_e
 //                 (the layer's 3H filter columns, computed here), ds += W_s x_r, dv += W_v1 x_r dir_e + W_v2 x_r v_r
 //                 with r = receivers[e]; s += clip(ds), v += clip(dv)  (v to the other buffer: the old v is gathered)
 //   k_pn_lin      [v_l | v_r] = v W_vm                                          (N*dim x H -> N*dim x 2H)
@@ -78,9 +79,9 @@ struct lb_painn {
   float* h1 = nullptr;     // [BN][H]
   float* ts = nullptr;     // [BN][2H]
   float* vm = nullptr;     // [BN][dim][2H]
-  lb_rev_err err;          // edges without a transpose
   int64_t e_alloc = 0;
   int32_t* rev = nullptr;  // [e_alloc]
+  int32_t* orph = nullptr; // [e_alloc + 1] edges without a transpose (count first)
   f32x4* geo = nullptr;    // [e_alloc]: dir (3), filter scale (0 on a dead edge)
   float* nrm = nullptr;    // [e_alloc]: norm, or -1 on a dead edge
   float* tap_s = nullptr;
@@ -238,6 +239,8 @@ struct pn_msg_args {
   int H, dim, n_rbf, ldf, fcol;  // ldf = filter_net's output width, fcol = this layer's first filter column
   const int32_t* row_ptr;
   const int32_t* rev;
+  const int32_t* orph;
+  const int32_t* senders;
   const int32_t* receivers;
   const f32x4* geo;
   const float* nrm;
@@ -269,11 +272,11 @@ __global__ void __launch_bounds__(128) k_pn_msg(pn_msg_args a) {
     k0 = k0 < E ? k0 : E;
     k1 = k1 < E ? k1 : E;
     float ds = 0.f, dv0 = 0.f, dv1 = 0.f, dv2 = 0.f;
-    // the edges whose SENDER is i (painn.py:301-303 aggregates at senders): the transposes of row i, in row order
-    for (int k = k0; k < k1; ++k) {
-      const int e = a.rev[k];
+    // the edges whose SENDER is i (painn.py:301-303 aggregates at senders): the transposes of row i, in row order, then
+    // the orphans sent by i (edges without a transpose: lb_internal.h, lbk_edge_rev) in slot order
+    auto add = [&](int e) {
       const float norm = a.nrm[e];
-      if (norm < 0.f) continue;  // dead: the filter is exactly 0
+      if (norm < 0.f) return;  // dead: the filter is exactly 0
       const f32x4 gm = a.geo[e];
       const int r = a.receivers[e];
       float f0 = 0.f, f1 = 0.f, f2 = 0.f;
@@ -296,7 +299,12 @@ __global__ void __launch_bounds__(128) k_pn_msg(pn_msg_args a) {
       dv0 += wv1 * gm[0] + wv2 * vr[0];
       dv1 += wv1 * gm[1] + wv2 * vr[H];
       if (dim == 3) dv2 += wv1 * gm[2] + wv2 * vr[2 * H];
+    };
+    for (int k = k0; k < k1; ++k) {
+      const int e = a.rev[k];
+      if (e >= 0) add(e);   // (rev = -1: i does not send to the sender of slot k)
     }
+    lb_for_orphans(a.orph, a.senders, i, add);
     a.s[i * H + j] = a.s[i * H + j] + pn_clip(ds);
     const float* vi = a.vin + i * dim * H + j;
     float* vo = a.vout + i * dim * H + j;
@@ -413,13 +421,14 @@ static int pn_ensure_edges(lb_painn* m) {
   lb_engine* e = m->eng;
   if (m->e_alloc >= e->e_alloc && m->rev) return LB_OK;
   LB_HIP(hipStreamSynchronize(e->stream));
-  for (void* b : {(void*)m->rev, (void*)m->geo, (void*)m->nrm})
+  for (void* b : {(void*)m->rev, (void*)m->orph, (void*)m->geo, (void*)m->nrm})
     if (b) (void)hipFree(b);
-  m->rev = nullptr;
+  m->rev = m->orph = nullptr;
   m->geo = nullptr;
   m->nrm = nullptr;
   const size_t n = (size_t)e->e_alloc;
   LB_TRY(lb_alloc(&m->rev, n));
+  LB_TRY(lb_alloc(&m->orph, n + 1));
   LB_TRY(lb_alloc(&m->geo, n));
   LB_TRY(lb_alloc(&m->nrm, n));
   m->e_alloc = e->e_alloc;
@@ -429,10 +438,9 @@ static int pn_ensure_edges(lb_painn* m) {
 extern "C" void lb_painn_destroy(lb_painn* m) {
   if (!m) return;
   for (void* b : {(void*)m->blob, (void*)m->packed, (void*)m->xnode, (void*)m->s, (void*)m->va, (void*)m->vb,
-                  (void*)m->x3, (void*)m->h1, (void*)m->ts, (void*)m->vm, (void*)m->rev, (void*)m->geo,
+                  (void*)m->x3, (void*)m->h1, (void*)m->ts, (void*)m->vm, (void*)m->rev, (void*)m->orph, (void*)m->geo,
                   (void*)m->nrm})
     if (b) (void)hipFree(b);
-  lb_rev_err_free(&m->err);
   delete m;
 }
 
@@ -494,7 +502,6 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
   step(lb_alloc(&m->h1, (size_t)BN * H));
   step(lb_alloc(&m->ts, (size_t)BN * 2 * H));
   step(lb_alloc(&m->vm, (size_t)BN * dim * 2 * H));
-  step(lb_rev_err_alloc(&m->err));
   if (rc) {
     lb_painn_destroy(m);
     return rc;
@@ -635,7 +642,7 @@ static int lbk_painn_forward(lb_engine* e, lb_painn* m) {
   hipLaunchKernelGGL(k_pn_embed, dim3(nb_t), dim3(128), 0, st, ea);
   hipLaunchKernelGGL(k_pn_edge, dim3(nb_e ? nb_e : 1), dim3(256), 0, st, e->ctrl, ecap, dim, m->desc.has_cutoff,
                      m->desc.cutoff, e->efeat, m->geo, m->nrm);
-  LB_TRY(lbk_edge_rev(e, m->rev, m->err.dev));
+  LB_TRY(lbk_edge_rev(e, m->rev, m->orph));
   lb_toc(e);
   LB_HIP(hipGetLastError());
   LB_TRY(tap(0));
@@ -655,6 +662,8 @@ static int lbk_painn_forward(lb_engine* e, lb_painn* m) {
     ma.fcol = m->desc.shared_filters ? 0 : k * 3 * H;
     ma.row_ptr = e->row_ptr;
     ma.rev = m->rev;
+    ma.orph = m->orph;
+    ma.senders = e->senders;
     ma.receivers = e->receivers;
     ma.geo = m->geo;
     ma.nrm = m->nrm;
@@ -696,10 +705,10 @@ static int lbk_painn_forward(lb_engine* e, lb_painn* m) {
 extern "C" int lb_painn_forward(lb_engine* e, lb_painn* m, float* acc_out_dev) {
   LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
   LB_TRY(lb_forward_check(e, "lb_painn_forward"));
-  LB_TRY(lb_rev_err_reset(e, m->err));
   LB_TRY(lbk_painn_forward(e, m));
   if (acc_out_dev) LB_TRY(lb_export_rows(e, e->acc, acc_out_dev, true));
-  return lb_rev_err_check(e, m->err, "PaiNN");
+  LB_HIP(hipStreamSynchronize(e->stream));
+  return LB_OK;
 }
 
 // one rollout step's model; lb_rollout_generic integrates e->acc with the GNS integrator
@@ -709,7 +718,5 @@ extern "C" int lb_painn_rollout(lb_engine* e, lb_painn* m, const double* traj_de
                                 double* pred_out_dev, int32_t* n_realloc_out) {
   if (!traj_dev || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   LB_TRY(lb_model_check(e, m ? m->eng : nullptr));
-  LB_TRY(lb_rev_err_reset(e, m->err));
-  LB_TRY(lb_rollout_generic(e, pn_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out));
-  return lb_rev_err_check(e, m->err, "PaiNN");
+  return lb_rollout_generic(e, pn_forward_thunk, m, traj_dev, T, n_steps, pred_out_dev, n_realloc_out);
 }

@@ -133,6 +133,7 @@ struct lb_gns_train {
   float* da2 = nullptr;         // second d(hidden) buffer: the middle Linears' backward ping-pongs between da and da2
   int32_t* dw_flag = nullptr;   // [1 + LB_DW_CALLS] (bit 4 of [0]: k_sender_transpose met an edge without its transpose)
   int32_t dw_fallbacks = 0;     // steps repeated because of the guard
+  int32_t sort_fallbacks = 0;   // steps repeated with the radix sort (guard bit 4: an edge without its transpose)
   int dw_call = 0;              // k_dw_part_h launches of the current step so far
   std::vector<int8_t> dw_xexp;  // per call site
   std::vector<uint8_t> dw_xdyn;
@@ -718,6 +719,11 @@ __global__ void __launch_bounds__(256) k_ln_bwd2(const float* __restrict__ z, co
 //   the epilogue of the edge-sized product: k_lin32f<4>)
 // the transpose of the two gathers: dPs[i] = sum over the edges i SENDS of da[e] (sender-sorted permutation, ascending edge index),
 // dPr[i] = sum over the edges i RECEIVES (its CSR row).  One 32-lane group per node, no atomics.
+// A slot of snd_perm outside [0, E) is skipped.  k_sender_transpose leaves the slot of an edge without a transpose
+// unwritten (guard bit 4: the attempt is thrown away and repeated with the radix sort), so that slot may hold anything -
+// a stale index of a longer earlier list, or the garbage of a fresh hipMalloc.  The bound check keeps the discarded
+// attempt's gather inside da whatever the slot holds; zeroing the buffer would not (a stale in-range index is as
+// likely as garbage).  On a complete view every slot is in range and the sums are those without the check.
 __global__ void k_edge_dP(const float* __restrict__ da, const int32_t* __restrict__ snd_ptr, const int32_t* __restrict__ snd_perm,
                           const int32_t* __restrict__ row_ptr, float* __restrict__ dPs, float* __restrict__ dPr, int64_t N,
                           int64_t E) {
@@ -727,7 +733,10 @@ __global__ void k_edge_dP(const float* __restrict__ da, const int32_t* __restric
   const int q = (int)(i % 32);
   f32x4 as = {0.f, 0.f, 0.f, 0.f}, ar = {0.f, 0.f, 0.f, 0.f};
   const int s0 = snd_ptr[r], s1 = snd_ptr[r + 1];
-  for (int j = s0; j < s1; ++j) as = as + reinterpret_cast<const f32x4*>(da)[(int64_t)snd_perm[j] * 32 + q];
+  for (int j = s0; j < s1; ++j) {
+    const uint32_t p = (uint32_t)snd_perm[j];
+    if (p < (uint64_t)E) as = as + reinterpret_cast<const f32x4*>(da)[(int64_t)p * 32 + q];
+  }
   int k0 = row_ptr[r], k1 = row_ptr[r + 1];
   k0 = k0 < E ? k0 : (int)E;
   k1 = k1 < E ? k1 : (int)E;
@@ -1694,6 +1703,7 @@ static int train_loss_grad_guarded(lb_gns_train* t, const float* target_dev, flo
     if (flag & 4) {
       if (t->cub_sort) { rc = lb_fail(LB_ERR_STATE, "training: sender view failed with the radix sort"); break; }
       t->cub_sort = true;
+      ++t->sort_fallbacks;
     }
     if (flag & 3) {   // re-centre the X exponent of every call site that fired: largest |X| -> [2^3, 2^4)
       const int n = std::min(t->dw_call, LB_DW_CALLS);
@@ -1715,6 +1725,7 @@ static int train_loss_grad_guarded(lb_gns_train* t, const float* target_dev, flo
   return rc;
 }
 extern "C" int32_t lb_gns_train_math_fallbacks(lb_gns_train* t) { return t ? t->dw_fallbacks : -1; }
+extern "C" int32_t lb_gns_train_sort_fallbacks(lb_gns_train* t) { return t ? t->sort_fallbacks : -1; }
 
 extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                       float* pred_out_dev) {

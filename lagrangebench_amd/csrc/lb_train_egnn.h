@@ -15,9 +15,10 @@
 // tall-skinny product on the exact-fp32 kernels of the training core (k_lin32f, k_dw_part + the ordered k_part_reduce; the
 // handle has f16x2 off: the reference trains EGNN in fp32).  The first edge Linear is split by rows as in the forward:
 // [h_s | h_r] W0 = P_s[s] + P_r[r] with P = h W0 per NODE; its backward sums dz0 per node first (the sender sum through the
-// transposed edge rev[], the receiver sum over the CSR row) and takes node-sized products.  What is left is elementwise
+// transposed edge rev[] and then the orphans - edges without a transpose, lb_internal.h: lbk_edge_rev -, the receiver sum
+// over the CSR row) and takes node-sized products.  What is left is elementwise
 // (silu and its derivative, gathers, the 128-long dots of the two scalar heads with a fixed-order lane reduction) and the
-// per-node sums of the position gradients through rev[] - every sum in a fixed order, no float atomics: two calls give the
+// per-node sums of the position gradients through rev[] and the orphans - every sum in a fixed order, no float atomics: two calls give the
 // same gradient bits.
 // Limits: normalize = 1 is refused (coord_diff / (sqrt(radial) + 1e-8) has a 0 * inf derivative on the self-edges every radius
 // graph here holds: the reference's own gradient is NaN for num_mp_steps >= 2); num_mp_steps <= 40 (the step's reductions
@@ -278,9 +279,10 @@ __global__ void k_egt_drad(int64_t E, const float* __restrict__ dz0, const float
   }
 }
 
-// transpose of the first edge Linear's gathers: dPs[i] = sum of dz0 over the edges i SENDS (rev[] of row i, row order),
-// dPr[i] = sum over the edges i RECEIVES (its CSR row)
+// transpose of the first edge Linear's gathers: dPs[i] = sum of dz0 over the edges i SENDS (rev[] of row i, row order, then
+// i's orphans in slot order: the forward's sender sum), dPr[i] = sum over the edges i RECEIVES (its CSR row)
 __global__ void k_egt_dP(int64_t BN, int64_t E, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ rev,
+                         const int32_t* __restrict__ orph, const int32_t* __restrict__ senders,
                          const float* __restrict__ dz0, float* __restrict__ dps, float* __restrict__ dpr) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= BN * 32) return;
@@ -291,15 +293,18 @@ __global__ void k_egt_dP(int64_t BN, int64_t E, const int32_t* __restrict__ row_
   k1 = k1 < E ? k1 : (int)E;
   f32x4 as = {0.f, 0.f, 0.f, 0.f}, ar = {0.f, 0.f, 0.f, 0.f};
   for (int k = k0; k < k1; ++k) {
-    as = as + reinterpret_cast<const f32x4*>(dz0)[(int64_t)rev[k] * 32 + qd];
+    const int e = rev[k];
+    if (e >= 0) as = as + reinterpret_cast<const f32x4*>(dz0)[(int64_t)e * 32 + qd];
     ar = ar + reinterpret_cast<const f32x4*>(dz0)[(int64_t)k * 32 + qd];
   }
+  lb_for_orphans(orph, senders, n, [&](int e) { as = as + reinterpret_cast<const f32x4*>(dz0)[(int64_t)e * 32 + qd]; });
   reinterpret_cast<f32x4*>(dps)[i] = as;
   reinterpret_cast<f32x4*>(dpr)[i] = ar;
 }
 
 // positions: coord_diff = disp(x_s, x_r) -> dx[i] += sum over the edges i sends of d coord_diff - sum over those it receives
 __global__ void k_egt_dx(int64_t BN, int64_t E, const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ rev,
+                         const int32_t* __restrict__ orph, const int32_t* __restrict__ senders,
                          const f32x4* __restrict__ dcd, float* __restrict__ dx) {
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= BN) return;
@@ -308,9 +313,11 @@ __global__ void k_egt_dx(int64_t BN, int64_t E, const int32_t* __restrict__ row_
   k1 = k1 < E ? k1 : (int)E;
   f32x4 s = {0.f, 0.f, 0.f, 0.f}, r = {0.f, 0.f, 0.f, 0.f};
   for (int k = k0; k < k1; ++k) {
-    s = s + dcd[rev[k]];
+    const int e = rev[k];
+    if (e >= 0) s = s + dcd[e];
     r = r + dcd[k];
   }
+  lb_for_orphans(orph, senders, n, [&](int e) { s = s + dcd[e]; });
   f32x4 d = reinterpret_cast<f32x4*>(dx)[n];
   d = d + (s - r);
   reinterpret_cast<f32x4*>(dx)[n] = d;
@@ -625,13 +632,15 @@ extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, c
       LB_TRY(egt_dw(t, E, 2, g->ea2, 2, g->de2, G + l.w0 + (size_t)2 * W * W, G + l.b0));
       hipLaunchKernelGGL(k_egt_drad, GRID1(eq), 0, s, E, g->de2, Wt + l.w0 + (size_t)2 * W * W,
                          reinterpret_cast<const f32x4*>(g->cdr), reinterpret_cast<f32x4*>(g->dcd));
-      hipLaunchKernelGGL(k_egt_dP, GRID1(nq), 0, s, BN, E, e->row_ptr, st.rev, g->de2, g->ps, g->pr);   // ps / pr = dPs / dPr
+      hipLaunchKernelGGL(k_egt_dP, GRID1(nq), 0, s, BN, E, e->row_ptr, st.rev, st.orph, e->senders, g->de2, g->ps,
+                         g->pr);   // ps / pr = dPs / dPr
       LB_TRY(egt_dw(t, BN, W, h, W, g->ps, G + l.w0, nullptr));
       LB_TRY(egt_dw(t, BN, W, h, W, g->pr, G + l.w0 + (size_t)W * W, nullptr));
       LB_TRY(gemm_nt(t, BN, W, W, g->ps, Wt + l.w0, g->dh, W, 1.f));
       LB_TRY(gemm_nt(t, BN, W, W, g->pr, Wt + l.w0 + (size_t)W * W, g->dh, W, 1.f));
       // positions: d x^k = d x^{k+1} + the coord_diff terms of both endpoints
-      hipLaunchKernelGGL(k_egt_dx, GRID1(BN), 0, s, BN, E, e->row_ptr, st.rev, reinterpret_cast<const f32x4*>(g->dcd), g->dx);
+      hipLaunchKernelGGL(k_egt_dx, GRID1(BN), 0, s, BN, E, e->row_ptr, st.rev, st.orph, e->senders,
+                         reinterpret_cast<const f32x4*>(g->dcd), g->dx);
     }
   }
   // embedding: h^0 = xin W_emb + b_emb

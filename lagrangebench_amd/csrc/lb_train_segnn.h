@@ -235,7 +235,10 @@ __global__ void k_sgt_scatter(const float* __restrict__ A, const float* __restri
   const int q = (int)(i % 32);
   f32x4 as = {0.f, 0.f, 0.f, 0.f}, ar = {0.f, 0.f, 0.f, 0.f};
   const int s0 = snd_ptr[r], s1 = snd_ptr[r + 1];
-  for (int j = s0; j < s1; ++j) as = as + reinterpret_cast<const f32x4*>(A)[(int64_t)snd_perm[j] * 32 + q];
+  for (int j = s0; j < s1; ++j) {   // an out-of-range slot is skipped: see k_edge_dP
+    const uint32_t p = (uint32_t)snd_perm[j];
+    if (p < (uint64_t)E) as = as + reinterpret_cast<const f32x4*>(A)[(int64_t)p * 32 + q];
+  }
   int k0 = row_ptr[r], k1 = row_ptr[r + 1];
   k0 = k0 < E ? k0 : (int)E;
   k1 = k1 < E ? k1 : (int)E;

@@ -484,6 +484,11 @@ class GnsTrainHandle(_Handle):
         """Training steps the X range guard of the f16x2 weight-gradient kernel sent to the exact-fp32 kernels (include/lbhip.h)."""
         return int(self.engine.lib.lb_gns_train_math_fallbacks(self._h))
 
+    def sort_fallbacks(self) -> int:
+        """Training steps repeated with the radix sort of the senders because an edge of the list had no transpose
+        (include/lbhip.h: lb_gns_train_sort_fallbacks)."""
+        return int(self.engine.lib.lb_gns_train_sort_fallbacks(self._h))
+
     def write(self, which: str, blob: np.ndarray, step: int = -1) -> None:
         idx = {"weights": 0, "grads": 1, "m": 2, "v": 3}[which]
         blob = np.ascontiguousarray(blob, dtype=np.float32)

@@ -181,41 +181,13 @@ _GRAD_CASES = [
 ]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("cid,name,B,scale,free,mkw,lw", _GRAD_CASES, ids=[c[0] for c in _GRAD_CASES])
-def test_hip_egnn_gradients_match_torch_autograd(cid, name, B, scale, free, mkw, lw):
-    """lb_egnn_train_loss_grad against float64 autograd of the restatement on engine-built graphs: the prediction is
-    EGNN.apply's bit for bit, the loss within 1e-5, every leaf's gradient within 1e-4 of its largest entry (or, where fp32
-    positions dominate, within 3x the float32 restatement's own deviation); two calls give identical bits; one AdamW step
-    matches torch.optim.AdamW."""
-    _need_gpu()
-    from lagrangebench_amd.data import make_case
-    from lagrangebench_amd.models import EGNN
-    from tests._common import hip_case, oracle_case
-    isl, L = 6, 3
-    mkw = dict(mkw)
-    H = mkw.pop("H", 128)
-    ds = make_case(name, n_trajs=B, extra_seq_length=3, input_seq_length=isl, scale=scale)
-    if free:
-        ds.metadata["periodic_boundary_conditions"] = [False] * len(ds.box)
-    pos = np.stack([ds[b][0] for b in range(B)])
-    pt = np.stack([ds[b][1] for b in range(B)])
-    Bn, N, dim = pos.shape[0], pos.shape[1], len(ds.box)
-    model = EGNN(H, 1, 0.01, isl - 1, num_mp_steps=L, **mkw)
-    params = random_biases(model.init_params(7, ds.external_force_fn is not None), 8)
-    hcase, ocase = hip_case(ds), oracle_case(ds)
-    feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
-    eng = feats.engine
-    apply_pos = model.apply(params, {}, (feats, pt))[0]["pos"].detach().cpu().numpy()   # (B, N, dim) fp64 of fp32
-    kw = dict(case_kwargs(ds), num_mp_steps=L, n_vels=isl - 1, homogeneous=mkw.get("homogeneous_particles", True),
-              residual=mkw.get("residual", True), tanh=mkw.get("tanh", False))
-    box, periodic = kw["box"], kw["periodic"]
-    r_c = float(ds.metadata["default_connectivity_radius"])
-    g = torch.Generator().manual_seed(3)
-    tg = {"pos": torch.as_tensor(apply_pos) + 1e-2 * r_c * torch.randn((Bn, N, dim), generator=g, dtype=torch.float64),
-          "vel": torch.randn((Bn, N, dim), generator=g, dtype=torch.float64),
-          "acc": torch.randn((Bn, N, dim), generator=g, dtype=torch.float64)}
-    th = model.train_handle(eng, params)
+def _egnn_grad_check(th, model, params, ocase, pos, pt, tg, lw, kw, apply_pos, cid):
+    """One lb_egnn_train_loss_grad on the engine's current window / list against float64 autograd of the restatement on
+    the oracle's graph: the prediction is EGNN.apply's (apply_pos) bit for bit, the loss within 1e-5, every leaf within
+    1e-4 of its largest entry (or 3x the float32 restatement's own deviation); two more calls give the same bits.  Returns
+    (loss, gradients, the float64 torch leaves)."""
+    Bn, isl = pos.shape[0], kw["n_vels"] + 1
+    box = kw["box"]
     th.zero_grad()
     loss_h, pred_h = th.loss_grad(tg, lw, want_pred=True)
     pred_h = pred_h.cpu().numpy()
@@ -256,6 +228,45 @@ def test_hip_egnn_gradients_match_torch_autograd(cid, name, B, scale, free, mkw,
                 worst = max(worst, err)
     print(f"[egnn grad {cid}] loss {loss_h:.6e}; worst relative gradient error {worst:.2e}; leaves held to the fp32 "
           f"restatement: {loose or 'none'}")
+    return loss_h, g_h, tp64
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cid,name,B,scale,free,mkw,lw", _GRAD_CASES, ids=[c[0] for c in _GRAD_CASES])
+def test_hip_egnn_gradients_match_torch_autograd(cid, name, B, scale, free, mkw, lw):
+    """lb_egnn_train_loss_grad against float64 autograd of the restatement on engine-built graphs: the prediction is
+    EGNN.apply's bit for bit, the loss within 1e-5, every leaf's gradient within 1e-4 of its largest entry (or, where fp32
+    positions dominate, within 3x the float32 restatement's own deviation); two calls give identical bits; one AdamW step
+    matches torch.optim.AdamW."""
+    _need_gpu()
+    from lagrangebench_amd.data import make_case
+    from lagrangebench_amd.models import EGNN
+    from tests._common import hip_case, oracle_case
+    isl, L = 6, 3
+    mkw = dict(mkw)
+    H = mkw.pop("H", 128)
+    ds = make_case(name, n_trajs=B, extra_seq_length=3, input_seq_length=isl, scale=scale)
+    if free:
+        ds.metadata["periodic_boundary_conditions"] = [False] * len(ds.box)
+    pos = np.stack([ds[b][0] for b in range(B)])
+    pt = np.stack([ds[b][1] for b in range(B)])
+    Bn, N, dim = pos.shape[0], pos.shape[1], len(ds.box)
+    model = EGNN(H, 1, 0.01, isl - 1, num_mp_steps=L, **mkw)
+    params = random_biases(model.init_params(7, ds.external_force_fn is not None), 8)
+    hcase, ocase = hip_case(ds), oracle_case(ds)
+    feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
+    eng = feats.engine
+    apply_pos = model.apply(params, {}, (feats, pt))[0]["pos"].detach().cpu().numpy()   # (B, N, dim) fp64 of fp32
+    kw = dict(case_kwargs(ds), num_mp_steps=L, n_vels=isl - 1, homogeneous=mkw.get("homogeneous_particles", True),
+              residual=mkw.get("residual", True), tanh=mkw.get("tanh", False))
+    box, periodic = kw["box"], kw["periodic"]
+    r_c = float(ds.metadata["default_connectivity_radius"])
+    g = torch.Generator().manual_seed(3)
+    tg = {"pos": torch.as_tensor(apply_pos) + 1e-2 * r_c * torch.randn((Bn, N, dim), generator=g, dtype=torch.float64),
+          "vel": torch.randn((Bn, N, dim), generator=g, dtype=torch.float64),
+          "acc": torch.randn((Bn, N, dim), generator=g, dtype=torch.float64)}
+    th = model.train_handle(eng, params)
+    loss_h, g_h, tp64 = _egnn_grad_check(th, model, params, ocase, pos, pt, tg, lw, kw, apply_pos, cid)
 
     for mod, lv in tp64.items():
         for leaf, v in lv.items():

@@ -425,14 +425,20 @@ def test_nonperiodic_bound_feature_and_vel_mag():
 def test_gns_forward_parity(name, scale, L, fused):
     _need_gpu()
     from lagrangebench_amd.data import make_case
-    from lagrangebench_amd.models import GNS
     ds = make_case(name, n_trajs=2, extra_seq_length=3, scale=scale)
+    pos = np.stack([ds[0][0], ds[1][0]])
+    pt = np.stack([ds[0][1], ds[1][1]])
+    _gns_forward_check(ds, pos, pt, L, fused)
+
+
+def _gns_forward_check(ds, pos, pt, L, fused):
+    """GNS forward of a batch of two on the engine (per-layer taps) against the fp64 oracle, trajectory by trajectory, and
+    element-wise against the float64 evaluation of the same network.  Returns the predicted accelerations."""
+    from lagrangebench_amd.models import GNS
     ocase, hcase = oracle_case(ds), hip_case(ds)
     isl, dim = ds.input_seq_length, len(ds.box)
     params = make_params(ds, num_mp_steps=L, decoder_scale=1.0)
     model = GNS(dim, 128, 2, L, 16)
-    pos = np.stack([ds[0][0], ds[1][0]])
-    pt = np.stack([ds[0][1], ds[1][1]])
     feats, nbrs = hcase.allocate_eval((pos[:, :, :isl], pt))
     eng = feats.engine
     eng.set_fused_aggregation(fused)
@@ -464,6 +470,7 @@ def test_gns_forward_parity(name, scale, L, fused):
         assert p999_h <= max(4.0 * p999_o, 1e-5), (p999_h, p999_o)
         assert max_h <= max(4.0 * max_o, 1e-4), (max_h, max_o)
     handle.set_tap(False)
+    return acc
 
 
 def test_segment_sum_matches_oracle():

@@ -136,10 +136,16 @@ def _setup(name, scale, L, magnitudes=True, seed=7, out_scale=1.0):
 def test_segnn_forward_parity(name, scale, L, mag):
     _need_gpu()
     ds, model, params, homog = _setup(name, scale, L, mag)
-    ocase, hcase = oracle_case(ds), hip_case(ds)
-    isl = ds.input_seq_length
     pos = np.stack([ds[0][0], ds[1][0]])
     pt = np.stack([ds[0][1], ds[1][1]])
+    _segnn_parity(ds, model, params, homog, pos, pt, name)
+
+
+def _segnn_parity(ds, model, params, homog, pos, pt, name):
+    """lmax-1 SEGNN forward of a batch of two on the engine (hidden-state taps, acceleration) against the float32 oracle
+    and element-wise against its float64 evaluation.  Returns the accelerations."""
+    ocase, hcase = oracle_case(ds), hip_case(ds)
+    isl = ds.input_seq_length
     feats, nbrs = hcase.allocate_eval((pos[:, :, :isl], pt))
     eng = feats.engine
     handle = model.handle(eng, params)
@@ -172,6 +178,7 @@ def test_segnn_forward_parity(name, scale, L, mag):
         assert p999_h <= max(4.0 * p999_o, 2e-4), (p999_h, p999_o)
         assert max_h <= max(4.0 * max_o, 5e-4), (max_h, max_o)
     handle.set_tap(False)
+    return acc
 
 
 @pytest.mark.gpu

@@ -209,11 +209,17 @@ def _gpu_setup(name, scale, L, lh, la, norm, blocks=2, units=64, seed=7, velocit
 def test_general_segnn_forward_parity(name, scale, L, lh, la, norm, blocks, units):
     _need_gpu()
     ds, model, params, homog = _gpu_setup(name, scale, L, lh, la, norm, blocks, units)
+    pos = np.stack([ds[0][0], ds[1][0]])
+    pt = np.stack([ds[0][1], ds[1][1]])
+    _gen_parity(ds, model, params, homog, pos, pt, norm, name)
+
+
+def _gen_parity(ds, model, params, homog, pos, pt, norm, name):
+    """General-irreps SEGNN forward of a batch of two on the engine (hidden-state taps, acceleration) against
+    segnn_irreps_oracle, and a bit-identical repeat."""
     assert model.generic
     ocase, hcase = oracle_case(ds), hip_case(ds)
     isl = ds.input_seq_length
-    pos = np.stack([ds[0][0], ds[1][0]])
-    pt = np.stack([ds[0][1], ds[1][1]])
     feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
     handle = model.handle(feats.engine, params)
     tap = handle.set_tap(True)

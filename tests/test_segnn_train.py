@@ -66,35 +66,12 @@ def test_torch_gradients_match_finite_differences():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.mark.gpu
-@pytest.mark.parametrize("name,scale,L,B,blocks", [("small2d", 1.0, 2, 2, 2), ("small3d", 1.0, 3, 1, 2), ("dam2d", 0.3, 2, 2, 2),
-                                                   ("rpf2d", 0.5, 10, 1, 2), ("small2d", 1.0, 2, 1, 1), ("small3d", 1.0, 2, 1, 3)])
-def test_hip_segnn_gradients_match_torch_autograd(name, scale, L, B, blocks):
-    """The device step (lb_segnn_train_loss_grad) against float64 autograd of oracle/segnn_torch.py on engine-built graphs:
-    prediction, loss (mean over the batch) and every weight / bias gradient (summed over the batch, trainer.py:63-89) within
-    1e-4 of the leaf's largest entry; two runs give the same bits; one AdamW step against torch.optim.AdamW."""
-    from lagrangebench_amd.data import make_case
-    from lagrangebench_amd.models import SEGNN, node_irreps
+def _segnn_grad_check(model, th, params, ocase, pos, pt, target, L, blocks, homog, tag):
+    """One lb_segnn_train_loss_grad on the engine's current window / list against float64 autograd of the restatement on
+    the oracle's graph of the same window: prediction, loss and every weight / bias gradient within 1e-4 of the leaf's
+    largest entry; two more calls give the same bits.  Returns (loss, gradients, the torch leaves)."""
     from oracle import lb_oracle as O
-    from tests._common import hip_case, oracle_case
-    ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
-    ds.magnitude_features = True
-    isl, dim = ds.input_seq_length, len(ds.box)
-    homog = bool(np.all(ds[0][1] == 0))
-    irr = node_irreps(ds.metadata, isl, ds.external_force_fn is not None, True, homog)
-    model = SEGNN(irr, "1x1o+1x0e", 64, 1, 1, "1x1o", num_mp_steps=L, n_vels=isl - 1, homogeneous_particles=homog,
-                  blocks_per_step=blocks)
-    params = S.segnn_init(np.random.default_rng(11), node_ns=model._node_ns, node_nv=model._node_nv, num_mp_steps=L,
-                          blocks_per_step=blocks, random_bias=True)
-    params = {k: v for k, v in params.items() if isinstance(v, dict)}
-    ocase, hcase = oracle_case(ds), hip_case(ds)
-    pos = np.stack([ds[b][0] for b in range(B)])
-    pt = np.stack([ds[b][1] for b in range(B)])
-    feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
-    eng = feats.engine
-    N = pos.shape[1]
-    target = torch.randn((B, N, dim), generator=torch.Generator().manual_seed(5))
-    th = model.train_handle(eng, params)
+    B, isl = target.shape[0], model._n_vels + 1
     th.zero_grad()
     loss_h, pred_h = th.loss_grad(target, 1.0, want_pred=True)
     g_flat = th.read("grads")
@@ -128,7 +105,42 @@ def test_hip_segnn_gradients_match_torch_autograd(name, scale, L, B, blocks):
             err = np.abs(g_h[blk][leaf] - ref).max() / max(np.abs(ref).max(), 1e-30)
             worst = max(worst, err)
             assert err < 1e-4, (blk, leaf, err)
-    print(f"[segnn grad {name} L={L} B={B} blocks={blocks}] loss {loss_h:.6f}, worst relative gradient error {worst:.2e}")
+    print(f"[segnn grad {tag}] loss {loss_h:.6f}, worst relative gradient error {worst:.2e}")
+    return loss_h, g_h, tp
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,scale,L,B,blocks", [("small2d", 1.0, 2, 2, 2), ("small3d", 1.0, 3, 1, 2), ("dam2d", 0.3, 2, 2, 2),
+                                                   ("rpf2d", 0.5, 10, 1, 2), ("small2d", 1.0, 2, 1, 1), ("small3d", 1.0, 2, 1, 3)])
+def test_hip_segnn_gradients_match_torch_autograd(name, scale, L, B, blocks):
+    """The device step (lb_segnn_train_loss_grad) against float64 autograd of oracle/segnn_torch.py on engine-built graphs:
+    prediction, loss (mean over the batch) and every weight / bias gradient (summed over the batch, trainer.py:63-89) within
+    1e-4 of the leaf's largest entry; two runs give the same bits; one AdamW step against torch.optim.AdamW."""
+    from lagrangebench_amd.data import make_case
+    from lagrangebench_amd.models import SEGNN, node_irreps
+    from oracle import lb_oracle as O
+    from tests._common import hip_case, oracle_case
+    ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
+    ds.magnitude_features = True
+    isl, dim = ds.input_seq_length, len(ds.box)
+    homog = bool(np.all(ds[0][1] == 0))
+    irr = node_irreps(ds.metadata, isl, ds.external_force_fn is not None, True, homog)
+    model = SEGNN(irr, "1x1o+1x0e", 64, 1, 1, "1x1o", num_mp_steps=L, n_vels=isl - 1, homogeneous_particles=homog,
+                  blocks_per_step=blocks)
+    params = S.segnn_init(np.random.default_rng(11), node_ns=model._node_ns, node_nv=model._node_nv, num_mp_steps=L,
+                          blocks_per_step=blocks, random_bias=True)
+    params = {k: v for k, v in params.items() if isinstance(v, dict)}
+    ocase, hcase = oracle_case(ds), hip_case(ds)
+    pos = np.stack([ds[b][0] for b in range(B)])
+    pt = np.stack([ds[b][1] for b in range(B)])
+    feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
+    eng = feats.engine
+    N = pos.shape[1]
+    target = torch.randn((B, N, dim), generator=torch.Generator().manual_seed(5))
+    th = model.train_handle(eng, params)
+    loss_h, g_h, tp = _segnn_grad_check(model, th, params, ocase, pos, pt, target, L, blocks, homog,
+                                        f"{name} L={L} B={B} blocks={blocks}")
+    assert th.sort_fallbacks() == 0   # a symmetric list: the sender view by transposition, never the radix sort
 
     for blk, lv in tp.items():
         for leaf, v in lv.items():

@@ -150,35 +150,14 @@ def test_torch_forward_on_engine_graph_equals_hip_forward():
         assert err < 1e-5, err
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name,scale,L,B,latent,depth", [("small2d", 1.0, 3, 2, 128, 2), ("small3d", 1.0, 2, 1, 128, 2),
-                                                         ("tgv2d", 0.6, 10, 2, 128, 2), ("ldc3d", 0.4, 2, 2, 128, 2),
-                                                         ("small2d", 1.0, 5, 2, 64, 2), ("small3d", 1.0, 2, 2, 40, 2),
-                                                         ("small3d", 1.0, 2, 2, 128, 3), ("small2d", 1.0, 3, 2, 48, 4)])
-def test_hip_gradients_match_torch_autograd(name, scale, L, B, latent, depth):
-    """VERDICT r02 item 5: the hand-written backward (csrc/lb_train.hip: lb_gns_train_loss_grad) against torch
-    autograd of the checker network (oracle/gns_torch.py, itself checked against the oracle and finite differences
-    above) on engine-built graphs: loss and every parameter gradient of _mse (trainer.py:35-60), gradients summed and
-    loss averaged over the batch (trainer.py:63-89), within 1e-4 relative per leaf; then one AdamW step against
-    torch.optim.AdamW.  depth = num_mlp_layers (Linears per MLP, models/utils.py:100-115): 2 in every shipped config; 3 and 4
-    exercise the middle Linears of the training step (round 6)."""
-    from lagrangebench_amd.data import make_case
-    from lagrangebench_amd.models import GNS
+def _gns_grad_check(model, th, feats, params, target, pt, L, depth, name):
+    """One lb_gns_train_loss_grad on the engine's current window / list against torch autograd in float64 on the same
+    graph (gns_inputs_from_features): loss, and every gradient leaf within 1e-4 relative; three more calls give the same
+    bits.  Returns (loss, gradients by module / leaf, the torch leaves)."""
     from oracle.gns_torch import gns_apply_torch, gns_inputs_from_features, params_to_torch
     from lagrangebench_amd.utils import get_kinematic_mask
-    from tests._common import hip_case
-    ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
-    hcase = hip_case(ds)
-    isl, dim = ds.input_seq_length, len(ds.box)
-    pos = np.stack([ds[b][0] for b in range(B)])
-    pt = np.stack([ds[b][1] for b in range(B)])
-    # latent < 128 (round 4: GNS-5-64 of the reference's baselines): the device step runs 128-wide with zero padding
-    params = make_params(ds, num_mp_steps=L, decoder_scale=1.0, latent_size=latent, blocks_per_step=depth)
-    model = GNS(dim, latent, depth, L, 16)
-    feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
     eng = feats.engine
-    target = torch.randn((B, pos.shape[1], dim), generator=torch.Generator().manual_seed(5))
-    th = model.train_handle(eng, params)
+    B = target.shape[0]
     th.zero_grad()
     loss_h, pred_h = th.loss_grad(target, 1.0, want_pred=True)
     g_flat = th.read("grads")
@@ -217,6 +196,39 @@ def test_hip_gradients_match_torch_autograd(name, scale, L, B, latent, depth):
             worst = max(worst, err)
             assert err < 1e-4, (mod, leaf, err)
     print(f"[grad {name}] loss {loss_h:.6f}, worst relative gradient error over the leaves {worst:.2e}")
+    return loss_h, g_h, pt_t
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,scale,L,B,latent,depth", [("small2d", 1.0, 3, 2, 128, 2), ("small3d", 1.0, 2, 1, 128, 2),
+                                                         ("tgv2d", 0.6, 10, 2, 128, 2), ("ldc3d", 0.4, 2, 2, 128, 2),
+                                                         ("small2d", 1.0, 5, 2, 64, 2), ("small3d", 1.0, 2, 2, 40, 2),
+                                                         ("small3d", 1.0, 2, 2, 128, 3), ("small2d", 1.0, 3, 2, 48, 4)])
+def test_hip_gradients_match_torch_autograd(name, scale, L, B, latent, depth):
+    """VERDICT r02 item 5: the hand-written backward (csrc/lb_train.hip: lb_gns_train_loss_grad) against torch
+    autograd of the checker network (oracle/gns_torch.py, itself checked against the oracle and finite differences
+    above) on engine-built graphs: loss and every parameter gradient of _mse (trainer.py:35-60), gradients summed and
+    loss averaged over the batch (trainer.py:63-89), within 1e-4 relative per leaf; then one AdamW step against
+    torch.optim.AdamW.  depth = num_mlp_layers (Linears per MLP, models/utils.py:100-115): 2 in every shipped config; 3 and 4
+    exercise the middle Linears of the training step (round 6)."""
+    from lagrangebench_amd.data import make_case
+    from lagrangebench_amd.models import GNS
+    from tests._common import hip_case
+    ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
+    hcase = hip_case(ds)
+    isl, dim = ds.input_seq_length, len(ds.box)
+    pos = np.stack([ds[b][0] for b in range(B)])
+    pt = np.stack([ds[b][1] for b in range(B)])
+    # latent < 128 (round 4: GNS-5-64 of the reference's baselines): the device step runs 128-wide with zero padding
+    params = make_params(ds, num_mp_steps=L, decoder_scale=1.0, latent_size=latent, blocks_per_step=depth)
+    model = GNS(dim, latent, depth, L, 16)
+    feats, _ = hcase.allocate_eval((pos[:, :, :isl], pt))
+    eng = feats.engine
+    target = torch.randn((B, pos.shape[1], dim), generator=torch.Generator().manual_seed(5))
+    th = model.train_handle(eng, params)
+    loss_h, g_h, pt_t = _gns_grad_check(model, th, feats, params, target, pt, L, depth, name)
+    assert th.sort_fallbacks() == 0   # a symmetric list: the sender view by transposition, never the radix sort
+    dev = eng.device
 
     # one optimiser step: optax.adamw == torch AdamW (decoupled decay).  Both get the SAME gradients (the engine's):
     # the first Adam step is sign(g) * lr for |g| >> eps, so rounding-level differences of near-zero gradients
