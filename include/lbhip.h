@@ -88,7 +88,15 @@ int lb_version(void);
 int lb_engine_create(const lb_case_desc* desc, void* hip_stream, lb_engine** out);
 void lb_engine_destroy(lb_engine* eng);
 
-/* sample[1] of the reference's (pos, particle_type) tuple: (B,N) int32. */
+/* sample[1] of the reference's (pos, particle_type) tuple: (B,N) int32.
+ * Padded trajectories (data/data.py:183-197, case_setup/case.py:180-190: variable particle counts, the `matscipy` backend):
+ * a particle of type -1 (NodeType.PAD_VALUE) is NOT THERE for the neighbor search - it is binned into no cell, is never a
+ * sender or a receiver, has no self-edge, and counts towards no cell occupancy, edge count or capacity.  It is kinematic
+ * (lb_integrate / lb_rollout write its target position, 0 in a padded dataset), its node rows are computed (finite,
+ * deterministic, read by no edge) and it is outside the training loss, whose denominator is the non-kinematic real
+ * particles of its trajectory.  Pads may sit anywhere in a trajectory and their number may differ between trajectories.
+ * Also counts the live particles per trajectory (asynchronous, on the engine's stream).  With no particle of type -1
+ * every call computes what it did before this was added, bit for bit. */
 int lb_set_particle_type(lb_engine* eng, const int32_t* ptype_dev);
 
 /* LB_FORCE_BUFFER only: (B,N,dim) fp64 = vmap(external_force_fn)(most_recent_position). */

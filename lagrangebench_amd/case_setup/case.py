@@ -245,9 +245,11 @@ def case_builder(
         raise NotImplementedError(f"case_builder: dtype {dtype!r} (float64 and float32 are built)")
     if cfg_neighbors.multiplier < 1.25:
         warnings.warn(f"cfg_neighbors.multiplier={cfg_neighbors.multiplier} < 1.25 is very low.")
-    if cfg_neighbors.backend not in ("jaxmd_vmap", "jaxmd_scan", "hip"):
-        raise NotImplementedError(f"neighbor backend {cfg_neighbors.backend!r} (padded variable-N "
-                                  "data, matscipy) is not built")
+    # "matscipy" stands for padded trajectories (samples padded to num_particles_max with NodeType.PAD_VALUE particles at
+    # position 0, data/data.py): the HIP search leaves a pad out of the cells, so it is in no edge; there is no matscipy
+    # here.  The engine takes the pad mask from the particle types, whatever the backend name.
+    if cfg_neighbors.backend not in ("jaxmd_vmap", "jaxmd_scan", "hip", "matscipy"):
+        raise NotImplementedError(f"neighbor backend {cfg_neighbors.backend!r} is not built")
     return CaseSetupFn(box=box, metadata=metadata, input_seq_length=input_seq_length,
                        cfg_neighbors=cfg_neighbors, cfg_model=cfg_model, noise_std=noise_std,
                        force=_force_spec(external_force_fn, metadata.get("bounds")), dtype=dtype, device=device)

@@ -214,6 +214,7 @@ extern "C" int lb_engine_create(const lb_case_desc* d, void* hip_stream, lb_engi
   auto A = [&](int r) { if (!rc) rc = r; };
   A(lb_alloc(&e->win, (size_t)d->isl * d->dim * BN));
   A(lb_alloc(&e->ptype, (size_t)BN));
+  A(lb_alloc(&e->live_cnt, (size_t)g.B));
   A(lb_alloc(&e->ctrl, 1));
   A(lb_alloc(&e->blocks_done, 1));
   A(lb_alloc(&e->cell_of, (size_t)BN));
@@ -261,6 +262,13 @@ extern "C" int lb_engine_create(const lb_case_desc* d, void* hip_stream, lb_engi
     lb_engine_destroy(e);
     return lb_fail(LB_ERR_HIP, "engine init copies failed");
   }
+  {  // particle types start as zeros (no pads): every trajectory has its N particles
+    std::vector<int32_t> lc((size_t)g.B, d->n_particles);
+    if (hipMemcpy(e->live_cnt, lc.data(), sizeof(int32_t) * lc.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      lb_engine_destroy(e);
+      return lb_fail(LB_ERR_HIP, "engine init copies failed");
+    }
+  }
   *out = e;
   return LB_OK;
 }
@@ -269,7 +277,7 @@ extern "C" void lb_engine_destroy(lb_engine* e) {
   if (!e) return;
   lb_timers_collect(e);
   for (auto ev : e->epool) (void)hipEventDestroy(ev);
-  void* bufs[] = {e->win, e->ptype, e->force, e->ctrl, e->cell_of, e->cell_count, e->cell_start,
+  void* bufs[] = {e->win, e->ptype, e->live_cnt, e->force, e->ctrl, e->cell_of, e->cell_count, e->cell_start,
                   e->cell_part, e->deg, e->nl_wg_sum, e->row_ptr, e->scan_part, e->cpos, e->tmp_send, e->tmp_feat, e->tmp_feat64,
                   e->senders, e->receivers, e->efeat, e->efeat64,
                   e->overflow, e->nedges_b, e->xnode, e->nlat, e->agg, e->psr, e->elat, e->msg,
@@ -324,10 +332,24 @@ int lb_ensure_edges(lb_engine* e, int64_t need) {
   return LB_OK;
 }
 
+// live_cnt[b] = particles of trajectory b whose type is not LB_PAD_TYPE (one workgroup per trajectory; integer sums)
+__global__ void __launch_bounds__(256) k_live_count(const int32_t* __restrict__ ptype, int N, int32_t* __restrict__ live_cnt) {
+  __shared__ int s_red[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  int n = 0;
+  for (int i = tid; i < N; i += 256) n += ptype[(int64_t)b * N + i] != LB_PAD_TYPE ? 1 : 0;
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if ((tid & 63) == 0) s_red[tid >> 6] = n;
+  __syncthreads();
+  if (tid == 0) live_cnt[b] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+}
+
 extern "C" int lb_set_particle_type(lb_engine* e, const int32_t* ptype_dev) {
   if (!e || !ptype_dev) return lb_fail(LB_ERR_ARG, "null argument");
   LB_HIP(hipMemcpyAsync(e->ptype, ptype_dev, sizeof(int32_t) * e->BN, hipMemcpyDeviceToDevice,
                         e->stream));
+  hipLaunchKernelGGL(k_live_count, dim3(e->g.B), dim3(256), 0, e->stream, e->ptype, e->g.N, e->live_cnt);
+  LB_HIP(hipGetLastError());
   return LB_OK;
 }
 

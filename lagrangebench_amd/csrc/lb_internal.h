@@ -16,6 +16,7 @@
 #define LB_MAX_ROW_DENSE 4096     // ... of the dense fall-back (wave-per-receiver kernel, dynamic LDS)
 #define LB_TILE 32                // rows (edges / nodes) per wave tile: the N of the 32x32x2 MFMA
 #define LB_D 128                  // latent width built so far
+#define LB_PAD_TYPE (-1)          // NodeType.PAD_VALUE: a particle of a padded trajectory that is not there (utils.py:17-25)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -129,6 +130,7 @@ struct lb_engine {
   // state
   double* win;        // [isl][dim][B*N] SoA ring of positions
   int32_t* ptype;     // [B*N]
+  int32_t* live_cnt = nullptr;  // [B] particles of each trajectory that are not pads (lb_set_particle_type; N without pads)
   double* force;      // [B*N*dim] (LB_FORCE_BUFFER) or null
   lb_ctrl* ctrl;      // device
   int32_t* blocks_done = nullptr;  // k_integrate: workgroups that have read the step counter (the last one advances it)

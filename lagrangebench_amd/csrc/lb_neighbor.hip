@@ -40,9 +40,14 @@
 enum { NL_COUNT = 0, NL_FILL = 1, NL_ROWS = 2 };
 
 // ------------------------------------------------------------------------------------ cells
+// Padded trajectories (particle_type == LB_PAD_TYPE, the reference's NodeType.PAD_VALUE): a pad is not there for the search.
+// Every binning kernel below reads the particle's type next to its position and leaves a pad out of the cells - so it is
+// never a stencil candidate (sender) and never a receiver of the per-cell kernels - and writes its degree 0, which the
+// search kernels (they write the degrees of the receivers they visit) would otherwise leave stale.  Occupancies, capacities
+// and edge counts therefore see real particles only.
 __global__ void k_cell_count(lb_geom g, int64_t BN, const double* __restrict__ win,
-                             lb_ctrl* __restrict__ ctrl, int32_t* __restrict__ cell_of,
-                             int32_t* __restrict__ cell_count) {
+                             lb_ctrl* __restrict__ ctrl, const int32_t* __restrict__ ptype, int32_t* __restrict__ deg,
+                             int32_t* __restrict__ cell_of, int32_t* __restrict__ cell_count) {
   if (ctrl->overflow_step >= 0) return;
   int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (gi == 0) {
@@ -52,6 +57,11 @@ __global__ void k_cell_count(lb_geom g, int64_t BN, const double* __restrict__ w
     ctrl->row_overflow = 0;
   }
   if (gi >= BN) return;
+  if (ptype[gi] == LB_PAD_TYPE) {
+    cell_of[gi] = -1;
+    deg[gi] = 0;
+    return;
+  }
   const int step = ctrl->step;
   const int b = (int)(gi / g.N);
   int h = 0, mult = 1;
@@ -149,6 +159,7 @@ __global__ void k_cell_fill(lb_geom g, int64_t BN, const double* __restrict__ wi
   if (gi >= BN) return;
   const int step = ctrl->step;
   const int gc = cell_of[gi];
+  if (gc < 0) return;  // a pad: in no cell
   const int slot = cell_start[gc] + atomicAdd(&cell_fill[gc], 1);
   cell_part[slot] = (int32_t)gi;
   for (int d = 0; d < g.dim; ++d) cpos[(int64_t)d * BN + slot] = lb_pos(win, g, BN, step, g.isl - 1, d, gi);
@@ -169,14 +180,20 @@ __global__ void k_cell_zero(lb_ctrl* __restrict__ ctrl, int32_t* __restrict__ ce
   if (i < n) cell_count[i] = 0;
 }
 __global__ void __launch_bounds__(256) k_cell_bin(lb_geom g, int64_t BN, const double* __restrict__ win,
-                                                  lb_ctrl* __restrict__ ctrl, int32_t* __restrict__ cell_of,
+                                                  lb_ctrl* __restrict__ ctrl, const int32_t* __restrict__ ptype,
+                                                  int32_t* __restrict__ deg, int32_t* __restrict__ cell_of,
                                                   int32_t* __restrict__ cell_count, int32_t* __restrict__ cell_part,
                                                   double* __restrict__ cpos, int32_t cap, int64_t cstride) {
   if (ctrl->overflow_step >= 0) return;
   const int64_t gi = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int step = ctrl->step;
   int occ = 0;
-  if (gi < BN) {
+  const bool pad = gi < BN && ptype[gi] == LB_PAD_TYPE;
+  if (pad) {
+    cell_of[gi] = -1;
+    deg[gi] = 0;
+  }
+  if (gi < BN && !pad) {
     const int b = (int)(gi / g.N);
     int h = 0, mult = 1;
     double p[3] = {0, 0, 0};
@@ -229,6 +246,7 @@ __device__ __forceinline__ int lb_cell_coord(double p, float inv_cs32, double cs
 template <int PER>
 __global__ void __launch_bounds__(LB_SMALL_T)
     k_cells_small(lb_geom g, int64_t BN, const double* __restrict__ win, lb_ctrl* __restrict__ ctrl,
+                  const int32_t* __restrict__ ptype, int32_t* __restrict__ deg,
                   int32_t* __restrict__ cell_of, int32_t* __restrict__ cell_start, int32_t* __restrict__ cell_part,
                   double* __restrict__ cpos, int ncell_tot) {
   extern __shared__ int s_cnt[];  // [ncell_tot]
@@ -242,10 +260,12 @@ __global__ void __launch_bounds__(LB_SMALL_T)
   const int tid = threadIdx.x;
   int gcs[PER], rk[PER];
   double pos[PER][3];
+  bool pad[PER];
 #pragma unroll
   for (int k = 0; k < PER; ++k) {  // all position loads of a thread in flight together
     const int64_t gi = tid + (int64_t)LB_SMALL_T * k;
     const int64_t gc = gi < BN ? gi : BN - 1;
+    pad[k] = ptype[gc] == LB_PAD_TYPE;
 #pragma unroll
     for (int d = 0; d < 3; ++d) pos[k][d] = d < g.dim ? lb_pos(win, g, BN, step, g.isl - 1, d, gc) : 0.0;
   }
@@ -264,7 +284,11 @@ __global__ void __launch_bounds__(LB_SMALL_T)
     const int64_t gi = tid + (int64_t)LB_SMALL_T * k;
     gcs[k] = -1;
     rk[k] = 0;
-    if (gi < BN) {
+    if (gi < BN && pad[k]) {
+      cell_of[gi] = -1;
+      deg[gi] = 0;
+    }
+    if (gi < BN && !pad[k]) {
       const int b = (int)(gi / g.N);
       int h = 0, mult = 1;
 #pragma unroll
@@ -329,7 +353,7 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int64_t gi = tid + (int64_t)LB_SMALL_T * k;
-    if (gi < BN) {
+    if (gcs[k] >= 0) {
       const int slot = s_cnt[gcs[k]] + rk[k];
       cell_part[slot] = (int32_t)gi;
 #pragma unroll
@@ -342,12 +366,15 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 // Batches (round 4): binning of trajectory b by workgroup b, ONE launch instead of memset + count + two scan passes + fill
 // (five launches, ~35 us of kernels + their dependency gaps per step).  Trajectories are independent here: every trajectory
 // has exactly N particles, so its cells start at slot b * N of the cell-sorted arrays and no prefix crosses workgroups.
+// (Padded trajectories: b's live particles; its cells start at the sum of the live counts before it, live_cnt[0 .. b), which
+// is b * N when nothing is padded - the cell-sorted arrays stay one gapless CSR.)
 // k_cells_small's arithmetic (same cell coordinates, arbitrary order inside a cell - the rows are sorted by sender id later).
 // The per-trajectory maximum occupancy goes to occ[b]; the workgroup that finishes last (ticket counter occ[B], left at 0)
 // publishes the maximum to the control block.
 template <int PER>
 __global__ void __launch_bounds__(LB_SMALL_T)
     k_cells_traj(lb_geom g, int64_t BN, const double* __restrict__ win, lb_ctrl* __restrict__ ctrl,
+                 const int32_t* __restrict__ ptype, const int32_t* __restrict__ live_cnt, int32_t* __restrict__ deg,
                  int32_t* __restrict__ cell_of, int32_t* __restrict__ cell_start, int32_t* __restrict__ cell_part,
                  double* __restrict__ cpos, int32_t* __restrict__ occ) {
   extern __shared__ int s_cnt[];  // [g.ncells]
@@ -360,13 +387,17 @@ __global__ void __launch_bounds__(LB_SMALL_T)
   const int64_t p0 = (int64_t)b * N;
   int lcs[PER], rk[PER];
   double pos[PER][3];
+  bool pad[PER];
 #pragma unroll
   for (int k = 0; k < PER; ++k) {  // all position loads of a thread in flight together
     const int li = tid + LB_SMALL_T * k;
     const int64_t gi = p0 + (li < N ? li : N - 1);
+    pad[k] = ptype[gi] == LB_PAD_TYPE;
 #pragma unroll
     for (int d = 0; d < 3; ++d) pos[k][d] = d < g.dim ? lb_pos(win, g, BN, step, g.isl - 1, d, gi) : 0.0;
   }
+  int s0 = 0;  // first slot of this trajectory in the cell-sorted arrays
+  for (int i = 0; i < b; ++i) s0 += live_cnt[i];
   if (tid == 0) {
     s_max = 0;
     if (b == 0) {
@@ -384,7 +415,11 @@ __global__ void __launch_bounds__(LB_SMALL_T)
     const int li = tid + LB_SMALL_T * k;
     lcs[k] = -1;
     rk[k] = 0;
-    if (li < N) {
+    if (li < N && pad[k]) {
+      cell_of[p0 + li] = -1;
+      deg[p0 + li] = 0;
+    }
+    if (li < N && !pad[k]) {
       int h = 0, mult = 1;
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
@@ -426,7 +461,7 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 #pragma unroll
   for (int w = 0; w < LB_SMALL_T / 64; ++w)
     if (w < (tid >> 6)) wbase += s_scan[w];
-  int run = (int)p0 + wbase + incl - sum;  // global slot of the trajectory's first particle + local start
+  int run = s0 + wbase + incl - sum;  // global slot of the trajectory's first particle + local start
   for (int j = 0; j < per; ++j) {
     const int c = c_lo + j;
     if (c < nc) {
@@ -437,11 +472,11 @@ __global__ void __launch_bounds__(LB_SMALL_T)
   }
   __syncthreads();
   for (int c = tid; c < nc; c += LB_SMALL_T) cell_start[(int64_t)b * nc + c] = s_cnt[c];
-  if (b == (int)gridDim.x - 1 && tid == 0) cell_start[(int64_t)gridDim.x * nc] = (int32_t)BN;
+  if (b == (int)gridDim.x - 1 && tid == 0) cell_start[(int64_t)gridDim.x * nc] = s0 + live_cnt[b];
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     const int li = tid + LB_SMALL_T * k;
-    if (li < N) {
+    if (lcs[k] >= 0) {
       const int slot = s_cnt[lcs[k]] + rk[k];
       cell_part[slot] = (int32_t)(p0 + li);
 #pragma unroll
@@ -764,7 +799,7 @@ __global__ void __launch_bounds__(64 * NLW_WAVES)
   int* const s_row = s_dyn + (size_t)wave * 2 * row_cap;
   int* const s_id = s_row + row_cap;
   const int64_t r = (int64_t)blockIdx.x * NLW_WAVES + wave;  // receiver slot in cell-sorted order
-  if (r >= BN) return;
+  if (r >= a.cell_start[g.B * g.ncells]) return;  // (the binned particles: all BN, or the live ones of padded trajectories)
   const int gr = a.cell_part[r];
   lb_stencil_table(g, a, a.cell_of[gr], lane, g.dim, s_cstart[wave], s_coff[wave]);
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -1233,6 +1268,7 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 #define NLS_CAND 512  // stencil candidates per receiver (row buffer entries; >= LB_MAX_ROW)
 struct lb_nls_args {
   const double* win;
+  const int32_t* ptype;
   lb_edge_out out;
   int32_t *deg, *row_ptr, *overflow, *nedges_b;
   unsigned long long* wg_sum;  // [ceil(N / NLS_WAVES)]
@@ -1336,10 +1372,12 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
     const int slot = (step + g.isl - 1) % g.isl;
     const double* const w0 = a.win + (int64_t)slot * DIM * N;
     double pv[PER][3];
+    bool pad[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int i = tid + (int)blockDim.x * k;
       const int ic = i < N ? i : N - 1;
+      pad[k] = a.ptype[ic] == LB_PAD_TYPE;
       pv[k][0] = w0[ic];
       pv[k][1] = w0[N + ic];
       pv[k][2] = DIM == 3 ? w0[2 * N + ic] : 0.0;
@@ -1356,7 +1394,7 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
           s_p[d * npad + i] = p;
           packed |= lb_cell_coord<F32>(p, inv_cs[d], g.cell_size[d], g.ncell[d]) << (11 * d);
         }
-        s_cell[i] = i < N ? packed : -1;
+        s_cell[i] = (i < N && !pad[k]) ? packed : -1;  // (a pad is in no cell: no mask bit, never a candidate)
       }
     }
   }
@@ -1382,9 +1420,9 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
   if (r < N) {
     if (a.feat.xnode) lb_node_features_wave(g, N, a.win, step, a.feat, r);
     lb_load_pos(pr, s_p, npad, r, DIM);
-    int ncand = N;  // (no cell list: every particle is a candidate, pass 2 walks the ids)
-    if (g.use_cell_list) {
-      const int pc = s_cell[r];
+    const int pc = s_cell[r];
+    int ncand = pc < 0 ? 0 : N;  // (no cell list: every particle is a candidate, pass 2 walks the ids; a pad receiver: none)
+    if (g.use_cell_list && pc >= 0) {
       unsigned long long m = ~0ull, ms = ~0ull;
       if (lane < nwords) {
         _Pragma("unroll") for (int d = 0; d < DIM; ++d) {
@@ -1427,6 +1465,7 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
       if (t < ncand) {
         j = g.use_cell_list ? row[t] : t;
         ok = lb_pair_in_cutoff<F32>(g, [&](int d) { return s_p[d * npad + j]; }, pr, DIM);
+        if (!g.use_cell_list) ok = ok && s_cell[j] >= 0;  // all-pairs candidates: pads are among the ids
       }
       const unsigned long long mask = __ballot(ok);
       // (in place: hit k of this sweep lands at count + k <= c0 + lane's own index, and every lane has read its j)
@@ -1498,10 +1537,12 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
   {
     constexpr int PER = NLM_N / (64 * NLM_WAVES);
     double pv[PER][3];
+    bool pad[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int i = tid + 64 * NLM_WAVES * k;
       const int ic = i < N ? i : N - 1;
+      pad[k] = a.ptype[ic] == LB_PAD_TYPE;
       pv[k][0] = w0[ic];
       pv[k][1] = w0[N + ic];
       pv[k][2] = DIM == 3 ? w0[2 * N + ic] : 0.0;
@@ -1515,7 +1556,7 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
         int packed = 0;
         _Pragma("unroll") for (int d = 0; d < DIM; ++d)
           packed |= lb_cell_coord<F32>(pv[k][d], inv_cs[d], g.cell_size[d], g.ncell[d]) << (11 * d);
-        s_cell[i] = i < N ? packed : -1;
+        s_cell[i] = (i < N && !pad[k]) ? packed : -1;
       }
     }
   }
@@ -1550,6 +1591,10 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
     double pr[3];
     lb_load_pos(pr, w0, N, r, DIM);
     const int pc = s_cell[r];
+    if (pc < 0) {  // a pad: no row
+      if (lane == 0) a.deg[r] = 0;
+      continue;
+    }
     unsigned long long m[2], ms[2];
 #pragma unroll
     for (int wi = 0; wi < 2; ++wi) {
@@ -1754,6 +1799,7 @@ static void lb_launch_nl(lb_engine* e, int small, const lb_nl_args& a) {
 static lb_nls_args lb_nls_setup(lb_engine* e, bool want_efeat64, int npad) {
   lb_nls_args a{};
   a.win = e->win;
+  a.ptype = e->ptype;
   a.out = {e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : nullptr};
   a.deg = e->deg;
   a.row_ptr = e->row_ptr;
@@ -1848,30 +1894,31 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
     }
     e->cells_traj_ready = false;   // (cell_count is rewritten: k_cells_traj's occupancy slots must be zeroed again after this)
     hipLaunchKernelGGL(k_cell_zero, dim3((ncell_tot + 255) / 256), dim3(256), 0, s, e->ctrl, e->cell_count, ncell_tot);
-    hipLaunchKernelGGL(k_cell_bin, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->cell_of,
-                       e->cell_count, e->cell_part, e->cpos, e->cell_capacity, strided_slots);
+    hipLaunchKernelGGL(k_cell_bin, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
+                       e->cell_of, e->cell_count, e->cell_part, e->cpos, e->cell_capacity, strided_slots);
   } else if (small_cells) {
     hipLaunchKernelGGL((k_cells_small<LB_SMALL_N / LB_SMALL_T>), dim3(1), dim3(LB_SMALL_T), sizeof(int) * (size_t)ncell_tot, s, g,
-                       BN, e->win, e->ctrl, e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
+                       BN, e->win, e->ctrl, e->ptype, e->deg, e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
   } else if (traj_cells) {
     if (!e->cells_traj_ready) {  // occ[0 .. B] (max occupancy per trajectory, arrival ticket) live in the unused cell_count
       LB_HIP(hipMemsetAsync(e->cell_count, 0, sizeof(int32_t) * (size_t)(g.B + 1), s));
       e->cells_traj_ready = true;
     }
     lb_launch_lds<k_cells_traj<LB_CELLS1_PER>>(sizeof(int) * LB_CELLS1_NCELL, dim3(g.B), dim3(LB_SMALL_T),
-                                               sizeof(int) * (size_t)g.ncells, s, g, BN, e->win, e->ctrl, e->cell_of,
-                                               e->cell_start, e->cell_part, e->cpos, e->cell_count);
+                                               sizeof(int) * (size_t)g.ncells, s, g, BN, e->win, e->ctrl, e->ptype,
+                                               e->live_cnt, e->deg, e->cell_of, e->cell_start, e->cell_part, e->cpos,
+                                               e->cell_count);
   } else if (mid_cells) {
     lb_launch_lds<k_cells_small<LB_CELLS1_PER>>(sizeof(int) * LB_CELLS1_NCELL, dim3(1), dim3(LB_SMALL_T),
-                                                sizeof(int) * (size_t)ncell_tot, s, g, BN, e->win, e->ctrl, e->cell_of,
-                                                e->cell_start, e->cell_part, e->cpos, ncell_tot);
+                                                sizeof(int) * (size_t)ncell_tot, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
+                                                e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
   } else {
     e->cells_traj_ready = false;  // (the counting sort uses cell_count: k_cells_traj's occ[] must be zeroed again after it)
     LB_HIP(hipMemsetAsync(e->cell_count, 0, sizeof(int32_t) * 2 * (size_t)ncell_tot, s));
     // (max_cell_occ, max_deg, row_overflow are reset by k_cell_count)
     const int nb = (int)((BN + 255) / 256);
-    hipLaunchKernelGGL(k_cell_count, dim3(nb), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->cell_of,
-                       e->cell_count);
+    hipLaunchKernelGGL(k_cell_count, dim3(nb), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
+                       e->cell_of, e->cell_count);
     const int nsb_c = (ncell_tot + SCAN_CHUNK - 1) / SCAN_CHUNK;
     hipLaunchKernelGGL(k_scan_partials, dim3(nsb_c), dim3(SCAN_THREADS), 0, s, e->cell_count, ncell_tot,
                        e->scan_part, e->ctrl, &e->ctrl->max_cell_occ);

@@ -4,7 +4,10 @@ Same constructor, same windows (`get_window`, train) / trajectories (`get_trajec
 split into ``sequence_length // (input_seq_length + extra_seq_length)`` chunks), same attributes
 (``metadata``, ``input_seq_length``, ``num_samples``, ``external_force_fn``).  Files are read with
 ``lagrangebench_amd.data.h5`` (ctypes on libhdf5; h5py if present).  Not mirrored: the automatic
-Zenodo download (no network here - a missing dataset raises) and the matscipy padding branch.
+Zenodo download (no network here - a missing dataset raises).  ``nl_backend="matscipy"`` means what it means in the
+reference (data.py:183-197): the trajectories have different particle counts and every sample is padded to
+``metadata["num_particles_max"]`` with position 0 and particle type ``NodeType.PAD_VALUE``; the neighbor search
+itself is the HIP engine's, which leaves the pads out (case_setup/case.py).
 
 ``force.py`` shipped with the RPF / DAM datasets is JAX code; it is executed against a small
 ``jax.numpy`` -> NumPy shim (enough for the published force functions) and then *compiled* into a
@@ -149,8 +152,6 @@ class H5Dataset:
             raise FileNotFoundError(f"dataset {dataset_path} not found (automatic download is not available offline)")
         assert split in ["train", "valid", "test"]
         assert input_seq_length > 1, "To compute at least one past velocity, input_seq_length must be >= 2."
-        if nl_backend == "matscipy":
-            raise NotImplementedError("padded variable-N datasets (matscipy backend) are not built")
         self.dataset_path = dataset_path
         self.file_path = osp.join(dataset_path, split + ".h5")
         self.input_seq_length = input_seq_length
@@ -211,6 +212,17 @@ class H5Dataset:
         except Exception:
             pass
 
+    def _matscipy_pad(self, pos_input, particle_type):
+        """data.py:183-197: pad to num_particles_max with position 0 / NodeType.PAD_VALUE (trailing rows)."""
+        from ..utils import NodeType
+        padding_size = int(self.metadata["num_particles_max"]) - pos_input.shape[0]
+        if padding_size < 0:
+            raise ValueError(f"a trajectory has {pos_input.shape[0]} particles, metadata['num_particles_max'] is "
+                             f"{self.metadata['num_particles_max']}")
+        pos_input = np.pad(pos_input, ((0, padding_size), (0, 0), (0, 0)), mode="constant", constant_values=0.0)
+        particle_type = np.pad(particle_type, (0, padding_size), mode="constant", constant_values=int(NodeType.PAD_VALUE))
+        return pos_input, particle_type
+
     def get_trajectory(self, idx: int):
         """data.py:199-225."""
         db = self._open()
@@ -223,6 +235,8 @@ class H5Dataset:
         key = self.traj_keys[traj_idx]
         pos_input = np.asarray(db[f"{key}/position"][slice_from:slice_to]).transpose((1, 0, 2))
         particle_type = np.asarray(db[f"{key}/particle_type"][:])
+        if self.nl_backend == "matscipy":
+            pos_input, particle_type = self._matscipy_pad(pos_input, particle_type)
         return pos_input, particle_type
 
     def get_window(self, idx: int):
@@ -234,6 +248,8 @@ class H5Dataset:
         key = self.traj_keys[traj_idx]
         pos = np.asarray(db[f"{key}/position"][el_idx:el_idx + self.subseq_length]).transpose((1, 0, 2))
         particle_type = np.asarray(db[f"{key}/particle_type"][:])
+        if self.nl_backend == "matscipy":
+            pos, particle_type = self._matscipy_pad(pos, particle_type)
         return pos, particle_type
 
     def __getitem__(self, idx: int):

@@ -78,6 +78,12 @@ def _bind(lib):
         "H5Sselect_hyperslab": (herr_t, [hid_t, C.c_int, C.POINTER(hsize_t), C.POINTER(hsize_t),
                                         C.POINTER(hsize_t), C.POINTER(hsize_t)]),
         "H5Dread": (herr_t, [hid_t, hid_t, hid_t, hid_t, hid_t, C.c_void_p]),
+        # (write_file)
+        "H5Fcreate": (hid_t, [C.c_char_p, C.c_uint, hid_t, hid_t]),
+        "H5Gcreate2": (hid_t, [hid_t, C.c_char_p, hid_t, hid_t, hid_t]),
+        "H5Gclose": (herr_t, [hid_t]),
+        "H5Dcreate2": (hid_t, [hid_t, C.c_char_p, hid_t, hid_t, hid_t, hid_t, hid_t]),
+        "H5Dwrite": (herr_t, [hid_t, hid_t, hid_t, hid_t, hid_t, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -198,3 +204,44 @@ def open_file(path: str):
         return h5py.File(path, "r")
     except ImportError:
         return File(path, "r")
+
+
+def write_file(path: str, groups) -> None:
+    """Write ``{group: {dataset: array}}`` (float32 / float64 / int32 / int64 arrays, contiguous layout) to a new HDF5
+    file - the layout of a LagrangeBench split, ``{"00000": {"position": (T, N, dim), "particle_type": (N,)}, ...}``,
+    where N may differ from group to group.  h5py is used when it is importable."""
+    try:
+        import h5py  # type: ignore
+        with h5py.File(path, "w") as f:
+            for g, dsets in groups.items():
+                for name, arr in dsets.items():
+                    f.create_dataset(f"{g}/{name}", data=np.asarray(arr))
+        return
+    except ImportError:
+        pass
+    lib = _load()
+    fid = lib.H5Fcreate(path.encode(), 2, 0, 0)  # H5F_ACC_TRUNC
+    if fid < 0:
+        raise IOError(f"H5Fcreate failed on {path}")
+    try:
+        for g, dsets in groups.items():
+            gid = lib.H5Gcreate2(fid, g.encode(), 0, 0, 0)
+            if gid < 0:
+                raise IOError(f"H5Gcreate2 failed on {g}")
+            try:
+                for name, arr in dsets.items():
+                    a = np.ascontiguousarray(arr)
+                    tid = _native(lib, a.dtype)
+                    dims = (hsize_t * max(a.ndim, 1))(*a.shape)
+                    sid = lib.H5Screate_simple(a.ndim, dims, None)
+                    did = lib.H5Dcreate2(gid, name.encode(), tid, sid, 0, 0, 0)
+                    rc = lib.H5Dwrite(did, tid, 0, 0, 0, a.ctypes.data_as(C.c_void_p)) if did >= 0 else -1
+                    if did >= 0:
+                        lib.H5Dclose(did)
+                    lib.H5Sclose(sid)
+                    if rc < 0:
+                        raise IOError(f"writing {g}/{name} failed")
+            finally:
+                lib.H5Gclose(gid)
+    finally:
+        lib.H5Fclose(fid)

@@ -12,7 +12,10 @@ eval mode (data/data.py:33-269): ``ds[i] -> (pos (N,T,dim) float32, particle_typ
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Tuple
+import copy
+import json
+import os
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -250,3 +253,98 @@ def make_case(name: str, n_trajs: int = 1, extra_seq_length: int = 20, input_seq
                                 multiplier=2.0, noise_std=1e-3, isotropic_norm=True)
 
     raise ValueError(f"unknown synthetic case {name!r}")
+
+
+# ------------------------------------------------------------------------------------ padded trajectories
+PAD_VALUE = -1  # utils.NodeType.PAD_VALUE
+
+
+def _pad(pos: np.ndarray, pt: np.ndarray, n_max: int) -> Tuple[np.ndarray, np.ndarray]:
+    """H5Dataset._matscipy_pad: trailing rows, position 0, particle type PAD_VALUE."""
+    k = n_max - pos.shape[0]
+    return (np.pad(pos, ((0, k), (0, 0), (0, 0)), mode="constant", constant_values=0.0),
+            np.pad(pt, (0, k), mode="constant", constant_values=PAD_VALUE).astype(np.int32))
+
+
+def make_padded_case(name: str, n_particles: Sequence[int], n_max: Optional[int] = None, extra_seq_length: int = 20,
+                     input_seq_length: int = 6, scale: float = 1.0, vel_amp: float = 1.0) -> SyntheticDataset:
+    """A dataset whose trajectory i has ``n_particles[i]`` real particles, every sample already padded to ``n_max``
+    (default: the largest count) the way the reference pads variable-N data for its `matscipy` backend: trailing rows at
+    position 0 with particle type -1; ``metadata["num_particles_max"] == n_max``.  ``ds.n_real[i]`` is the real count.
+
+    ``name == "waterdrop2d"``: shaped like the GNS WaterDrop data - 2D, no periodic axis, bounds [0.1, 0.9]^2 (so the
+    boundary-distance features are on), no wall particles; a block of fluid falling under gravity.  Any ``make_case``
+    name (tgv2d, small2d, small3d, tgv3d, ...; ``scale`` / ``vel_amp`` as there): trajectory i is ``n_particles[i]``
+    randomly chosen particles (seeded, index order kept) of that case's trajectory i."""
+    name = name.lower()
+    counts = [int(n) for n in n_particles]
+    n_max = max(counts) if n_max is None else int(n_max)
+    assert counts and min(counts) > 0 and n_max >= max(counts)
+    isl = input_seq_length
+    T = isl + extra_seq_length
+    if name == "waterdrop2d":
+        dx = 0.008
+        lo, hi = 0.1, 0.9
+        rc = 1.45 * dx
+        vel_std, acc_std = 0.3 * dx, 0.04 * dx
+        md = _meta(2, n_max, [hi - lo, hi - lo], [False, False], rc, dx, vel_std, acc_std, T, name)
+        md["bounds"] = [[lo, hi], [lo, hi]]
+
+        def make(i):
+            rng = np.random.default_rng(1000 + i)
+            n = counts[i]
+            w = max(2, int(math.ceil(math.sqrt(2.0 * n))))          # a block about twice as wide as high
+            lat = _lattice([w, (n + w - 1) // w], dx)[:n]
+            org = np.array([lo + 0.1 + 0.25 * rng.random() * (hi - lo - 0.2 - w * dx), 0.45 + 0.1 * rng.random()])
+            p0 = lat + org + rng.normal(0, 0.08 * dx, size=(n, 2))
+            v0 = vel_amp * vel_std * np.array([0.8, 0.0]) + rng.normal(0, 0.05 * vel_std * vel_amp, size=(n, 2))
+            g = vel_amp * np.array([0.0, -0.5 * acc_std])
+            t = np.arange(T, dtype=np.float64)[None, :, None]
+            tr = p0[:, None, :] + v0[:, None, :] * t + 0.5 * g * t * t
+            tr = np.clip(tr, lo + 0.5 * dx, hi - 0.5 * dx).astype(np.float32)
+            return _pad(tr, np.zeros(n, np.int32), n_max)
+
+        # multiplier 2: a cell of this lattice holds 1 to 4 particles, and int(3 * 1.25) = 3 slots sized on one sample would
+        # not hold another sample's fourth
+        ds = SyntheticDataset(name, md, isl, extra_seq_length, len(counts), make, multiplier=2.0)
+    else:
+        base = make_case(name, n_trajs=len(counts), extra_seq_length=extra_seq_length, input_seq_length=isl, scale=scale,
+                         vel_amp=vel_amp)
+        n0 = int(base.metadata["num_particles_max"])
+        assert max(counts) <= n0, f"{name} (scale {scale}) has {n0} particles"
+        md = copy.deepcopy(base.metadata)
+        md["num_particles_max"] = n_max
+
+        def make(i):
+            pos, pt = base[i]
+            keep = np.sort(np.random.default_rng(2000 + i).choice(n0, counts[i], replace=False))
+            return _pad(pos[keep], pt[keep], n_max)
+
+        ds = SyntheticDataset(name, md, isl, extra_seq_length, len(counts), make, force=base.force,
+                              force_numpy=base.external_force_fn, multiplier=base.multiplier, noise_std=base.noise_std,
+                              isotropic_norm=base.isotropic_norm)
+    ds.n_real = counts
+    return ds
+
+
+def write_padded_h5(ds: SyntheticDataset, path: str, splits: Sequence[str] = ("train", "valid", "test")) -> str:
+    """Write a (padded) synthetic dataset as a LagrangeBench dataset directory: ``{split}.h5`` with one group per
+    trajectory (``position`` (T, n_i, dim) float32, ``particle_type`` (n_i,) int32 - the pads are stripped, so the shapes
+    differ from group to group, as in the variable-N data the reference reads with ``nl_backend="matscipy"``) and
+    ``metadata.json``.  Every split holds the same trajectories."""
+    from . import h5
+    os.makedirs(path, exist_ok=True)
+    groups = {}
+    for i in range(len(ds)):
+        pos, pt = ds[i]
+        real = pt != PAD_VALUE
+        groups[f"{i:05d}"] = {"position": np.ascontiguousarray(pos[real].transpose(1, 0, 2), dtype=np.float32),
+                              "particle_type": np.ascontiguousarray(pt[real], dtype=np.int32)}
+    for split in splits:
+        h5.write_file(os.path.join(path, split + ".h5"), groups)
+    md = copy.deepcopy(ds.metadata)
+    T = ds.input_seq_length + ds.extra_seq_length
+    md.update({"sequence_length_train": T, "num_trajs_train": len(ds), "sequence_length_test": T, "num_trajs_test": len(ds)})
+    with open(os.path.join(path, "metadata.json"), "w") as f:
+        json.dump(md, f, indent=1)
+    return path

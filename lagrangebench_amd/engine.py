@@ -116,6 +116,7 @@ class RolloutEngine:
         self.cell_capacity = 0
         self.e_cap = 0
         self.version = 0  # bumped whenever window / list change: ties FeatureDicts to a state
+        self.has_pads = False  # the current particle types hold NodeType.PAD_VALUE (set_particle_type)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -143,7 +144,11 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------ state
     def set_particle_type(self, ptype) -> None:
-        t = self._t(ptype, torch.int32).reshape(self.B, self.N)
+        """(B, N) particle types.  NodeType.PAD_VALUE (-1) marks a particle that is not there (padded trajectories): the
+        engine leaves it out of the neighbor search; `has_pads` tells the models (only GNS takes padded input)."""
+        src = ptype if isinstance(ptype, torch.Tensor) else torch.as_tensor(np.asarray(ptype))
+        self.has_pads = bool((src == -1).any())
+        t = self._t(src, torch.int32).reshape(self.B, self.N)
         check(self.lib.lb_set_particle_type(self._h, ptr(t)), "lb_set_particle_type")
 
     def prepare_traj(self, pos) -> torch.Tensor:

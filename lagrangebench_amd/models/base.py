@@ -22,6 +22,7 @@ class BaseModel(ABC):
     _FORWARD = ""
     _OUTPUT = "acc"
     _HAIKU_KEY = ""
+    _PADDED_OK = False  # runs on padded trajectories (particles of type NodeType.PAD_VALUE): GNS only
     _MAX_HANDLES = 4  # device copies kept per model object (LRU): a training loop that hands over a fresh
     #                   parameter tree every step must not accumulate one packed weight blob per step
 
@@ -50,9 +51,15 @@ class BaseModel(ABC):
                             float(flat[:: max(1, flat.size // 7)].astype(np.float64).sum())))
         return tuple(out)
 
+    def _check_padded(self, engine) -> None:
+        if getattr(engine, "has_pads", False) and not self._PADDED_OK:
+            raise NotImplementedError(f"{type(self).__name__}: padded trajectories (particles of type NodeType.PAD_VALUE, "
+                                      "the matscipy backend's variable particle counts) run with GNS only")
+
     def handle(self, engine, params, state=None):
         """The engine handle of (params, state): reused while `params` is the same object with the same content on the
         same engine, else created anew."""
+        self._check_padded(engine)
         handles = self._handles  # {(id(engine), id(params)): (handle, params, stamp)}, set by the model's __init__
         key = (id(engine), id(params))
         hit = handles.get(key)
@@ -107,6 +114,7 @@ class BaseModel(ABC):
     def train_handle(self, engine, params):
         """Device-resident training state (weights, gradients, AdamW moments) for `params` on `engine`."""
         self.check_trainable()
+        self._check_padded(engine)
         return self._train_create(engine, params)
 
     def _train_create(self, engine, params):
@@ -115,4 +123,5 @@ class BaseModel(ABC):
     def loss_grad(self, th, target, loss_weight) -> float:
         """One loss + gradient accumulation of the training handle `th` against the case's targets (trainer.py:35-89):
         _mse of the normalised acceleration."""
+        self._check_padded(th.engine)
         return th.loss_grad(target["acc"], loss_weight.get("acc", 1.0))

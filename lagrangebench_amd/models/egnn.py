@@ -180,4 +180,5 @@ class EGNN(BaseModel):
 
     def loss_grad(self, th, target, loss_weight) -> float:
         """_mse over every output the model predicts (pos, vel, acc)."""
+        self._check_padded(th.engine)
         return th.loss_grad(target, loss_weight)

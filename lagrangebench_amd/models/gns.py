@@ -36,6 +36,7 @@ def _trunc_normal(rng, shape, stddev):
 
 
 class GNS(BaseModel):
+    _PADDED_OK = True  # pads are in no edge and outside the loss (csrc/lb_neighbor.hip, csrc/lb_train.hip)
     def __init__(self, particle_dimension: int, latent_size: int, blocks_per_step: int,
                  num_mp_steps: int, particle_type_embedding_size: int,
                  num_particle_types: int = NodeType.SIZE):

@@ -155,7 +155,12 @@ class Trainer:
                     print(f"Reallocate neighbors list at step {step}")
                     ind = int(torch.argmax(neighbors.did_buffer_overflow.int()))
                     old = neighbors.max_occupancy
-                    _, _, _, neighbors = case.allocate(key, (raw_batch[0][ind], raw_batch[1][ind]), noise_std)
+                    if case.engine(B).has_pads:
+                        # padded trajectories: a list sized on ONE sample cannot serve a batch that mixes particle counts
+                        # (the next, larger trajectory overflows it again, and so on): size it on the whole batch
+                        _, _, _, neighbors = case.allocate(key, sample, noise_std)
+                    else:
+                        _, _, _, neighbors = case.allocate(key, (raw_batch[0][ind], raw_batch[1][ind]), noise_std)
                     print(f"From (2, {old}) to (2, {neighbors.max_occupancy})")
                     continue
                 # value_and_grad of _mse vmapped over the batch, gradients summed, loss averaged (trainer.py:63-89) +
