@@ -227,6 +227,21 @@ int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* in_host, int
 /* optax's `count`: AdamW steps taken so far (the bias-correction exponent of the NEXT step is count + 1); what a
  * checkpoint has to store to resume bit-identically (utils.py:61-91 pickles it inside opt_state). */
 int64_t lb_gns_train_step_count(lb_gns_train* t);
+/* Data-parallel training (one process per GPU, the batch split over the ranks).
+ * lb_gns_train_device_blob: the DEVICE pointer of blob `which` (0 weights, 1 gradients, 2 / 3 AdamW moments) and its
+ * float count in the device layout (latent padded to 128: >= the n_floats of read / write; the padding is zero and stays
+ * zero).  Every rank has the same layout, so this is what a collective gathers - no host copy, no re-ordering.  The
+ * engine's stream is synchronised before the call returns; the pointer lives as long as the handle.
+ * lb_adamw_step_gathered: gathered_dev = `world` rows of that many floats, row r = rank r's gradient blob (world 1 ... 16;
+ * for world > 1 it must not overlap the handle's own gradient blob).  ONE kernel sums the rows per parameter in rank
+ * order, g = ((row0 + row1) + row2) + ... in fp32 with plain adds, multiplies by grad_scale (1: the reference's
+ * "gradients summed over the batch"), stores g as the handle's gradient blob and applies lb_adamw_step's arithmetic to
+ * weights and moments; the step counter advances once.  No atomics, a fixed order: ranks that start from the same
+ * weights and get the same rows end with the same bits.  world 1 with the handle's own gradients, grad_scale 1 gives
+ * the bits of lb_adamw_step. */
+int lb_gns_train_device_blob(lb_gns_train* t, int32_t which, float** dev_out, int64_t* n_floats_out);
+int lb_adamw_step_gathered(lb_gns_train* t, const float* gathered_dev, int32_t world, float grad_scale, float lr,
+                           float b1, float b2, float eps, float weight_decay);
 /* Arithmetic of the training step (round 5 / 6).  Default: every tall-skinny product (Y = XW, dX = dY W^T, dW += X^T dY) runs
  * as three fp16 MFMA passes over hi / lo splits of fp32 operands, fp32 accumulate; the operands of the first two are put into
  * fp16's range by exact power-of-two scales per row block / matrix, dY of the third per row chunk.  Its X operand (saved

@@ -886,6 +886,67 @@ __global__ void k_adamw(float* __restrict__ w, const float* __restrict__ g, floa
   w[i] -= lr * (mh / (sqrtf(vh) + eps) + wd * w[i]);
 }
 
+// Data-parallel step: gath = `world` rows of n floats (row r: rank r's gradient blob).  Per parameter, by ONE lane:
+// g = (((row0 + row1) + row2) + ...) * scale in rank order, stored to the gradient blob, then k_adamw's arithmetic,
+// expression by expression (the file is compiled with -ffp-contract=off: same source, same roundings).  Bandwidth
+// bound at (world + 6) * 4 bytes per parameter: each lane of the grid-stride loop (capped grid) moves four consecutive
+// parameters with 16-byte loads / stores; no LDS, no atomics, no cross-lane traffic.  The blobs are 16-byte aligned;
+// a gathered row starts r * n floats in, which for n % 4 != 0 (GNS-10-128: n = 1212435) is only 4-byte aligned: those
+// loads are still one dwordx4 each (lb_f4u: global memory needs dword alignment only).  The n % 4 last parameters are
+// done one by one by the first lanes of block 0.  g and gath are not __restrict__: at world 1 the caller may pass the
+// gradient blob itself as the one row.
+struct __attribute__((packed, aligned(4))) lb_f4u { float f[4]; };
+__device__ __forceinline__ void adamw_elem(float gi, float& wk, float& mk, float& vk, float lr, float b1, float b2, float eps,
+                                           float wd, float c1, float c2) {
+  const float mn = b1 * mk + (1.f - b1) * gi;
+  const float vn = b2 * vk + (1.f - b2) * gi * gi;
+  mk = mn;
+  vk = vn;
+  const float mh = mn / c1, vh = vn / c2;
+  wk -= lr * (mh / (sqrtf(vh) + eps) + wd * wk);
+}
+__global__ void __launch_bounds__(256) k_adamw_gathered(float* __restrict__ w, float* g, float* __restrict__ m,
+                                                         float* __restrict__ v, const float* gath, int64_t n, int world,
+                                                         float scale, float lr, float b1, float b2, float eps, float wd,
+                                                         float c1, float c2) {
+  const int64_t nv = n / 4, stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t i = tid; i < nv; i += stride) {
+    lb_f4u acc = *reinterpret_cast<const lb_f4u*>(gath + 4 * i);
+#pragma unroll 4
+    for (int r = 1; r < world; ++r) {
+      const lb_f4u row = *reinterpret_cast<const lb_f4u*>(gath + (int64_t)r * n + 4 * i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc.f[k] = acc.f[k] + row.f[k];
+    }
+    union { float4 q; float f[4]; } gi, wi, mi, vi;
+    wi.q = reinterpret_cast<const float4*>(w)[i];
+    mi.q = reinterpret_cast<const float4*>(m)[i];
+    vi.q = reinterpret_cast<const float4*>(v)[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      gi.f[k] = acc.f[k] * scale;
+      adamw_elem(gi.f[k], wi.f[k], mi.f[k], vi.f[k], lr, b1, b2, eps, wd, c1, c2);
+    }
+    reinterpret_cast<float4*>(g)[i] = gi.q;
+    reinterpret_cast<float4*>(m)[i] = mi.q;
+    reinterpret_cast<float4*>(v)[i] = vi.q;
+    reinterpret_cast<float4*>(w)[i] = wi.q;
+  }
+  const int64_t j = 4 * nv + tid;   // the n % 4 parameters after the last whole vector
+  if (j < n) {
+    float acc = gath[j];
+    for (int r = 1; r < world; ++r) acc = acc + gath[(int64_t)r * n + j];
+    const float gi = acc * scale;
+    float wk = w[j], mk = m[j], vk = v[j];
+    adamw_elem(gi, wk, mk, vk, lr, b1, b2, eps, wd, c1, c2);
+    g[j] = gi;
+    m[j] = mk;
+    v[j] = vk;
+    w[j] = wk;
+  }
+}
+
 // ------------------------------------------------------------------------------------------- host helpers
 #define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
 
@@ -1808,6 +1869,35 @@ extern "C" int lb_adamw_step(lb_gns_train* t, float lr, float b1, float b2, floa
   const float c1 = 1.f - powf(b1, (float)t->step), c2 = 1.f - powf(b2, (float)t->step);
   hipLaunchKernelGGL(k_adamw, GRID1(t->n_floats), 0, t->eng->stream, t->w, t->g, t->m, t->v, t->n_floats, lr, b1, b2, eps,
                      weight_decay, c1, c2);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+
+// The device blob itself, in the device layout (n_floats: latent padded to 128) - what a collective gathers.
+extern "C" int lb_gns_train_device_blob(lb_gns_train* t, int32_t which, float** dev_out, int64_t* n_floats_out) {
+  if (!t || !dev_out || !n_floats_out || which < 0 || which > 3) return lb_fail(LB_ERR_ARG, "bad argument");
+  LB_HIP(hipStreamSynchronize(t->eng->stream));
+  *dev_out = which == 0 ? t->w : which == 1 ? t->g : which == 2 ? t->m : t->v;
+  *n_floats_out = t->n_floats;
+  return LB_OK;
+}
+
+// The data-parallel optimiser step: rank-ordered sum of `world` gathered gradient rows + AdamW, one launch (k_adamw_gathered)
+extern "C" int lb_adamw_step_gathered(lb_gns_train* t, const float* gathered_dev, int32_t world, float grad_scale, float lr,
+                                      float b1, float b2, float eps, float weight_decay) {
+  if (!t || !gathered_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (world < 1 || world > 16) return lb_fail(LB_ERR_ARG, "world = %d: 1 ... 16 rows of gradients", (int)world);
+  if ((uintptr_t)gathered_dev % sizeof(float)) return lb_fail(LB_ERR_ARG, "the gathered rows are not float aligned");
+  const int64_t n = t->n_floats;
+  if (world > 1 && gathered_dev < t->g + n && t->g < gathered_dev + (int64_t)world * n)
+    return lb_fail(LB_ERR_ARG, "the gathered rows overlap the handle's gradient blob");
+  if (n <= 0) return LB_OK;
+  t->step += 1;
+  const float c1 = 1.f - powf(b1, (float)t->step), c2 = 1.f - powf(b2, (float)t->step);
+  // one lane per four parameters; 256 CUs x 8 blocks at most, grid-stride the rest; >= 1 block for the n % 4 tail
+  const unsigned blocks = (unsigned)std::min<int64_t>((n / 4 + 255) / 256 + (n < 4 ? 1 : 0), 2048);
+  hipLaunchKernelGGL(k_adamw_gathered, dim3(blocks), dim3(256), 0, t->eng->stream, t->w, t->g, t->m, t->v, gathered_dev, n,
+                     (int)world, grad_scale, lr, b1, b2, eps, weight_decay, c1, c2);
   LB_HIP(hipGetLastError());
   return LB_OK;
 }

@@ -1,8 +1,13 @@
 """Multi-GPU: independent trajectories shard embarrassingly (the reference's only batching is a
-vmap over trajectories on one device, evaluate/rollout.py:226-230).  One process per GPU; there
-is NO data-path collective - torch.distributed (backend "nccl" = RCCL over xGMI on ROCm, "gloo"
+vmap over trajectories on one device, evaluate/rollout.py:226-230).  One process per GPU; inference
+has NO data-path collective - torch.distributed (backend "nccl" = RCCL over xGMI on ROCm, "gloo"
 in CPU tests) is used only to gather the per-trajectory metric vectors and to agree on the
 slowest rank's wall time.
+
+Training splits the batch (``shard_batch``) and gathers every rank's gradient blob
+(``all_gather_rows``); the sum over the ranks is NOT left to the collective library: one HIP kernel
+adds the gathered rows in rank order and applies AdamW (engine.GnsTrainHandle.adamw_step_gathered),
+so the gradients stay bit-reproducible and every rank ends a step with the same weight bits.
 """
 from __future__ import annotations
 
@@ -92,6 +97,44 @@ def group_info(device: Optional[torch.device] = None) -> dict:
 def shard_trajectories(n_trajs: int, rank: int, world: int) -> List[int]:
     """Trajectory i -> rank i % world."""
     return [i for i in range(n_trajs) if i % world == rank]
+
+
+def shard_batch(batch_size: int, rank: int, world: int) -> slice:
+    """The contiguous, equal slice of a global batch that `rank` trains on.  Equal shards are what makes "mean over the
+    ranks of the local mean losses" the global mean, so an indivisible batch is an error, not a remainder."""
+    batch_size, rank, world = int(batch_size), int(rank), int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_batch: rank {rank} of world {world}")
+    if batch_size % world != 0:
+        raise ValueError(f"batch_size = {batch_size} is not divisible by the world size {world}: data-parallel training "
+                         "splits train.batch_size (the GLOBAL batch) into equal shards")
+    per = batch_size // world
+    return slice(rank * per, (rank + 1) * per)
+
+
+def all_gather_rows(t: torch.Tensor) -> torch.Tensor:
+    """(n,) device tensor on every rank -> (world, n) tensor on the same device, row r = rank r's `t`.  Ranks that own
+    their GPU gather on the device; ranks that share one (gloo, as _coll_device decides) stage through host memory.
+    One rank: a view of `t`, no collective."""
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"all_gather_rows: expected a contiguous 1-D tensor, got {tuple(t.shape)}")
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return t.view(1, -1)
+    world = dist.get_world_size()
+    dev = _coll_device(t.device)
+    out = torch.empty((world, t.numel()), dtype=t.dtype, device=dev)
+    dist.all_gather(list(out.unbind(0)), t.to(dev))
+    return out.to(t.device)
+
+
+def gather_scalars(value: float, device: Optional[torch.device] = None) -> List[float]:
+    """One float64 per rank, in rank order, on every rank."""
+    if not dist.is_initialized():
+        return [float(value)]
+    t = torch.tensor([value], dtype=torch.float64, device=_coll_device(device))
+    out = [torch.empty_like(t) for _ in range(dist.get_world_size())]
+    dist.all_gather(out, t)
+    return [float(x.item()) for x in out]
 
 
 def barrier(device: Optional[torch.device] = None) -> None:

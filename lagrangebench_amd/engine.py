@@ -453,9 +453,19 @@ class GnsHandle(_Handle):
         return None
 
 
+class _DeviceSpan:
+    """n float32 at a device address owned by a training handle, in the form torch.as_tensor wraps without a copy
+    (__cuda_array_interface__); the tensor keeps this object, and with it the handle, referenced."""
+
+    def __init__(self, owner, addr: int, n: int):
+        self._owner = owner
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<f4", "data": (int(addr), False), "version": 2}
+
+
 class GnsTrainHandle(_Handle):
     """trainer.py:35-89 on the device: value_and_grad of _mse summed over the batch + optax.adamw."""
     _DESTROY = "lb_gns_train_destroy"
+    _dev_floats: Optional[int] = None
 
     def loss_grad(self, target: torch.Tensor, loss_weight: float = 1.0, want_pred: bool = False):
         """target (B, N, dim) normalised accelerations -> mean per-trajectory loss (float); gradients accumulate."""
@@ -473,6 +483,37 @@ class GnsTrainHandle(_Handle):
     def adamw_step(self, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8, weight_decay: float = 1e-8) -> None:
         check(self.engine.lib.lb_adamw_step(self._h, C.c_float(lr), C.c_float(b1), C.c_float(b2), C.c_float(eps),
                                             C.c_float(weight_decay)), "lb_adamw_step")
+
+    def device_blob(self, which: str = "grads") -> torch.Tensor:
+        """The device memory of a blob as a 1-D float32 tensor - a view, no copy - in the DEVICE layout (latents padded
+        to 128, so it can be longer than read(which); every rank of a data-parallel run has the same layout).  Valid
+        until close()."""
+        idx = {"weights": 0, "grads": 1, "m": 2, "v": 3}[which]
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.engine.lib.lb_gns_train_device_blob(self._h, idx, C.byref(p), C.byref(n)), "lb_gns_train_device_blob")
+        self._dev_floats = n.value
+        return torch.as_tensor(_DeviceSpan(self, p.value, n.value), device=self.engine.device)
+
+    def device_floats(self) -> int:
+        """Floats of a blob in the device layout (the length of device_blob)."""
+        if self._dev_floats is None:
+            self.device_blob("weights")
+        return self._dev_floats
+
+    def adamw_step_gathered(self, gathered: torch.Tensor, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
+                            weight_decay: float = 1e-8, grad_scale: float = 1.0) -> None:
+        """The data-parallel AdamW step: `gathered` (world, len(device_blob)) float32 on the engine's device, row r = the
+        gradients of rank r.  One kernel sums the rows in rank order, keeps the sum (x grad_scale) as this handle's
+        gradients and applies adamw_step's arithmetic (include/lbhip.h: lb_adamw_step_gathered)."""
+        e, n = self.engine, self.device_floats()
+        if gathered.dim() != 2 or gathered.shape[1] != n or not 1 <= gathered.shape[0] <= 16:
+            raise ValueError(f"adamw_step_gathered: expected (1 ... 16, {n}) gradient rows, got {tuple(gathered.shape)}")
+        if gathered.dtype != torch.float32 or gathered.device != e.device or not gathered.is_contiguous():
+            raise ValueError(f"adamw_step_gathered: the rows must be contiguous float32 on {e.device} "
+                             f"(got {gathered.dtype}, {gathered.device}, contiguous={gathered.is_contiguous()})")
+        check(e.lib.lb_adamw_step_gathered(self._h, ptr(gathered), int(gathered.shape[0]), C.c_float(grad_scale), C.c_float(lr),
+                                           C.c_float(b1), C.c_float(b2), C.c_float(eps), C.c_float(weight_decay)),
+              "lb_adamw_step_gathered")
 
     def read(self, which: str = "weights") -> np.ndarray:
         idx = {"weights": 0, "grads": 1, "m": 2, "v": 3}[which]

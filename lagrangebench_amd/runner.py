@@ -3,7 +3,9 @@
 ``train_or_infer(cfg)`` (runner.py:25-143), ``setup_data`` (:146-189) and ``setup_model`` (:192-292)
 keep their signatures.  ``cfg`` is a nested mapping with the reference's keys (a dict or anything
 dict-like such as an OmegaConf DictConfig); missing keys fall back to ``defaults``.  `mode: train | all`
-runs ``train.Trainer`` (GNS, SEGNN and EGNN).
+runs ``train.Trainer`` (GNS, SEGNN and EGNN).  Under torchrun (one process per GPU) training is data parallel over
+``train.batch_size``, the global batch, with no further config key (train/trainer.py); rank 0 alone
+prints and writes checkpoints.
 """
 from __future__ import annotations
 
@@ -13,6 +15,7 @@ from typing import Callable, Dict, Optional, Tuple, Type
 
 import numpy as np
 
+from . import dist as lbdist
 from . import models
 from .case_setup import case_builder
 from .data import H5Dataset
@@ -94,6 +97,8 @@ def train_or_infer(cfg):
         raise ValueError("mode must be one of 'train', 'infer', 'all'")
     if cfg.dtype not in ("float64", "float32"):
         raise NotImplementedError("dtype must be float64 (the reference default) or float32")
+    rank, _, world = lbdist.env_world()
+    say = print if rank == 0 else (lambda *a, **k: None)
     data_train, data_valid, data_test = setup_data(cfg)
     metadata = data_train.metadata
     bounds = np.array(metadata["bounds"])
@@ -109,17 +114,25 @@ def train_or_infer(cfg):
     if mode in ("train", "all"):  # runner.py:74-117
         import time
         from .train import Trainer
-        print("Start training...")
+        say("Start training...")
         if cfg.logging.run_name is None:
             cfg.logging.run_name = f"{cfg.model.name}_{data_train.name}_{time.strftime('%Y%m%d-%H%M%S')}"
         store_ckp = os.path.join(cfg.logging.ckp_dir, cfg.logging.run_name) if cfg.logging.ckp_dir else None
         trainer = Trainer(model, case, data_train, data_valid, cfg.train, cfg.eval, cfg.logging,
                           input_seq_length=cfg.model.input_seq_length, seed=cfg.seed)
+        if world > 1:
+            # one checkpoint tree, rank 0's: a run name made from the clock can differ between the ranks
+            import torch.distributed
+            lbdist.init()
+            names = [cfg.logging.run_name]
+            torch.distributed.broadcast_object_list(names, src=0)
+            cfg.logging.run_name = names[0]
+            store_ckp = os.path.join(cfg.logging.ckp_dir, cfg.logging.run_name) if cfg.logging.ckp_dir else None
         trainer.train(step_max=cfg.train.step_max, load_ckp=cfg.load_ckp, store_ckp=store_ckp)
         if mode == "train":
             return 0
         cfg.load_ckp = os.path.join(store_ckp, "best") if store_ckp else cfg.load_ckp
-    print("Start inference...")
+    say("Start inference...")
     model_dir = cfg.load_ckp
     assert model_dir, "model_dir must be specified for inference."
     is_test = cfg.eval.test
@@ -127,6 +140,6 @@ def train_or_infer(cfg):
                     cfg_eval_infer=cfg.eval.infer, rollout_dir=cfg.eval.rollout_dir,
                     n_rollout_steps=cfg.eval.n_rollout_steps, seed=cfg.seed)
     split = "test" if is_test else "valid"
-    print(f"Metrics of {model_dir} on {split} split:")
-    print(averaged_metrics(metrics))
+    say(f"Metrics of {model_dir} on {split} split:")
+    say(averaged_metrics(metrics))
     return 0

@@ -22,6 +22,13 @@ csrc/lb_train_segnn.h) and EGNN (``lb_egnn_train_loss_grad``, csrc/lb_train_egnn
 backward on the exact-fp32 MFMA products; the loss covers every output the model predicts - pos, vel, acc - weighted by
 ``loss_weight`` against the case's targets, as _mse does; ``normalize=True`` is refused) - the loop below is the
 reference's model-agnostic one; wandb logging is not wired (stdout).
+
+Data parallel (one process per GPU under torchrun, lagrangebench_amd/dist.py): ``train.batch_size``
+stays the GLOBAL batch.  Every rank draws the same permutation and the same push-forward unroll count from the common random
+stream and trains on its ``shard_batch`` slice of each batch (noise: a stream of its own); the gradient blobs are all-gathered
+and ONE HIP kernel sums them in rank order and applies AdamW (``lb_adamw_step_gathered``), so every rank holds the same weight
+bits after every step - checked at each evaluation.  The semantics are the single-process ones: gradients summed over the
+global batch, loss averaged, learning rate as configured.  One rank runs the code below exactly as before.
 """
 from __future__ import annotations
 
@@ -31,6 +38,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
+from .. import dist as lbdist
 from ..defaults import defaults, merge
 from ..evaluate import MetricsComputer, averaged_metrics, eval_rollout
 from ..evaluate.rollout import _Loader
@@ -48,16 +56,17 @@ def exponential_decay(step: int, init_value: float, transition_steps: float, dec
 
 
 class _ShuffledLoader:
-    """DataLoader(dataset, batch_size, shuffle=True, drop_last=True, collate_fn=numpy_collate), in process."""
+    """DataLoader(dataset, batch_size, shuffle=True, drop_last=True, collate_fn=numpy_collate), in process.  `shard`: the
+    slice of every batch that is read and yielded (data parallel: the permutation is the common one, a rank reads its part)."""
 
-    def __init__(self, dataset, batch_size: int, generator: torch.Generator):
-        self.dataset, self.batch_size, self.generator = dataset, batch_size, generator
+    def __init__(self, dataset, batch_size: int, generator: torch.Generator, shard: slice = slice(None)):
+        self.dataset, self.batch_size, self.generator, self.shard = dataset, batch_size, generator, shard
 
     def __iter__(self):
         n = len(self.dataset)
         perm = torch.randperm(n, generator=self.generator).tolist()
         for s in range(0, n - self.batch_size + 1, self.batch_size):
-            items = [self.dataset[k] for k in perm[s:s + self.batch_size]]
+            items = [self.dataset[k] for k in perm[s:s + self.batch_size][self.shard]]
             yield (np.stack([it[0] for it in items]), np.stack([it[1] for it in items]))
 
 
@@ -67,6 +76,10 @@ class Trainer:
         model.check_trainable()   # fail HERE, before datasets and neighbor lists are set up
         self.model, self.case, self.input_seq_length = model, case, input_seq_length
         self.cfg_train = merge(defaults.train, cfg_train)
+        # data parallel: this rank's slice of every (global) batch; an indivisible batch_size fails HERE as well
+        self.rank, self.local_rank, self.world = lbdist.env_world()
+        self.shard = lbdist.shard_batch(self.cfg_train.batch_size, self.rank, self.world)
+        self.seed = int(seed)
         self.cfg_eval = merge(defaults.eval, cfg_eval)
         self.cfg_logging = merge(defaults.logging, cfg_logging)
         available = data_valid.subseq_length - input_seq_length
@@ -81,7 +94,7 @@ class Trainer:
         self.loss_weight = dict(self.cfg_train.loss_weight)
         self.base_key = torch.Generator()
         self.base_key.manual_seed(int(seed))
-        self.loader_train = _ShuffledLoader(data_train, self.cfg_train.batch_size, self.base_key)
+        self.loader_train = _ShuffledLoader(data_train, self.cfg_train.batch_size, self.base_key, self.shard)
         self.loader_valid = _Loader(data_valid, self.cfg_eval.infer.batch_size)
         self.loader_valid.dataset = data_valid
         self.metrics_computer = MetricsComputer(self.cfg_eval.train.metrics, dist_fn=case.displacement,
@@ -92,6 +105,18 @@ class Trainer:
         o = self.cfg_train.optimizer
         return exponential_decay(step, o.lr_start, o.lr_decay_steps, o.lr_decay_rate, o.lr_final)
 
+    def _check_drift(self, th, device) -> None:
+        """Every rank must hold the same weight bits (the rank-ordered sum guarantees it from equal starts): compare an
+        fp64 sum and strided samples of the device weights across the ranks; raises on EVERY rank on a mismatch."""
+        w = th.device_blob("weights").cpu().numpy()
+        sig = np.concatenate([[w.sum(dtype=np.float64)], w[::max(1, w.size // 61)].astype(np.float64)])
+        rows = lbdist.all_gather_rows(torch.from_numpy(sig).to(device)).cpu().numpy()
+        bad = [r for r in range(rows.shape[0]) if not np.array_equal(rows[r].view(np.uint64), rows[0].view(np.uint64))]
+        if bad:
+            raise RuntimeError(f"data-parallel training: the weights of rank(s) {bad} differ from rank 0's (fp64 sums "
+                               f"{[float(rows[r, 0]) for r in bad]} vs {float(rows[0, 0])}): the ranks no longer train "
+                               "the same model")
+
     def train(self, step_max: int = defaults.train.step_max, params=None, state=None, opt_state=None,
               store_ckp: Optional[str] = None, load_ckp: Optional[str] = None, wandb_config=None
               ) -> Tuple[Dict, Dict, Dict]:
@@ -99,6 +124,18 @@ class Trainer:
         model, case, cfg_train, cfg_eval, cfg_logging = self.model, self.case, self.cfg_train, self.cfg_eval, self.cfg_logging
         noise_std, pushforward = cfg_train.noise_std, cfg_train.pushforward
         isl = self.input_seq_length
+        rank, world = self.rank, self.world
+        ddp = world > 1
+        if ddp:
+            # the process group: RCCL with one GPU per rank; LB_DIST_BACKEND=gloo when ranks share a device
+            lbdist.init()
+            if case.device is None:
+                torch.cuda.set_device(lbdist.local_device(self.local_rank))
+            # the common stream (base_key: permutations, unroll counts, the initial weights) steers control flow and is
+            # identical on all ranks; the noise of a rank's shard comes from a stream of its own
+            noise_key = torch.Generator()
+            noise_key.manual_seed((self.seed * 1000003 + rank + 1) % (2**63 - 1))
+        say = print if rank == 0 else (lambda *a, **k: None)
         key = self.base_key
         raw_batch = next(iter(self.loader_train))
         raw_sample = (raw_batch[0][0], raw_batch[1][0])
@@ -113,7 +150,7 @@ class Trainer:
             params = model.params_from_haiku(params)
         else:
             params, state = model.init(torch.randint(0, 2**31 - 1, (1,), generator=key).numpy(), (features, raw_sample[1]))
-        B = self.loader_train.batch_size
+        B = self.shard.stop - self.shard.start   # the local batch (= train.batch_size on one rank)
         th = model.train_handle(case.engine(B), params)   # weights, gradients, AdamW moments: device resident
         if isinstance(opt_state, dict) and "m" in opt_state and "v" in opt_state:
             th.write("m", np.asarray(opt_state["m"], np.float32))
@@ -129,7 +166,7 @@ class Trainer:
             # again after neighbor-list overflow `continue`s); a resumed run restores it, as optax does from opt_state
             return {"kind": "lagrangebench_amd adamw (flat blobs in the model's flatten order)", "m": th.read("m"),
                     "v": th.read("v"), "step": int(step), "count": th.step_count()}
-        if store_ckp is not None:
+        if store_ckp is not None and rank == 0:
             os.makedirs(os.path.join(store_ckp, "best"), exist_ok=True)
 
         push_forward = push_forward_build(model.apply, case)
@@ -137,9 +174,13 @@ class Trainer:
         while step < step_max + 1:
             for raw_batch in self.loader_train:
                 key, unroll_steps = push_forward_sample_steps(key, step, pushforward)
-                sample = (raw_batch[0], raw_batch[1])
-                key, features_batch, target_batch, neighbors = case.preprocess(key, sample, noise_std, neighbors,
-                                                                               unroll_steps)
+                sample = (raw_batch[0], raw_batch[1])   # (this rank's shard of the batch)
+                if ddp:
+                    _, features_batch, target_batch, neighbors = case.preprocess(noise_key, sample, noise_std, neighbors,
+                                                                                 unroll_steps)
+                else:
+                    key, features_batch, target_batch, neighbors = case.preprocess(key, sample, noise_std, neighbors,
+                                                                                   unroll_steps)
                 if unroll_steps > 0 and not bool(neighbors.did_buffer_overflow.sum() > 0):
                     params_np = current_params()
                     # the noisy positions the features were computed from ARE the engine's window
@@ -148,42 +189,58 @@ class Trainer:
                     for _ in range(unroll_steps):
                         if neighbors.did_buffer_overflow.sum() > 0:
                             break
-                        cur, neighbors, features_batch = push_forward(features_batch, cur, torch.as_tensor(raw_batch[1]),
+                        cur, neighbors, features_batch = push_forward(features_batch, cur, torch.as_tensor(sample[1]),
                                                                       neighbors, params_np, state)
                     del tshift
-                if neighbors.did_buffer_overflow.sum() > 0:
-                    print(f"Reallocate neighbors list at step {step}")
+                overflow = bool(neighbors.did_buffer_overflow.sum() > 0)
+                # a step is skipped by ALL ranks or by none (no rank may reach a collective that another one skips); only
+                # the ranks whose list overflowed re-allocate
+                skip = lbdist.max_over_ranks(float(overflow), device) > 0 if ddp else overflow
+                if overflow:
+                    say(f"Reallocate neighbors list at step {step}")
                     ind = int(torch.argmax(neighbors.did_buffer_overflow.int()))
                     old = neighbors.max_occupancy
+                    akey = noise_key if ddp else key
                     if case.engine(B).has_pads:
                         # padded trajectories: a list sized on ONE sample cannot serve a batch that mixes particle counts
                         # (the next, larger trajectory overflows it again, and so on): size it on the whole batch
-                        _, _, _, neighbors = case.allocate(key, sample, noise_std)
+                        _, _, _, neighbors = case.allocate(akey, sample, noise_std)
                     else:
-                        _, _, _, neighbors = case.allocate(key, (raw_batch[0][ind], raw_batch[1][ind]), noise_std)
-                    print(f"From (2, {old}) to (2, {neighbors.max_occupancy})")
+                        _, _, _, neighbors = case.allocate(akey, (sample[0][ind], sample[1][ind]), noise_std)
+                    say(f"From (2, {old}) to (2, {neighbors.max_occupancy})")
+                if skip:
                     continue
                 # value_and_grad of _mse vmapped over the batch, gradients summed, loss averaged (trainer.py:63-89) +
                 # optax.adamw(lr(step), weight_decay 1e-8): on the engine's current window / neighbor list
                 th.zero_grad()
                 loss = model.loss_grad(th, target_batch, self.loss_weight)
-                th.adamw_step(self._lr(step), 0.9, 0.999, 1e-8, float(getattr(o, "weight_decay", 1e-8)))
+                if ddp:
+                    # every rank's gradient blob -> every rank; summed in rank order and applied in one launch
+                    th.adamw_step_gathered(lbdist.all_gather_rows(th.device_blob("grads")), self._lr(step), 0.9, 0.999, 1e-8,
+                                           float(getattr(o, "weight_decay", 1e-8)))
+                else:
+                    th.adamw_step(self._lr(step), 0.9, 0.999, 1e-8, float(getattr(o, "weight_decay", 1e-8)))
 
                 if step % cfg_logging.log_steps == 0:
+                    if ddp:
+                        # mean over the (equal) shards of the local means = the mean over the global batch; fp64, rank order
+                        loss = sum(lbdist.gather_scalars(float(loss), device)) / world
                     step_str = str(step).zfill(len(str(int(step_max))))
-                    print(f"{step_str}, train/loss: {float(loss):.5f}.")
+                    say(f"{step_str}, train/loss: {float(loss):.5f}.")
                     log.append((step, float(loss)))
                 if step % cfg_logging.eval_steps == 0 and step > 0:
                     params_np = current_params()
+                    if ddp:
+                        self._check_drift(th, device)
                     eval_metrics = eval_rollout(model_apply=model.apply, case=case, params=params_np, state=state,
                                                 loader_eval=self.loader_valid, neighbors=broadcast_from_batch(neighbors, 0),
                                                 metrics_computer=self.metrics_computer,
                                                 n_rollout_steps=cfg_eval.n_rollout_steps, n_trajs=cfg_eval.train.n_trajs,
                                                 rollout_dir=cfg_eval.rollout_dir, out_type=cfg_eval.train.out_type)
                     metrics = averaged_metrics(eval_metrics)
-                    if store_ckp is not None:
+                    if store_ckp is not None and rank == 0:
                         save_haiku(store_ckp, model.params_to_haiku(params_np), state, opt_state_dict(), {"step": step, "loss": metrics.get("val/loss", None)})
-                    print(metrics)
+                    say(metrics)
                     # the validation rollouts re-sized / re-used the engine: the training list is rebuilt
                     key, _, _, neighbors = case.allocate(key, raw_sample)
                 step += 1
@@ -192,4 +249,6 @@ class Trainer:
         self.loss_log = log
         out = (current_params(), state, opt_state_dict())
         th.close()
+        if ddp:
+            lbdist.barrier(device)   # rank 0's last checkpoint is on disk before any rank goes on to load it
         return out
