@@ -107,6 +107,36 @@ int lb_set_force(lb_engine* eng, const double* force_dev);
  * ring, and reset the step counter to `step` (normally 0).  rollout.py:113. */
 int lb_load_window(lb_engine* eng, const double* traj_dev, int32_t T, int32_t t0, int32_t step);
 
+/* The input of one training step from a device-resident dataset, in ONE launch with no host arithmetic and no
+ * host-to-device copy (csrc/lb_train_input.hip).  It replaces, for training samples, H5Dataset.get_window + numpy_collate
+ * (data/data.py:227-257), add_gns_noise with its random walk (train/strats.py:12-83) and the noise and target part of
+ * _preprocess / _compute_target (case_setup/case.py:142-178).
+ *   pos_dev    [n_traj][seq_len][N][dim] positions in the file's dtype: float, or double when pos_is_f64 (the order of the
+ *              H5 `position` arrays; a trajectory with fewer than N particles padded with zeros),
+ *   ptype_dev  [n_traj][N] particle types (-1 on the pads),
+ *   traj_host, t0_host, slot_host: B entries each, HOST memory, passed to the kernel by value (B <= LB_TRAIN_BATCH_MAX):
+ *              sample b of the batch is frames [t0, t0 + T) of trajectory traj[b]; slot[b] is its number in the GLOBAL
+ *              batch (data parallel: rank * local batch + b).
+ * Per particle: the T frames are gathered and converted to fp64 exactly (to float first on a dtype=float32 engine,
+ * case.py:169).  With noise_std != 0, N(0, 1) draws from Philox4x32-10 keyed by `seed`, counter (step, slot, particle,
+ * draw / 4), Box-Muller in fp64 on u = (x + 0.5) * 2^-32 (cos then sin of each pair) are scaled by noise_std / sqrt(isl - 1)
+ * and summed twice along the isl - 1 velocity slots; frame 0 gets no noise, every frame after isl - 1 the noise of frame
+ * isl - 1, particles of type 1, 2 or -1 none; the noise is applied with the case's shift in fp64 on the box as given
+ * (result rounded to float on a float32 engine).  With noise_std == 0 the frames are the data, unshifted, as on the host.
+ * A slot's draws depend on (seed, step, slot, particle, velocity slot, component) only - not on B, on the sample's place
+ * in the batch or on the rank.
+ * Outputs, all device memory: traj_out (B,N,T,dim) fp64, the tensor lb_load_window takes; ptype_out (B,N) for
+ * lb_set_particle_type; the targets of frames isl-2+unroll_steps ... isl+unroll_steps of traj_out, (B,N,dim) fp64 each:
+ * normalised acceleration and velocity and the raw position, in float arithmetic on a float32 engine (operation for
+ * operation what _compute_target does); want_normals_dev: null, or (B,N,isl-1,dim) fp64 receiving the raw draws (tests).
+ * Asynchronous on the engine's stream; changes no engine state. */
+#define LB_TRAIN_BATCH_MAX 128
+int lb_train_batch(lb_engine* eng, const void* pos_dev, int32_t pos_is_f64, const int32_t* ptype_dev, int32_t n_traj,
+                   int32_t seq_len, const int32_t* traj_host, const int32_t* t0_host, const int32_t* slot_host,
+                   uint64_t seed, int64_t step, double noise_std, int32_t T, int32_t unroll_steps, double* traj_out_dev,
+                   int32_t* ptype_out_dev, double* target_acc_dev, double* target_vel_dev, double* target_pos_dev,
+                   double* want_normals_dev);
+
 /* Copy the current window back out as (B,N,isl,dim) fp64 (oldest frame first). */
 int lb_read_window(lb_engine* eng, double* win_out_dev);
 

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "liblbhip.so")
 
 LB_OK = 0
 LB_FORCE_NONE, LB_FORCE_PIECEWISE, LB_FORCE_BUFFER = 0, 1, 2
+LB_TRAIN_BATCH_MAX = 128
 
 D3 = C.c_double * 3
 
@@ -87,6 +88,9 @@ _SIGS = {
     "lb_set_particle_type": (C.c_int, [_P, _P]),
     "lb_set_force": (C.c_int, [_P, _P]),
     "lb_load_window": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_train_batch": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32), C.c_uint64, C.c_int64, C.c_double, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                 _P]),
     "lb_read_window": (C.c_int, [_P, _P]),
     "lb_nl_allocate": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lb_nl_set_capacity": (C.c_int, [_P, C.c_int32, C.c_int32]),

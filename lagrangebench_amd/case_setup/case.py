@@ -167,6 +167,49 @@ class CaseSetupFn:
     def preprocess_eval(self, sample, neighbors):
         return self._preprocess(sample, neighbors, False, "eval")
 
+    # ---------------------------------------------------------------- device-resident training input
+    def _preprocess_device(self, dd, idx, slots, seed, step, noise_std, neighbors, is_allocate, unroll_steps,
+                           want_normals=False):
+        """_preprocess(mode="train") with the sample made on the device: `lb_train_batch` gathers the windows `idx` of the
+        DeviceDataset `dd`, adds the random-walk noise keyed by (seed, step, global slot) and writes trajectory and
+        targets; particle types, window and neighbor list then go the usual way."""
+        batched = not isinstance(idx, (int, np.integer))
+        idx, slots = ([int(i) for i in idx], [int(s) for s in slots]) if batched else ([int(idx)], [int(np.ravel(slots)[0])])
+        isl = self.input_seq_length
+        trajs, t0s = dd.locate_batch(idx)
+        eng = self.engine(len(idx))
+        traj, ptype, target, normals = eng.train_batch(dd, trajs, t0s, slots, seed, step, float(noise_std), unroll_steps,
+                                                       want_normals)
+        eng.set_particle_type_device(ptype, dd.has_pads(trajs))
+        eng.load_window(traj, t0=0, step=0)
+        if is_allocate:
+            eng.nl_allocate()
+        else:
+            if neighbors is None:
+                raise ValueError("preprocess_device needs a NeighborList (use allocate_device first)")
+            if (eng.e_cap, eng.cell_capacity) != (neighbors.max_occupancy, neighbors.cell_capacity):
+                eng.nl_set_capacity(neighbors.cell_capacity, neighbors.max_occupancy)
+            eng.nl_update()
+        nbrs = NeighborList(eng, batched)
+        features = FeatureDict(eng, traj[:, :, :isl], batched)
+        if self.f32:  # _compute_target's dtype
+            target = {k: v.to(torch.float32) for k, v in target.items()}
+        if not batched:
+            target = {k: v[0] for k, v in target.items()}
+        if want_normals:
+            return features, target, nbrs, (traj, normals)
+        return features, target, nbrs
+
+    def allocate_device(self, dd, idx, slots, seed: int, step: int, noise_std: float = 0.0, unroll_steps: int = 0, **kw):
+        """`allocate` on samples of a data.DeviceDataset: idx = window numbers (an int: un-batched), slots = their numbers
+        in the global batch.  Returns (features, targets, neighbors)."""
+        return self._preprocess_device(dd, idx, slots, seed, step, noise_std, None, True, unroll_steps, **kw)
+
+    def preprocess_device(self, dd, idx, slots, seed: int, step: int, noise_std: float, neighbors, unroll_steps: int = 0,
+                          **kw):
+        """`preprocess` on samples of a data.DeviceDataset (see allocate_device)."""
+        return self._preprocess_device(dd, idx, slots, seed, step, noise_std, neighbors, False, unroll_steps, **kw)
+
     def integrate(self, normalized_in: Dict[str, torch.Tensor], position_sequence):
         """integrate_fn - case.py:230-259."""
         assert any(k in normalized_in for k in ["pos", "vel", "acc"])

@@ -37,6 +37,7 @@ defaults = _wrap({
         "optimizer": {"lr_start": 1e-4, "lr_final": 1e-6, "lr_decay_rate": 0.1, "lr_decay_steps": 1e5},
         "pushforward": {"steps": [-1, 20000, 300000, 400000], "unrolls": [0, 1, 2, 3], "probs": [18, 2, 1, 1]},
         "loss_weight": {"acc": 1.0, "vel": 0.0, "pos": 0.0},
+        "device_data": False,                 # not in the reference: train split in HBM, samples made on the device
     },
     "logging": {"log_steps": 1000, "eval_steps": 10000, "wandb": False, "wandb_project": None,
                 "wandb_entity": "lagrangebench", "ckp_dir": "ckp", "run_name": None},  # defaults.py:153-168

@@ -151,6 +151,40 @@ class RolloutEngine:
         t = self._t(src, torch.int32).reshape(self.B, self.N)
         check(self.lib.lb_set_particle_type(self._h, ptr(t)), "lb_set_particle_type")
 
+    def train_batch(self, dd, trajs: Sequence[int], t0s: Sequence[int], slots: Sequence[int], seed: int, step: int,
+                    noise_std: float, unroll_steps: int = 0, want_normals: bool = False):
+        """One launch of lb_train_batch (include/lbhip.h) on the DeviceDataset `dd`: sample b = frames [t0s[b], t0s[b] +
+        dd.subseq_length) of trajectory trajs[b], global slot slots[b].  Returns (traj (B,N,T,dim) fp64, particle types
+        (B,N) int32, {"acc", "vel", "pos"} (B,N,dim) fp64, the raw normal draws (B,N,isl-1,dim) or None), all on the
+        device; the engine's state is not touched."""
+        B, T = self.B, int(dd.subseq_length)
+        if not (len(trajs) == len(t0s) == len(slots) == B):
+            raise ValueError(f"train_batch: {len(trajs)} trajectories, {len(t0s)} offsets, {len(slots)} slots for B={B}")
+        if dd.N != self.N or dd.dim != self.dim or dd.pos.device != self.device:
+            raise ValueError(f"train_batch: dataset (N={dd.N}, dim={dd.dim}, {dd.pos.device}) does not match the engine "
+                             f"(N={self.N}, dim={self.dim}, {self.device})")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        traj = torch.empty((B, self.N, T, self.dim), **f64)
+        ptype = torch.empty((B, self.N), dtype=torch.int32, device=self.device)
+        tgt = torch.empty((3, B, self.N, self.dim), **f64)
+        normals = torch.empty((B, self.N, self.isl - 1, self.dim), **f64) if want_normals and noise_std != 0 else None
+        I32 = C.c_int32 * B
+        check(self.lib.lb_train_batch(self._h, ptr(dd.pos), int(dd.pos_f64), ptr(dd.ptype), dd.n_traj, dd.sequence_length,
+                                      I32(*[int(v) for v in trajs]), I32(*[int(v) for v in t0s]), I32(*[int(v) for v in slots]),
+                                      C.c_uint64(int(seed) & (2**64 - 1)), int(step), float(noise_std), T, int(unroll_steps),
+                                      ptr(traj), ptr(ptype), ptr(tgt[0]), ptr(tgt[1]), ptr(tgt[2]), ptr(normals)),
+              "lb_train_batch")
+        return traj, ptype, {"acc": tgt[0], "vel": tgt[1], "pos": tgt[2]}, normals
+
+    def set_particle_type_device(self, ptype: torch.Tensor, has_pads: bool) -> None:
+        """set_particle_type for (B, N) int32 types already on the device, with `has_pads` known to the caller (no
+        read-back)."""
+        if ptype.dtype != torch.int32 or ptype.device != self.device or tuple(ptype.shape) != (self.B, self.N):
+            raise ValueError(f"set_particle_type_device: expected ({self.B}, {self.N}) int32 on {self.device}")
+        self.has_pads = bool(has_pads)
+        self._t(ptype, torch.int32)
+        check(self.lib.lb_set_particle_type(self._h, ptr(ptype)), "lb_set_particle_type")
+
     def prepare_traj(self, pos) -> torch.Tensor:
         """(B,N,T,dim) or (N,T,dim) positions -> fp64 contiguous device tensor."""
         t = pos if isinstance(pos, torch.Tensor) else torch.as_tensor(np.asarray(pos))

@@ -29,6 +29,11 @@ stream and trains on its ``shard_batch`` slice of each batch (noise: a stream of
 and ONE HIP kernel sums them in rank order and applies AdamW (``lb_adamw_step_gathered``), so every rank holds the same weight
 bits after every step - checked at each evaluation.  The semantics are the single-process ones: gradients summed over the
 global batch, loss averaged, learning rate as configured.  One rank runs the code below exactly as before.
+
+``train.device_data`` (default off): the train split is uploaded once (data.DeviceDataset) and the
+sample of a step - window, random-walk noise, shift, targets - is made by one HIP launch (``case.preprocess_device``) instead
+of on the host.  Permutation and unroll count still come from the common stream; the noise is keyed by (seed, step, global
+slot), so a rank's shard gets the single-process noise of its slots.  With the key off nothing below changes.
 """
 from __future__ import annotations
 
@@ -57,15 +62,22 @@ def exponential_decay(step: int, init_value: float, transition_steps: float, dec
 
 class _ShuffledLoader:
     """DataLoader(dataset, batch_size, shuffle=True, drop_last=True, collate_fn=numpy_collate), in process.  `shard`: the
-    slice of every batch that is read and yielded (data parallel: the permutation is the common one, a rank reads its part)."""
+    slice of every batch that is read and yielded (data parallel: the permutation is the common one, a rank reads its part).
+    `indices_only` (train.device_data): nothing is read; a batch is (the shard's window numbers, their slot numbers in the
+    global batch) - the same permutation, drawn the same way."""
 
-    def __init__(self, dataset, batch_size: int, generator: torch.Generator, shard: slice = slice(None)):
+    def __init__(self, dataset, batch_size: int, generator: torch.Generator, shard: slice = slice(None),
+                 indices_only: bool = False):
         self.dataset, self.batch_size, self.generator, self.shard = dataset, batch_size, generator, shard
+        self.indices_only = indices_only
 
     def __iter__(self):
         n = len(self.dataset)
         perm = torch.randperm(n, generator=self.generator).tolist()
         for s in range(0, n - self.batch_size + 1, self.batch_size):
+            if self.indices_only:
+                yield perm[s:s + self.batch_size][self.shard], list(range(self.batch_size))[self.shard]
+                continue
             items = [self.dataset[k] for k in perm[s:s + self.batch_size][self.shard]]
             yield (np.stack([it[0] for it in items]), np.stack([it[1] for it in items]))
 
@@ -80,6 +92,11 @@ class Trainer:
         self.rank, self.local_rank, self.world = lbdist.env_world()
         self.shard = lbdist.shard_batch(self.cfg_train.batch_size, self.rank, self.world)
         self.seed = int(seed)
+        self.device_data = bool(self.cfg_train.get("device_data", False))
+        self._dd = None
+        if self.device_data:
+            from ..data.device import trajectory_source
+            trajectory_source(data_train)   # TypeError HERE for a dataset that does not expose its trajectories
         self.cfg_eval = merge(defaults.eval, cfg_eval)
         self.cfg_logging = merge(defaults.logging, cfg_logging)
         available = data_valid.subseq_length - input_seq_length
@@ -94,7 +111,8 @@ class Trainer:
         self.loss_weight = dict(self.cfg_train.loss_weight)
         self.base_key = torch.Generator()
         self.base_key.manual_seed(int(seed))
-        self.loader_train = _ShuffledLoader(data_train, self.cfg_train.batch_size, self.base_key, self.shard)
+        self.loader_train = _ShuffledLoader(data_train, self.cfg_train.batch_size, self.base_key, self.shard,
+                                            indices_only=self.device_data)
         self.loader_valid = _Loader(data_valid, self.cfg_eval.infer.batch_size)
         self.loader_valid.dataset = data_valid
         self.metrics_computer = MetricsComputer(self.cfg_eval.train.metrics, dist_fn=case.displacement,
@@ -138,7 +156,17 @@ class Trainer:
         say = print if rank == 0 else (lambda *a, **k: None)
         key = self.base_key
         raw_batch = next(iter(self.loader_train))
-        raw_sample = (raw_batch[0][0], raw_batch[1][0])
+        dd = None
+        if self.device_data:
+            # the train split goes to the device once; a sample is then (window number, global slot) and its noise is keyed
+            # by (seed, step, slot) - on every rank the single-process noise of that slot (noise_key is not used)
+            from ..data.device import DeviceDataset
+            if self._dd is None:
+                self._dd = DeviceDataset(self.loader_train.dataset, device=case.device)
+            dd = self._dd
+            raw_sample = tuple(self.loader_train.dataset[raw_batch[0][0]])   # the one host read: sizes lists and weights
+        else:
+            raw_sample = (raw_batch[0][0], raw_batch[1][0])
         key, features, _, neighbors = case.allocate(key, raw_sample)
         device = case.engine(1).device
 
@@ -175,7 +203,12 @@ class Trainer:
             for raw_batch in self.loader_train:
                 key, unroll_steps = push_forward_sample_steps(key, step, pushforward)
                 sample = (raw_batch[0], raw_batch[1])   # (this rank's shard of the batch)
-                if ddp:
+                if dd is not None:
+                    idx, slots = raw_batch
+                    sample = (None, dd.particle_types(idx))
+                    features_batch, target_batch, neighbors = case.preprocess_device(dd, idx, slots, self.seed, step, noise_std,
+                                                                                     neighbors, unroll_steps)
+                elif ddp:
                     _, features_batch, target_batch, neighbors = case.preprocess(noise_key, sample, noise_std, neighbors,
                                                                                  unroll_steps)
                 else:
@@ -201,7 +234,10 @@ class Trainer:
                     ind = int(torch.argmax(neighbors.did_buffer_overflow.int()))
                     old = neighbors.max_occupancy
                     akey = noise_key if ddp else key
-                    if case.engine(B).has_pads:
+                    if dd is not None:
+                        sel = slice(None) if case.engine(B).has_pads else ind   # the same two branches, on the device
+                        _, _, neighbors = case.allocate_device(dd, idx[sel], slots[sel], self.seed, step, noise_std)
+                    elif case.engine(B).has_pads:
                         # padded trajectories: a list sized on ONE sample cannot serve a batch that mixes particle counts
                         # (the next, larger trajectory overflows it again, and so on): size it on the whole batch
                         _, _, _, neighbors = case.allocate(akey, sample, noise_std)
