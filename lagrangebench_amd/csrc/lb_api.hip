@@ -533,383 +533,6 @@ extern "C" int lb_segment_sum(lb_engine* e, const float* msg_dev, float* out_dev
 }
 
 // ------------------------------------------------------------------------------------- GNS
-extern "C" int lb_gns_create(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats,
-                             lb_gns** out) {
-  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  if (d->latent_size < 16 || d->latent_size > LB_D || d->latent_size % 16)
-    return lb_fail(LB_ERR_UNSUPPORTED, "latent_size %d not built (multiples of 16 up to 128)", d->latent_size);
-  if (d->out_dim != e->g.dim) return lb_fail(LB_ERR_ARG, "out_dim %d != case dim %d", d->out_dim, e->g.dim);
-  if (d->node_in != e->g.node_in) return lb_fail(LB_ERR_ARG, "node_in %d != case feature width %d", d->node_in, e->g.node_in);
-  if (d->edge_in != e->g.dim + 1) return lb_fail(LB_ERR_ARG, "edge_in %d != dim+1", d->edge_in);
-  if (d->num_mp_steps < 0 || d->num_mp_steps > 64) return lb_fail(LB_ERR_ARG, "bad num_mp_steps");
-  // any MLP depth other than the published two Linears runs on the one-Linear-per-launch kernels
-  if (d->blocks_per_step != 2) return lb_gns_create_generic(e, d, w, n_floats, out);
-  const int D = LB_D, L = d->num_mp_steps;
-  const bool has_emb = d->num_particle_types > 1;
-  const int emb = has_emb ? d->embedding_size : 0;
-  const int nin = d->node_in + emb;
-  if (nin > 128) return lb_fail(LB_ERR_UNSUPPORTED, "node input width %d > 128 not built", nin);
-  const int kpad = (nin + 31) / 32 * 32;  // 32 .. 128
-
-  // expected blob length
-  auto mlp_len = [&](int in, int outw, bool ln) -> int64_t {
-    return (int64_t)in * D + D + (int64_t)D * outw + outw + (ln ? 2 * outw : 0);
-  };
-  int64_t expect = (has_emb ? (int64_t)d->num_particle_types * emb : 0) + mlp_len(nin, D, true) +
-                   mlp_len(d->edge_in, D, true) +
-                   (int64_t)L * (mlp_len(3 * D, D, true) + mlp_len(2 * D, D, true)) +
-                   mlp_len(D, d->out_dim, false);
-  if (d->latent_size == D && expect != n_floats)
-    return lb_fail(LB_ERR_ARG, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
-
-  // A latent narrower than the 128-wide tiles (GNS-5-64, docs/pages/baselines.rst:54) runs on the same
-  // kernels: every Linear is zero-padded to 128 columns / its input blocks to 128-row strides, LayerNorm
-  // scale / offset are padded with zeros (the padded features stay exactly 0 through every layer) and the
-  // kernels divide by the true width (lb_ctrl::ln_inv_d / ln_pad).
-  std::vector<float> widened;
-  const int dl = d->latent_size;
-  if (dl != D) {
-    auto mlp_len_d = [&](int in, int outw, bool ln) -> int64_t {
-      return (int64_t)in * dl + dl + (int64_t)dl * outw + outw + (ln ? 2 * outw : 0);
-    };
-    const int64_t expect_d = (has_emb ? (int64_t)d->num_particle_types * emb : 0) + mlp_len_d(nin, dl, true) +
-                             mlp_len_d(d->edge_in, dl, true) +
-                             (int64_t)L * (mlp_len_d(3 * dl, dl, true) + mlp_len_d(2 * dl, dl, true)) +
-                             mlp_len_d(dl, d->out_dim, false);
-    if (expect_d != n_floats)
-      return lb_fail(LB_ERR_ARG, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect_d);
-    const float* q = w;
-    auto copy = [&](size_t n) {
-      widened.insert(widened.end(), q, q + n);
-      q += n;
-    };
-    // one Linear (in_blocks x blk_in rows, out columns) -> (in_blocks x blk_pad rows, out_pad columns)
-    auto linear = [&](int in_blocks, int blk_in, int blk_pad, int out, int out_pad) {
-      const size_t base = widened.size();
-      widened.resize(base + (size_t)in_blocks * blk_pad * out_pad, 0.f);
-      for (int b = 0; b < in_blocks; ++b)
-        for (int r = 0; r < blk_in; ++r)
-          for (int c = 0; c < out; ++c)
-            widened[base + ((size_t)b * blk_pad + r) * out_pad + c] = q[((size_t)b * blk_in + r) * out + c];
-      q += (size_t)in_blocks * blk_in * out;
-    };
-    auto vec = [&](int n, int n_pad) {
-      const size_t base = widened.size();
-      widened.resize(base + n_pad, 0.f);
-      for (int i = 0; i < n; ++i) widened[base + i] = q[i];
-      q += n;
-    };
-    auto mlp = [&](int in_blocks, int blk_in, int blk_pad, int outw, int outw_pad, bool ln) {
-      linear(in_blocks, blk_in, blk_pad, dl, D);   // w0
-      vec(dl, D);                                  // b0
-      linear(1, dl, D, outw, outw_pad);            // w1
-      vec(outw, outw_pad);                         // b1
-      if (ln) {
-        vec(outw, outw_pad);
-        vec(outw, outw_pad);
-      }
-    };
-    if (has_emb) copy((size_t)d->num_particle_types * emb);
-    mlp(1, nin, nin, dl, D, true);
-    mlp(1, d->edge_in, d->edge_in, dl, D, true);
-    for (int k = 0; k < L; ++k) {
-      mlp(3, dl, D, dl, D, true);
-      mlp(2, dl, D, dl, D, true);
-    }
-    mlp(1, dl, D, d->out_dim, d->out_dim, false);
-    if (q - w != n_floats) return lb_fail(LB_ERR_ARG, "internal: widening walk mismatch");
-    w = widened.data();
-    n_floats = (int64_t)widened.size();
-  }
-
-  std::vector<float> host;
-  auto put = [&](const float* src, size_t n) -> size_t {
-    size_t off = host.size();
-    off = (off + 63) & ~(size_t)63;  // 256-byte alignment of every block
-    host.resize(off + n, 0.f);
-    if (src) memcpy(host.data() + off, src, n * sizeof(float));
-    return off;
-  };
-  auto put_packed16 = [&](const float* src, int K, int M, int Kp) -> size_t {
-    std::vector<float> tmp((size_t)Kp * 128);
-    lb_pack_weight16(src, K, M, Kp, tmp.data());
-    return put(tmp.data(), tmp.size());
-  };
-  auto put_packed16h = [&](const float* src, int K, int M, int Kp, int Mp = 128) -> size_t {
-    std::vector<float> tmp((size_t)Kp * Mp);
-    lb_pack_weight16h(src, K, M, Kp, tmp.data(), Mp);
-    return put(tmp.data(), tmp.size());
-  };
-  auto put_packed = [&](const float* src, int K, int M, int Kp, int Mp) -> size_t {
-    std::vector<float> tmp((size_t)Kp * Mp);
-    lb_pack_weight(src, K, M, Kp, Mp, tmp.data());
-    return put(tmp.data(), tmp.size());
-  };
-  struct Off { size_t w0, b0, w1, b1, lns, lno; bool ln; };
-  const float* p = w;
-  size_t off_embed = 0;
-  if (has_emb) {
-    off_embed = put(p, (size_t)d->num_particle_types * emb);
-    p += (size_t)d->num_particle_types * emb;
-  }
-  // f16x2 carries a weight as fp16 hi + fp16 lo with an ABSOLUTE floor of 2^-25 on the pair: a matrix whose
-  // entries are uniformly small (rms < 2^-7) would lose the 1e-5 class - noted here, acted on below
-  double w_rms_min = 1e30;
-  auto note_rms = [&](const float* m, size_t n) {
-    double s2 = 0;
-    size_t nz = 0;
-    for (size_t i = 0; i < n; ++i) {
-      s2 += (double)m[i] * m[i];
-      nz += m[i] != 0.f;
-    }
-    if (nz) w_rms_min = std::min(w_rms_min, std::sqrt(s2 / (double)nz));
-  };
-  // generic 2-layer MLP reader; k0pad = padded K of layer 0; outp = padded out width
-  auto read_mlp = [&](int in, int k0pad, int outw, int outp, bool ln) -> Off {
-    Off o{};
-    note_rms(p, (size_t)in * D);
-    o.w0 = put_packed(p, in, D, k0pad, D); p += (size_t)in * D;
-    o.b0 = put(p, D); p += D;
-    if (ln) note_rms(p, (size_t)D * outw);  // (the decoder's output Linear is rescaled instead, see below)
-    o.w1 = put_packed(p, D, outw, D, outp); p += (size_t)D * outw;
-    {
-      std::vector<float> b(outp, 0.f);
-      memcpy(b.data(), p, sizeof(float) * outw);
-      o.b1 = put(b.data(), outp);
-      p += outw;
-    }
-    o.ln = ln;
-    if (ln) {
-      o.lns = put(p, outw); p += outw;
-      o.lno = put(p, outw); p += outw;
-    }
-    return o;
-  };
-  const size_t o_en_w0_h = put_packed16h(p, nin, D, kpad);
-  const size_t o_en_w1_h = put_packed16h(p + (size_t)nin * D + D, D, D, D);
-  std::vector<size_t> o_pn_w0_h(L), o_pn_w1_h(L), o_pw_h(L), o_pw_h2(L);
-  Off o_enc_node = read_mlp(nin, kpad, D, D, true);
-  const float* p_enc_edge = p;
-  Off o_enc_edge = read_mlp(d->edge_in, 8, D, D, true);
-  const size_t o_ee_w0_16 = put_packed16(p_enc_edge, d->edge_in, D, 16);
-  const size_t o_ee_w1_16 = put_packed16(p_enc_edge + (size_t)d->edge_in * D + D, D, D, D);
-  const size_t o_ee_w0_16h = put_packed16h(p_enc_edge, d->edge_in, D, 32);
-  const size_t o_ee_w1_16h = put_packed16h(p_enc_edge + (size_t)d->edge_in * D + D, D, D, D);
-  std::vector<size_t> o_pe_w0_16(L), o_pe_w1_16(L), o_pe_w0_16h(L), o_pe_w1_16h(L);
-  std::vector<Off> o_pe(L), o_pn(L);
-  std::vector<size_t> o_pw(L), o_pb(L);
-  for (int k = 0; k < L; ++k) {
-    // edge MLP: w0 is (3D, D) over [sender | receiver | edge] (gns.py:97-100)
-    const float* w0 = p;
-    const float* b0 = p + (size_t)3 * D * D;
-    // projection for the node kernel: (D, 2D) = [Ws | Wr], bias [0 | b0]
-    {
-      std::vector<float> wsr((size_t)D * 2 * D);
-      for (int kk = 0; kk < D; ++kk)
-        for (int m = 0; m < D; ++m) {
-          wsr[(size_t)kk * 2 * D + m] = w0[(size_t)kk * D + m];
-          wsr[(size_t)kk * 2 * D + D + m] = w0[(size_t)(D + kk) * D + m];
-        }
-      o_pw[k] = put_packed(wsr.data(), D, 2 * D, D, 2 * D);
-      o_pw_h[k] = put_packed16h(wsr.data(), D, 2 * D, D, 2 * D);
-      {  // the same projection as two 128-wide halves [Ws | Wr]: uniform 32 KiB chunks for lb_node16s.hip
-        std::vector<float> two((size_t)2 * D * D);
-        lb_pack_weight16h(w0, D, D, D, two.data(), D);
-        lb_pack_weight16h(w0 + (size_t)D * D, D, D, D, two.data() + (size_t)D * D, D);
-        o_pw_h2[k] = put(two.data(), two.size());
-      }
-      std::vector<float> bb(2 * D, 0.f);
-      memcpy(bb.data() + D, b0, sizeof(float) * D);
-      o_pb[k] = put(bb.data(), 2 * D);
-    }
-    Off o{};
-    o.w0 = put_packed(w0 + (size_t)2 * D * D, D, D, D, D);  // edge rows only
-    o_pe_w0_16[k] = put_packed16(w0 + (size_t)2 * D * D, D, D, D);
-    o_pe_w0_16h[k] = put_packed16h(w0 + (size_t)2 * D * D, D, D, D);
-    o.b0 = put(b0, D);
-    p += (size_t)3 * D * D + D;
-    o_pe_w1_16[k] = put_packed16(p, D, D, D);
-    o_pe_w1_16h[k] = put_packed16h(p, D, D, D);
-    o.w1 = put_packed(p, D, D, D, D); p += (size_t)D * D;
-    o.b1 = put(p, D); p += D;
-    o.ln = true;
-    o.lns = put(p, D); p += D;
-    o.lno = put(p, D); p += D;
-    o_pe[k] = o;
-    o_pn_w0_h[k] = put_packed16h(p, 2 * D, D, 2 * D);
-    o_pn_w1_h[k] = put_packed16h(p + (size_t)2 * D * D + D, D, D, D);
-    o_pn[k] = read_mlp(2 * D, 2 * D, D, D, true);
-  }
-  const float* p_dec = p;
-  Off o_dec = read_mlp(D, D, d->out_dim, 32, false);
-  const size_t o_dec_w0_h = put_packed16h(p_dec, D, D, D);
-  const size_t o_dec_w0_f = put_packed16(p_dec, D, D, D);
-  // decoder head: the f16x2 copy is packed times 2^s (max |w| -> [0.25, 0.5)) and the kernel multiplies the result
-  // by 2^-s: exact, and independent of the output normalisation a checkpoint was trained with
-  float dec_unscale = 1.f;
-  size_t o_dec_w1_h;
-  {
-    const float* w1d = p_dec + (size_t)D * D + D;
-    const size_t n = (size_t)D * d->out_dim;
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w1d[i]));
-    int sh = 0;
-    if (mx > 0.f && std::isfinite(mx)) sh = std::max(-60, std::min(60, (int)std::floor(std::log2(0.5 / (double)mx))));
-    std::vector<float> scaled(w1d, w1d + n);
-    for (float& x : scaled) x = std::ldexp(x, sh);
-    dec_unscale = std::ldexp(1.f, -sh);
-    o_dec_w1_h = put_packed16h(scaled.data(), D, d->out_dim, D, 16);
-  }
-  const size_t o_dec_w1_f = put_packed16(p_dec + (size_t)D * D + D, D, d->out_dim, D);
-  if (p - w != n_floats) return lb_fail(LB_ERR_ARG, "internal: blob walk mismatch");
-  // M-split images (lb_msplit.hip): one block per MLP = [W0 | W1 | projection of the next edge MLP]
-  auto put_ms = [&](std::initializer_list<std::tuple<const float*, int, int, int, int, bool>> mats) -> size_t {
-    std::vector<float> img;
-    for (const auto& m : mats) {
-      const float* src; int K, M, nkb, npw; bool perm;
-      std::tie(src, K, M, nkb, npw, perm) = m;
-      const size_t base = img.size();
-      img.resize(base + (size_t)nkb * npw * 4096);
-      lb_pack_ms(src, K, M, nkb, npw, perm, img.data() + base);
-    }
-    return put(img.data(), img.size());
-  };
-  // walk the blob once more for the source pointers (same order as above)
-  size_t o_ms_enc_node, o_ms_enc_edge;
-  std::vector<size_t> o_ms_pe(L), o_ms_pn(L);
-  {
-    const float* q = w + (has_emb ? (size_t)d->num_particle_types * emb : 0);
-    auto wsr_of = [&](const float* w0e, std::vector<float>& wsr) {  // [Ws | Wr] of an edge MLP's first Linear
-      wsr.assign((size_t)D * 2 * D, 0.f);
-      for (int kk = 0; kk < D; ++kk)
-        for (int m = 0; m < D; ++m) {
-          wsr[(size_t)kk * 2 * D + m] = w0e[(size_t)kk * D + m];
-          wsr[(size_t)kk * 2 * D + D + m] = w0e[(size_t)(D + kk) * D + m];
-        }
-    };
-    const float* en_w0 = q;
-    const float* en_w1 = q + (size_t)nin * D + D;
-    q += (size_t)nin * D + D + (size_t)D * D + D + 2 * D;
-    const float* ee_w0 = q;
-    const float* ee_w1 = q + (size_t)d->edge_in * D + D;
-    q += (size_t)d->edge_in * D + D + (size_t)D * D + D + 2 * D;
-    std::vector<const float*> pe_w0(L), pe_w1(L), pn_w0(L), pn_w1(L);
-    for (int k = 0; k < L; ++k) {
-      pe_w0[k] = q;
-      pe_w1[k] = q + (size_t)3 * D * D + D;
-      q += (size_t)3 * D * D + D + (size_t)D * D + D + 2 * D;
-      pn_w0[k] = q;
-      pn_w1[k] = q + (size_t)2 * D * D + D;
-      q += (size_t)2 * D * D + D + (size_t)D * D + D + 2 * D;
-    }
-    std::vector<float> wsr;
-    if (L > 0) {
-      wsr_of(pe_w0[0], wsr);
-      o_ms_enc_node = put_ms({{en_w0, nin, D, kpad / 32, 1, true}, {en_w1, D, D, 4, 1, true}, {wsr.data(), D, 2 * D, 4, 2, true}});
-    } else {
-      o_ms_enc_node = put_ms({{en_w0, nin, D, kpad / 32, 1, true}, {en_w1, D, D, 4, 1, true}});
-    }
-    o_ms_enc_edge = put_ms({{ee_w0, d->edge_in, D, 1, 1, false}, {ee_w1, D, D, 4, 1, true}});
-    for (int k = 0; k < L; ++k) {
-      o_ms_pe[k] = put_ms({{pe_w0[k] + (size_t)2 * D * D, D, D, 4, 1, true}, {pe_w1[k], D, D, 4, 1, true}});
-      if (k + 1 < L) {
-        wsr_of(pe_w0[k + 1], wsr);
-        o_ms_pn[k] = put_ms({{pn_w0[k], 2 * D, D, 8, 1, true}, {pn_w1[k], D, D, 4, 1, true}, {wsr.data(), D, 2 * D, 4, 2, true}});
-      } else {
-        // last layer: [W0 | W1 | decoder W0 | decoder W1 (out_dim block, scaled like dec_w1_h)] - k_node_ms<DEC>
-        std::vector<float> img((size_t)8 * 4096 + 4 * 4096 + 4 * 4096 + 2048, 0.f), tmp((size_t)4 * 4096);
-        lb_pack_ms(pn_w0[k], 2 * D, D, 8, 1, true, img.data());
-        lb_pack_ms(pn_w1[k], D, D, 4, 1, true, img.data() + (size_t)8 * 4096);
-        lb_pack_ms(p_dec, D, D, 4, 1, true, img.data() + (size_t)12 * 4096);
-        {
-          const float* w1d = p_dec + (size_t)D * D + D;
-          std::vector<float> scaled(w1d, w1d + (size_t)D * d->out_dim);
-          for (float& x : scaled) x = x / dec_unscale;  // dec_unscale is a power of two: exact
-          lb_pack_ms(scaled.data(), D, d->out_dim, 4, 1, true, tmp.data());
-          memcpy(img.data() + (size_t)16 * 4096, tmp.data(), sizeof(float) * 2048);  // block 0 = outputs 0 .. 15
-        }
-        o_ms_pn[k] = put(img.data(), img.size());
-      }
-    }
-  }
-
-  lb_gns* g = new lb_gns();
-  g->desc = *d;
-  g->eng = e;
-  g->tap = nullptr;
-  g->kq_node = kpad / 8;
-  if (hipMalloc((void**)&g->blob, host.size() * sizeof(float)) != hipSuccess) {
-    delete g;
-    return lb_fail(LB_ERR_HIP, "hipMalloc(weights) failed");
-  }
-  if (hipMemcpy(g->blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(g->blob);
-    delete g;
-    return lb_fail(LB_ERR_HIP, "weight upload failed");
-  }
-  auto mk = [&](const Off& o) {
-    lb_mlp_w m{};
-    m.w0 = g->blob + o.w0;
-    m.b0 = g->blob + o.b0;
-    m.w1 = g->blob + o.w1;
-    m.b1 = g->blob + o.b1;
-    m.ln_s = o.ln ? g->blob + o.lns : nullptr;
-    m.ln_o = o.ln ? g->blob + o.lno : nullptr;
-    return m;
-  };
-  g->embed = has_emb ? g->blob + off_embed : nullptr;
-  g->enc_node = mk(o_enc_node);
-  g->enc_edge = mk(o_enc_edge);
-  g->dec = mk(o_dec);
-  for (int k = 0; k < L; ++k) {
-    g->proc_edge.push_back(mk(o_pe[k]));
-    g->proc_node.push_back(mk(o_pn[k]));
-    g->proj_w.push_back(g->blob + o_pw[k]);
-    g->proj_b.push_back(g->blob + o_pb[k]);
-    g->proc_edge_w0_16.push_back(g->blob + o_pe_w0_16[k]);
-    g->proc_edge_w1_16.push_back(g->blob + o_pe_w1_16[k]);
-    g->proc_node_w0_h.push_back(g->blob + o_pn_w0_h[k]);
-    g->proc_node_w1_h.push_back(g->blob + o_pn_w1_h[k]);
-    g->proj_w_h.push_back(g->blob + o_pw_h[k]);
-    g->proj_w_h2.push_back(g->blob + o_pw_h2[k]);
-    g->proc_edge_w0_16h.push_back(g->blob + o_pe_w0_16h[k]);
-    g->proc_edge_w1_16h.push_back(g->blob + o_pe_w1_16h[k]);
-  }
-  g->ms_enc_node = g->blob + o_ms_enc_node;
-  g->ms_enc_edge = g->blob + o_ms_enc_edge;
-  for (int k = 0; k < L; ++k) {
-    g->ms_proc_edge.push_back(g->blob + o_ms_pe[k]);
-    g->ms_proc_node.push_back(g->blob + o_ms_pn[k]);
-  }
-  g->dec_unscale = dec_unscale;
-  g->dec_w0_h = g->blob + o_dec_w0_h;
-  g->dec_w0_f = g->blob + o_dec_w0_f;
-  g->dec_w1_h = g->blob + o_dec_w1_h;
-  g->dec_w1_f = g->blob + o_dec_w1_f;
-  g->enc_edge_w0_16 = g->blob + o_ee_w0_16;
-  g->enc_edge_w1_16 = g->blob + o_ee_w1_16;
-  g->enc_node_w0_h = g->blob + o_en_w0_h;
-  g->enc_node_w1_h = g->blob + o_en_w1_h;
-  g->enc_edge_w0_16h = g->blob + o_ee_w0_16h;
-  g->enc_edge_w1_16h = g->blob + o_ee_w1_16h;
-  // LayerNorm width of this model (read by every network kernel through the control block: lb_gns_bind)
-  g->lnc[0] = 1.0f / (float)dl;
-  g->lnc[1] = (float)(D - dl);
-  if (w_rms_min < 0.0078125 && e->f16x2 && e->math_auto) {
-    fprintf(stderr, "[lbhip] a weight matrix has rms %.3g < 2^-7: its fp16 hi/lo split would fall short of the 1e-5 class - "
-                    "this engine uses exact-fp32 MFMA arithmetic\n", w_rms_min);
-    e->f16x2 = 0;
-  }
-  int rc = lb_ensure_node_scratch(e);
-  if (!rc) rc = lb_gns_bind(e, g);
-  if (rc) {
-    lb_gns_destroy(g);
-    return rc;
-  }
-  *out = g;
-  return LB_OK;
-}
-
 int lb_ensure_node_scratch(lb_engine* e) {
   const int64_t BN = e->BN;
   if (!e->xnode) LB_TRY(lb_alloc(&e->xnode, (size_t)BN * LB_D));  // widest node input row
@@ -919,35 +542,9 @@ int lb_ensure_node_scratch(lb_engine* e) {
   return LB_OK;
 }
 
-// Per-model constants that live in engine-wide state (the LayerNorm width in the control block, the node feature
-// row stride in the geometry): re-applied whenever another model of the same engine runs.
-int lb_gns_bind(lb_engine* e, lb_gns* g) {
-  if (e->bound_model == g) return LB_OK;
-  LB_HIP(hipMemcpyAsync(&e->ctrl->ln_inv_d, g->lnc, sizeof(g->lnc), hipMemcpyHostToDevice, e->stream));
-  e->g.kpad = g->kq_node * 8;
-  e->bound_model = g;
-  return LB_OK;
-}
-
-extern "C" void lb_gns_destroy(lb_gns* g) {
-  if (!g) return;
-  if (g->eng && g->eng->bound_model == g) g->eng->bound_model = nullptr;
-  if (g->blob) (void)hipFree(g->blob);
-  for (float* b : g->gen_hn)
-    if (b) (void)hipFree(b);
-  if (g->gen_he) (void)hipFree(g->gen_he);
-  delete g;
-}
-
 extern "C" int lb_set_fused_aggregation(lb_engine* e, int32_t on) {
   if (!e) return lb_fail(LB_ERR_ARG, "null engine");
   e->fused_agg = on ? 1 : 0;
-  return LB_OK;
-}
-
-extern "C" int lb_gns_set_tap(lb_gns* g, float* tap) {
-  if (!g) return lb_fail(LB_ERR_ARG, "null model");
-  g->tap = tap;
   return LB_OK;
 }
 

@@ -354,12 +354,13 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
     if (rc) return rc;
   }
 
-  // Kernel families.  f16x2 (default): M-split kernels on small graphs, else k_edge16v / k_edge_enc16v (edges) and
-  // k_node16s (nodes).  Exact fp32 (LB_MATH=f32, or the range guard's fall-back): k_edge16<*, f32> and the 32-row
-  // k_node_mlp.  Stand-alone aggregation (lb_set_fused_aggregation(0)): k_edge16 writes the messages, k_segment_sum
-  // adds them up.
-  auto node_mlp = [&](const lb_mlp_w& w, const float* xin, int kq, bool with_agg, bool resid, int next,
-                      const float* ms_img, const float* w0h, const float* w1h, bool ms, bool dec = false) -> int {
+  // Kernel families, and the lb_mlp_w images they read.  f16x2 (default): M-split kernels on small graphs (.ms), else
+  // k_edge16v / w / k_edge_enc16v (edges) and k_node16s (nodes; .w0_16h / .w1_16h, the next edge MLP's .proj_w_h2).
+  // Exact fp32 (LB_MATH=f32, or the range guard's fall-back): k_edge16<*, f32> (.w0_16 / .w1_16) and the 32-row
+  // k_node_mlp (.w0 / .w1, .proj_w).  Stand-alone aggregation (lb_set_fused_aggregation(0)): k_edge16 writes the
+  // messages, k_segment_sum adds them up.
+  auto node_mlp = [&](const lb_mlp_w& w, const float* xin, int kq, bool with_agg, bool resid, int next, bool ms,
+                      bool dec = false) -> int {
     const bool proj = next < L;
     lb_node_args a{};
     a.ctrl = e->ctrl;
@@ -373,8 +374,8 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
     a.b1 = w.b1;
     a.ln_s = w.ln_s;
     a.ln_o = w.ln_o;
-    a.wpp = proj ? g->proj_w[next] : nullptr;
-    a.bp = proj ? g->proj_b[next] : nullptr;
+    a.wpp = proj ? g->proc_edge[next].proj_w : nullptr;
+    a.bp = proj ? g->proc_edge[next].proj_b : nullptr;
     a.psr = e->psr;
     a.fused = e->fused_agg;
     a.tile_shift = 4;
@@ -390,7 +391,7 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
       m.part = e->part;
       m.fused = e->fused_agg;
       m.nlat = e->nlat;
-      m.w = ms_img;
+      m.w = w.ms;
       m.b0 = a.b0;
       m.b1 = a.b1;
       m.ln_s = a.ln_s;
@@ -411,7 +412,8 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
       return lbk_node_ms(e, m, kq / 4, with_agg, resid, proj, dec);
     }
     if (e->f16x2)
-      return lbk_node16s(e, a, w0h, w1h, proj ? g->proj_w_h2[next] : nullptr, kq / 4, with_agg ? 4 : 0, resid);
+      return lbk_node16s(e, a, w.w0_16h, w.w1_16h, proj ? g->proc_edge[next].proj_w_h2 : nullptr, kq / 4, with_agg ? 4 : 0,
+                         resid);
     if (with_agg)
       hipLaunchKernelGGL((k_node_mlp<16, 16, true>), dim3(ntile_n), dim3(64), 0, s, a);
     else if (kq == 4)
@@ -426,8 +428,7 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
   };
 
   lb_tic(e, LB_T_ENC_NODE);
-  rc = node_mlp(g->enc_node, e->xnode, g->kq_node, false, false, 0, g->ms_enc_node, g->enc_node_w0_h,
-                g->enc_node_w1_h, ms_en);
+  rc = node_mlp(g->enc_node, e->xnode, g->kq_node, false, false, 0, ms_en);
   lb_toc(e);
   if (rc) return rc;
 
@@ -438,7 +439,7 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
     m.ctrl = e->ctrl;
     m.efeat = e->efeat;
     m.elat = e->elat;
-    m.w = g->ms_enc_edge;
+    m.w = g->enc_edge.ms;
     m.b0 = g->enc_edge.b0;
     m.b1 = g->enc_edge.b1;
     m.ln_s = g->enc_edge.ln_s;
@@ -449,9 +450,9 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
     b.ctrl = e->ctrl;
     b.efeat = e->efeat;
     b.elat = e->elat;
-    b.w0p = e->f16x2 ? g->enc_edge_w0_16h : g->enc_edge_w0_16;
+    b.w0p = e->f16x2 ? g->enc_edge.w0_16h : g->enc_edge.w0_16;
     b.b0 = g->enc_edge.b0;
-    b.w1p = e->f16x2 ? g->enc_edge_w1_16h : g->enc_edge_w1_16;
+    b.w1p = e->f16x2 ? g->enc_edge.w1_16h : g->enc_edge.w1_16;
     b.b1 = g->enc_edge.b1;
     b.ln_s = g->enc_edge.ln_s;
     b.ln_o = g->enc_edge.ln_o;
@@ -473,7 +474,7 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
       m.receivers = e->receivers;
       m.elat = e->elat;
       m.psr = e->psr;
-      m.w = g->ms_proc_edge[k];
+      m.w = pe.ms;
       m.b1 = pe.b1;
       m.ln_s = pe.ln_s;
       m.ln_o = pe.ln_o;
@@ -489,8 +490,8 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
       b.elat = e->elat;
       b.msg = e->msg;
       b.psr = e->psr;
-      b.w0p = e->f16x2 ? g->proc_edge_w0_16h[k] : g->proc_edge_w0_16[k];
-      b.w1p = e->f16x2 ? g->proc_edge_w1_16h[k] : g->proc_edge_w1_16[k];
+      b.w0p = e->f16x2 ? pe.w0_16h : pe.w0_16;
+      b.w1p = e->f16x2 ? pe.w1_16h : pe.w1_16;
       b.b1 = pe.b1;
       b.ln_s = pe.ln_s;
       b.ln_o = pe.ln_o;
@@ -519,8 +520,7 @@ int lbk_gns_forward(lb_engine* e, lb_gns* g) {
     const bool ms_dec_ok = lb_fused_launches();
     const bool with_dec = ms_pn && ms_dec_ok && k == L - 1 && e->f16x2 && g->desc.out_dim <= 4;
     lb_tic_single(e, LB_T_NODE_MLP);
-    rc = node_mlp(g->proc_node[k], e->nlat, 16, true, true, k + 1, g->ms_proc_node[k], g->proc_node_w0_h[k],
-                  g->proc_node_w1_h[k], ms_pn, with_dec);
+    rc = node_mlp(g->proc_node[k], e->nlat, 16, true, true, k + 1, ms_pn, with_dec);
     lb_toc(e);
     decoded = with_dec;
     if (rc) return rc;

@@ -16,7 +16,7 @@
 //   * jraph.segment_sum is the stand-alone k_segment_sum on the receiver-sorted list.
 // Arithmetic: the same f16x2 split products (or exact fp32 MFMA under LB_MATH=f32 / after the range
 // guard fired) and the same LayerNorm code as the fused kernels, so the 1e-5 parity bar applies.
-// A latent narrower than 128 is zero-padded exactly as in lb_gns_create (lb_ctrl::ln_inv_d / ln_pad).
+// A latent narrower than 128 is zero-padded as on the fused path (lb_gns_weights.hip; lb_ctrl::ln_inv_d / ln_pad).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -327,9 +327,9 @@ int lbk_decoder16(lb_engine* e, lb_gns* g) {
   a.ctrl = e->ctrl;
   a.n_rows = e->BN;
   a.nlat = e->nlat;
-  a.w0 = e->f16x2 ? g->dec_w0_h : g->dec_w0_f;
+  a.w0 = e->f16x2 ? g->dec.w0_16h : g->dec.w0_16;
   a.b0 = g->dec.b0;
-  a.w1 = e->f16x2 ? g->dec_w1_h : g->dec_w1_f;
+  a.w1 = e->f16x2 ? g->dec.w1_16h : g->dec.w1_16;
   a.b1 = g->dec.b1;
   a.unscale = e->f16x2 ? g->dec_unscale : 1.f;
   a.acc_out = e->acc;
@@ -345,170 +345,6 @@ int lbk_decoder16(lb_engine* e, lb_gns* g) {
   else
     hipLaunchKernelGGL((k_decoder16<false>), dim3(grid), dim3(GD_THREADS), 0, e->stream, a, e->g);
   LB_HIP(hipGetLastError());
-  return LB_OK;
-}
-
-// ---------------------------------------------------------------------------------- model build
-// Blob order (models/gns.py GNS.flatten): [embed] then per MLP, in module-creation order,
-// linear_0 .. linear_{n-1} as (w [in][out], b [out]) and, if present, LayerNorm scale, offset.
-int lb_gns_create_generic(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats, lb_gns** out) {
-  const int D = LB_D, L = d->num_mp_steps, nl = d->blocks_per_step, dl = d->latent_size;
-  if (nl < 1 || nl > 16) return lb_fail(LB_ERR_ARG, "num_mlp_layers %d out of range (1..16)", nl);
-  const bool has_emb = d->num_particle_types > 1;
-  const int emb = has_emb ? d->embedding_size : 0;
-  const int nin = d->node_in + emb;
-  if (nin > 128) return lb_fail(LB_ERR_UNSUPPORTED, "node input width %d > 128 not built", nin);
-  const int kpad = (nin + 31) / 32 * 32;  // 32 .. 128
-
-  std::vector<float> host;
-  auto put = [&](const float* src, size_t n) -> size_t {
-    size_t off = (host.size() + 63) & ~(size_t)63;
-    host.resize(off + n, 0.f);
-    if (src) memcpy(host.data() + off, src, n * sizeof(float));
-    return off;
-  };
-  struct LinOff {
-    std::vector<size_t> wh, wf;
-    size_t b;
-  };
-  struct MlpOff {
-    std::vector<LinOff> lin;
-    size_t lns = 0, lno = 0;
-    bool ln = false;
-  };
-  const float* p = w;
-  const float* p_end = w + n_floats;
-  bool short_blob = false;
-  double w_rms_min = 1e30;  // see lb_gns_create: uniformly small weight matrices fall out of the f16x2 accuracy class
-  auto note_rms = [&](const float* m, size_t n) {
-    double s2 = 0;
-    size_t nz = 0;
-    for (size_t i = 0; i < n; ++i) {
-      s2 += (double)m[i] * m[i];
-      nz += m[i] != 0.f;
-    }
-    if (nz) w_rms_min = std::min(w_rms_min, std::sqrt(s2 / (double)nz));
-  };
-  // one Linear: in_blocks x blk_in input rows (each block padded to 128 k's), `outw` columns (padded to 128)
-  auto read_linear = [&](int in_blocks, int blk_in, int outw) -> LinOff {
-    LinOff o;
-    const size_t need = (size_t)in_blocks * blk_in * outw + outw;
-    if (p + need > p_end) {
-      short_blob = true;
-      o.b = 0;
-      return o;
-    }
-    note_rms(p, (size_t)in_blocks * blk_in * outw);
-    std::vector<float> tmp((size_t)128 * 128);
-    for (int b = 0; b < in_blocks; ++b) {
-      const float* src = p + (size_t)b * blk_in * outw;
-      lb_pack_weight16h(src, blk_in, outw, 128, tmp.data(), 128);
-      o.wh.push_back(put(tmp.data(), tmp.size()));
-      lb_pack_weight16(src, blk_in, outw, 128, tmp.data());
-      o.wf.push_back(put(tmp.data(), tmp.size()));
-    }
-    p += (size_t)in_blocks * blk_in * outw;
-    std::vector<float> bias(128, 0.f);
-    memcpy(bias.data(), p, sizeof(float) * outw);
-    o.b = put(bias.data(), 128);
-    p += outw;
-    return o;
-  };
-  auto read_mlp = [&](int in_blocks, int blk_in, int outw, bool ln) -> MlpOff {
-    MlpOff m;
-    for (int li = 0; li < nl; ++li) {
-      const bool first = li == 0, last = li == nl - 1;
-      m.lin.push_back(read_linear(first ? in_blocks : 1, first ? blk_in : dl, last ? outw : dl));
-      if (short_blob) return m;
-    }
-    m.ln = ln;
-    if (ln) {
-      if (p + 2 * (size_t)outw > p_end) {
-        short_blob = true;
-        return m;
-      }
-      std::vector<float> v(128, 0.f);
-      memcpy(v.data(), p, sizeof(float) * outw);
-      m.lns = put(v.data(), 128);
-      p += outw;
-      std::fill(v.begin(), v.end(), 0.f);
-      memcpy(v.data(), p, sizeof(float) * outw);
-      m.lno = put(v.data(), 128);
-      p += outw;
-    }
-    return m;
-  };
-  size_t off_embed = 0;
-  if (has_emb) {
-    const size_t n = (size_t)d->num_particle_types * emb;
-    if (p + n > p_end) return lb_fail(LB_ERR_ARG, "weight blob too short (embedding)");
-    off_embed = put(p, n);
-    p += n;
-  }
-  MlpOff o_en = read_mlp(1, nin, dl, true);
-  MlpOff o_ee = read_mlp(1, d->edge_in, dl, true);
-  std::vector<MlpOff> o_pe, o_pn;
-  for (int k = 0; k < L && !short_blob; ++k) {
-    o_pe.push_back(read_mlp(3, dl, dl, true));
-    o_pn.push_back(read_mlp(2, dl, dl, true));
-  }
-  MlpOff o_dec;
-  if (!short_blob) o_dec = read_mlp(1, dl, d->out_dim, false);
-  if (short_blob || p != p_end)
-    return lb_fail(LB_ERR_ARG, "weight blob has %lld floats, the model (num_mlp_layers %d, latent %d) needs %s",
-                   (long long)n_floats, nl, dl, short_blob ? "more" : "fewer");
-
-  lb_gns* g = new lb_gns();
-  g->desc = *d;
-  g->eng = e;
-  g->tap = nullptr;
-  g->generic = true;
-  g->kq_node = kpad / 8;
-  if (hipMalloc((void**)&g->blob, host.size() * sizeof(float)) != hipSuccess) {
-    delete g;
-    return lb_fail(LB_ERR_HIP, "hipMalloc(weights) failed");
-  }
-  if (hipMemcpy(g->blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    lb_gns_destroy(g);
-    return lb_fail(LB_ERR_HIP, "weight upload failed");
-  }
-  auto mk = [&](const MlpOff& m) {
-    lb_gen_mlp r;
-    for (const LinOff& lo : m.lin) {
-      lb_gen_lin x;
-      for (size_t o : lo.wh) x.wh.push_back(g->blob + o);
-      for (size_t o : lo.wf) x.wf.push_back(g->blob + o);
-      x.b = g->blob + lo.b;
-      r.lin.push_back(x);
-    }
-    r.ln_s = m.ln ? g->blob + m.lns : nullptr;
-    r.ln_o = m.ln ? g->blob + m.lno : nullptr;
-    return r;
-  };
-  g->embed = has_emb ? g->blob + off_embed : nullptr;
-  g->g_enc_node = mk(o_en);
-  g->g_enc_edge = mk(o_ee);
-  g->g_dec = mk(o_dec);
-  for (int k = 0; k < L; ++k) {
-    g->g_proc_edge.push_back(mk(o_pe[k]));
-    g->g_proc_node.push_back(mk(o_pn[k]));
-  }
-  g->lnc[0] = 1.0f / (float)dl;  // LayerNorm width of this model (lb_gns_bind)
-  g->lnc[1] = (float)(D - dl);
-  if (w_rms_min < 0.0078125 && e->f16x2 && e->math_auto) {
-    fprintf(stderr, "[lbhip] a weight matrix has rms %.3g < 2^-7: its fp16 hi/lo split would fall short of the 1e-5 class - "
-                    "this engine uses exact-fp32 MFMA arithmetic\n", w_rms_min);
-    e->f16x2 = 0;
-  }
-  const int64_t BN = e->BN;
-  int rc = lb_ensure_node_scratch(e);
-  if (!rc) rc = lb_gns_bind(e, g);
-  for (int i = 0; i < 3 && !rc; ++i) rc = lb_alloc(&g->gen_hn[i], (size_t)BN * D);
-  if (rc) {
-    lb_gns_destroy(g);
-    return rc;
-  }
-  *out = g;
   return LB_OK;
 }
 

@@ -207,13 +207,32 @@ struct lb_engine {
   int64_t t_n[LB_T_COUNT];
 };
 
-struct lb_mlp_w {      // one packed 2-layer MLP on the device
-  const float* w0;     // packed fragments, K0pad x D
-  const float* b0;     // [D]
-  const float* w1;     // packed, D x Mpad
-  const float* b1;     // [Mpad]
-  const float* ln_s;   // [D] or null
+// One GNS MLP of the default depth (two Linears) on the device: its matrices in the packing of every kernel family that
+// reads this MLP, null for the others (lb_gns_weights.hip: lb_pack_fused).  Narrow latents are zero-padded to the tiles.
+//                     32-row fp32    16-row fp32        16-row f16x2                       M-split image
+//                     k_node_mlp     k_edge16<f32>,     k_edge16v / w, k_edge_enc16v,      k_node_ms, k_edge_ms,
+//                                    k_decoder16<false> k_edge16<f16x2>, k_node16s,        k_edge_enc_ms
+//                                                       k_decoder16<true>
+//   enc_node, proc_node   w0, w1         -              w0_16h, w1_16h                     ms
+//   enc_edge, proc_edge   -              w0_16, w1_16   w0_16h, w1_16h                     ms
+//   dec                   -              w0_16, w1_16   w0_16h, w1_16h (head: 128 x 16)    (in the last proc_node's)
+struct lb_mlp_w {
+  const float* b0;     // [128]; null in a processor edge MLP (its b0 is the second half of proj_b)
+  const float* b1;     // [128] (decoder: [32])
+  const float* ln_s;   // [128] LayerNorm scale / offset, null in the decoder
   const float* ln_o;
+  const float* w0;     // lb_pack_weight: Kpad x 128
+  const float* w1;     //   128 x 128
+  const float* w0_16;  // lb_pack_weight16: Kpad x 128; a processor edge MLP's w0 images hold the edge-latent rows only
+  const float* w1_16;
+  const float* w0_16h; // lb_pack_weight16h (hi | lo)
+  const float* w1_16h; //   decoder: the out_dim block of the head, times a power of two (lb_gns::dec_unscale)
+  const float* ms;     // lb_pack_ms: [W0 | W1], a node MLP's then [Ws | Wr of the NEXT edge MLP] or, after the last
+                       // layer, [decoder W0 | out_dim block of the scaled head] (k_node_ms<DEC>)
+  // processor edge MLPs only: the sender / receiver rows of W0, applied per node by the node kernel of the layer before
+  const float* proj_w;     // lb_pack_weight, 128 x 256 = [Ws | Wr]: k_node_mlp
+  const float* proj_w_h2;  // lb_pack_weight16h of Ws, then of Wr (two 128-wide halves): k_node16s
+  const float* proj_b;     // [256]: zeros | b0
 };
 
 struct lb_edge16_args {  // lb_edge16.hip
@@ -275,36 +294,15 @@ struct lb_gen_mlp {
 struct lb_gns {
   lb_gns_desc desc;
   lb_engine* eng;
-  float* blob;         // single device allocation holding everything below
-  const float* embed;  // [types][emb]
-  lb_mlp_w enc_node, enc_edge, dec;
-  std::vector<lb_mlp_w> proc_edge, proc_node;  // proc_edge[k].w0 packs only the edge-latent rows
-  std::vector<const float*> proj_w;            // packed [D x 2D]: sender | receiver rows of w0
-  std::vector<const float*> proj_b;            // [2D]: zeros | b0
-  const float* enc_edge_w0_16;                 // 16-row-tile packings of the edge MLP matrices
-  const float* enc_edge_w1_16;
-  std::vector<const float*> proc_edge_w0_16, proc_edge_w1_16;
-  const float* enc_edge_w0_16h;                // f16x2 (hi|lo) packings
-  const float* enc_edge_w1_16h;
-  std::vector<const float*> proc_edge_w0_16h, proc_edge_w1_16h;
-  // f16x2 node-MLP packings: w0 (Kpad x 128), w1 (128 x 128), projection (128 x 256)
-  const float* enc_node_w0_h;
-  const float* enc_node_w1_h;
-  std::vector<const float*> proc_node_w0_h, proc_node_w1_h, proj_w_h;
-  std::vector<const float*> proj_w_h2;  // projection packed as two 128-wide halves [Ws | Wr] (lb_node16s.hip)
+  float* blob;         // single device allocation holding every image below
+  const float* embed;  // [types][emb] or null
   int kq_node;         // node_in(+emb) padded to a multiple of 32, in units of 8
   float lnc[2] = {1.0f / LB_D, 0.f};  // lb_ctrl::ln_inv_d, ln_pad of this model (latent width < 128: zero padded)
   float* tap;
-  // decoder on the 16-row tile scheme (k_decoder16): W0 and the out_dim block of W1, both packings
-  const float* dec_w0_h = nullptr;
-  const float* dec_w0_f = nullptr;
-  const float* dec_w1_h = nullptr;
-  const float* dec_w1_f = nullptr;
+  // num_mlp_layers == 2 (lb_gns.hip)
+  lb_mlp_w enc_node, enc_edge, dec;
+  std::vector<lb_mlp_w> proc_edge, proc_node;
   float dec_unscale = 1.f;  // the f16x2 copy of the decoder's output Linear is packed times a power of two
-  // M-split images (lb_msplit.hip, small graphs): per MLP [W0 | W1 (| projection of the NEXT edge MLP)]
-  const float* ms_enc_node = nullptr;
-  const float* ms_enc_edge = nullptr;
-  std::vector<const float*> ms_proc_edge, ms_proc_node;
   // num_mlp_layers != 2 (lb_gns_generic.hip): one packed 128x128 Linear per input block, both packings
   bool generic = false;
   lb_gen_mlp g_enc_node, g_enc_edge, g_dec;
@@ -467,14 +465,14 @@ void lb_sg_readout_image(const float* ws0, const float* wv0, const float* b0, co
 int lb_sg_readout_image_floats(void);
 int lbk_sg_readout(lb_engine* e, const float* f, const float* nattr, const float* image, float* acc_out);
 
-// lb_api.hip: node-sized network scratch (allocated once per engine, xnode at the full 128-column width) and the
-// per-model constants that live in engine-wide state; several models may share one engine
+// lb_api.hip: node-sized network scratch (allocated once per engine, xnode at the full 128-column width)
 int lb_ensure_node_scratch(lb_engine* e);
+// lb_gns_weights.hip: lb_gns_create / lb_gns_destroy / lb_gns_set_tap, and the per-model constants that live in
+// engine-wide state; several models may share one engine
 int lb_gns_bind(lb_engine* e, lb_gns* g);
 // lb_gns.hip
 int lbk_gns_forward(lb_engine* e, lb_gns* g);
 // lb_gns_generic.hip: num_mlp_layers != 2
-int lb_gns_create_generic(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats, lb_gns** out);
 int lbk_gns_forward_generic(lb_engine* e, lb_gns* g);
 int lbk_decoder16(lb_engine* e, lb_gns* g);
 int lbk_segment_sum(lb_engine* e, const float* msg, float* out, int D);
