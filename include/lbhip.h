@@ -288,6 +288,26 @@ int32_t lb_gns_train_math_fallbacks(lb_gns_train* t);
  * same either way. */
 int32_t lb_gns_train_sort_fallbacks(lb_gns_train* t);
 
+/* Push-forward from device weights.
+ * Re-make every packed image of `g` from the CURRENT weights of training handle `t`, on the device.
+ * g and t: same engine, same lb_gns_desc (else LB_ERR_ARG).  Afterwards g is what lb_gns_create would
+ * have made from lb_gns_train_read(t, 0): the same image bytes, dec_unscale, and f16x2 / rms decision
+ * (the rms is an fp64 sum in another fixed order than lb_gns_create's: the decision can differ only for a
+ * matrix whose rms lies within rounding of 2^-7).
+ * Runs on the engine's stream; may read back a few scalars, never the weights. */
+int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g);
+/* Test support: the packed device blob of a model (every image, in packing order), for byte comparison. */
+int64_t lb_gns_image_bytes(lb_gns* g);
+int lb_gns_image_read(lb_gns* g, void* out_host, int64_t n_bytes);
+/* Test support, NO HIP call: stage the images of (desc, weights_host) with the host packers of lb_gns_create, stage them
+ * again by replaying the recorded job table of lb_gns_train_sync_model on the host - through the element function the
+ * device kernel uses, from the training handle's 128-padded layout of the weights - and return the number of differing
+ * bytes (a differing dec_unscale counts 4, an rms further apart than summation order explains 8); < 0: an error code.
+ * node_in_kq: 0 = the node input's row padding as lb_gns_create derives it from the description (units of 8 columns),
+ * else 4, 8, 12 or 16 to widen it.  *n_bytes_out (optional): bytes compared. */
+int64_t lb_gns_pack_selftest(const lb_gns_desc* desc, int32_t node_in_kq, const float* weights_host, int64_t n_floats,
+                             int64_t* n_bytes_out);
+
 typedef struct lb_segnn lb_segnn;
 
 /* SEGNN hyper-parameters (runner.py:217-237; configs: scalar_units 64 -> hidden irreps
@@ -393,6 +413,10 @@ int lb_egnn_train_create(lb_engine* eng, const lb_egnn_desc* desc, const float* 
  * or NULL: the prediction, bit-identical to lb_egnn_forward's.  Host-synchronous. */
 int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
                             float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev);
+/* The inference model of an EGNN training handle: a view of its device weights, so lb_egnn_forward / lb_egnn_rollout on it
+ * run on the CURRENT weights (bit-identical to a model created from lb_gns_train_read(t, 0)).  BORROWED: owned by t,
+ * valid until lb_gns_train_destroy(t); never pass it to lb_egnn_destroy. */
+int lb_egnn_train_model(lb_gns_train* t, lb_egnn** out);
 
 /* ---- PaiNN (models/painn.py:372-510) -----------------------------------------------------------
  * Construction by runner.py:270-284: hidden_size = latent_dim, output_size 1, n_vels = isl - 1, gaussian_rbf(20,

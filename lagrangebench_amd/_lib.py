@@ -137,6 +137,10 @@ _SIGS = {
                                          C.c_float]),
     "lb_gns_train_math_fallbacks": (C.c_int32, [_P]),
     "lb_gns_train_sort_fallbacks": (C.c_int32, [_P]),
+    "lb_gns_train_sync_model": (C.c_int, [_P, _P]),
+    "lb_gns_image_bytes": (C.c_int64, [_P]),
+    "lb_gns_image_read": (C.c_int, [_P, _P, C.c_int64]),
+    "lb_gns_pack_selftest": (C.c_int64, [C.POINTER(GnsDesc), C.c_int32, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)]),
     "lb_segnn_train_create": (C.c_int, [_P, C.POINTER(SegnnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_segnn_train_loss_grad": (C.c_int, [_P, _P, C.c_float, C.POINTER(C.c_double), _P]),
     "lb_segment_sum": (C.c_int, [_P, _P, _P, C.c_int32]),
@@ -153,6 +157,7 @@ _SIGS = {
     "lb_egnn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "lb_egnn_train_create": (C.c_int, [_P, C.POINTER(EgnnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_egnn_train_loss_grad": (C.c_int, [_P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), _P]),
+    "lb_egnn_train_model": (C.c_int, [_P, C.POINTER(_P)]),
     "lb_painn_create": (C.c_int, [_P, C.POINTER(PainnDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_painn_destroy": (None, [_P]),
     "lb_painn_forward": (C.c_int, [_P, _P, _P]),

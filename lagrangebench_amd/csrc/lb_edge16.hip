@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "lb_device.h"
+#include "lb_gns_repack.h"
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -40,53 +41,7 @@
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 #define MFMA16H(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
-static uint16_t lb_f32_to_f16_rne(float f) {
-  uint32_t x;
-  memcpy(&x, &f, 4);
-  const uint32_t sign = (x >> 16) & 0x8000u;
-  x &= 0x7fffffffu;
-  if (x >= 0x47800000u) return (uint16_t)(sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u));  // inf / nan
-  if (x < 0x38800000u) {  // subnormal half (or zero): value * 2^24 rounded to nearest even
-    if (x < 0x33000000u) return (uint16_t)sign;
-    const int shift = 126 - (int)(x >> 23);  // 14 .. 24
-    uint32_t m = (x & 0x7fffffu) | 0x800000u;
-    const uint32_t lsb = 1u << shift, half = lsb >> 1;
-    uint32_t r = m >> shift;
-    const uint32_t rem = m & (lsb - 1);
-    if (rem > half || (rem == half && (r & 1))) ++r;
-    return (uint16_t)(sign | r);
-  }
-  uint32_t r = x - 0x38000000u;  // rebias exponent 127 -> 15
-  const uint32_t rem = r & 0x1fffu;
-  r >>= 13;
-  if (rem > 0x1000u || (rem == 0x1000u && (r & 1))) ++r;
-  return (uint16_t)(sign | r);
-}
-static float lb_f16_to_f32(uint16_t h) {
-  const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-  const uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ffu;
-  uint32_t x;
-  if (e == 0) {
-    if (m == 0) {
-      x = sign;
-    } else {
-      int k = 0;
-      uint32_t mm = m;
-      while (!(mm & 0x400u)) {
-        mm <<= 1;
-        ++k;
-      }
-      x = sign | ((uint32_t)(113 - k) << 23) | ((mm & 0x3ffu) << 13);
-    }
-  } else if (e == 31) {
-    x = sign | 0x7f800000u | (m << 13);
-  } else {
-    x = sign | ((e + 112) << 23) | (m << 13);
-  }
-  float f;
-  memcpy(&f, &x, 4);
-  return f;
-}
+// lb_f32_to_f16_rne / lb_f16_to_f32: lb_gns_repack.h (shared with the device repack of these images)
 
 // out: Kpad*Mpad "floats" worth of storage holding [(p*NMBO + mbo)][part: 0 hi, 1 lo][lane][8 halfs]
 void lb_pack_weight16h(const float* w, int K, int M, int Kpad, float* out, int Mpad) {

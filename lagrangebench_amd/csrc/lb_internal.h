@@ -295,6 +295,8 @@ struct lb_gns {
   lb_gns_desc desc;
   lb_engine* eng;
   float* blob;         // single device allocation holding every image below
+  int64_t blob_floats = 0;
+  struct lb_repack* repack = nullptr;  // lb_gns_repack.hip: the uploaded job table of lb_gns_train_sync_model, made at its first call
   const float* embed;  // [types][emb] or null
   int kq_node;         // node_in(+emb) padded to a multiple of 32, in units of 8
   float lnc[2] = {1.0f / LB_D, 0.f};  // lb_ctrl::ln_inv_d, ln_pad of this model (latent width < 128: zero padded)
@@ -470,6 +472,7 @@ int lb_ensure_node_scratch(lb_engine* e);
 // lb_gns_weights.hip: lb_gns_create / lb_gns_destroy / lb_gns_set_tap, and the per-model constants that live in
 // engine-wide state; several models may share one engine
 int lb_gns_bind(lb_engine* e, lb_gns* g);
+void lb_gns_rms_guard(lb_engine* e, double w_rms_min);
 // lb_gns.hip
 int lbk_gns_forward(lb_engine* e, lb_gns* g);
 // lb_gns_generic.hip: num_mlp_layers != 2

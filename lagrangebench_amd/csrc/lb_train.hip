@@ -38,6 +38,7 @@
 
 #include "lb_device.h"
 #include "lb_lin32.h"
+#include "lb_gns_repack.h"
 
 #include <hipcub/hipcub.hpp>  // header-only device radix sort (the sender-sorted edge permutation of the gather's transpose)
 
@@ -1583,19 +1584,13 @@ static int train_sender_sort(lb_gns_train* t, int64_t E, int64_t BN) {
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
-extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats,
-                                   lb_gns_train** out) {
-  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
-    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
-  if (d->out_dim != e->g.dim || d->node_in != e->g.node_in || d->edge_in != e->g.dim + 1)
-    return lb_fail(LB_ERR_ARG, "model widths do not match the case");
+// The layout of a GNS training handle's blobs for description d (no HIP call): the offsets of every MLP in the device
+// blob, its float count (t->n_floats), the caller blob's (t->n_compact) and the index map between them (t->cmap)
+static void gns_train_layout(lb_gns_train* t, const lb_gns_desc* d) {
   const int L = d->num_mp_steps;
   const bool has_emb = d->num_particle_types > 1;
   const int emb = has_emb ? d->embedding_size : 0;
-  lb_gns_train* t = new lb_gns_train();
   t->desc = *d;
-  t->eng = e;
   t->nlin = d->blocks_per_step;
   const int nmid = t->nlin - 2;
   t->nin = d->node_in + emb;
@@ -1669,12 +1664,36 @@ extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const flo
     map_mlp(t->pn[k], 2 * lat, 2, lat);
   }
   map_mlp(t->dec, lat, 1, d->out_dim);
+  t->n_floats = o;
+  t->n_compact = oc;
+}
+int lb_gns_train_padded_map(const lb_gns_desc* d, std::vector<int64_t>* cmap, int64_t* n_dev, int64_t* n_compact) {
+  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
+    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
+  lb_gns_train t;
+  gns_train_layout(&t, d);
+  cmap->swap(t.cmap);
+  *n_dev = t.n_floats;
+  *n_compact = t.n_compact;
+  return LB_OK;
+}
+
+extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats,
+                                   lb_gns_train** out) {
+  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
+  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
+    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
+  if (d->out_dim != e->g.dim || d->node_in != e->g.node_in || d->edge_in != e->g.dim + 1)
+    return lb_fail(LB_ERR_ARG, "model widths do not match the case");
+  lb_gns_train* t = new lb_gns_train();
+  t->eng = e;
+  gns_train_layout(t, d);
+  const int L = d->num_mp_steps;
+  const int64_t o = t->n_floats, oc = t->n_compact;
   if (oc != n_floats) {
     delete t;
     return lb_fail(LB_ERR_ARG, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)oc);
   }
-  t->n_floats = o;
-  t->n_compact = oc;
   t->nlat.assign(L + 1, nullptr);
   t->elat.assign(L + 1, nullptr);
   t->ae.assign(L, nullptr); t->ze.assign(L, nullptr);
@@ -1931,6 +1950,20 @@ extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* i
   }
   if (step >= 0) t->step = step;
   return LB_OK;
+}
+
+// The inference images of g re-made on the device from this handle's current weights (lb_gns_repack.hip)
+extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
+  if (!t || !g) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->sg || t->eg) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
+  if (g->eng != t->eng) return lb_fail(LB_ERR_ARG, "the model was created for another engine");
+  const lb_gns_desc &a = t->desc, &b = g->desc;
+  if (a.latent_size != b.latent_size || a.blocks_per_step != b.blocks_per_step || a.num_mp_steps != b.num_mp_steps ||
+      a.embedding_size != b.embedding_size || a.num_particle_types != b.num_particle_types || a.node_in != b.node_in ||
+      a.edge_in != b.edge_in || a.out_dim != b.out_dim)
+    return lb_fail(LB_ERR_ARG, "the model's description differs from the training handle's (latent %d vs %d)", b.latent_size,
+                   a.latent_size);
+  return lbk_gns_repack(t->eng, g, t->w, t->cmap, t->n_compact, t->n_floats);
 }
 
 // ------------------------------------------------------------------------------------------------ SEGNN

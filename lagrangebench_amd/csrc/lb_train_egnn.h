@@ -526,6 +526,15 @@ extern "C" int lb_egnn_train_create(lb_engine* e, const lb_egnn_desc* d, const f
 }
 
 // value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h)
+// The inference view of the handle (lbk_egnn_view_create on t->w): lb_egnn_forward / lb_egnn_rollout on it run on the CURRENT
+// weights.  Borrowed: it lives and dies with t.
+extern "C" int lb_egnn_train_model(lb_gns_train* t, lb_egnn** out) {
+  if (!t || !out) return lb_fail(LB_ERR_ARG, "null argument");
+  if (!t->eg || !t->eg->view) return lb_fail(LB_ERR_ARG, "not an EGNN training handle");
+  *out = t->eg->view;
+  return LB_OK;
+}
+
 extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
                                        float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev) {
   if (!t || !t->eg) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");

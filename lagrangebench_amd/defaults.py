@@ -38,6 +38,7 @@ defaults = _wrap({
         "pushforward": {"steps": [-1, 20000, 300000, 400000], "unrolls": [0, 1, 2, 3], "probs": [18, 2, 1, 1]},
         "loss_weight": {"acc": 1.0, "vel": 0.0, "pos": 0.0},
         "device_data": False,                 # not in the reference: train split in HBM, samples made on the device
+        "device_unroll": False,               # not in the reference: push-forward unroll from the device weights (no host repack)
     },
     "logging": {"log_steps": 1000, "eval_steps": 10000, "wandb": False, "wandb_project": None,
                 "wandb_entity": "lagrangebench", "ckp_dir": "ckp", "run_name": None},  # defaults.py:153-168

@@ -486,6 +486,13 @@ class GnsHandle(_Handle):
         check(e.lib.lb_gns_set_tap(self._h, None))
         return None
 
+    def image(self) -> np.ndarray:
+        """The packed device blob of the model - every weight image, in packing order - as bytes (test support)."""
+        lib = self.engine.lib
+        out = np.empty(int(lib.lb_gns_image_bytes(self._h)), np.uint8)
+        check(lib.lb_gns_image_read(self._h, out.ctypes.data_as(C.c_void_p), C.c_int64(out.size)), "lb_gns_image_read")
+        return out
+
 
 class _DeviceSpan:
     """n float32 at a device address owned by a training handle, in the form torch.as_tensor wraps without a copy
@@ -556,6 +563,12 @@ class GnsTrainHandle(_Handle):
                                                 C.c_int64(out.size)), "lb_gns_train_read")
         return out
 
+    def sync_model(self, handle: "GnsHandle") -> None:
+        """Re-make the packed images of the inference model `handle` (same engine, same description) from this handle's
+        CURRENT weights, on the device: afterwards it is the model lb_gns_create would make from read("weights"), bit for
+        bit, without the weights leaving the device (include/lbhip.h: lb_gns_train_sync_model)."""
+        check(self.engine.lib.lb_gns_train_sync_model(self._h, handle._h), "lb_gns_train_sync_model")
+
     def step_count(self) -> int:
         """AdamW steps taken on the device (optax's `count`)."""
         return int(self.engine.lib.lb_gns_train_step_count(self._h))
@@ -598,6 +611,22 @@ class EgnnTrainHandle(GnsTrainHandle):
                                             ptr(pred) if want_pred else None), "lb_egnn_train_loss_grad")
         return (loss.value, pred) if want_pred else loss.value
 
+    _view: Optional["EgnnHandle"] = None
+
+    def model_handle(self) -> "EgnnHandle":
+        """The inference model of this handle: a view of its device weights, so engine.egnn_forward / rollout on it run on
+        the CURRENT weights.  Borrowed - it is this handle's; closing it frees nothing, closing this handle ends it."""
+        if self._view is None or not self._view._h:
+            h = C.c_void_p()
+            check(self.engine.lib.lb_egnn_train_model(self._h, C.byref(h)), "lb_egnn_train_model")
+            self._view = _BorrowedEgnnHandle(self.engine, h, self.desc, self.n_floats)
+        return self._view
+
+    def close(self):
+        if self._view is not None:
+            self._view._h = None   # the view dies with the handle
+        super().close()
+
 
 class SegnnHandle(_Handle):
     _DESTROY, _ROLLOUT = "lb_segnn_destroy", "lb_segnn_rollout"
@@ -632,6 +661,13 @@ class EgnnHandle(_Handle):
             self._tap = None
             check(e.lib.lb_egnn_set_tap(self._h, None, None), "lb_egnn_set_tap")
         return self._tap
+
+
+class _BorrowedEgnnHandle(EgnnHandle):
+    """An EgnnHandle whose lb_egnn belongs to a training handle (EgnnTrainHandle.model_handle): close() only lets go."""
+
+    def close(self):
+        self._h = None
 
 
 class PainnHandle(_Handle):

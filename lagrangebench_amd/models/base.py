@@ -76,7 +76,8 @@ class BaseModel(ABC):
         handles[key] = (h, params, stamp)
         return h
 
-    def apply(self, params, state, sample):
+    def _engine_of(self, sample):
+        """The engine whose state `sample`'s features describe; refuses features the engine has moved on from."""
         features, particle_type = sample
         engine = getattr(features, "engine", None)
         if engine is None:
@@ -84,8 +85,20 @@ class BaseModel(ABC):
                             "allocate_eval (it names the engine state to run on)")
         if features.version != engine.version:
             raise RuntimeError("features are stale: the engine state changed since they were produced")
-        out = getattr(engine, self._FORWARD)(self.handle(engine, params, state))
-        return {self._OUTPUT: out if features.batched else out[0]}, state
+        return engine
+
+    def apply(self, params, state, sample):
+        engine = self._engine_of(sample)
+        return self.apply_handle(self.handle(engine, params, state), state, sample)
+
+    def apply_handle(self, handle, state, sample):
+        """``apply`` on a device handle the caller holds (``unroll_handle``) instead of a parameter tree."""
+        engine = self._engine_of(sample)
+        if handle.engine is not engine:
+            raise ValueError(f"{type(self).__name__}.apply_handle: the handle belongs to another engine than the features")
+        self._check_padded(engine)
+        out = getattr(engine, self._FORWARD)(handle)
+        return {self._OUTPUT: out if sample[0].batched else out[0]}, state
 
     def __call__(self, params, state, sample):
         return self.apply(params, state, sample)
@@ -125,3 +138,10 @@ class BaseModel(ABC):
         _mse of the normalised acceleration."""
         self._check_padded(th.engine)
         return th.loss_grad(target["acc"], loss_weight.get("acc", 1.0))
+
+    def unroll_handle(self, engine, th, params_like):
+        """An inference handle on `engine` that runs on the CURRENT weights of training handle `th` without copying them
+        to the host (``train.device_unroll``), or None: the model has no such route and the
+        push-forward unroll goes through ``th.read("weights")`` and ``apply``.  `params_like`: a parameter tree of the
+        model's shapes (the one `th` was created from)."""
+        return None

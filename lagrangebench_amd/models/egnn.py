@@ -178,6 +178,11 @@ class EGNN(BaseModel):
         "acc"} targets and the loss weights."""
         return engine._new_handle(EgnnTrainHandle, "lb_egnn_train_create", self._desc(), self.flatten(params))
 
+    def unroll_handle(self, engine, th, params_like):
+        """The training handle's own inference view (csrc/lb_train_egnn.h): it reads th's weight blob, nothing to refresh."""
+        self._check_padded(engine)
+        return th.model_handle()
+
     def loss_grad(self, th, target, loss_weight) -> float:
         """_mse over every output the model predicts (pos, vel, acc)."""
         self._check_padded(th.engine)

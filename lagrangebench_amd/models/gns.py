@@ -162,3 +162,14 @@ class GNS(BaseModel):
     def _train_create(self, engine, params):
         """csrc/lb_train.hip."""
         return engine._new_handle(GnsTrainHandle, "lb_gns_train_create", self._desc(engine), self.flatten(params))
+
+    def unroll_handle(self, engine, th, params_like):
+        """csrc/lb_gns_repack.hip: one inference handle per training handle, made by the host route (``_create`` from
+        `params_like`) the first time and kept for the life of `th`; at EVERY use its packed images are re-made on the device
+        from th's current weights (``th.sync_model``), so what it computes never depends on `params_like`'s values."""
+        self._check_padded(engine)
+        h = getattr(th, "_unroll_model", None)
+        if h is None or not h._h or h.engine is not engine:
+            h = th._unroll_model = self._create(engine, params_like, None)
+        th.sync_model(h)
+        return h

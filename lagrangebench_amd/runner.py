@@ -5,7 +5,8 @@ keep their signatures.  ``cfg`` is a nested mapping with the reference's keys (a
 dict-like such as an OmegaConf DictConfig); missing keys fall back to ``defaults``.  `mode: train | all`
 runs ``train.Trainer`` (GNS, SEGNN and EGNN).  Under torchrun (one process per GPU) training is data parallel over
 ``train.batch_size``, the global batch, with no further config key (train/trainer.py); rank 0 alone
-prints and writes checkpoints.
+prints and writes checkpoints.  ``train.device_unroll: true`` makes the push-forward unroll of GNS / EGNN run from the
+device weights; like ``train.device_data`` it is read by the ``Trainer``, default off.
 """
 from __future__ import annotations
 

@@ -34,6 +34,10 @@ global batch, loss averaged, learning rate as configured.  One rank runs the cod
 sample of a step - window, random-walk noise, shift, targets - is made by one HIP launch (``case.preprocess_device``) instead
 of on the host.  Permutation and unroll count still come from the common stream; the noise is keyed by (seed, step, global
 slot), so a rank's shard gets the single-process noise of its slots.  With the key off nothing below changes.
+
+``train.device_unroll`` (default off): the push-forward unroll of GNS and EGNN runs on an inference
+handle fed from the training handle's device weights (``model.unroll_handle``: ``lb_gns_train_sync_model`` re-packs the GNS
+images in HIP, EGNN lends its view) instead of ``th.read("weights")`` + a host repack; same bits, every rank does the same.
 """
 from __future__ import annotations
 
@@ -93,6 +97,7 @@ class Trainer:
         self.shard = lbdist.shard_batch(self.cfg_train.batch_size, self.rank, self.world)
         self.seed = int(seed)
         self.device_data = bool(self.cfg_train.get("device_data", False))
+        self.device_unroll = bool(self.cfg_train.get("device_unroll", False))
         self._dd = None
         if self.device_data:
             from ..data.device import trajectory_source
@@ -198,6 +203,14 @@ class Trainer:
             os.makedirs(os.path.join(store_ckp, "best"), exist_ok=True)
 
         push_forward = push_forward_build(model.apply, case)
+        # train.device_unroll: the unroll's model is a device handle on th's weights.  Asked for HERE, while `params` are
+        # the weights th holds, so that a model that makes its handle by the host route does not read them back for it.
+        push_forward_dev = None
+        if self.device_unroll:
+            if model.unroll_handle(case.engine(B), th, params) is None:
+                say(f"train.device_unroll: {type(model).__name__} has no device route; the unroll copies the weights to the host")
+            else:
+                push_forward_dev = push_forward_build(model.apply_handle, case)   # (its "params" are the handle)
         log = []
         while step < step_max + 1:
             for raw_batch in self.loader_train:
@@ -215,15 +228,19 @@ class Trainer:
                     key, features_batch, target_batch, neighbors = case.preprocess(key, sample, noise_std, neighbors,
                                                                                    unroll_steps)
                 if unroll_steps > 0 and not bool(neighbors.did_buffer_overflow.sum() > 0):
-                    params_np = current_params()
+                    if push_forward_dev is not None:
+                        # (GNS: its images re-made from the weights of the last AdamW step; no host copy of them)
+                        pf, params_np = push_forward_dev, model.unroll_handle(case.engine(B), th, params)
+                    else:
+                        pf, params_np = push_forward, current_params()
                     # the noisy positions the features were computed from ARE the engine's window
                     cur = case.engine(B).read_window()
                     tshift = unroll_steps
                     for _ in range(unroll_steps):
                         if neighbors.did_buffer_overflow.sum() > 0:
                             break
-                        cur, neighbors, features_batch = push_forward(features_batch, cur, torch.as_tensor(sample[1]),
-                                                                      neighbors, params_np, state)
+                        cur, neighbors, features_batch = pf(features_batch, cur, torch.as_tensor(sample[1]), neighbors,
+                                                            params_np, state)
                     del tshift
                 overflow = bool(neighbors.did_buffer_overflow.sum() > 0)
                 # a step is skipped by ALL ranks or by none (no rank may reach a collective that another one skips); only
