@@ -61,7 +61,7 @@ struct lb_red_ent {
 };
 
 // LB_TRAIN_MATH=f32: the exact-fp32 product kernels (k_lin32f); default: f16x2 (k_lin32h)
-#define LB_DW_CALLS 512   // k_dw_part_h launches per step the X range bookkeeping covers (GNS-10: 62, SEGNN-10-64: ~90)
+#define LB_DW_CALLS 512   // k_dw_part_h sites the X range bookkeeping covers (GNS-10: 62, SEGNN-10-64: ~90)
 static bool lb_train_f16x2_default() {
   const char* m = getenv("LB_TRAIN_MATH");
   return !(m && (m[0] == 'f' && m[1] == '3'));
@@ -85,7 +85,7 @@ struct lb_gns_train {
   std::vector<lb_train_mlp> pe, pn;
   int nin = 0, kpad = 0;
   int64_t step = 0;
-  // activations (sized for cap_n nodes / cap_e edges)
+  // scratch of every model is sized for cap_n nodes / cap_e edges (train_ensure)
   int64_t cap_n = 0, cap_e = 0;
   float *xnode = nullptr, *a_en = nullptr, *z_en = nullptr, *a_ee = nullptr, *z_ee = nullptr;
   std::vector<float*> nlat, elat;            // [L+1] node / edge latents entering layer k
@@ -121,22 +121,24 @@ struct lb_gns_train {
   // same packed blob + one inverse power-of-two scale per matrix.  LB_TRAIN_MATH=f32 keeps the exact-fp32 kernels.
   bool f16x2 = lb_train_f16x2_default();
   // Range of k_dw_part_h's X operand (saved activations; round 6).  dY is scaled per row chunk inside the
-  // kernel; X is multiplied by ONE power of two per call site (operand of the step: the c-th k_dw_part_h launch of every
-  // step has the same producer), 2^dw_xexp[c], initially 1, under a range guard: a block whose largest scaled |X| leaves
-  // [2^-8, 2^15) raises dw_flag[0] and leaves the largest raw |X| of the call in dw_flag[1 + c].  The step's gradient
-  // reductions then add NOTHING, lb_gns_train_loss_grad re-centres the exponents of the calls that fired and repeats the
-  // step.  A call whose chunks do not fit one window (it fires again right after a re-centring) switches to per-chunk
-  // scaling inside the kernel (dw_xdyn[c]: one more pass over its X slice).
+  // kernel; X is multiplied by ONE power of two per site, 2^dw_xexp[c], initially 1.  A site is the weight matrix whose
+  // gradient the launch produces: slot c belongs to the offset dW - g kept in dw_site[c] (first-seen order; a paired launch
+  // goes by its first matrix), so a launch that a step leaves out (no rows) shifts nobody else's state.  Under a range
+  // guard: a block whose largest scaled |X| leaves [2^-8, 2^15) raises dw_flag[0] and leaves the largest raw |X| of the
+  // site in dw_flag[1 + c].  The step's gradient reductions then add NOTHING, train_loss_grad_guarded re-centres the
+  // exponents of the sites that fired and repeats the step in f16x2.  A site whose chunks do not fit one window (it fires
+  // again right after a re-centring) switches to per-chunk scaling inside the kernel (dw_xdyn[c]: one more pass over its
+  // X slice).
   // MLP depth (round 6: any num_mlp_layers >= 2, models/utils.py:100-115): a block keeps nlin - 1 hidden activations, the
   // first at its `a` pointer, the next ones hs_n / hs_e floats further on (node- / edge-sized blocks)
   int nlin = 2;
   int64_t hs_n = 0, hs_e = 0;
   float* da2 = nullptr;         // second d(hidden) buffer: the middle Linears' backward ping-pongs between da and da2
-  int32_t* dw_flag = nullptr;   // [1 + LB_DW_CALLS] (bit 4 of [0]: k_sender_transpose met an edge without its transpose)
+  int32_t* dw_flag = nullptr;   // [1 + LB_DW_CALLS], behind loss_dev (bit 4 of [0]: k_sender_transpose met an edge without its transpose)
   int32_t dw_fallbacks = 0;     // steps repeated because of the guard
   int32_t sort_fallbacks = 0;   // steps repeated with the radix sort (guard bit 4: an edge without its transpose)
-  int dw_call = 0;              // k_dw_part_h launches of the current step so far
-  std::vector<int8_t> dw_xexp;  // per call site
+  std::vector<int64_t> dw_site;  // slot -> dW - g of the site that owns it (at most LB_DW_CALLS - 1: the last slot is shared)
+  std::vector<int8_t> dw_xexp;   // per slot
   std::vector<uint8_t> dw_xdyn;
   bool cub_sort = false;        // this step's sender-sorted view comes from the radix sort
   float* tmax = nullptr;       // [rows / 16] largest |X| per row tile of the last k_lin32h call that was asked for it
@@ -319,8 +321,8 @@ __global__ void __launch_bounds__(512) k_dw_part_h(const float* __restrict__ X, 
   unsigned ex = (__float_as_uint(m) >> 23) & 0xffu;
   ex = m == 0.f ? 127u : (ex < 1u ? 1u : (ex > 253u ? 253u : ex));
   const float sc = __uint_as_float((254u - ex) << 23), inv = __uint_as_float(ex << 23);
-  // X (activations): multiplied by the call site's power of two 2^xexp (host side, lb_gns_train::dw_xexp) under the range
-  // guard at the end of the kernel; xscale (a call site whose chunks do not fit one window): dY's treatment - a first pass over
+  // X (activations): multiplied by the site's power of two 2^xexp (host side, lb_gns_train::dw_xexp) under the range
+  // guard at the end of the kernel; xscale (a site whose chunks do not fit one window): dY's treatment - a first pass over
   // this block's 128-column slice of the chunk finds the largest |X| (the slice is read again right after), the operand is
   // multiplied by the power of two that puts it into [1, 2) and the partial result by its inverse.
   float scx = __uint_as_float((unsigned)(127 + xexp) << 23), invx = __uint_as_float((unsigned)(127 - xexp) << 23);
@@ -475,7 +477,8 @@ __global__ void __launch_bounds__(512) k_dw_part_h(const float* __restrict__ X, 
       }
   // X range guard: the chunk's largest |X| (this block's 128-column slice).  >= 2^15: the hi half is about to leave fp16
   // (65504; infinities land here too); < 2^-8 and not all zero: every lo half of the slice is a fp16 subnormal, the terms
-  // keep 2^-25 absolute instead of 2^-22 relative precision.  Either way the whole step is redone in exact fp32.
+  // keep 2^-25 absolute instead of 2^-22 relative precision.  Either way the step is repeated with the site's X scale
+  // re-centred, or scaled per chunk, in f16x2 (train_loss_grad_guarded).
   {
     float m = xmax * xkeep;
 #pragma unroll
@@ -515,7 +518,7 @@ __global__ void __launch_bounds__(512) k_dw_part_h(const float* __restrict__ X, 
 __global__ void __launch_bounds__(1024) k_part_reduce(const float* __restrict__ part_base, const lb_red_ent* __restrict__ tab,
                                                       int n_ent, float* __restrict__ grad, const int32_t* __restrict__ skip) {
   __shared__ f32x4 s_red[16][64];
-  if (skip && *skip) return;   // k_dw_part_h's range guard fired: this step adds nothing, the host repeats it in fp32
+  if (skip && *skip) return;   // the step's guard fired: this attempt adds nothing, the host repeats the step
   int lo = 0, hi = n_ent - 1;  // the last descriptor with blk0 <= blockIdx.x
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -1267,7 +1270,9 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
 #define DW_GO(NA, DEPTH) hipLaunchKernelGGL((k_dw_part<NA, DEPTH>), dim3(G), dim3(512), 0, s, X, ldx, K, dY, rows, chunk, part)
   const bool deep = chunk >= 192;
   if (t->f16x2 && K >= 32) {   // (narrower operands - the encoders' raw features - stay on the fp32 kernel)
-    const int c = std::min(t->dw_call++, LB_DW_CALLS - 1);
+    const int64_t site = dW - t->g;   // (no two launches of a step produce the same matrix's gradient: GNS splits w0 by rows)
+    int c = (int)(std::find(t->dw_site.begin(), t->dw_site.end(), site) - t->dw_site.begin());
+    if (c == (int)t->dw_site.size() && c < LB_DW_CALLS - 1) t->dw_site.push_back(site);   // (past the cap: the shared last slot)
     if ((int)t->dw_xexp.size() <= c) { t->dw_xexp.resize(c + 1, 0); t->dw_xdyn.resize(c + 1, 0); }
     hipLaunchKernelGGL(k_dw_part_h, dim3((unsigned)G, (unsigned)((K + 127) / 128), part_b ? 2u : 1u), dim3(512), 0, s, X, ldx, K, dY,
                        rows, chunk, part, tmax, t->dw_flag, t->dw_flag + 1 + c, (int)t->dw_xexp[c], (int)t->dw_xdyn[c], dY_b, part_b);
@@ -1445,55 +1450,65 @@ static int tr_alloc(T** p, size_t n) {
   return lb_alloc(p, n);
 }
 
-static int train_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
-  const int L = t->desc.num_mp_steps;
-  if (BN <= t->cap_n && E <= t->cap_e && t->xnode) return LB_OK;
+// Scratch for BN nodes and E edges - the frame every model shares: the capacity test, the growth rule (edges with head
+// room: the list changes from step to step) and the training core's own buffers.  model(cn, ce, cm) allocates the model's
+// buffers for cn nodes / ce edges (cm: the larger of the two) and sets t->red_cap, the floats of partial-sum slots its
+// backward pass needs.
+template <typename F>
+static int train_ensure(lb_gns_train* t, int64_t BN, int64_t E, F model) {
+  if (BN <= t->cap_n && E <= t->cap_e && t->loss_part) return LB_OK;
   LB_HIP(hipStreamSynchronize(t->eng->stream));
-  const int64_t cn = std::max(BN, t->cap_n), ce = std::max(E + E / 8 + 1024, t->cap_e);
-  const size_t nh = (size_t)(t->nlin - 1);   // hidden activations kept per block
-  t->hs_n = cn * TD;
-  t->hs_e = ce * TD;
-  LB_TRY(tr_alloc(&t->xnode, (size_t)cn * t->kpad));
-  LB_TRY(tr_alloc(&t->a_en, nh * cn * TD));
-  LB_TRY(tr_alloc(&t->z_en, (size_t)cn * TD));
-  LB_TRY(tr_alloc(&t->a_ee, nh * ce * TD));
-  LB_TRY(tr_alloc(&t->z_ee, (size_t)ce * TD));
-  for (int k = 0; k <= L; ++k) {
-    LB_TRY(tr_alloc(&t->nlat[k], (size_t)cn * TD));
-    LB_TRY(tr_alloc(&t->elat[k], (size_t)ce * TD));
-  }
-  for (int k = 0; k < L; ++k) {
-    LB_TRY(tr_alloc(&t->ae[k], nh * ce * TD));
-    LB_TRY(tr_alloc(&t->ze[k], (size_t)ce * TD));
-    LB_TRY(tr_alloc(&t->xn[k], (size_t)cn * 2 * TD));
-    LB_TRY(tr_alloc(&t->an[k], nh * cn * TD));
-    LB_TRY(tr_alloc(&t->zn[k], (size_t)cn * TD));
-  }
-  const int64_t cm = std::max(cn, ce);
-  LB_TRY(tr_alloc(&t->a_d, nh * cn * TD));
-  LB_TRY(tr_alloc(&t->pred, (size_t)cn * 4));
-  LB_TRY(tr_alloc(&t->dn, (size_t)cn * TD));
-  LB_TRY(tr_alloc(&t->de, (size_t)ce * TD));
-  LB_TRY(tr_alloc(&t->dy, (size_t)cm * TD));
-  LB_TRY(tr_alloc(&t->dz, (size_t)cm * TD));
-  LB_TRY(tr_alloc(&t->da, (size_t)cm * TD));
-  if (t->nlin > 2) LB_TRY(tr_alloc(&t->da2, (size_t)cm * TD));
-  LB_TRY(tr_alloc(&t->dx, (size_t)cn * std::max(3 * TD, t->kpad)));
-  LB_TRY(tr_alloc(&t->dagg, (size_t)cn * TD));
-  LB_TRY(tr_alloc(&t->agg, (size_t)cn * TD));
+  const int64_t cn = std::max(BN, t->cap_n), ce = std::max(E + E / 8 + 1024, t->cap_e), cm = std::max(cn, ce);
+  LB_TRY(model(cn, ce, cm));
   LB_TRY(tr_alloc(&t->tmax, (size_t)(cm / 16 + 64)));
-  t->red_cap = red_capacity(t, cn, ce);
   LB_TRY(tr_alloc(&t->dwpart, (size_t)t->red_cap));
   if (!t->red_dev) {
     LB_TRY(lb_alloc(&t->red_dev, (size_t)LB_RED_MAX));
     LB_HIP(hipHostMalloc((void**)&t->red_host, sizeof(lb_red_ent) * (LB_RED_MAX + 1)));   // (+ the step's status words)
   }
-  LB_TRY(tr_alloc(&t->proj, (size_t)cn * 2 * TD));
   LB_TRY(tr_alloc(&t->node_w, (size_t)cn));
   LB_TRY(tr_alloc(&t->loss_part, (size_t)(cn / 64 + 8)));
   t->cap_n = cn;
   t->cap_e = ce;
   return LB_OK;
+}
+static int gns_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
+  return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t cm) -> int {
+    const int L = t->desc.num_mp_steps;
+    const size_t nh = (size_t)(t->nlin - 1);   // hidden activations kept per block
+    t->hs_n = cn * TD;
+    t->hs_e = ce * TD;
+    LB_TRY(tr_alloc(&t->xnode, (size_t)cn * t->kpad));
+    LB_TRY(tr_alloc(&t->a_en, nh * cn * TD));
+    LB_TRY(tr_alloc(&t->z_en, (size_t)cn * TD));
+    LB_TRY(tr_alloc(&t->a_ee, nh * ce * TD));
+    LB_TRY(tr_alloc(&t->z_ee, (size_t)ce * TD));
+    for (int k = 0; k <= L; ++k) {
+      LB_TRY(tr_alloc(&t->nlat[k], (size_t)cn * TD));
+      LB_TRY(tr_alloc(&t->elat[k], (size_t)ce * TD));
+    }
+    for (int k = 0; k < L; ++k) {
+      LB_TRY(tr_alloc(&t->ae[k], nh * ce * TD));
+      LB_TRY(tr_alloc(&t->ze[k], (size_t)ce * TD));
+      LB_TRY(tr_alloc(&t->xn[k], (size_t)cn * 2 * TD));
+      LB_TRY(tr_alloc(&t->an[k], nh * cn * TD));
+      LB_TRY(tr_alloc(&t->zn[k], (size_t)cn * TD));
+    }
+    LB_TRY(tr_alloc(&t->a_d, nh * cn * TD));
+    LB_TRY(tr_alloc(&t->pred, (size_t)cn * 4));
+    LB_TRY(tr_alloc(&t->dn, (size_t)cn * TD));
+    LB_TRY(tr_alloc(&t->de, (size_t)ce * TD));
+    LB_TRY(tr_alloc(&t->dy, (size_t)cm * TD));
+    LB_TRY(tr_alloc(&t->dz, (size_t)cm * TD));
+    LB_TRY(tr_alloc(&t->da, (size_t)cm * TD));
+    if (t->nlin > 2) LB_TRY(tr_alloc(&t->da2, (size_t)cm * TD));
+    LB_TRY(tr_alloc(&t->dx, (size_t)cn * std::max(3 * TD, t->kpad)));
+    LB_TRY(tr_alloc(&t->dagg, (size_t)cn * TD));
+    LB_TRY(tr_alloc(&t->agg, (size_t)cn * TD));
+    LB_TRY(tr_alloc(&t->proj, (size_t)cn * 2 * TD));
+    t->red_cap = red_capacity(t, cn, ce);
+    return LB_OK;
+  });
 }
 
 // _mse of trainer.py:35-60 on the device: loss (into t->loss_dev) and d loss / d pred (BN x dim) for the whole batch
@@ -1678,6 +1693,30 @@ int lb_gns_train_padded_map(const lb_gns_desc* d, std::vector<int64_t>* cmap, in
   return LB_OK;
 }
 
+// The rest of a handle's construction, once its create has filled the layout (n_floats, n_compact, cmap): the four blobs,
+// the small buffers of every step, and the caller's weights (`what`, for the message) scattered through cmap into the device
+// layout; gradients and moments start at zero.  The caller destroys the handle on failure.
+static int train_handle_init(lb_gns_train* t, const char* what, const float* w, int64_t n_floats) {
+  const int64_t o = t->n_floats, oc = t->n_compact;
+  if (oc != n_floats) return lb_fail(LB_ERR_ARG, "%s has %lld floats, expected %lld", what, (long long)n_floats, (long long)oc);
+  for (float** p : {&t->w, &t->g, &t->m, &t->v}) LB_TRY(lb_alloc(p, (size_t)o));
+  // the loss and the guard words in ONE allocation, [loss | dw_flag]: one copy brings the loss and dw_flag[0] to the host
+  LB_TRY(lb_alloc(&t->loss_dev, (size_t)(1 + (1 + LB_DW_CALLS + 1) / 2)));
+  t->dw_flag = reinterpret_cast<int32_t*>(t->loss_dev + 1);
+  LB_HIP(hipMemset(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS)));
+  LB_TRY(lb_alloc(&t->cnt_dev, (size_t)t->eng->g.B));
+  std::vector<float> padded;
+  const float* src = w;
+  if (!t->cmap.empty()) {
+    padded.assign((size_t)o, 0.f);
+    for (int64_t i = 0; i < oc; ++i) padded[(size_t)t->cmap[(size_t)i]] = w[i];
+    src = padded.data();
+  }
+  LB_HIP(hipMemcpy(t->w, src, sizeof(float) * o, hipMemcpyHostToDevice));
+  for (float* p : {t->g, t->m, t->v}) LB_HIP(hipMemset(p, 0, sizeof(float) * o));
+  return LB_OK;
+}
+
 extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats,
                                    lb_gns_train** out) {
   if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
@@ -1689,35 +1728,11 @@ extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const flo
   t->eng = e;
   gns_train_layout(t, d);
   const int L = d->num_mp_steps;
-  const int64_t o = t->n_floats, oc = t->n_compact;
-  if (oc != n_floats) {
-    delete t;
-    return lb_fail(LB_ERR_ARG, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)oc);
-  }
   t->nlat.assign(L + 1, nullptr);
   t->elat.assign(L + 1, nullptr);
   t->ae.assign(L, nullptr); t->ze.assign(L, nullptr);
   t->xn.assign(L, nullptr); t->an.assign(L, nullptr); t->zn.assign(L, nullptr);
-  int rc = LB_OK;
-  for (float** p : {&t->w, &t->g, &t->m, &t->v})
-    if (!rc) rc = lb_alloc(p, (size_t)o);
-  if (!rc) rc = lb_alloc(&t->loss_dev, 1);
-  if (!rc) rc = lb_alloc(&t->dw_flag, (size_t)(1 + LB_DW_CALLS));
-  if (!rc && hipMemset(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS)) != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemset");
-  if (!rc) rc = lb_alloc(&t->cnt_dev, (size_t)e->g.B);
-  if (!rc) {
-    std::vector<float> padded;
-    const float* src = w;
-    if (!t->cmap.empty()) {
-      padded.assign((size_t)o, 0.f);
-      for (int64_t i = 0; i < oc; ++i) padded[(size_t)t->cmap[(size_t)i]] = w[i];
-      src = padded.data();
-    }
-    if (hipMemcpy(t->w, src, sizeof(float) * o, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(t->g, 0, sizeof(float) * o) != hipSuccess || hipMemset(t->m, 0, sizeof(float) * o) != hipSuccess ||
-        hipMemset(t->v, 0, sizeof(float) * o) != hipSuccess)
-      rc = lb_fail(LB_ERR_HIP, "weight upload failed");
-  }
+  const int rc = train_handle_init(t, "weight blob", w, n_floats);
   if (rc) {
     lb_gns_train_destroy(t);
     return rc;
@@ -1734,7 +1749,7 @@ extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   egt_free(t);
   std::vector<void*> bufs = {t->w, t->g, t->m, t->v, t->xnode, t->a_en, t->z_en, t->a_ee, t->z_ee, t->a_d, t->pred,
                              t->dn, t->de, t->dy, t->dz, t->da, t->dx, t->dagg, t->agg, t->dwpart, t->red_dev, t->proj, t->node_w,
-                             t->loss_dev, t->dw_flag, t->da2, t->loss_part, t->cnt_dev, t->snd_key, t->snd_perm, t->iota, t->snd_ptr, t->sort_tmp,
+                             t->loss_dev, t->da2, t->loss_part, t->cnt_dev, t->snd_key, t->snd_perm, t->iota, t->snd_ptr, t->sort_tmp,
                              t->wpack, t->pack_dev, t->pack_dev_h, t->wsc, t->tmax};
   for (auto* v : {&t->nlat, &t->elat, &t->ae, &t->ze, &t->xn, &t->an, &t->zn})
     for (float* p : *v) bufs.push_back(p);
@@ -1744,38 +1759,26 @@ extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   delete t;
 }
 
-// value_and_grad of _mse, summed over the batch (trainer.py:63-89), on the engine's CURRENT window / neighbor list.
-// target_dev: (B*N, dim) fp32 normalised accelerations.  Gradients ACCUMULATE into the gradient blob (zero it with
-// lb_gns_train_zero_grad); *loss_out = mean over the batch of the per-trajectory losses (host-synchronous).
-static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                    float* pred_out_dev);
-static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                      float* pred_out_dev);
 // One training step's loss + gradients with the step's guard flag around it: if a k_dw_part_h block saw activations outside
 // [2^-8, 2^15) (bits 1 | 2), or k_sender_transpose an edge without its transpose (bit 4), the reductions have added nothing
-// (k_part_reduce / k_embed_grad read the flag) and the step runs again - with X scaled per chunk from now on, or with
-// the radix sort for this step.
-// the step's loss and guard flag come back through pinned words behind the descriptor table (ONE stream synchronisation per
+// (k_part_reduce / k_embed_grad read the flag) and the step runs again, still in f16x2 - with the X scale of the sites that
+// fired re-centred (or, for a site that fires again, taken per chunk from now on), or with the radix sort for this step.
+// The step's loss and guard flag come back through pinned words behind the descriptor table (ONE stream synchronisation per
 // step: round 5 took the loss and the flag with a pageable copy each)
 static_assert(sizeof(lb_red_ent) >= sizeof(double) + sizeof(int32_t), "status words live in one spare descriptor");
 static double* status_loss(lb_gns_train* t) { return reinterpret_cast<double*>(t->red_host + LB_RED_MAX); }
 static int32_t* status_flag(lb_gns_train* t) { return reinterpret_cast<int32_t*>(status_loss(t) + 1); }
-static int train_loss_grad_guarded(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                   float* pred_out_dev) {
-  auto once = [&]() {
-    return t->sg ? segnn_train_loss_grad_once(t, target_dev, loss_weight, loss_out, pred_out_dev)
-                 : gns_train_loss_grad_once(t, target_dev, loss_weight, loss_out, pred_out_dev);
-  };
+// once(): the model's step between train_step_begin and train_step_end
+template <typename F>
+static int train_loss_grad_guarded(lb_gns_train* t, double* loss_out, F once) {
   hipStream_t s = t->eng->stream;
   int rc = LB_OK;
   std::vector<int32_t> slots;
   for (int attempt = 0; attempt < 4; ++attempt) {
     LB_HIP(hipMemsetAsync(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS), s));
-    t->dw_call = 0;
     rc = once();
     if (rc) break;
-    LB_HIP(hipMemcpyAsync(status_flag(t), t->dw_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    LB_HIP(hipStreamSynchronize(s));   // (also delivers the loss the attempt left in status_loss)
+    LB_HIP(hipStreamSynchronize(s));   // (delivers the loss and the flag: train_step_end's copy)
     const int32_t flag = *status_flag(t);
     if (!flag) break;
     // the reductions of this attempt added nothing (k_part_reduce / k_embed_grad saw the flag): repeat with what it asks for
@@ -1785,13 +1788,13 @@ static int train_loss_grad_guarded(lb_gns_train* t, const float* target_dev, flo
       t->cub_sort = true;
       ++t->sort_fallbacks;
     }
-    if (flag & 3) {   // re-centre the X exponent of every call site that fired: largest |X| -> [2^3, 2^4)
-      const int n = std::min(t->dw_call, LB_DW_CALLS);
+    if (flag & 3) {   // re-centre the X exponent of every site that fired: largest |X| -> [2^3, 2^4)
+      const int n = (int)t->dw_xexp.size();   // (the slots in use, <= LB_DW_CALLS)
       slots.assign((size_t)n, 0);
       LB_HIP(hipMemcpy(slots.data(), t->dw_flag + 1, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
       for (int c = 0; c < n; ++c) {
         if (!slots[c]) continue;
-        const int ex = (int)(((uint32_t)slots[c] >> 23) & 0xffu);   // biased exponent of the call's largest raw |X|
+        const int ex = (int)(((uint32_t)slots[c] >> 23) & 0xffu);   // biased exponent of the site's largest raw |X|
         const int want = std::max(-100, std::min(100, 130 - ex));
         if (ex >= 255 || t->dw_xdyn[c]) continue;                    // (non-finite activations: non-finite gradients in any arithmetic)
         if (attempt > 0 || t->dw_xexp[c] == want) t->dw_xdyn[c] = 1;   // fired again after a re-centring: its chunks need their own scales
@@ -1807,27 +1810,42 @@ static int train_loss_grad_guarded(lb_gns_train* t, const float* target_dev, flo
 extern "C" int32_t lb_gns_train_math_fallbacks(lb_gns_train* t) { return t ? t->dw_fallbacks : -1; }
 extern "C" int32_t lb_gns_train_sort_fallbacks(lb_gns_train* t) { return t ? t->sort_fallbacks : -1; }
 
-extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                      float* pred_out_dev) {
-  if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
-  return train_loss_grad_guarded(t, target_dev, loss_weight, loss_out, pred_out_dev);
-}
-static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                    float* pred_out_dev) {
+// The frame of a step, around every model's forward and backward.  Begin (`entry`: the caller's name, for the message): the
+// neighbor list is there and did not overflow, its edge count (ONE host synchronisation), the Linear operands in fragment
+// order from the current weights, an empty reduction table.  The model's *_ensure comes next.
+static int train_step_begin(lb_gns_train* t, const char* entry, int64_t* E, int64_t* BN) {
   lb_engine* e = t->eng;
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_gns_train_loss_grad before lb_nl_allocate");
-  hipStream_t s = e->stream;
-  LB_HIP(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(lb_ctrl), hipMemcpyDeviceToHost, s));
-  LB_HIP(hipStreamSynchronize(s));
+  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "%s before lb_nl_allocate", entry);
+  LB_HIP(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(lb_ctrl), hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipStreamSynchronize(e->stream));
   if (e->ctrl_host->overflow_step >= 0) return lb_fail(LB_ERR_STATE, "neighbor list overflowed: re-allocate first");
-  const int64_t E = e->ctrl_host->n_edges_total, BN = e->BN;
-  const int L = t->desc.num_mp_steps, dim = t->desc.out_dim;
-  LB_TRY(train_ensure(t, BN, E));
-  pack_all(t);  // the Linear operands in fragment order, from the current weights
+  *E = e->ctrl_host->n_edges_total;
+  *BN = e->BN;
+  pack_all(t);
   t->red_tab.clear();
   t->red_off = 0;
   t->red_blocks = 0;
+  return LB_OK;
+}
+// End: every weight / bias / LayerNorm gradient, partials -> gradient blob in one launch; the loss and the guard flag behind
+// it on their way to the pinned status words (train_loss_grad_guarded synchronises and reads them)
+static int train_step_end(lb_gns_train* t) {
+  LB_TRY(red_flush(t));
+  LB_HIP(hipGetLastError());
+  LB_HIP(hipMemcpyAsync(status_loss(t), t->loss_dev, sizeof(double) + sizeof(int32_t), hipMemcpyDeviceToHost, t->eng->stream));
+  return LB_OK;
+}
+
+// value_and_grad of _mse, summed over the batch (trainer.py:63-89), on the engine's CURRENT window / neighbor list.
+// target_dev: (B*N, dim) fp32 normalised accelerations.  Gradients ACCUMULATE into the gradient blob (zero it with
+// lb_gns_train_zero_grad); *loss_out = mean over the batch of the per-trajectory losses (host-synchronous).
+static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
+  lb_engine* e = t->eng;
+  hipStream_t s = e->stream;
+  int64_t E = 0, BN = 0;
+  LB_TRY(train_step_begin(t, "lb_gns_train_loss_grad", &E, &BN));
+  const int L = t->desc.num_mp_steps, dim = t->desc.out_dim;
+  LB_TRY(gns_ensure(t, BN, E));
   const bool has_emb = t->desc.num_particle_types > 1;
   const int emb = has_emb ? t->desc.embedding_size : 0;
   // ---- features (engine kernels): node row [features | embedding | 0-pad], edge features from the neighbor build
@@ -1867,11 +1885,14 @@ static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, fl
   if (has_emb)
     hipLaunchKernelGGL(k_embed_grad, dim3(t->desc.num_particle_types), dim3(1024), 0, s, t->dx, t->kpad, t->desc.node_in, emb,
                        e->ptype, t->desc.num_particle_types, BN, t->g + t->off_embed, t->dw_flag);
-  LB_TRY(red_flush(t));  // every weight / bias / LayerNorm gradient: partials -> gradient blob, one launch
-  LB_HIP(hipGetLastError());
-  if (loss_out)   // (train_loss_grad_guarded synchronises and hands it over)
-    LB_HIP(hipMemcpyAsync(status_loss(t), t->loss_dev, sizeof(double), hipMemcpyDeviceToHost, s));
-  return LB_OK;
+  return train_step_end(t);
+}
+extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
+                                      float* pred_out_dev) {
+  if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
+  if (t->sg) return lb_segnn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
+  return train_loss_grad_guarded(t, loss_out, [&] { return gns_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
 }
 
 extern "C" int lb_gns_train_zero_grad(lb_gns_train* t) {

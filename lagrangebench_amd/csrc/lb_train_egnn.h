@@ -39,7 +39,6 @@ struct lb_egt {
   int node_in = 0, n_attr = 0;
   int64_t w_emb = 0, b_emb = 0;
   std::vector<lb_egt_layer> layers;
-  int64_t cap_n = 0, cap_e = 0;
   // taps: h^l (L+1 x BN x 128), x^l (L+1 x BN x dim)
   float *tap_h = nullptr, *tap_x = nullptr;
   // node scratch
@@ -390,41 +389,32 @@ static void egt_free(lb_gns_train* t) {
 }
 
 static int egt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
-  lb_egt* g = t->eg;
-  if (BN <= g->cap_n && E <= g->cap_e && g->z0) return LB_OK;
-  LB_HIP(hipStreamSynchronize(t->eng->stream));
-  const int L = g->desc.num_mp_steps, dim = t->eng->g.dim;
-  const int64_t cn = std::max(BN, g->cap_n), ce = std::max<int64_t>(E + E / 8 + 1024, g->cap_e);
-  const size_t W = EGT_W;
-  LB_TRY(tr_alloc(&g->tap_h, (size_t)(L + 1) * cn * W));
-  LB_TRY(tr_alloc(&g->tap_x, (size_t)(L + 1) * cn * dim));
-  LB_TRY(tr_alloc(&g->xin, (size_t)cn * EGT_XIN));
-  LB_TRY(tr_alloc(&g->attr2, (size_t)cn * 2));
-  LB_TRY(tr_alloc(&g->xn, (size_t)cn * 2 * W));
-  LB_TRY(tr_alloc(&g->dpsi, (size_t)cn));
-  LB_TRY(tr_alloc(&g->dx, (size_t)cn * 4));
-  for (float** p : {&g->ps, &g->pr, &g->zn0, &g->u, &g->zv0, &g->vv, &g->dh, &g->dzn, &g->du, &g->dagg})
-    LB_TRY(tr_alloc(p, (size_t)cn * W));
-  LB_TRY(tr_alloc(&g->cdr, (size_t)ce * 4));
-  LB_TRY(tr_alloc(&g->dcd, (size_t)ce * 4));
-  LB_TRY(tr_alloc(&g->ea2, (size_t)ce * 2));
-  LB_TRY(tr_alloc(&g->phi, (size_t)ce));
-  LB_TRY(tr_alloc(&g->dphi, (size_t)ce));
-  for (float** p : {&g->z0, &g->a, &g->z1, &g->m, &g->zx0, &g->q, &g->de1, &g->de2}) LB_TRY(tr_alloc(p, (size_t)ce * W));
-  // partial-sum slots of the step's reductions (mirrors the backward below)
-  auto slot = [](int64_t rows, int K) { return (dw_groups_max(std::max<int64_t>(rows, 1)) * (K + 1) * 128 + 63) / 64 * 64; };
-  auto narrow = [](int64_t rows) { return (std::min<int64_t>(DW_MAX_G, (rows + 63) / 64 + 1) * 128 + 63) / 64 * 64; };
-  t->red_cap = (int64_t)L * (4 * slot(cn, 128) + slot(cn, 256) + slot(cn, 1) + 2 * slot(ce, 128) + slot(ce, 2) + narrow(cn) +
-                             narrow(ce)) + slot(cn, EGT_XIN) + 4096;
-  LB_TRY(tr_alloc(&t->dwpart, (size_t)t->red_cap));
-  if (!t->red_dev) {
-    LB_TRY(lb_alloc(&t->red_dev, (size_t)LB_RED_MAX));
-    LB_HIP(hipHostMalloc((void**)&t->red_host, sizeof(lb_red_ent) * (LB_RED_MAX + 1)));   // (+ the step's status words)
-  }
-  LB_TRY(tr_alloc(&t->loss_part, (size_t)(cn / 64 + 8)));
-  g->cap_n = cn;
-  g->cap_e = ce;
-  return LB_OK;
+  return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t) -> int {
+    lb_egt* g = t->eg;
+    const int L = g->desc.num_mp_steps, dim = t->eng->g.dim;
+    const size_t W = EGT_W;
+    LB_TRY(tr_alloc(&g->tap_h, (size_t)(L + 1) * cn * W));
+    LB_TRY(tr_alloc(&g->tap_x, (size_t)(L + 1) * cn * dim));
+    LB_TRY(tr_alloc(&g->xin, (size_t)cn * EGT_XIN));
+    LB_TRY(tr_alloc(&g->attr2, (size_t)cn * 2));
+    LB_TRY(tr_alloc(&g->xn, (size_t)cn * 2 * W));
+    LB_TRY(tr_alloc(&g->dpsi, (size_t)cn));
+    LB_TRY(tr_alloc(&g->dx, (size_t)cn * 4));
+    for (float** p : {&g->ps, &g->pr, &g->zn0, &g->u, &g->zv0, &g->vv, &g->dh, &g->dzn, &g->du, &g->dagg})
+      LB_TRY(tr_alloc(p, (size_t)cn * W));
+    LB_TRY(tr_alloc(&g->cdr, (size_t)ce * 4));
+    LB_TRY(tr_alloc(&g->dcd, (size_t)ce * 4));
+    LB_TRY(tr_alloc(&g->ea2, (size_t)ce * 2));
+    LB_TRY(tr_alloc(&g->phi, (size_t)ce));
+    LB_TRY(tr_alloc(&g->dphi, (size_t)ce));
+    for (float** p : {&g->z0, &g->a, &g->z1, &g->m, &g->zx0, &g->q, &g->de1, &g->de2}) LB_TRY(tr_alloc(p, (size_t)ce * W));
+    // partial-sum slots of the step's reductions (mirrors the backward below)
+    auto slot = [](int64_t rows, int K) { return (dw_groups_max(std::max<int64_t>(rows, 1)) * (K + 1) * 128 + 63) / 64 * 64; };
+    auto narrow = [](int64_t rows) { return (std::min<int64_t>(DW_MAX_G, (rows + 63) / 64 + 1) * 128 + 63) / 64 * 64; };
+    t->red_cap = (int64_t)L * (4 * slot(cn, 128) + slot(cn, 256) + slot(cn, 1) + 2 * slot(ce, 128) + slot(ce, 2) + narrow(cn) +
+                               narrow(ce)) + slot(cn, EGT_XIN) + 4096;
+    return LB_OK;
+  });
 }
 
 // dW += X^T dY (+ db), refusals reported as LB_ERR_STATE (red_slot / dw_acc said why); nothing to add for zero rows
@@ -486,32 +476,9 @@ extern "C" int lb_egnn_train_create(lb_engine* e, const lb_egnn_desc* d, const f
     l.wv1 = mat(H, 1, same); o += W;
     g->layers.push_back(l);
   }
-  if (oc != n_floats) {
-    lb_gns_train_destroy(t);
-    return lb_fail(LB_ERR_ARG, "egnn weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)oc);
-  }
   t->n_floats = o;
   t->n_compact = oc;
-  int rc = LB_OK;
-  for (float** p : {&t->w, &t->g, &t->m, &t->v})
-    if (!rc) rc = lb_alloc(p, (size_t)o);
-  if (!rc) rc = lb_alloc(&t->loss_dev, 1);
-  if (!rc) rc = lb_alloc(&t->dw_flag, (size_t)(1 + LB_DW_CALLS));
-  if (!rc && hipMemset(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS)) != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemset");
-  if (!rc) rc = lb_alloc(&t->cnt_dev, (size_t)e->g.B);
-  if (!rc) {
-    std::vector<float> padded;
-    const float* src = w;
-    if (!t->cmap.empty()) {
-      padded.assign((size_t)o, 0.f);
-      for (int64_t i = 0; i < oc; ++i) padded[(size_t)t->cmap[(size_t)i]] = w[i];
-      src = padded.data();
-    }
-    if (hipMemcpy(t->w, src, sizeof(float) * o, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(t->g, 0, sizeof(float) * o) != hipSuccess || hipMemset(t->m, 0, sizeof(float) * o) != hipSuccess ||
-        hipMemset(t->v, 0, sizeof(float) * o) != hipSuccess)
-      rc = lb_fail(LB_ERR_HIP, "weight upload failed");
-  }
+  int rc = train_handle_init(t, "egnn weight blob", w, n_floats);
   if (!rc) {
     lb_egnn_desc vd = *d;
     vd.hidden = W;
@@ -525,7 +492,6 @@ extern "C" int lb_egnn_train_create(lb_engine* e, const lb_egnn_desc* d, const f
   return LB_OK;
 }
 
-// value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h)
 // The inference view of the handle (lbk_egnn_view_create on t->w): lb_egnn_forward / lb_egnn_rollout on it run on the CURRENT
 // weights.  Borrowed: it lives and dies with t.
 extern "C" int lb_egnn_train_model(lb_gns_train* t, lb_egnn** out) {
@@ -535,19 +501,13 @@ extern "C" int lb_egnn_train_model(lb_gns_train* t, lb_egnn** out) {
   return LB_OK;
 }
 
-extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
-                                       float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev) {
-  if (!t || !t->eg) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");
-  if ((w_pos != 0.f && !tgt_pos) || (w_vel != 0.f && !tgt_vel) || (w_acc != 0.f && !tgt_acc))
-    return lb_fail(LB_ERR_ARG, "egnn training: a target with a non-zero loss weight is null");
+static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
+                                     float w_pos, float w_vel, float w_acc, float* pred_pos_out_dev) {
   lb_engine* e = t->eng;
   lb_egt* g = t->eg;
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_egnn_train_loss_grad before lb_nl_allocate");
   hipStream_t s = e->stream;
-  LB_HIP(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(lb_ctrl), hipMemcpyDeviceToHost, s));
-  LB_HIP(hipStreamSynchronize(s));
-  if (e->ctrl_host->overflow_step >= 0) return lb_fail(LB_ERR_STATE, "neighbor list overflowed: re-allocate first");
-  const int64_t E = e->ctrl_host->n_edges_total, BN = e->BN;
+  int64_t E = 0, BN = 0;
+  LB_TRY(train_step_begin(t, "lb_egnn_train_loss_grad", &E, &BN));
   const int L = g->desc.num_mp_steps, dim = e->g.dim, W = EGT_W;
   LB_TRY(egt_ensure(t, BN, E));
   // ---- forward: the inference kernels on the current weights, taps on (returns after checking every edge's transpose:
@@ -557,12 +517,6 @@ extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, c
   LB_TRY(lbk_egnn_train_forward(e, g->view, &st));
   const float* xl = g->tap_x + (size_t)L * BN * dim;
   if (pred_pos_out_dev) LB_HIP(hipMemcpyAsync(pred_pos_out_dev, xl, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
-  pack_all(t);
-  t->red_tab.clear();
-  t->red_off = 0;
-  t->red_blocks = 0;
-  LB_HIP(hipMemsetAsync(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS), s));
-  t->dw_call = 0;
   // ---- loss and d loss / d x^L
   LB_HIP(hipMemsetAsync(t->cnt_dev, 0, sizeof(int32_t) * e->g.B, s));
   LB_HIP(hipMemsetAsync(t->loss_dev, 0, sizeof(double), s));
@@ -654,10 +608,18 @@ extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, c
   }
   // embedding: h^0 = xin W_emb + b_emb
   LB_TRY(egt_dw(t, BN, g->node_in, g->xin, EGT_XIN, g->dh, G + g->w_emb, G + g->b_emb));
-  LB_TRY(red_flush(t));
-  LB_HIP(hipGetLastError());
-  LB_HIP(hipMemcpyAsync(status_loss(t), t->loss_dev, sizeof(double), hipMemcpyDeviceToHost, s));
-  LB_HIP(hipStreamSynchronize(s));
-  if (loss_out) *loss_out = *status_loss(t);
-  return LB_OK;
+  return train_step_end(t);
+}
+// value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h)
+extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
+                                       float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev) {
+  if (!t || !t->eg) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");
+  if ((w_pos != 0.f && !tgt_pos) || (w_vel != 0.f && !tgt_vel) || (w_acc != 0.f && !tgt_acc))
+    return lb_fail(LB_ERR_ARG, "egnn training: a target with a non-zero loss weight is null");
+  // The guard never fires here: the handle has f16x2 off, so no k_dw_part_h launch can raise bits 1 | 2, and the step does
+  // not build a sender view (its sender sums go through rev[] and the orphans), so k_sender_transpose never raises bit 4.
+  // The loop is then one attempt and its synchronisation the step's last.
+  return train_loss_grad_guarded(t, loss_out, [&] {
+    return egnn_train_loss_grad_once(t, tgt_pos, tgt_vel, tgt_acc, w_pos, w_vel, w_acc, pred_pos_out_dev);
+  });
 }

@@ -56,7 +56,6 @@ struct lb_sgt {
   lb_segnn_desc desc;
   int node_ns, node_nv, node_ns4, node_nv4, node_stride;
   std::vector<lb_sgt_block> blocks;  // call order: embedding; per layer message_0.., update_0..; readout_0..; output
-  int64_t cap_n = 0, cap_e = 0;
   float *xnode = nullptr, *nodesv = nullptr, *nattr = nullptr, *eattr = nullptr, *msgsv = nullptr;
   float *f = nullptr, *agg = nullptr, *tn[2] = {nullptr, nullptr}, *te[2] = {nullptr, nullptr};  // SV rows (BN / E x 128)
   float *df = nullptr, *dagg = nullptr, *dtn[2] = {nullptr, nullptr}, *dte[2] = {nullptr, nullptr};
@@ -263,40 +262,29 @@ static void sgt_free(lb_gns_train* t) {
 }
 
 static int sgt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
-  lb_sgt* g = t->sg;
-  if (BN <= g->cap_n && E <= g->cap_e && g->f) return LB_OK;
-  LB_HIP(hipStreamSynchronize(t->eng->stream));
-  const int64_t cn = std::max(BN, g->cap_n), ce = std::max<int64_t>(E + E / 8 + 1024, g->cap_e), cm = std::max(cn, ce);
-  LB_TRY(tr_alloc(&g->xnode, (size_t)cn * 32));
-  LB_TRY(tr_alloc(&g->nodesv, (size_t)cn * g->node_stride));
-  LB_TRY(tr_alloc(&g->nattr, (size_t)cn * 4));
-  LB_TRY(tr_alloc(&g->eattr, (size_t)ce * 4));
-  LB_TRY(tr_alloc(&g->msgsv, (size_t)ce * 16));
-  for (float** p : {&g->f, &g->agg, &g->tn[0], &g->tn[1], &g->df, &g->dagg, &g->dtn[0], &g->dtn[1]}) LB_TRY(tr_alloc(p, (size_t)cn * 128));
-  for (float** p : {&g->te[0], &g->te[1], &g->dte[0], &g->dte[1], &g->dFs, &g->dFr}) LB_TRY(tr_alloc(p, (size_t)ce * 128));
-  LB_TRY(tr_alloc(&g->draw, (size_t)4 * cm * 128));
-  LB_TRY(tr_alloc(&g->dZ, (size_t)4 * cm * 256));
-  int64_t red = 4096;
-  for (lb_sgt_block& b : g->blocks) {
-    const int64_t R = b.edge ? ce : cn;
-    LB_TRY(tr_alloc(&b.Z, (size_t)4 * R * b.Kp));
-    LB_TRY(tr_alloc(&b.raw, (size_t)4 * R * 128));
-    red += (dw_groups_max(4 * R) * (b.Kp + 1) * 128 + 63) / 64 * 64 + (4 * R + 127) / 128 * 128 + 64;
-  }
-  // the training core's scratch (train_ensure's part that both models need)
-  t->red_cap = red;
-  LB_TRY(tr_alloc(&t->dwpart, (size_t)t->red_cap));
-  if (!t->red_dev) {
-    LB_TRY(lb_alloc(&t->red_dev, (size_t)LB_RED_MAX));
-    LB_HIP(hipHostMalloc((void**)&t->red_host, sizeof(lb_red_ent) * (LB_RED_MAX + 1)));   // (+ the step's status words)
-  }
-  LB_TRY(tr_alloc(&t->pred, (size_t)cn * 4));
-  LB_TRY(tr_alloc(&t->dy, (size_t)cn * 4));
-  LB_TRY(tr_alloc(&t->node_w, (size_t)cn));
-  LB_TRY(tr_alloc(&t->loss_part, (size_t)(cn / 64 + 8)));
-  g->cap_n = cn;
-  g->cap_e = ce;
-  return LB_OK;
+  return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t cm) -> int {
+    lb_sgt* g = t->sg;
+    LB_TRY(tr_alloc(&g->xnode, (size_t)cn * 32));
+    LB_TRY(tr_alloc(&g->nodesv, (size_t)cn * g->node_stride));
+    LB_TRY(tr_alloc(&g->nattr, (size_t)cn * 4));
+    LB_TRY(tr_alloc(&g->eattr, (size_t)ce * 4));
+    LB_TRY(tr_alloc(&g->msgsv, (size_t)ce * 16));
+    for (float** p : {&g->f, &g->agg, &g->tn[0], &g->tn[1], &g->df, &g->dagg, &g->dtn[0], &g->dtn[1]}) LB_TRY(tr_alloc(p, (size_t)cn * 128));
+    for (float** p : {&g->te[0], &g->te[1], &g->dte[0], &g->dte[1], &g->dFs, &g->dFr}) LB_TRY(tr_alloc(p, (size_t)ce * 128));
+    LB_TRY(tr_alloc(&g->draw, (size_t)4 * cm * 128));
+    LB_TRY(tr_alloc(&g->dZ, (size_t)4 * cm * 256));
+    int64_t red = 4096;
+    for (lb_sgt_block& b : g->blocks) {
+      const int64_t R = b.edge ? ce : cn;
+      LB_TRY(tr_alloc(&b.Z, (size_t)4 * R * b.Kp));
+      LB_TRY(tr_alloc(&b.raw, (size_t)4 * R * 128));
+      red += (dw_groups_max(4 * R) * (b.Kp + 1) * 128 + 63) / 64 * 64 + (4 * R + 127) / 128 * 128 + 64;
+    }
+    t->red_cap = red;
+    LB_TRY(tr_alloc(&t->pred, (size_t)cn * 4));
+    LB_TRY(tr_alloc(&t->dy, (size_t)cn * 4));
+    return LB_OK;
+  });
 }
 
 // one block forward: operands -> Z -> raw = Z W -> out
@@ -420,10 +408,6 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
   }
   for (int i = 0; i < B; ++i) add({{C, C}}, 2 * C, C, SGT_GATE, false);
   add({{C, C}}, 0, 1, SGT_OUTVEC, false);
-  if (oc != n_floats) {
-    lb_gns_train_destroy(t);
-    return lb_fail(LB_ERR_ARG, "segnn weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)oc);
-  }
   for (const lb_sgt_block& b : g->blocks)
     if (b.K > 256) {
       lb_gns_train_destroy(t);
@@ -431,21 +415,7 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
     }
   t->n_floats = o;
   t->n_compact = oc;
-  int rc = LB_OK;
-  for (float** p : {&t->w, &t->g, &t->m, &t->v})
-    if (!rc) rc = lb_alloc(p, (size_t)o);
-  if (!rc) rc = lb_alloc(&t->loss_dev, 1);
-  if (!rc) rc = lb_alloc(&t->dw_flag, (size_t)(1 + LB_DW_CALLS));
-  if (!rc && hipMemset(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS)) != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemset");
-  if (!rc) rc = lb_alloc(&t->cnt_dev, (size_t)e->g.B);
-  if (!rc) {
-    std::vector<float> padded((size_t)o, 0.f);
-    for (int64_t i = 0; i < oc; ++i) padded[(size_t)t->cmap[(size_t)i]] = w[i];
-    if (hipMemcpy(t->w, padded.data(), sizeof(float) * o, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemset(t->g, 0, sizeof(float) * o) != hipSuccess || hipMemset(t->m, 0, sizeof(float) * o) != hipSuccess ||
-        hipMemset(t->v, 0, sizeof(float) * o) != hipSuccess)
-      rc = lb_fail(LB_ERR_HIP, "weight upload failed");
-  }
+  const int rc = train_handle_init(t, "segnn weight blob", w, n_floats);
   if (rc) {
     lb_gns_train_destroy(t);
     return rc;
@@ -454,30 +424,16 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
   return LB_OK;
 }
 
-// value_and_grad of _mse for SEGNN on the engine's CURRENT window / neighbor list: same contract as lb_gns_train_loss_grad
-extern "C" int lb_segnn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                        float* pred_out_dev) {
-  if (!t || !t->sg || !target_dev) return lb_fail(LB_ERR_ARG, "null argument / not a SEGNN training handle");
-  return train_loss_grad_guarded(t, target_dev, loss_weight, loss_out, pred_out_dev);   // (X range guard: lb_train.hip)
-}
-static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                      float* pred_out_dev) {
+static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
   lb_engine* e = t->eng;
   lb_sgt* g = t->sg;
-  if (e->e_cap <= 0) return lb_fail(LB_ERR_STATE, "lb_segnn_train_loss_grad before lb_nl_allocate");
   hipStream_t s = e->stream;
-  LB_HIP(hipMemcpyAsync(e->ctrl_host, e->ctrl, sizeof(lb_ctrl), hipMemcpyDeviceToHost, s));
-  LB_HIP(hipStreamSynchronize(s));
-  if (e->ctrl_host->overflow_step >= 0) return lb_fail(LB_ERR_STATE, "neighbor list overflowed: re-allocate first");
-  const int64_t E = e->ctrl_host->n_edges_total, BN = e->BN;
+  int64_t E = 0, BN = 0;
+  LB_TRY(train_step_begin(t, "lb_segnn_train_loss_grad", &E, &BN));
   const int B = g->desc.blocks_per_step, L = g->desc.num_mp_steps, C = g->desc.hidden, dim = e->g.dim;
   LB_TRY(sgt_ensure(t, BN, E));
-  pack_all(t);
-  t->red_tab.clear();
-  t->red_off = 0;
-  t->red_blocks = 0;
   LB_TRY(lbk_sg_prep(e, g->desc.homogeneous, g->desc.velocity_avg, g->node_ns4, g->node_nv4, g->xnode, g->eattr, g->msgsv,
-                     g->nodesv, g->nattr, g->cap_e));
+                     g->nodesv, g->nattr, t->cap_e));
   // ---- forward (segnn.py:595-610)
   size_t bi = 0;
   {
@@ -572,9 +528,11 @@ static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, 
     LB_TRY(sgt_bwd(t, g->blocks[--bi], BN, g->df, nullptr, &op, g->nattr));             // embedding: parameters only
   }
   if (bi != 0) return lb_fail(LB_ERR_STATE, "segnn training: block bookkeeping");
-  LB_TRY(red_flush(t));
-  LB_HIP(hipGetLastError());
-  if (loss_out)   // (train_loss_grad_guarded synchronises and hands it over)
-    LB_HIP(hipMemcpyAsync(status_loss(t), t->loss_dev, sizeof(double), hipMemcpyDeviceToHost, s));
-  return LB_OK;
+  return train_step_end(t);
+}
+// value_and_grad of _mse for SEGNN on the engine's CURRENT window / neighbor list: same contract as lb_gns_train_loss_grad
+extern "C" int lb_segnn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
+                                        float* pred_out_dev) {
+  if (!t || !t->sg || !target_dev) return lb_fail(LB_ERR_ARG, "null argument / not a SEGNN training handle");
+  return train_loss_grad_guarded(t, loss_out, [&] { return segnn_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
 }

@@ -574,7 +574,8 @@ class GnsTrainHandle(_Handle):
         return int(self.engine.lib.lb_gns_train_step_count(self._h))
 
     def math_fallbacks(self) -> int:
-        """Training steps the X range guard of the f16x2 weight-gradient kernel sent to the exact-fp32 kernels (include/lbhip.h)."""
+        """Steps repeated because the X range guard of the f16x2 weight-gradient kernel fired: each ran again with the
+        site's X scale re-centred, or scaled per chunk, in f16x2 (include/lbhip.h)."""
         return int(self.engine.lib.lb_gns_train_math_fallbacks(self._h))
 
     def sort_fallbacks(self) -> int:

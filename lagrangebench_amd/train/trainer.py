@@ -14,8 +14,9 @@ backward kernels, MFMA products of our own for the dense contractions) accumulat
 Arithmetic of the products (include/lbhip.h, ``lb_gns_train_math_fallbacks``): by default three fp16 MFMA passes over hi / lo
 splits of the fp32 operands under exact power-of-two scaling, fp32 accumulate (error per term <= 2^-22 of the operand
 block's scale; gradients within 1e-4 per leaf of float64 autograd), with a range guard on the weight-gradient kernel's
-activation operand that repeats a step on the exact-fp32 MFMA kernels; ``LB_TRAIN_MATH=f32`` in the environment when the
-handle is created selects the exact kernels throughout (1.7x slower).
+activation operand: a step that trips it is repeated with the site's X scale re-centred, or scaled per chunk, in f16x2;
+``LB_TRAIN_MATH=f32`` in the environment when the handle is created selects the exact-fp32 MFMA kernels throughout (1.7x
+slower).
 torch is used for the noise / sampling random streams and as the tensor container only.  Trainable: GNS (latent <= 128,
 two to eight Linears per MLP), since round 5 SEGNN (lmax 1, hidden <= 32x0e+32x1o: ``lb_segnn_train_loss_grad``,
 csrc/lb_train_segnn.h) and EGNN (``lb_egnn_train_loss_grad``, csrc/lb_train_egnn.h: the inference forward, a hand-written

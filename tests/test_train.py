@@ -320,8 +320,8 @@ def test_activation_range_guard_of_the_weight_gradient_kernel(shift, monkeypatch
     hidden activations of the node encoder and of the first processor node block out of range without changing the network
     function (first Linear x 2^shift, second Linear x 2^-shift: exact in fp32): 2^18 pushes |a| past fp16's 65504 (NaN weight
     gradients before round 6), 2^-14 pushes every lo half into fp16 subnormals.  The kernel's range guard must catch it: the
-    step is repeated with X scaled per chunk (no gradient of the first attempt is added), the handle reports one repeated
-    step, and the gradients agree with an LB_TRAIN_MATH=f32 handle like those of an in-range network do (2e-5 per leaf)."""
+    step is repeated with the site's X scale re-centred, or scaled per chunk, in f16x2 (no gradient of the first attempt is
+    added), the handle reports one repeated step, and the gradients agree with an LB_TRAIN_MATH=f32 handle like those of an in-range network do (2e-5 per leaf)."""
     from lagrangebench_amd.data import make_case
     from lagrangebench_amd.models import GNS
     from tests._common import hip_case
