@@ -288,6 +288,28 @@ int32_t lb_gns_train_math_fallbacks(lb_gns_train* t);
  * same either way. */
 int32_t lb_gns_train_sort_fallbacks(lb_gns_train* t);
 
+/* The step split at d loss / d pred, for a loss the CALLER computes.  trainer.py:63-89 takes
+ * value_and_grad of _mse only; these two are the halves of that step around any loss: forward with saved activations, then
+ * the hand-written backward from the caller's d loss / d pred.  t: a GNS, SEGNN or EGNN training handle.
+ * lb_train_forward: on the engine's current window + neighbor list; pred_out_dev receives (B*N, dim) fp32 - the normalised
+ * accelerations (GNS, SEGNN) or the positions x^L (EGNN) - with the bits lb_*_train_loss_grad reports.  The handle's
+ * forward is then LIVE until the next call on the handle other than lb_gns_train_zero_grad.
+ * lb_train_backward: needs a live forward (else LB_ERR_STATE) and ends it.  dpred_dev (B*N, dim) fp32 is copied into the
+ * handle (rows of pad particles zeroed); the gradients ACCUMULATE into the gradient blob exactly as in lb_*_train_loss_grad.
+ * If the step's guard fires, the repeated attempt re-runs the forward (same weights, same window: the same activations)
+ * and starts from the saved copy.  dpos_out_dev: null, or (B, N, isl, dim) fp64 that receives (overwritten) d loss / d window
+ * through the feature builder (velocity history and magnitudes, wall distances, edge displacements and distances; the
+ * external force counts as constant, the neighbor list as fixed) - GNS only, LB_ERR_UNSUPPORTED for SEGNN / EGNN handles. */
+int lb_train_forward(lb_gns_train* t, float* pred_out_dev);
+int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double* dpos_out_dev);
+/* The arithmetic of the handle's products from the next forward on: exact != 0 selects the exact-fp32 kernels (what
+ * LB_TRAIN_MATH=f32 selects at creation), 0 the handle's default (EGNN handles are always exact).  A live forward stays
+ * live: lb_train_forward in one arithmetic may be followed by lb_train_backward in the other.  Why: a ReLU unit within the
+ * forward's rounding of zero takes either side of its kink, which moves its particle's gradient by per cent, and the f16x2
+ * forward has about ten times as many of them as the exact one.  autograd.DeviceModule therefore runs the forward of a GNS
+ * in exact arithmetic, and the backward too where the window's gradient (a per-particle quantity) is asked for. */
+int lb_train_exact_math(lb_gns_train* t, int32_t exact);
+
 /* Push-forward from device weights.
  * Re-make every packed image of `g` from the CURRENT weights of training handle `t`, on the device.
  * g and t: same engine, same lb_gns_desc (else LB_ERR_ARG).  Afterwards g is what lb_gns_create would

@@ -137,6 +137,9 @@ _SIGS = {
                                          C.c_float]),
     "lb_gns_train_math_fallbacks": (C.c_int32, [_P]),
     "lb_gns_train_sort_fallbacks": (C.c_int32, [_P]),
+    "lb_train_forward": (C.c_int, [_P, _P]),
+    "lb_train_backward": (C.c_int, [_P, _P, _P]),
+    "lb_train_exact_math": (C.c_int, [_P, C.c_int32]),
     "lb_gns_train_sync_model": (C.c_int, [_P, _P]),
     "lb_gns_image_bytes": (C.c_int64, [_P]),
     "lb_gns_image_read": (C.c_int, [_P, _P, C.c_int64]),

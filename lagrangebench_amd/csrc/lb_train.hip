@@ -146,6 +146,15 @@ struct lb_gns_train {
   std::vector<lb_pack_ent_h> pack_tab_h;
   lb_pack_ent_h* pack_dev_h = nullptr;
   float* wsc = nullptr;
+  // The step split at d loss / d pred (lb_train_forward / lb_train_backward): the edge and node counts of the step between
+  // its two parts, whether a forward's activations are still those of the engine's window, the caller's d loss / d pred
+  // (pads zeroed; what a repeated attempt starts from again) and, for d loss / d window, the gradient of the edge features
+  bool fwd_live = false;
+  bool fwd_f16x2 = false;       // the arithmetic lb_train_forward ran in (a repeated attempt of the backward re-runs it so)
+  int64_t fwd_E = 0, fwd_BN = 0;
+  bool want_dx = false;         // this step's backward also forms d xnode (t->dx) and d efeat (t->dxe)
+  float* dsave = nullptr;       // [cap_n][4]
+  float* dxe = nullptr;         // [cap_e][8], the stride of lb_engine::efeat (GNS)
 };
 #define LB_PACK_MAX 1024
 
@@ -964,7 +973,7 @@ static int pack_lookup(lb_gns_train* t, const float* W, int NR, int NO, int ldw,
       return LB_OK;
     }
   if (!t->wpack) {
-    t->wpack_cap = 2 * t->n_floats + ((int64_t)1 << 21);
+    t->wpack_cap = 4 * t->n_floats + ((int64_t)1 << 21);   // both orientations, in both arithmetics (lb_train_exact_math)
     LB_TRY(lb_alloc(&t->wpack, (size_t)t->wpack_cap));
     LB_TRY(lb_alloc(&t->pack_dev, (size_t)LB_PACK_MAX));
   }
@@ -994,7 +1003,7 @@ static int pack_lookup_h(lb_gns_train* t, const float* W, int NR, int NO, int ld
       return LB_OK;
     }
   if (!t->wpack) {
-    t->wpack_cap = 2 * t->n_floats + ((int64_t)1 << 21);
+    t->wpack_cap = 4 * t->n_floats + ((int64_t)1 << 21);   // both orientations, in both arithmetics (lb_train_exact_math)
     LB_TRY(lb_alloc(&t->wpack, (size_t)t->wpack_cap));
     LB_TRY(lb_alloc(&t->pack_dev, (size_t)LB_PACK_MAX));
   }
@@ -1467,6 +1476,7 @@ static int train_ensure(lb_gns_train* t, int64_t BN, int64_t E, F model) {
     LB_HIP(hipHostMalloc((void**)&t->red_host, sizeof(lb_red_ent) * (LB_RED_MAX + 1)));   // (+ the step's status words)
   }
   LB_TRY(tr_alloc(&t->node_w, (size_t)cn));
+  LB_TRY(tr_alloc(&t->dsave, (size_t)cn * 4));
   LB_TRY(tr_alloc(&t->loss_part, (size_t)(cn / 64 + 8)));
   t->cap_n = cn;
   t->cap_e = ce;
@@ -1506,6 +1516,7 @@ static int gns_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
     LB_TRY(tr_alloc(&t->dagg, (size_t)cn * TD));
     LB_TRY(tr_alloc(&t->agg, (size_t)cn * TD));
     LB_TRY(tr_alloc(&t->proj, (size_t)cn * 2 * TD));
+    LB_TRY(tr_alloc(&t->dxe, (size_t)ce * 8));
     t->red_cap = red_capacity(t, cn, ce);
     return LB_OK;
   });
@@ -1750,7 +1761,7 @@ extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   std::vector<void*> bufs = {t->w, t->g, t->m, t->v, t->xnode, t->a_en, t->z_en, t->a_ee, t->z_ee, t->a_d, t->pred,
                              t->dn, t->de, t->dy, t->dz, t->da, t->dx, t->dagg, t->agg, t->dwpart, t->red_dev, t->proj, t->node_w,
                              t->loss_dev, t->da2, t->loss_part, t->cnt_dev, t->snd_key, t->snd_perm, t->iota, t->snd_ptr, t->sort_tmp,
-                             t->wpack, t->pack_dev, t->pack_dev_h, t->wsc, t->tmax};
+                             t->wpack, t->pack_dev, t->pack_dev_h, t->wsc, t->tmax, t->dsave, t->dxe};
   for (auto* v : {&t->nlat, &t->elat, &t->ae, &t->ze, &t->xn, &t->an, &t->zn})
     for (float* p : *v) bufs.push_back(p);
   for (void* b : bufs)
@@ -1839,11 +1850,15 @@ static int train_step_end(lb_gns_train* t) {
 // value_and_grad of _mse, summed over the batch (trainer.py:63-89), on the engine's CURRENT window / neighbor list.
 // target_dev: (B*N, dim) fp32 normalised accelerations.  Gradients ACCUMULATE into the gradient blob (zero it with
 // lb_gns_train_zero_grad); *loss_out = mean over the batch of the per-trajectory losses (host-synchronous).
-static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
+// The step in two parts, split at d loss / d pred (a plain (B*N, dim) fp32 buffer, t->dy).  Forward part: the frame's begin,
+// scratch, features, the network with saved activations -> t->pred (and pred_out_dev).
+static int gns_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
   lb_engine* e = t->eng;
   hipStream_t s = e->stream;
   int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, "lb_gns_train_loss_grad", &E, &BN));
+  LB_TRY(train_step_begin(t, entry, &E, &BN));
+  t->fwd_E = E;
+  t->fwd_BN = BN;
   const int L = t->desc.num_mp_steps, dim = t->desc.out_dim;
   LB_TRY(gns_ensure(t, BN, E));
   const bool has_emb = t->desc.num_particle_types > 1;
@@ -1866,8 +1881,19 @@ static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, fl
   }
   LB_TRY(mlp_fwd(t, t->dec, BN, t->nlat[L], TD, t->a_d, nullptr, nullptr, t->pred, t->hs_n));
   if (pred_out_dev) LB_HIP(hipMemcpyAsync(pred_out_dev, t->pred, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
-  // ---- loss and d loss / d pred, the sender-sorted view of this step's edge list
-  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));
+  return LB_OK;
+}
+static int feat_bwd(lb_gns_train* t, double* dpos_out_dev);
+// Backward part: the sender-sorted view of this step's edge list, the hand-written backward from t->dy, the frame's end.
+// dpos_out_dev != null: also d loss / d window through the feature builder (k_feat_bwd)
+static int gns_backward_part(lb_gns_train* t, double* dpos_out_dev) {
+  lb_engine* e = t->eng;
+  hipStream_t s = e->stream;
+  const int64_t E = t->fwd_E, BN = t->fwd_BN;
+  const int L = t->desc.num_mp_steps;
+  const bool has_emb = t->desc.num_particle_types > 1;
+  const int emb = has_emb ? t->desc.embedding_size : 0;
+  const bool want_dx = dpos_out_dev != nullptr;
   LB_TRY(train_sender_sort(t, E, BN));
   // ---- backward
   LB_TRY(mlp_bwd(t, t->dec, BN, t->nlat[L], TD, t->a_d, nullptr, t->dy, t->dn, t->hs_n));  // dn = d loss / d n_L
@@ -1880,18 +1906,118 @@ static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, fl
     LB_TRY(gemm_nt_pair(t, BN, t->da, t->w + t->pn[k].w0, t->dn, 1.f, t->w + t->pn[k].w0 + (size_t)TD * TD, t->dagg, 0.f));
     LB_TRY(edge_bwd(t, t->pe[k], E, BN, t->nlat[k], t->elat[k], t->ae[k], t->ze[k], t->dagg, t->de, t->dn));
   }
-  LB_TRY(mlp_bwd(t, t->enc_edge, E, e->efeat, 8, t->a_ee, t->z_ee, t->de, nullptr, t->hs_e));
-  LB_TRY(mlp_bwd(t, t->enc_node, BN, t->xnode, t->kpad, t->a_en, t->z_en, t->dn, has_emb ? t->dx : nullptr, t->hs_n));
+  // (d efeat: [E][8] like efeat, rel_disp in the first dim columns, rel_dist in column dim - a 128 x (dim + 1) operand)
+  LB_TRY(mlp_bwd(t, t->enc_edge, E, e->efeat, 8, t->a_ee, t->z_ee, t->de, want_dx ? t->dxe : nullptr, t->hs_e));
+  LB_TRY(mlp_bwd(t, t->enc_node, BN, t->xnode, t->kpad, t->a_en, t->z_en, t->dn, has_emb || want_dx ? t->dx : nullptr, t->hs_n));
   if (has_emb)
     hipLaunchKernelGGL(k_embed_grad, dim3(t->desc.num_particle_types), dim3(1024), 0, s, t->dx, t->kpad, t->desc.node_in, emb,
                        e->ptype, t->desc.num_particle_types, BN, t->g + t->off_embed, t->dw_flag);
+  if (want_dx) LB_TRY(feat_bwd(t, dpos_out_dev));
   return train_step_end(t);
+}
+// ---- the transpose of the feature builder (features.py:47-126; lb_features.h, the edge features of the neighbor build):
+// d loss / d window (B, N, isl, dim) fp64 from d loss / d xnode (t->dx, row stride kpad) and d loss / d efeat (t->dxe,
+// [E][8]: rel_disp in the first dim columns, rel_dist in column dim).  One thread per particle, workgroup-strided; every
+// sum in a fixed order - frames ascending, then the walls, the edges of the particle's CSR row (it is their receiver), the
+// edges it sends in ascending edge order (the sender view of train_sender_sort) - in fp64 over fp32 terms, no atomics.
+//   vel_hist   vn_k = (disp(p_{k+1}, p_k) - mean) / std: g_k / std to frame k + 1, -g_k / std to frame k (the periodic
+//              displacement has derivative 1)
+//   vel_mag    |vn_k|: the same path with g = dmag_k vn_k / |vn_k| (0 where |vn_k| = 0)
+//   bound      clip((p - lo) / r_c), clip((hi - p) / r_c): (d_lo - d_hi) / r_c on the newest frame where the feature is
+//              strictly inside (-1, 1)
+//   force      constant in the positions (piecewise / constant forces: derivative 0 almost everywhere)
+//   edges      rel_disp_e = disp(p_r, p_s) / r_c, rel_dist_e = |rel_disp_e|:
+//              h_e = (d rel_disp_e + d rel_dist_e rel_disp_e / rel_dist_e) / r_c (second term 0 where rel_dist_e = 0),
+//              +h_e to the receiver's newest frame, -h_e to the sender's
+// Rows of pad particles are 0.  A slot of snd_perm outside [0, E) is skipped (see k_edge_dP: a discarded attempt).
+struct lb_feat_bwd_args {
+  int64_t BN, E;
+  int dim, isl, kpad, has_mag, has_bound;
+  double rc, inv_std[3];
+  const int32_t *ptype, *row_ptr, *snd_ptr, *snd_perm;
+  const float *xnode, *dx, *efeat, *dxe;
+  double* dpos;
+};
+__device__ __forceinline__ void lb_edge_h(const lb_feat_bwd_args& a, int64_t e, double sign, double (&acc)[3]) {
+  const float* f = a.efeat + e * 8;
+  const float* df = a.dxe + e * 8;
+  const float dist = f[a.dim];
+  const double w = dist != 0.f ? (double)df[a.dim] / (double)dist : 0.0;
+  for (int d = 0; d < a.dim; ++d) acc[d] += sign * (((double)df[d] + w * (double)f[d]) / a.rc);
+}
+__global__ void __launch_bounds__(256) k_feat_bwd(lb_feat_bwd_args a) {
+  const int K = a.isl - 1, dim = a.dim;
+  const int c_mag = K * dim, c_bnd = c_mag + (a.has_mag ? K : 0);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.BN; i += (int64_t)gridDim.x * blockDim.x) {
+    double* out = a.dpos + i * a.isl * dim;
+    if (a.ptype[i] == LB_PAD_TYPE) {
+      for (int j = 0; j < a.isl * dim; ++j) out[j] = 0.0;
+      continue;
+    }
+    const float* x = a.xnode + i * a.kpad;
+    const float* g = a.dx + i * a.kpad;
+    double prev[3] = {0.0, 0.0, 0.0};   // g_{f-1} / std: what velocity f - 1 sends to its later frame f
+    for (int f = 0; f <= K; ++f) {
+      double acc[3] = {0.0, 0.0, 0.0};
+      double cur[3] = {0.0, 0.0, 0.0};
+      if (f < K) {
+        const float m = a.has_mag ? x[c_mag + f] : 0.f;
+        const double wm = (a.has_mag && m != 0.f) ? (double)g[c_mag + f] / (double)m : 0.0;
+        for (int d = 0; d < dim; ++d) cur[d] = ((double)g[f * dim + d] + wm * (double)x[f * dim + d]) * a.inv_std[d];
+      }
+      for (int d = 0; d < dim; ++d) acc[d] = prev[d] - cur[d];
+      for (int d = 0; d < dim; ++d) prev[d] = cur[d];
+      if (f == K) {
+        if (a.has_bound)
+          for (int d = 0; d < dim; ++d) {
+            const float lo = x[c_bnd + d], hi = x[c_bnd + dim + d];
+            if (lo > -1.f && lo < 1.f) acc[d] += (double)g[c_bnd + d] / a.rc;
+            if (hi > -1.f && hi < 1.f) acc[d] -= (double)g[c_bnd + dim + d] / a.rc;
+          }
+        int64_t k0 = a.row_ptr[i], k1 = a.row_ptr[i + 1];
+        k0 = k0 < a.E ? k0 : a.E;
+        k1 = k1 < a.E ? k1 : a.E;
+        for (int64_t k = k0; k < k1; ++k) lb_edge_h(a, k, 1.0, acc);
+        const int s0 = a.snd_ptr[i], s1 = a.snd_ptr[i + 1];
+        for (int j = s0; j < s1; ++j) {
+          const uint32_t p = (uint32_t)a.snd_perm[j];
+          if (p < (uint64_t)a.E) lb_edge_h(a, (int64_t)p, -1.0, acc);
+        }
+      }
+      for (int d = 0; d < dim; ++d) out[f * dim + d] = acc[d];
+    }
+  }
+}
+static int feat_bwd(lb_gns_train* t, double* dpos_out_dev) {
+  lb_engine* e = t->eng;
+  lb_feat_bwd_args a{};
+  a.BN = t->fwd_BN; a.E = t->fwd_E;
+  a.dim = e->g.dim; a.isl = e->g.isl; a.kpad = t->kpad; a.has_mag = e->g.has_vel_mag; a.has_bound = e->g.has_bound;
+  a.rc = e->g.rc;
+  for (int d = 0; d < 3; ++d) a.inv_std[d] = 1.0 / e->g.vel_std[d];
+  a.ptype = e->ptype; a.row_ptr = e->row_ptr; a.snd_ptr = t->snd_ptr; a.snd_perm = t->snd_perm;
+  a.xnode = t->xnode; a.dx = t->dx; a.efeat = e->efeat; a.dxe = t->dxe; a.dpos = dpos_out_dev;
+  if (a.E == 0) {   // no edges: no sender view was built; with row_ptr (all zero) in its place the loops over it are empty
+    a.snd_ptr = e->row_ptr;
+    a.snd_perm = e->row_ptr;
+  }
+  if (!a.snd_ptr || !a.snd_perm) return lb_fail(LB_ERR_STATE, "feature transpose: no sender view");
+  const unsigned blocks = (unsigned)std::min<int64_t>((a.BN + 255) / 256, 2048);
+  hipLaunchKernelGGL(k_feat_bwd, dim3(blocks), dim3(256), 0, e->stream, a);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
+  LB_TRY(gns_forward_part(t, "lb_gns_train_loss_grad", pred_out_dev));
+  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));   // loss and d loss / d pred
+  return gns_backward_part(t, nullptr);
 }
 extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                       float* pred_out_dev) {
   if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
   if (t->sg) return lb_segnn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
+  t->fwd_live = false;
   return train_loss_grad_guarded(t, loss_out, [&] { return gns_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
 }
 
@@ -1905,6 +2031,7 @@ extern "C" int lb_gns_train_zero_grad(lb_gns_train* t) {
 // in the handle (set_step restores it from a checkpoint)
 extern "C" int lb_adamw_step(lb_gns_train* t, float lr, float b1, float b2, float eps, float weight_decay) {
   if (!t) return lb_fail(LB_ERR_ARG, "null argument");
+  t->fwd_live = false;
   t->step += 1;
   const float c1 = 1.f - powf(b1, (float)t->step), c2 = 1.f - powf(b2, (float)t->step);
   hipLaunchKernelGGL(k_adamw, GRID1(t->n_floats), 0, t->eng->stream, t->w, t->g, t->m, t->v, t->n_floats, lr, b1, b2, eps,
@@ -1931,6 +2058,7 @@ extern "C" int lb_adamw_step_gathered(lb_gns_train* t, const float* gathered_dev
   const int64_t n = t->n_floats;
   if (world > 1 && gathered_dev < t->g + n && t->g < gathered_dev + (int64_t)world * n)
     return lb_fail(LB_ERR_ARG, "the gathered rows overlap the handle's gradient blob");
+  t->fwd_live = false;
   if (n <= 0) return LB_OK;
   t->step += 1;
   const float c1 = 1.f - powf(b1, (float)t->step), c2 = 1.f - powf(b2, (float)t->step);
@@ -1961,6 +2089,7 @@ extern "C" int64_t lb_gns_train_step_count(lb_gns_train* t) { return t ? (int64_
 extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* in_host, int64_t n_floats, int64_t step) {
   if (!t || !in_host || n_floats != t->n_compact || which < 0 || which > 3) return lb_fail(LB_ERR_ARG, "bad argument");
   float* dst = which == 0 ? t->w : which == 1 ? t->g : which == 2 ? t->m : t->v;
+  t->fwd_live = false;
   LB_HIP(hipStreamSynchronize(t->eng->stream));
   if (t->cmap.empty()) {
     LB_HIP(hipMemcpy(dst, in_host, sizeof(float) * n_floats, hipMemcpyHostToDevice));
@@ -1992,3 +2121,82 @@ extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
 
 // ------------------------------------------------------------------------------------------------ EGNN
 #include "lb_train_egnn.h"
+
+// ------------------------------------------------------------------- the step split for a caller-side loss
+// lb_train_forward / lb_train_backward (include/lbhip.h): the two halves of every model's step around a d loss / d pred the
+// CALLER computes (trainer.py:63-89 with any loss in place of _mse) - the seam of *_forward_part / *_backward_part above.
+// dsave[i] = dpred[i], 0 in the rows of pad particles: a padded batch cannot train on its pads whatever the caller's loss does
+__global__ void k_dpred_ingest(const float* __restrict__ dpred, const int32_t* __restrict__ ptype, int64_t BN, int dim,
+                               float* __restrict__ dsave) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= BN) return;
+  const bool pad = ptype[i] == LB_PAD_TYPE;
+  for (int d = 0; d < dim; ++d) dsave[i * dim + d] = pad ? 0.f : dpred[i * dim + d];
+}
+// rows of dim floats -> rows of ld floats (EGNN's d x^L: rows of 4)
+__global__ void k_dpred_spread(const float* __restrict__ dsave, int64_t BN, int dim, int ld, float* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= BN) return;
+  for (int d = 0; d < dim; ++d) dst[i * ld + d] = dsave[i * dim + d];
+}
+// The arithmetic of the handle's products from now on: exact != 0 selects the exact-fp32 kernels (what LB_TRAIN_MATH=f32 selects
+// at creation), 0 the handle's default.  A gradient with respect to the WINDOW is a per-particle quantity: a ReLU unit whose
+// pre-activation lies within the forward's rounding of zero takes either side of its kink, which changes that particle's
+// gradient (and its neighbours') by per cent; a weight gradient - a sum over all rows - notices only where the sum cancels
+// (the embedding row of a one-type batch).  The f16x2 forward puts about ten times as many units there as the exact one
+// (DESIGN.md section 4.9d).
+extern "C" int lb_train_exact_math(lb_gns_train* t, int32_t exact) {
+  if (!t) return lb_fail(LB_ERR_ARG, "null argument");
+  // (a live forward stays live: saved activations do not depend on the arithmetic that reads them, so a forward in exact
+  // products may be followed by a backward in the default ones)
+  t->f16x2 = !exact && !t->eg && lb_train_f16x2_default();
+  return LB_OK;
+}
+static int train_forward_part(lb_gns_train* t, float* pred_out_dev) {
+  if (t->eg) return egnn_forward_part(t, "lb_train_forward", pred_out_dev);
+  if (t->sg) return segnn_forward_part(t, "lb_train_forward", pred_out_dev);
+  return gns_forward_part(t, "lb_train_forward", pred_out_dev);
+}
+extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
+  if (!t || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  t->fwd_live = false;
+  LB_TRY(train_forward_part(t, pred_out_dev));
+  LB_HIP(hipGetLastError());
+  t->fwd_f16x2 = t->f16x2;
+  t->fwd_live = true;
+  return LB_OK;
+}
+extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double* dpos_out_dev) {
+  if (!t || !dpred_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (!t->fwd_live)
+    return lb_fail(LB_ERR_STATE, "lb_train_backward needs a live forward: call lb_train_forward first (any other call on the "
+                   "handle but lb_gns_train_zero_grad ends it)");
+  if (dpos_out_dev && (t->sg || t->eg))
+    return lb_fail(LB_ERR_UNSUPPORTED, "lb_train_backward: the gradient with respect to the window is built for GNS only, "
+                   "not for %s handles", t->sg ? "SEGNN" : "EGNN");
+  t->fwd_live = false;   // the backward consumes the forward's scratch
+  lb_engine* e = t->eng;
+  hipStream_t s = e->stream;
+  const int64_t BN = t->fwd_BN;
+  const int dim = e->g.dim;
+  hipLaunchKernelGGL(k_dpred_ingest, GRID1(BN), 0, s, dpred_dev, e->ptype, BN, dim, t->dsave);
+  LB_HIP(hipMemsetAsync(t->loss_dev, 0, sizeof(double), s));   // (the frame's end copies the loss word: no loss here)
+  int attempt = 0;
+  // a repeated attempt (the guard fired): weights and window are unchanged, so the forward it re-runs is the same one; the
+  // saved d loss / d pred goes back into the buffer the backward starts from (t->dy is scratch of the forward)
+  return train_loss_grad_guarded(t, nullptr, [&] {
+    if (attempt++ > 0) {   // (in the arithmetic of the forward it repeats)
+      const bool bwd_f16x2 = t->f16x2;
+      t->f16x2 = t->fwd_f16x2;
+      const int rc = train_forward_part(t, nullptr);
+      t->f16x2 = bwd_f16x2;
+      if (rc) return rc;
+    }
+    if (t->eg) {
+      hipLaunchKernelGGL(k_dpred_spread, GRID1(BN), 0, s, t->dsave, BN, dim, 4, t->eg->dx);
+      return egnn_backward_part(t);
+    }
+    LB_HIP(hipMemcpyAsync(t->dy, t->dsave, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
+    return t->sg ? segnn_backward_part(t) : gns_backward_part(t, dpos_out_dev);
+  });
+}

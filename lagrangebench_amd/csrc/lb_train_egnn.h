@@ -48,6 +48,7 @@ struct lb_egt {
   // edge scratch
   float *cdr = nullptr, *ea2 = nullptr, *z0 = nullptr, *a = nullptr, *z1 = nullptr, *m = nullptr, *zx0 = nullptr, *q = nullptr,
         *phi = nullptr, *dphi = nullptr, *dcd = nullptr, *de1 = nullptr, *de2 = nullptr;
+  lb_egnn_state st{};      // what the step's forward part hands to its loss and backward part
 };
 
 // ---------------------------------------------------------------------------------------------------------- kernels
@@ -501,23 +502,35 @@ extern "C" int lb_egnn_train_model(lb_gns_train* t, lb_egnn** out) {
   return LB_OK;
 }
 
-static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
-                                     float w_pos, float w_vel, float w_acc, float* pred_pos_out_dev) {
+// The step in three parts, split at d loss / d x^L (g->dx, rows of 4 floats).  Forward part: the inference kernels on the
+// current weights, taps on (returns after checking every edge's transpose: nothing has been accumulated yet when it refuses)
+static int egnn_forward_part(lb_gns_train* t, const char* entry, float* pred_pos_out_dev) {
   lb_engine* e = t->eng;
   lb_egt* g = t->eg;
   hipStream_t s = e->stream;
   int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, "lb_egnn_train_loss_grad", &E, &BN));
-  const int L = g->desc.num_mp_steps, dim = e->g.dim, W = EGT_W;
+  LB_TRY(train_step_begin(t, entry, &E, &BN));
+  t->fwd_E = E;
+  t->fwd_BN = BN;
+  const int L = g->desc.num_mp_steps, dim = e->g.dim;
   LB_TRY(egt_ensure(t, BN, E));
-  // ---- forward: the inference kernels on the current weights, taps on (returns after checking every edge's transpose:
-  // nothing has been accumulated yet when it refuses)
   LB_TRY(lb_egnn_set_tap(g->view, g->tap_h, g->tap_x));
-  lb_egnn_state st{};
-  LB_TRY(lbk_egnn_train_forward(e, g->view, &st));
+  g->st = lb_egnn_state{};
+  LB_TRY(lbk_egnn_train_forward(e, g->view, &g->st));
   const float* xl = g->tap_x + (size_t)L * BN * dim;
   if (pred_pos_out_dev) LB_HIP(hipMemcpyAsync(pred_pos_out_dev, xl, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
-  // ---- loss and d loss / d x^L
+  return LB_OK;
+}
+// ---- loss and d loss / d x^L
+static int egnn_loss_part(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc, float w_pos,
+                          float w_vel, float w_acc) {
+  lb_engine* e = t->eng;
+  lb_egt* g = t->eg;
+  hipStream_t s = e->stream;
+  const int64_t BN = t->fwd_BN;
+  const int L = g->desc.num_mp_steps, dim = e->g.dim;
+  const lb_egnn_state& st = g->st;
+  const float* xl = g->tap_x + (size_t)L * BN * dim;
   LB_HIP(hipMemsetAsync(t->cnt_dev, 0, sizeof(int32_t) * e->g.B, s));
   LB_HIP(hipMemsetAsync(t->loss_dev, 0, sizeof(double), s));
   hipLaunchKernelGGL(k_count_nonkin, GRID1(BN), 0, s, e->ptype, BN, e->g.N, t->cnt_dev);
@@ -530,6 +543,15 @@ static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, con
   la.ptype = e->ptype; la.cnt = t->cnt_dev; la.dx = g->dx; la.loss_part = t->loss_part;
   hipLaunchKernelGGL(k_egt_loss, GRID1(BN), 0, s, la);
   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, s, t->loss_part, (int64_t)((BN + 255) / 256) * 4, t->loss_dev);
+  return LB_OK;
+}
+static int egnn_backward_part(lb_gns_train* t) {
+  lb_engine* e = t->eng;
+  lb_egt* g = t->eg;
+  hipStream_t s = e->stream;
+  const int64_t E = t->fwd_E, BN = t->fwd_BN;
+  const int L = g->desc.num_mp_steps, dim = e->g.dim, W = EGT_W;
+  const lb_egnn_state& st = g->st;
   hipLaunchKernelGGL(k_egt_xin, GRID1(BN), 0, s, BN, dim, g->desc.n_vels, g->desc.homogeneous, st.xnode, e->ptype, st.nattr,
                      g->n_attr, g->xin, g->attr2);
   LB_HIP(hipMemsetAsync(g->dh, 0, sizeof(float) * BN * W, s));   // h^L has no reader
@@ -610,12 +632,19 @@ static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, con
   LB_TRY(egt_dw(t, BN, g->node_in, g->xin, EGT_XIN, g->dh, G + g->w_emb, G + g->b_emb));
   return train_step_end(t);
 }
+static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
+                                     float w_pos, float w_vel, float w_acc, float* pred_pos_out_dev) {
+  LB_TRY(egnn_forward_part(t, "lb_egnn_train_loss_grad", pred_pos_out_dev));
+  LB_TRY(egnn_loss_part(t, tgt_pos, tgt_vel, tgt_acc, w_pos, w_vel, w_acc));
+  return egnn_backward_part(t);
+}
 // value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h)
 extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
                                        float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev) {
   if (!t || !t->eg) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");
   if ((w_pos != 0.f && !tgt_pos) || (w_vel != 0.f && !tgt_vel) || (w_acc != 0.f && !tgt_acc))
     return lb_fail(LB_ERR_ARG, "egnn training: a target with a non-zero loss weight is null");
+  t->fwd_live = false;
   // The guard never fires here: the handle has f16x2 off, so no k_dw_part_h launch can raise bits 1 | 2, and the step does
   // not build a sender view (its sender sums go through rev[] and the orphans), so k_sender_transpose never raises bit 4.
   // The loop is then one attempt and its synchronisation the step's last.

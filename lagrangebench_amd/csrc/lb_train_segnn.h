@@ -424,12 +424,15 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
   return LB_OK;
 }
 
-static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
+// The step in two parts, split at d loss / d pred (t->dy), as gns_forward_part / gns_backward_part
+static int segnn_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
   lb_engine* e = t->eng;
   lb_sgt* g = t->sg;
   hipStream_t s = e->stream;
   int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, "lb_segnn_train_loss_grad", &E, &BN));
+  LB_TRY(train_step_begin(t, entry, &E, &BN));
+  t->fwd_E = E;
+  t->fwd_BN = BN;
   const int B = g->desc.blocks_per_step, L = g->desc.num_mp_steps, C = g->desc.hidden, dim = e->g.dim;
   LB_TRY(sgt_ensure(t, BN, E));
   LB_TRY(lbk_sg_prep(e, g->desc.homogeneous, g->desc.velocity_avg, g->node_ns4, g->node_nv4, g->xnode, g->eattr, g->msgsv,
@@ -481,7 +484,16 @@ static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, 
     LB_TRY(sgt_fwd(t, g->blocks[bi++], BN, &op, g->nattr, nullptr, t->pred));
   }
   if (pred_out_dev) LB_HIP(hipMemcpyAsync(pred_out_dev, t->pred, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
-  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));
+  if (bi != g->blocks.size()) return lb_fail(LB_ERR_STATE, "segnn training: block bookkeeping");
+  return LB_OK;
+}
+static int segnn_backward_part(lb_gns_train* t) {
+  lb_engine* e = t->eng;
+  lb_sgt* g = t->sg;
+  hipStream_t s = e->stream;
+  const int64_t E = t->fwd_E, BN = t->fwd_BN;
+  const int B = g->desc.blocks_per_step, L = g->desc.num_mp_steps, C = g->desc.hidden;
+  size_t bi = g->blocks.size();
   LB_TRY(train_sender_sort(t, E, BN));
   // ---- backward, blocks in reverse call order
   {
@@ -530,9 +542,15 @@ static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, 
   if (bi != 0) return lb_fail(LB_ERR_STATE, "segnn training: block bookkeeping");
   return train_step_end(t);
 }
+static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
+  LB_TRY(segnn_forward_part(t, "lb_segnn_train_loss_grad", pred_out_dev));
+  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));
+  return segnn_backward_part(t);
+}
 // value_and_grad of _mse for SEGNN on the engine's CURRENT window / neighbor list: same contract as lb_gns_train_loss_grad
 extern "C" int lb_segnn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                         float* pred_out_dev) {
   if (!t || !t->sg || !target_dev) return lb_fail(LB_ERR_ARG, "null argument / not a SEGNN training handle");
+  t->fwd_live = false;
   return train_loss_grad_guarded(t, loss_out, [&] { return segnn_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
 }

@@ -518,6 +518,34 @@ class GnsTrainHandle(_Handle):
                                            ptr(pred) if want_pred else None), "lb_gns_train_loss_grad")
         return (loss.value, pred) if want_pred else loss.value
 
+    def forward(self) -> torch.Tensor:
+        """The model's forward with saved activations on the engine's current window and neighbor list -> (B, N, dim)
+        float32: the normalised accelerations (GNS, SEGNN) or the positions x^L (EGNN), the `pred` of loss_grad bit for
+        bit.  The forward stays live - backward() may follow - until any other call on the handle but zero_grad
+        (include/lbhip.h: lb_train_forward)."""
+        e = self.engine
+        pred = torch.empty((e.B, e.N, e.dim), dtype=torch.float32, device=e.device)
+        check(e.lib.lb_train_forward(self._h, ptr(pred)), "lb_train_forward")
+        return pred
+
+    def backward(self, dpred: torch.Tensor, want_dpos: bool = False) -> Optional[torch.Tensor]:
+        """The hand-written backward of the live forward from the caller's d loss / d pred (B, N, dim): the gradients
+        accumulate into the gradient blob, as in loss_grad.  Rows of pad particles count as zero.  want_dpos (GNS only):
+        also returns d loss / d window (B, N, isl, dim) float64 through the feature builder, with the neighbor list held
+        fixed and the external force treated as constant in the positions (include/lbhip.h: lb_train_backward)."""
+        e = self.engine
+        if tuple(dpred.shape) not in ((e.B, e.N, e.dim), (e.B * e.N, e.dim)):
+            raise ValueError(f"backward: dpred must be ({e.B}, {e.N}, {e.dim}), got {tuple(dpred.shape)}")
+        d = dpred.detach().to(device=e.device, dtype=torch.float32).contiguous()
+        dpos = torch.empty((e.B, e.N, e.isl, e.dim), dtype=torch.float64, device=e.device) if want_dpos else None
+        check(e.lib.lb_train_backward(self._h, ptr(d), ptr(dpos) if want_dpos else None), "lb_train_backward")
+        return dpos
+
+    def exact_math(self, on: bool) -> None:
+        """Exact-fp32 products from the next forward on (True), or the handle's default arithmetic (False): what
+        LB_TRAIN_MATH=f32 selects at creation, per step (include/lbhip.h: lb_train_exact_math)."""
+        check(self.engine.lib.lb_train_exact_math(self._h, int(bool(on))), "lb_train_exact_math")
+
     def zero_grad(self) -> None:
         check(self.engine.lib.lb_gns_train_zero_grad(self._h), "lb_gns_train_zero_grad")
 

@@ -133,6 +133,8 @@ class GNS(BaseModel):
 
     # ------------------------------------------------------------------ engine binding (models/base.py)
     _FORWARD, _OUTPUT, _HAIKU_KEY = "gns_forward", "acc", "enc_node/linear_0"
+    _WINDOW_GRAD = True
+    _EXACT_FORWARD = True
 
     def _desc(self, engine) -> GnsDesc:
         d = GnsDesc()
