@@ -212,34 +212,31 @@ extern "C" int lb_engine_create(const lb_case_desc* d, void* hip_stream, lb_engi
   const size_t nc = (size_t)g.B * g.ncells;
   int rc = LB_OK;
   auto A = [&](int r) { if (!rc) rc = r; };
-  A(lb_alloc(&e->win, (size_t)d->isl * d->dim * BN));
-  A(lb_alloc(&e->ptype, (size_t)BN));
-  A(lb_alloc(&e->live_cnt, (size_t)g.B));
-  A(lb_alloc(&e->ctrl, 1));
-  A(lb_alloc(&e->blocks_done, 1));
-  A(lb_alloc(&e->cell_of, (size_t)BN));
-  A(lb_alloc(&e->cell_count, 2 * nc));  // cell_count | cell_fill contiguous (one memset)
-  A(lb_alloc(&e->cell_start, nc + 1));
-  A(lb_alloc(&e->cell_part, (size_t)BN));
-  A(lb_alloc(&e->deg, (size_t)BN));
-  A(lb_alloc(&e->nl_wg_sum, (size_t)BN / 8 + 2));
-  A(lb_alloc(&e->row_ptr, (size_t)BN + 1));
-  A(lb_alloc(&e->scan_part, (size_t)((BN > (int64_t)nc ? BN : (int64_t)nc) / 2048 + 2)));
-  A(lb_alloc(&e->cpos, (size_t)d->dim * BN));
+  A(e->mem.get(&e->win, (size_t)d->isl * d->dim * BN));
+  A(e->mem.get(&e->ptype, (size_t)BN));
+  A(e->mem.get(&e->live_cnt, (size_t)g.B));
+  A(e->mem.get(&e->ctrl, 1));
+  A(e->mem.get(&e->blocks_done, 1));
+  A(e->mem.get(&e->cell_of, (size_t)BN));
+  A(e->mem.get(&e->cell_count, 2 * nc));  // cell_count | cell_fill contiguous (one memset)
+  A(e->mem.get(&e->cell_start, nc + 1));
+  A(e->mem.get(&e->cell_part, (size_t)BN));
+  A(e->mem.get(&e->deg, (size_t)BN));
+  A(e->mem.get(&e->nl_wg_sum, (size_t)BN / 8 + 2));
+  A(e->mem.get(&e->row_ptr, (size_t)BN + 1));
+  A(e->mem.get(&e->scan_part, (size_t)((BN > (int64_t)nc ? BN : (int64_t)nc) / 2048 + 2)));
+  A(e->mem.get(&e->cpos, (size_t)d->dim * BN));
   e->cell_slots = BN;
-  A(lb_alloc(&e->overflow, (size_t)g.B));
-  A(lb_alloc(&e->nedges_b, (size_t)g.B));
-  A(lb_alloc(&e->acc, (size_t)BN * 4));
+  A(e->mem.get(&e->overflow, (size_t)g.B));
+  A(e->mem.get(&e->nedges_b, (size_t)g.B));
+  A(e->mem.get(&e->acc, (size_t)BN * 4));
+  A(e->mem.get_pinned(&e->ctrl_host, 1));
+  A(e->mem.get_pinned(&e->host_flag, 4, hipHostMallocMapped));
   if (rc) { lb_engine_destroy(e); return rc; }
   e->cell_fill = e->cell_count + nc;
-  if (hipHostMalloc((void**)&e->ctrl_host, sizeof(lb_ctrl)) != hipSuccess) {
+  if (hipHostGetDevicePointer((void**)&e->host_flag_dev, e->host_flag, 0) != hipSuccess) {
     lb_engine_destroy(e);
-    return lb_fail(LB_ERR_HIP, "hipHostMalloc failed");
-  }
-  if (hipHostMalloc((void**)&e->host_flag, sizeof(int32_t) * 4, hipHostMallocMapped) != hipSuccess ||
-      hipHostGetDevicePointer((void**)&e->host_flag_dev, e->host_flag, 0) != hipSuccess) {
-    lb_engine_destroy(e);
-    return lb_fail(LB_ERR_HIP, "hipHostMalloc(mapped flag) failed");
+    return lb_fail(LB_ERR_HIP, "hipHostGetDevicePointer(mapped flag) failed");
   }
   e->host_flag[0] = -1;
   for (int i = 0; i < 4; ++i)
@@ -277,29 +274,19 @@ extern "C" void lb_engine_destroy(lb_engine* e) {
   if (!e) return;
   lb_timers_collect(e);
   for (auto ev : e->epool) (void)hipEventDestroy(ev);
-  void* bufs[] = {e->win, e->ptype, e->live_cnt, e->force, e->ctrl, e->cell_of, e->cell_count, e->cell_start,
-                  e->cell_part, e->deg, e->nl_wg_sum, e->row_ptr, e->scan_part, e->cpos, e->tmp_send, e->tmp_feat, e->tmp_feat64,
-                  e->senders, e->receivers, e->efeat, e->efeat64,
-                  e->overflow, e->nedges_b, e->xnode, e->nlat, e->agg, e->psr, e->elat, e->msg,
-                  e->acc, e->blocks_done};  // (e->part lives inside the e->agg allocation)
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (e->ctrl_host) (void)hipHostFree(e->ctrl_host);
-  if (e->host_flag) (void)hipHostFree(e->host_flag);
   for (int i = 0; i < 4; ++i)
     if (e->step_ev[i]) (void)hipEventDestroy(e->step_ev[i]);
   if (e->gstream) (void)hipStreamDestroy(e->gstream);
-  delete e;
+  delete e;  // (e->mem frees the buffers)
 }
 
 // Aggregated messages [BN][128] and the partial sums of the receivers a tile (chunk) boundary cuts [tiles + 2][2][128] in ONE
 // allocation: the fused segment_sum of the edge kernels stores both through one buffer resource with branch-free
 // raw-buffer stores (a lane with nothing to write has its offset pushed out of range).  Contents are transient (one layer).
-int lb_alloc_aggpart(lb_engine* e) {
-  if (e->agg) (void)hipFree(e->agg);
-  e->agg = e->part = nullptr;
-  const size_t n_agg = (size_t)e->BN * LB_D, n_part = (size_t)(e->e_alloc / 16 + 2) * 2 * LB_D;
-  LB_TRY(lb_alloc(&e->agg, n_agg + n_part));
+int lb_alloc_aggpart(lb_engine* e, int64_t n_edges) {
+  e->part = nullptr;
+  const size_t n_agg = (size_t)e->BN * LB_D, n_part = (size_t)(n_edges / 16 + 2) * 2 * LB_D;
+  LB_TRY(e->mem.get(&e->agg, n_agg + n_part));
   e->part = e->agg + n_agg;
   e->aggpart_bytes = (int64_t)(n_agg + n_part) * (int64_t)sizeof(float);
   return LB_OK;
@@ -307,29 +294,20 @@ int lb_alloc_aggpart(lb_engine* e) {
 
 // Edge-sized buffers grow geometrically; contents are not preserved (rebuilt every step).
 int lb_ensure_edges(lb_engine* e, int64_t need) {
-  if (need <= e->e_alloc && e->senders) return LB_OK;
-  LB_HIP(hipStreamSynchronize(e->stream));
-  int64_t n = std::max<int64_t>(need + need / 8 + 1024, 4096);
-  void* old[] = {e->senders, e->receivers, e->efeat, e->efeat64, e->elat, e->msg};
-  for (void* b : old)
-    if (b) (void)hipFree(b);
-  e->senders = e->receivers = nullptr;
-  e->efeat = nullptr;
-  e->efeat64 = nullptr;
-  e->elat = e->msg = nullptr;
-  e->e_alloc = n;
-  LB_TRY(lb_alloc_aggpart(e));  // agg | part (sized for the 16-row tiles of the new capacity)
-  LB_TRY(lb_alloc(&e->senders, (size_t)n));
-  LB_TRY(lb_alloc(&e->receivers, (size_t)n));
-  // (kernels may gather through index rows past the current edge count before they know it: keep every row a valid id)
-  LB_HIP(hipMemsetAsync(e->senders, 0, sizeof(int32_t) * (size_t)n, e->stream));
-  LB_HIP(hipMemsetAsync(e->receivers, 0, sizeof(int32_t) * (size_t)n, e->stream));
-  LB_TRY(lb_alloc(&e->efeat, (size_t)n * 8));
-  LB_TRY(lb_alloc(&e->efeat64, (size_t)n * 4));
-  LB_TRY(lb_alloc(&e->elat, (size_t)(n + 32) * LB_D));  // tile-blocked in the 16-row kernels: pad to a tile
-  LB_TRY(lb_alloc(&e->msg, (size_t)(n + 32) * LB_D));  // also the second edge-latent buffer of the ping-pong
-  e->e_alloc = n;
-  return LB_OK;
+  if (need <= e->e_alloc) return LB_OK;
+  return lb_regrow(e->stream, &e->e_alloc, std::max<int64_t>(need + need / 8 + 1024, 4096), [&](int64_t n) {
+    LB_TRY(lb_alloc_aggpart(e, n));  // agg | part (sized for the 16-row tiles of the new capacity)
+    LB_TRY(e->mem.get(&e->senders, (size_t)n));
+    LB_TRY(e->mem.get(&e->receivers, (size_t)n));
+    // (kernels may gather through index rows past the current edge count before they know it: keep every row a valid id)
+    LB_HIP(hipMemsetAsync(e->senders, 0, sizeof(int32_t) * (size_t)n, e->stream));
+    LB_HIP(hipMemsetAsync(e->receivers, 0, sizeof(int32_t) * (size_t)n, e->stream));
+    LB_TRY(e->mem.get(&e->efeat, (size_t)n * 8));
+    LB_TRY(e->mem.get(&e->efeat64, (size_t)n * 4));
+    LB_TRY(e->mem.get(&e->elat, (size_t)(n + 32) * LB_D));  // tile-blocked in the 16-row kernels: pad to a tile
+    LB_TRY(e->mem.get(&e->msg, (size_t)(n + 32) * LB_D));  // also the second edge-latent buffer of the ping-pong
+    return LB_OK;
+  });
 }
 
 // live_cnt[b] = particles of trajectory b whose type is not LB_PAD_TYPE (one workgroup per trajectory; integer sums)
@@ -357,7 +335,7 @@ extern "C" int lb_set_force(lb_engine* e, const double* force_dev) {
   if (!e || !force_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (e->g.force_kind != LB_FORCE_BUFFER)
     return lb_fail(LB_ERR_STATE, "engine was not created with LB_FORCE_BUFFER");
-  if (!e->force) LB_TRY(lb_alloc(&e->force, (size_t)e->BN * e->g.dim));
+  if (!e->force) LB_TRY(e->mem.get(&e->force, (size_t)e->BN * e->g.dim));
   LB_HIP(hipMemcpyAsync(e->force, force_dev, sizeof(double) * e->BN * e->g.dim,
                         hipMemcpyDeviceToDevice, e->stream));
   return LB_OK;
@@ -431,18 +409,13 @@ extern "C" int lb_nl_allocate(lb_engine* e, int32_t* cell_capacity_out, int32_t*
     int32_t want = std::max(16, ((2 * h->max_deg + 7) / 8) * 8);
     want = std::min<int32_t>(want, e->nl_dense ? LB_MAX_ROW_DENSE : LB_MAX_ROW);
     if (e->nl_dense) e->row_cap = std::max(e->row_cap, std::min<int32_t>((want + 63) / 64 * 64, LB_MAX_ROW_DENSE));
-    if (want > e->maxd || !e->tmp_send) {
-      LB_HIP(hipStreamSynchronize(e->stream));
-      for (void* b : {(void*)e->tmp_send, (void*)e->tmp_feat, (void*)e->tmp_feat64})
-        if (b) (void)hipFree(b);
-      e->tmp_send = nullptr;
-      e->tmp_feat = nullptr;
-      e->tmp_feat64 = nullptr;
-      e->maxd = want;
-      LB_TRY(lb_alloc(&e->tmp_send, (size_t)e->BN * want));
-      LB_TRY(lb_alloc(&e->tmp_feat, (size_t)e->BN * want * 4));
-      LB_TRY(lb_alloc(&e->tmp_feat64, (size_t)e->BN * want * 4));
-    }
+    if (want > e->maxd)
+      LB_TRY(lb_regrow(e->stream, &e->maxd, want, [&](int32_t n) {
+        LB_TRY(e->mem.get(&e->tmp_send, (size_t)e->BN * n));
+        LB_TRY(e->mem.get(&e->tmp_feat, (size_t)e->BN * n * 4));
+        LB_TRY(e->mem.get(&e->tmp_feat64, (size_t)e->BN * n * 4));
+        return LB_OK;
+      }));
   }
   if (cell_capacity_out) *cell_capacity_out = e->cell_capacity;
   if (e_cap_out) *e_cap_out = e->e_cap;
@@ -535,10 +508,10 @@ extern "C" int lb_segment_sum(lb_engine* e, const float* msg_dev, float* out_dev
 // ------------------------------------------------------------------------------------- GNS
 int lb_ensure_node_scratch(lb_engine* e) {
   const int64_t BN = e->BN;
-  if (!e->xnode) LB_TRY(lb_alloc(&e->xnode, (size_t)BN * LB_D));  // widest node input row
-  if (!e->nlat) LB_TRY(lb_alloc(&e->nlat, (size_t)BN * LB_D));
-  if (!e->agg) LB_TRY(lb_alloc_aggpart(e));
-  if (!e->psr) LB_TRY(lb_alloc(&e->psr, (size_t)BN * 2 * LB_D));
+  if (!e->xnode) LB_TRY(e->mem.get(&e->xnode, (size_t)BN * LB_D));  // widest node input row
+  if (!e->nlat) LB_TRY(e->mem.get(&e->nlat, (size_t)BN * LB_D));
+  if (!e->agg) LB_TRY(lb_alloc_aggpart(e, e->e_alloc));
+  if (!e->psr) LB_TRY(e->mem.get(&e->psr, (size_t)BN * 2 * LB_D));
   return LB_OK;
 }
 

@@ -44,6 +44,7 @@ struct lb_egnn_layer {
 };
 
 struct lb_egnn {
+  lb_arena mem;  // owns every buffer below (a view's weights belong to its caller)
   lb_egnn_desc desc;
   lb_engine* eng;
   int node_in, n_attr;
@@ -540,27 +541,29 @@ __global__ void k_eg_integrate(lb_geom g, int64_t BN, double* __restrict__ win, 
 // ------------------------------------------------------------------------------- model
 static int eg_ensure_edges(lb_egnn* m) {
   lb_engine* e = m->eng;
-  if (m->e_alloc >= e->e_alloc && m->msg) return LB_OK;
-  LB_HIP(hipStreamSynchronize(e->stream));
-  for (void* b : {(void*)m->msg, (void*)m->trans, (void*)m->rev, (void*)m->orph})
-    if (b) (void)hipFree(b);
-  m->msg = m->trans = nullptr;
-  m->rev = m->orph = nullptr;
-  const size_t n = (size_t)e->e_alloc;
-  LB_TRY(lb_alloc(&m->msg, n * m->desc.hidden));
-  LB_TRY(lb_alloc(&m->trans, n * 4));
-  LB_TRY(lb_alloc(&m->rev, n));
-  LB_TRY(lb_alloc(&m->orph, n + 1));
-  m->e_alloc = e->e_alloc;
-  return LB_OK;
+  if (m->e_alloc >= e->e_alloc) return LB_OK;
+  return lb_regrow(e->stream, &m->e_alloc, e->e_alloc, [&](int64_t cap) {
+    const size_t n = (size_t)cap;
+    LB_TRY(m->mem.get(&m->msg, n * m->desc.hidden));
+    LB_TRY(m->mem.get(&m->trans, n * 4));
+    LB_TRY(m->mem.get(&m->rev, n));
+    return m->mem.get(&m->orph, n + 1);
+  });
 }
 
 extern "C" void lb_egnn_destroy(lb_egnn* m) {
-  if (!m) return;
-  for (void* b : {(void*)m->blob, (void*)m->xnode, (void*)m->h, (void*)m->p, (void*)m->x32, (void*)m->vel,
-                  (void*)m->nattr, (void*)m->msg, (void*)m->trans, (void*)m->rev, (void*)m->orph})
-    if (b) (void)hipFree(b);
   delete m;
+}
+
+// the node-sized buffers of a model or a view
+static int eg_alloc_nodes(lb_egnn* m) {
+  const int64_t BN = m->eng->BN, H = m->desc.hidden;
+  LB_TRY(m->mem.get(&m->xnode, (size_t)BN * EG_KPAD));
+  LB_TRY(m->mem.get(&m->h, (size_t)BN * H));
+  LB_TRY(m->mem.get(&m->p, (size_t)BN * 2 * H));
+  LB_TRY(m->mem.get(&m->x32, (size_t)BN * 4));
+  LB_TRY(m->mem.get(&m->vel, (size_t)BN * 4));
+  return m->mem.get(&m->nattr, (size_t)BN);
 }
 
 static int64_t eg_n_floats(const lb_egnn_desc* d, int node_in, int n_attr) {
@@ -618,22 +621,12 @@ extern "C" int lb_egnn_create(lb_engine* e, const lb_egnn_desc* d, const float* 
   m->eng = e;
   m->node_in = node_in;
   m->n_attr = n_attr;
-  const int64_t BN = e->BN, H = d->hidden;
-  int rc = LB_OK;
-  auto step = [&](int r) {
-    if (!rc) rc = r;
-  };
-  step(lb_alloc(&m->blob, (size_t)n_floats));
+  int rc = m->mem.get(&m->blob, (size_t)n_floats);
   if (!rc) {
     const hipError_t he = hipMemcpy(m->blob, w, sizeof(float) * n_floats, hipMemcpyHostToDevice);
     if (he != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he));
   }
-  step(lb_alloc(&m->xnode, (size_t)BN * EG_KPAD));
-  step(lb_alloc(&m->h, (size_t)BN * H));
-  step(lb_alloc(&m->p, (size_t)BN * 2 * H));
-  step(lb_alloc(&m->x32, (size_t)BN * 4));
-  step(lb_alloc(&m->vel, (size_t)BN * 4));
-  step(lb_alloc(&m->nattr, (size_t)BN));
+  if (!rc) rc = eg_alloc_nodes(m);
   if (rc) {
     lb_egnn_destroy(m);
     return rc;
@@ -653,18 +646,7 @@ int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev
   m->eng = e;
   m->node_in = node_in;
   m->n_attr = e->g.force_kind != LB_FORCE_NONE ? 1 : 0;
-  const int64_t BN = e->BN, H = d->hidden;
-  int rc = LB_OK;
-  auto step = [&](int r) {
-    if (!rc) rc = r;
-  };
-  step(lb_alloc(&m->xnode, (size_t)BN * EG_KPAD));
-  step(lb_alloc(&m->h, (size_t)BN * H));
-  step(lb_alloc(&m->p, (size_t)BN * 2 * H));
-  step(lb_alloc(&m->x32, (size_t)BN * 4));
-  step(lb_alloc(&m->vel, (size_t)BN * 4));
-  step(lb_alloc(&m->nattr, (size_t)BN));
-  if (rc) {
+  if (const int rc = eg_alloc_nodes(m)) {
     lb_egnn_destroy(m);
     return rc;
   }

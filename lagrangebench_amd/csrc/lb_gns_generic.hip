@@ -355,14 +355,8 @@ int lbk_gns_forward_generic(lb_engine* e, lb_gns* g) {
   const int D = LB_D, L = g->desc.num_mp_steps, nl = g->desc.blocks_per_step;
   int rc;
   // edge-sized hidden buffer, grown with the edge capacity (tile-blocked like the edge latents)
-  if (nl > 1 && g->gen_he_cap < e->e_alloc) {
-    LB_HIP(hipStreamSynchronize(s));
-    if (g->gen_he) (void)hipFree(g->gen_he);
-    g->gen_he = nullptr;
-    g->gen_he_cap = 0;
-    LB_TRY(lb_alloc(&g->gen_he, (size_t)(e->e_alloc + 32) * D));
-    g->gen_he_cap = e->e_alloc;
-  }
+  if (nl > 1 && g->gen_he_cap < e->e_alloc)
+    LB_TRY(lb_regrow(s, &g->gen_he_cap, e->e_alloc, [&](int64_t cap) { return g->mem.get(&g->gen_he, (size_t)(cap + 32) * D); }));
   const int64_t e_bound = e->e_alloc;
   auto W = [&](const lb_gen_lin& l, int blk) { return e->f16x2 ? l.wh[blk] : l.wf[blk]; };
   auto base_args = [&]() {

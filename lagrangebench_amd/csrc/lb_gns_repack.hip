@@ -17,6 +17,7 @@
 #include "lb_internal.h"
 
 struct lb_repack {
+  lb_arena mem;  // owns every buffer below
   lb_pack_job* jobs = nullptr;
   lb_pack_piece* pieces = nullptr;
   lb_pack_block* blocks = nullptr;
@@ -30,10 +31,6 @@ struct lb_repack {
 };
 
 void lb_repack_free(lb_repack* r) {
-  if (!r) return;
-  for (void* p : {(void*)r->jobs, (void*)r->pieces, (void*)r->blocks, (void*)r->reds, (void*)r->rms, (void*)r->head_mx, (void*)r->stats})
-    if (p) (void)hipFree(p);
-  if (r->stats_host) (void)hipHostFree(r->stats_host);
   delete r;
 }
 
@@ -79,8 +76,8 @@ __global__ void __launch_bounds__(LB_PACK_LANES) k_repack(const lb_pack_job* __r
 }
 
 template <typename T>
-static int repack_upload(T** dev, const std::vector<T>& v) {
-  LB_TRY(lb_alloc(dev, v.size()));
+static int repack_upload(lb_arena& mem, T** dev, const std::vector<T>& v) {
+  LB_TRY(mem.get(dev, v.size()));
   if (!v.empty()) LB_HIP(hipMemcpy(*dev, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
   return LB_OK;
 }
@@ -99,15 +96,14 @@ static int repack_build(lb_gns* g, const std::vector<int64_t>& cmap, int64_t n_c
   r->src_floats = n_src;
   std::vector<lb_pack_red> reds = plan.rms;
   if (r->has_head) reds.push_back(plan.head);
-  LB_TRY(repack_upload(&r->jobs, plan.jobs));
-  LB_TRY(repack_upload(&r->pieces, plan.pieces));
-  LB_TRY(repack_upload(&r->blocks, plan.blocks));
-  LB_TRY(repack_upload(&r->reds, reds));
-  LB_TRY(lb_alloc(&r->rms, (size_t)r->n_rms));
-  LB_TRY(lb_alloc(&r->head_mx, 1));
-  LB_TRY(lb_alloc(&r->stats, 1));
-  LB_HIP(hipHostMalloc((void**)&r->stats_host, sizeof(lb_pack_stats), hipHostMallocDefault));
-  return LB_OK;
+  LB_TRY(repack_upload(r->mem, &r->jobs, plan.jobs));
+  LB_TRY(repack_upload(r->mem, &r->pieces, plan.pieces));
+  LB_TRY(repack_upload(r->mem, &r->blocks, plan.blocks));
+  LB_TRY(repack_upload(r->mem, &r->reds, reds));
+  LB_TRY(r->mem.get(&r->rms, (size_t)r->n_rms));
+  LB_TRY(r->mem.get(&r->head_mx, 1));
+  LB_TRY(r->mem.get(&r->stats, 1));
+  return r->mem.get_pinned(&r->stats_host, 1);
 }
 
 int lbk_gns_repack(lb_engine* e, lb_gns* g, const float* w_dev, const std::vector<int64_t>& cmap, int64_t n_compact,

@@ -254,11 +254,8 @@ struct lb_stage {
     for (size_t i = 0; i < (size_t)l.rows * l.out; ++i) mx = std::max(mx, std::fabs(l.w[i]));
     sh = lb_head_shift(mx);
   }
-  int upload(float** blob) {
-    if (hipMalloc((void**)blob, host.size() * sizeof(float)) != hipSuccess) {
-      *blob = nullptr;
-      return lb_fail(LB_ERR_HIP, "hipMalloc(weights) failed");
-    }
+  int upload(lb_arena& mem, float** blob) {
+    LB_TRY(mem.get(blob, host.size()));
     if (hipMemcpy(*blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
       return lb_fail(LB_ERR_HIP, "weight upload failed");
     for (const auto& f : fix) *f.first = *blob + f.second;
@@ -444,11 +441,11 @@ extern "C" int lb_gns_create(lb_engine* e, const lb_gns_desc* d, const float* w,
   lb_stage st;
   lb_gns_stage_all(st, v, g);
   g->blob_floats = (int64_t)st.host.size();
-  int rc = st.upload(&g->blob);
+  int rc = st.upload(g->mem, &g->blob);
   if (!rc) lb_gns_rms_guard(e, st.w_rms_min);
   if (!rc) rc = lb_ensure_node_scratch(e);
   if (!rc) rc = lb_gns_bind(e, g);
-  for (int i = 0; i < 3 && g->generic && !rc; ++i) rc = lb_alloc(&g->gen_hn[i], (size_t)e->BN * LB_D);  // hidden rows
+  for (int i = 0; i < 3 && g->generic && !rc; ++i) rc = g->mem.get(&g->gen_hn[i], (size_t)e->BN * LB_D);  // hidden rows
   if (rc) {
     lb_gns_destroy(g);
     return rc;
@@ -590,11 +587,7 @@ int lb_gns_bind(lb_engine* e, lb_gns* g) {
 extern "C" void lb_gns_destroy(lb_gns* g) {
   if (!g) return;
   if (g->eng && g->eng->bound_model == g) g->eng->bound_model = nullptr;
-  if (g->blob) (void)hipFree(g->blob);
   lb_repack_free(g->repack);
-  for (float* b : g->gen_hn)
-    if (b) (void)hipFree(b);
-  if (g->gen_he) (void)hipFree(g->gen_he);
   delete g;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/lbhip.h"
+#include "lb_arena.h"
 
 #define LB_MAX_STENCIL_CAND 2048  // candidates staged in LDS per cell block (27*cap must fit)
 #define LB_MAX_ROW 256            // row buffer of the default neighbor kernels (neighbors per particle)
@@ -122,6 +123,7 @@ struct lb_timer_rec {
 };
 
 struct lb_engine {
+  lb_arena mem;  // owns every device / pinned buffer below
   lb_case_desc desc;
   lb_geom g;
   hipStream_t stream;
@@ -292,6 +294,7 @@ struct lb_gen_mlp {
 };
 
 struct lb_gns {
+  lb_arena mem;  // owns blob, gen_hn, gen_he
   lb_gns_desc desc;
   lb_engine* eng;
   float* blob;         // single device allocation holding every image below
@@ -325,13 +328,6 @@ int lb_fail(int code, const char* fmt, ...);
                      __FILE__, __LINE__);                                              \
   } while (0)
 
-template <typename T>
-static inline int lb_alloc(T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) n = 1;
-  LB_HIP(hipMalloc((void**)p, n * sizeof(T)));
-  return LB_OK;
-}
 #define LB_TRY(x)          \
   do {                     \
     int _rc = (x);         \
@@ -366,7 +362,7 @@ void lb_tic_single(lb_engine* e, int cls);
 
 // lb_api.hip
 int lb_ensure_edges(lb_engine* e, int64_t need);
-int lb_alloc_aggpart(lb_engine* e);
+int lb_alloc_aggpart(lb_engine* e, int64_t n_edges);
 
 // lb_neighbor.hip
 int lbk_nl_build(lb_engine* e, bool want_efeat64);

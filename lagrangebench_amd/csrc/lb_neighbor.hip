@@ -1882,16 +1882,11 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
                        strided_slots < ((int64_t)1 << 30);
 #endif
   if (strided) {
-    if (strided_slots > e->cell_slots) {   // (first build after an allocation: never inside a graph capture)
-      LB_HIP(hipStreamSynchronize(s));
-      if (e->cell_part) (void)hipFree(e->cell_part);
-      if (e->cpos) (void)hipFree(e->cpos);
-      e->cell_part = nullptr;
-      e->cpos = nullptr;
-      e->cell_slots = strided_slots + strided_slots / 4;
-      LB_HIP(hipMalloc((void**)&e->cell_part, sizeof(int32_t) * (size_t)e->cell_slots));
-      LB_HIP(hipMalloc((void**)&e->cpos, sizeof(double) * (size_t)g.dim * (size_t)e->cell_slots));
-    }
+    if (strided_slots > e->cell_slots)   // (first build after an allocation: never inside a graph capture)
+      LB_TRY(lb_regrow(s, &e->cell_slots, strided_slots + strided_slots / 4, [&](int64_t n) {
+        LB_TRY(e->mem.get(&e->cell_part, (size_t)n));
+        return e->mem.get(&e->cpos, (size_t)g.dim * (size_t)n);
+      }));
     e->cells_traj_ready = false;   // (cell_count is rewritten: k_cells_traj's occupancy slots must be zeroed again after this)
     hipLaunchKernelGGL(k_cell_zero, dim3((ncell_tot + 255) / 256), dim3(256), 0, s, e->ctrl, e->cell_count, ncell_tot);
     hipLaunchKernelGGL(k_cell_bin, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,

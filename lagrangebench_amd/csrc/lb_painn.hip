@@ -59,6 +59,7 @@ struct pn_layer {
 };
 
 struct lb_painn {
+  lb_arena mem;  // owns every buffer below
   lb_painn_desc desc;
   lb_engine* eng;
   int n_scal, n_vec, c_frc, c_bnd;  // scalar inputs, vector channels, raw-row columns of force / bound (-1: absent)
@@ -419,28 +420,17 @@ static void pn_pack(const float* W, int K, int NO, float* dst) {
 
 static int pn_ensure_edges(lb_painn* m) {
   lb_engine* e = m->eng;
-  if (m->e_alloc >= e->e_alloc && m->rev) return LB_OK;
-  LB_HIP(hipStreamSynchronize(e->stream));
-  for (void* b : {(void*)m->rev, (void*)m->orph, (void*)m->geo, (void*)m->nrm})
-    if (b) (void)hipFree(b);
-  m->rev = m->orph = nullptr;
-  m->geo = nullptr;
-  m->nrm = nullptr;
-  const size_t n = (size_t)e->e_alloc;
-  LB_TRY(lb_alloc(&m->rev, n));
-  LB_TRY(lb_alloc(&m->orph, n + 1));
-  LB_TRY(lb_alloc(&m->geo, n));
-  LB_TRY(lb_alloc(&m->nrm, n));
-  m->e_alloc = e->e_alloc;
-  return LB_OK;
+  if (m->e_alloc >= e->e_alloc) return LB_OK;
+  return lb_regrow(e->stream, &m->e_alloc, e->e_alloc, [&](int64_t cap) {
+    const size_t n = (size_t)cap;
+    LB_TRY(m->mem.get(&m->rev, n));
+    LB_TRY(m->mem.get(&m->orph, n + 1));
+    LB_TRY(m->mem.get(&m->geo, n));
+    return m->mem.get(&m->nrm, n);
+  });
 }
 
 extern "C" void lb_painn_destroy(lb_painn* m) {
-  if (!m) return;
-  for (void* b : {(void*)m->blob, (void*)m->packed, (void*)m->xnode, (void*)m->s, (void*)m->va, (void*)m->vb,
-                  (void*)m->x3, (void*)m->h1, (void*)m->ts, (void*)m->vm, (void*)m->rev, (void*)m->orph, (void*)m->geo,
-                  (void*)m->nrm})
-    if (b) (void)hipFree(b);
   delete m;
 }
 
@@ -489,19 +479,19 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
   auto step = [&](int r) {
     if (!rc) rc = r;
   };
-  step(lb_alloc(&m->blob, (size_t)n_floats));
+  step(m->mem.get(&m->blob, (size_t)n_floats));
   if (!rc) {
     const hipError_t he = hipMemcpy(m->blob, w, sizeof(float) * n_floats, hipMemcpyHostToDevice);
     if (he != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he));
   }
-  step(lb_alloc(&m->xnode, (size_t)BN * PN_KPAD));
-  step(lb_alloc(&m->s, (size_t)BN * H));
-  step(lb_alloc(&m->va, (size_t)BN * dim * H));
-  step(lb_alloc(&m->vb, (size_t)BN * dim * H));
-  step(lb_alloc(&m->x3, (size_t)BN * 3 * H));
-  step(lb_alloc(&m->h1, (size_t)BN * H));
-  step(lb_alloc(&m->ts, (size_t)BN * 2 * H));
-  step(lb_alloc(&m->vm, (size_t)BN * dim * 2 * H));
+  step(m->mem.get(&m->xnode, (size_t)BN * PN_KPAD));
+  step(m->mem.get(&m->s, (size_t)BN * H));
+  step(m->mem.get(&m->va, (size_t)BN * dim * H));
+  step(m->mem.get(&m->vb, (size_t)BN * dim * H));
+  step(m->mem.get(&m->x3, (size_t)BN * 3 * H));
+  step(m->mem.get(&m->h1, (size_t)BN * H));
+  step(m->mem.get(&m->ts, (size_t)BN * 2 * H));
+  step(m->mem.get(&m->vm, (size_t)BN * dim * 2 * H));
   if (rc) {
     lb_painn_destroy(m);
     return rc;
@@ -581,7 +571,7 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
     offs.push_back(po);
     po += pn_frag_floats(j.K, j.NO);
   }
-  if (lb_alloc(&m->packed, (size_t)pf / 4) == LB_OK) {
+  if (m->mem.get(&m->packed, (size_t)pf / 4) == LB_OK) {
     const hipError_t he = hipMemcpy(m->packed, img.data(), sizeof(float) * pf, hipMemcpyHostToDevice);
     if (he != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he));
   } else {

@@ -71,41 +71,35 @@ struct lb_sg_block {       // one O3TensorProduct(+Gate) on the device
 };
 
 struct lb_segnn {
+  lb_arena mem;  // owns every buffer below
   lb_segnn_desc desc;
-  lb_engine* eng;
+  lb_engine* eng = nullptr;
   lb_sgg* gen = nullptr;   // non-null: general irreps / norm (lb_segnn_gen.hip); nothing else below is used then
-  int node_ns, node_nv, node_ns4, node_nv4, node_stride;
-  float* blob;
-  lb_sg_block embedding, output;
+  int node_ns = 0, node_nv = 0, node_ns4 = 0, node_nv4 = 0, node_stride = 0;
+  float* blob = nullptr;
+  lb_sg_block embedding{}, output{};
   std::vector<lb_sg_block> message, update, readout;  // [layer*B + i], readout[i]
   // node-sized scratch
-  float* xnode;    // [BN][32]  engine feature row (GNS column order, no embedding)
-  float* nodesv;   // [BN][node_stride]
-  float* nattr;    // [BN][4]
-  float* f;        // [BN][128] hidden state
-  float* agg;      // [BN][128]; followed in the SAME allocation by
-  float* part;     // [ceil(e_alloc / 16) + 2][2][128]: k_sg_msg's per-tile partial slots (one buffer descriptor)
-  int64_t aggpart_bytes;
-  float* tn[2];    // [BN][128] block intermediates
+  float* xnode = nullptr;    // [BN][32]  engine feature row (GNS column order, no embedding)
+  float* nodesv = nullptr;   // [BN][node_stride]
+  float* nattr = nullptr;    // [BN][4]
+  float* f = nullptr;        // [BN][128] hidden state
+  float* agg = nullptr;      // [BN][128]; followed in the SAME allocation by
+  float* part = nullptr;     // [ceil(e_alloc / 16) + 2][2][128]: k_sg_msg's per-tile partial slots (one buffer descriptor)
+  int64_t aggpart_bytes = 0;
+  float* tn[2] = {nullptr, nullptr};  // [BN][128] block intermediates
   // edge-sized scratch (regrown with the engine's e_alloc)
-  int64_t e_alloc;
-  float* eattr;    // [e_alloc][4]
-  float* msgsv;    // [e_alloc][16]
-  float* tap;
+  int64_t e_alloc = 0;
+  float* eattr = nullptr;    // [e_alloc][4]
+  float* msgsv = nullptr;    // [e_alloc][16]
+  float* tap = nullptr;
   std::vector<const float*> msg_image;  // per layer: LDS image of the fused message kernel
   std::vector<const float*> upd_image;  // per layer: LDS image of the fused update kernel
   const float* embed_image = nullptr;    // k_sg_embed (node prep + O3Embedding), k_sg_readout (O3Decoder + integrator)
   const float* readout_image = nullptr;
   bool fused_node = false;
-  bool fused_msg;  // gather + both message blocks + segment_sum in one kernel (blocks_per_step == 2)
+  bool fused_msg = false;  // gather + both message blocks + segment_sum in one kernel (blocks_per_step == 2)
 };
-
-template <typename T>
-static int sg_alloc(T** p, size_t n) {
-  *p = nullptr;
-  LB_HIP(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return LB_OK;
-}
 
 // ------------------------------------------------------------------------------- attributes
 // Edge attributes = spherical harmonics of the relative displacement, and the additional message
@@ -356,29 +350,22 @@ static int sg_launch(lb_engine* e, const lb_sg_block& b, int mode, int n_op_used
 // ------------------------------------------------------------------------------------ model
 static int sg_ensure_edges(lb_segnn* m) {
   lb_engine* e = m->eng;
-  if (m->e_alloc >= e->e_alloc && m->eattr) return LB_OK;
-  LB_HIP(hipStreamSynchronize(e->stream));
-  if (m->eattr) (void)hipFree(m->eattr);
-  if (m->msgsv) (void)hipFree(m->msgsv);
-  m->eattr = m->msgsv = nullptr;
-  LB_TRY(sg_alloc(&m->eattr, (size_t)e->e_alloc * 4));
-  LB_TRY(sg_alloc(&m->msgsv, (size_t)e->e_alloc * 16));
-  if (m->agg) (void)hipFree(m->agg);
-  m->agg = nullptr;
-  const size_t n_agg = (size_t)e->BN * 128, n_part = ((size_t)e->e_alloc / 16 + 2) * 2 * 128;
-  LB_TRY(sg_alloc(&m->agg, n_agg + n_part));
-  m->part = m->agg + n_agg;
-  m->aggpart_bytes = (int64_t)(n_agg + n_part) * 4;
-  m->e_alloc = e->e_alloc;
-  return LB_OK;
+  if (m->e_alloc >= e->e_alloc) return LB_OK;
+  return lb_regrow(e->stream, &m->e_alloc, e->e_alloc, [&](int64_t cap) {
+    LB_TRY(m->mem.get(&m->eattr, (size_t)cap * 4));
+    LB_TRY(m->mem.get(&m->msgsv, (size_t)cap * 16));
+    const size_t n_agg = (size_t)e->BN * 128, n_part = ((size_t)cap / 16 + 2) * 2 * 128;
+    m->part = nullptr;
+    LB_TRY(m->mem.get(&m->agg, n_agg + n_part));
+    m->part = m->agg + n_agg;
+    m->aggpart_bytes = (int64_t)(n_agg + n_part) * 4;
+    return LB_OK;
+  });
 }
 
 extern "C" void lb_segnn_destroy(lb_segnn* m) {
   if (!m) return;
   if (m->gen) lb_sgg_destroy(m->gen);
-  for (void* b : {(void*)m->blob, (void*)m->xnode, (void*)m->nodesv, (void*)m->nattr, (void*)m->f,
-                  (void*)m->agg, (void*)m->tn[0], (void*)m->tn[1], (void*)m->eattr, (void*)m->msgsv})
-    if (b) (void)hipFree(b);
   delete m;
 }
 
@@ -393,8 +380,6 @@ extern "C" int lb_segnn_create(lb_engine* e, const lb_segnn_desc* d, const float
     lb_segnn* m = new lb_segnn();
     m->desc = *d;
     m->eng = e;
-    m->blob = nullptr; m->xnode = m->nodesv = m->nattr = m->f = m->agg = m->part = nullptr;
-    m->tn[0] = m->tn[1] = nullptr; m->eattr = m->msgsv = nullptr; m->tap = nullptr; m->e_alloc = 0;
     const int rc = lb_sgg_create(e, d, w, n_floats, &m->gen);
     if (rc) {
       delete m;
@@ -520,7 +505,7 @@ extern "C" int lb_segnn_create(lb_engine* e, const lb_segnn_desc* d, const float
     lb_sg_readout_image(r0.raw_ws, r0.raw_wv, r0.raw_b, r1.raw_ws, r1.raw_wv, r1.raw_b, ro.raw_wv, ri.data());
     readout_off = put(ri.data(), ri.size());
   }
-  int rc = sg_alloc(&m->blob, host.size());
+  int rc = m->mem.get(&m->blob, host.size());
   if (!rc && hipMemcpy(m->blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
     rc = lb_fail(LB_ERR_HIP, "weight upload failed");
   size_t idx = 0;
@@ -551,12 +536,12 @@ extern "C" int lb_segnn_create(lb_engine* e, const lb_segnn_desc* d, const float
     }
   }
   const int64_t BN = e->BN;
-  if (!rc) rc = sg_alloc(&m->xnode, (size_t)BN * 32);
-  if (!rc) rc = sg_alloc(&m->nodesv, (size_t)BN * m->node_stride);
-  if (!rc) rc = sg_alloc(&m->nattr, (size_t)BN * 4);
-  if (!rc) rc = sg_alloc(&m->f, (size_t)BN * 128);
-  if (!rc) rc = sg_alloc(&m->tn[0], (size_t)BN * 128);
-  if (!rc) rc = sg_alloc(&m->tn[1], (size_t)BN * 128);
+  if (!rc) rc = m->mem.get(&m->xnode, (size_t)BN * 32);
+  if (!rc) rc = m->mem.get(&m->nodesv, (size_t)BN * m->node_stride);
+  if (!rc) rc = m->mem.get(&m->nattr, (size_t)BN * 4);
+  if (!rc) rc = m->mem.get(&m->f, (size_t)BN * 128);
+  if (!rc) rc = m->mem.get(&m->tn[0], (size_t)BN * 128);
+  if (!rc) rc = m->mem.get(&m->tn[1], (size_t)BN * 128);
   if (rc) {
     lb_segnn_destroy(m);
     return rc;

@@ -633,6 +633,7 @@ struct sgg_block {            // one O3TensorProduct on the device: everything o
 }  // namespace
 
 struct lb_sgg {
+  lb_arena mem;  // owns every buffer below
   lb_segnn_desc desc;
   lb_engine* eng = nullptr;
   int La = 1, Lh = 1, n = 0, norm = 0;
@@ -658,28 +659,16 @@ struct lb_sgg {
 
 namespace {
 
-template <typename T>
-int sgg_alloc(T** p, size_t n) {
-  *p = nullptr;
-  LB_HIP(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return LB_OK;
-}
-
 int sgg_ensure_edges(lb_sgg* m) {
   lb_engine* e = m->eng;
-  if (m->e_alloc >= e->e_alloc && m->eattr4) return LB_OK;
-  LB_HIP(hipStreamSynchronize(e->stream));
-  for (float** p : {&m->eattr4, &m->eattr, &m->msgsv, &m->te[0], &m->te[1]}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  LB_TRY(sgg_alloc(&m->eattr4, (size_t)e->e_alloc * 4));
-  if (m->La >= 2) LB_TRY(sgg_alloc(&m->eattr, (size_t)e->e_alloc * 12));
-  LB_TRY(sgg_alloc(&m->msgsv, (size_t)e->e_alloc * 16));
-  LB_TRY(sgg_alloc(&m->te[0], (size_t)e->e_alloc * m->HS));
-  LB_TRY(sgg_alloc(&m->te[1], (size_t)e->e_alloc * m->HS));
-  m->e_alloc = e->e_alloc;
-  return LB_OK;
+  if (m->e_alloc >= e->e_alloc) return LB_OK;
+  return lb_regrow(e->stream, &m->e_alloc, e->e_alloc, [&](int64_t cap) {
+    LB_TRY(m->mem.get(&m->eattr4, (size_t)cap * 4));
+    if (m->La >= 2) LB_TRY(m->mem.get(&m->eattr, (size_t)cap * 12));
+    LB_TRY(m->mem.get(&m->msgsv, (size_t)cap * 16));
+    LB_TRY(m->mem.get(&m->te[0], (size_t)cap * m->HS));
+    return m->mem.get(&m->te[1], (size_t)cap * m->HS);
+  });
 }
 
 int sgg_launch(lb_sgg* m, const sgg_block& b, int64_t rows, bool rows_from_ctrl, const float* const* xs, const int32_t* const* gathers,
@@ -746,11 +735,6 @@ int sgg_batch_norm(lb_sgg* m, int64_t off_w, int64_t off_b, float* x, bool edges
 }  // namespace
 
 void lb_sgg_destroy(lb_sgg* m) {
-  if (!m) return;
-  for (void* b : {(void*)m->blob, (void*)m->ktab, (void*)m->xnode, (void*)m->nodesv, (void*)m->nattr4, (void*)m->nattr, (void*)m->f, (void*)m->agg,
-                  (void*)m->tn[0], (void*)m->tn[1], (void*)m->eattr4, (void*)m->eattr, (void*)m->msgsv, (void*)m->te[0],
-                  (void*)m->te[1], (void*)m->bn_part, (void*)m->bn_mean, (void*)m->bn_scale, (void*)m->bn_shift})
-    if (b) (void)hipFree(b);
   delete m;
 }
 void lb_sgg_set_tap(lb_sgg* m, float* tap) { m->tap = tap; }
@@ -993,10 +977,10 @@ int lb_sgg_create(lb_engine* e, const lb_segnn_desc* d, const float* w, int64_t 
     return lb_fail(LB_ERR_HIP, "hipFuncSetAttribute(k_sgg_tp, %zu bytes of LDS) failed", max_lds);
   }
   lds_set[which] = std::max(lds_set[which], max_lds);
-  int rc = sgg_alloc(&m->blob, host.size());
+  int rc = m->mem.get(&m->blob, host.size());
   if (!rc && hipMemcpy(m->blob, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
     rc = lb_fail(LB_ERR_HIP, "weight upload failed");
-  if (!rc) rc = sgg_alloc(&m->ktab, ktab_host.size());
+  if (!rc) rc = m->mem.get(&m->ktab, ktab_host.size());
   if (!rc && hipMemcpy(m->ktab, ktab_host.data(), ktab_host.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
     rc = lb_fail(LB_ERR_HIP, "table upload failed");
   for (sgg_block& b : m->blocks) {
@@ -1006,16 +990,16 @@ int lb_sgg_create(lb_engine* e, const lb_segnn_desc* d, const float* w, int64_t 
     b.a.bias = m->blob + reinterpret_cast<size_t>(b.a.bias);
   }
   const int64_t BN = e->BN;
-  if (!rc) rc = sgg_alloc(&m->xnode, (size_t)BN * 32);
-  if (!rc) rc = sgg_alloc(&m->nodesv, (size_t)BN * m->node_stride);
-  if (!rc) rc = sgg_alloc(&m->nattr4, (size_t)BN * 4);
-  if (!rc && m->La >= 2) rc = sgg_alloc(&m->nattr, (size_t)BN * 12);
+  if (!rc) rc = m->mem.get(&m->xnode, (size_t)BN * 32);
+  if (!rc) rc = m->mem.get(&m->nodesv, (size_t)BN * m->node_stride);
+  if (!rc) rc = m->mem.get(&m->nattr4, (size_t)BN * 4);
+  if (!rc && m->La >= 2) rc = m->mem.get(&m->nattr, (size_t)BN * 12);
   for (float** q : {&m->f, &m->agg, &m->tn[0], &m->tn[1]})
-    if (!rc) rc = sgg_alloc(q, (size_t)BN * m->HS);
+    if (!rc) rc = m->mem.get(q, (size_t)BN * m->HS);
   if (!rc && m->norm == 2) {
-    rc = sgg_alloc(&m->bn_part, (size_t)e->g.B * m->bn_G * m->HS);
+    rc = m->mem.get(&m->bn_part, (size_t)e->g.B * m->bn_G * m->HS);
     for (float** q : {&m->bn_mean, &m->bn_scale, &m->bn_shift})
-      if (!rc) rc = sgg_alloc(q, (size_t)e->g.B * m->HS);
+      if (!rc) rc = m->mem.get(q, (size_t)e->g.B * m->HS);
   }
   if (rc) {
     lb_sgg_destroy(m);

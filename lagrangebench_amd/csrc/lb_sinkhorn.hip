@@ -163,14 +163,10 @@ __global__ void __launch_bounds__(256) k_sk_scalar(int op, const double* __restr
 
 namespace {
 struct SkScratch {
+  lb_arena mem;  // owns the buffers below for the length of one call
   double *f = nullptr, *g = nullptr, *f2 = nullptr, *g2 = nullptr, *marg = nullptr, *scal = nullptr;
   double* host = nullptr;
   int n = 0;
-  ~SkScratch() {
-    for (double* p : {f, g, f2, g2, marg, scal})
-      if (p) (void)hipFree(p);
-    if (host) (void)hipHostFree(host);
-  }
 };
 
 template <int MODE>
@@ -232,9 +228,9 @@ int lbk_sinkhorn(lb_engine* e, const double* pred, int pred_T, const double* tar
                  int n_out, double threshold, double* out_dev, int32_t* iters_host) {
   const int N = e->g.N, dim = e->g.dim;
   SkScratch s;
-  for (double** p : {&s.f, &s.g, &s.f2, &s.g2, &s.marg}) LB_HIP(hipMalloc((void**)p, sizeof(double) * N));
-  LB_HIP(hipMalloc((void**)&s.scal, sizeof(double) * 4));
-  LB_HIP(hipHostMalloc((void**)&s.host, sizeof(double) * 4));
+  for (double** p : {&s.f, &s.g, &s.f2, &s.g2, &s.marg}) LB_TRY(s.mem.get(p, (size_t)N));
+  LB_TRY(s.mem.get(&s.scal, 4));
+  LB_TRY(s.mem.get_pinned(&s.host, 4));
   std::vector<double> res((size_t)e->g.B * n_out);
   for (int b = 0; b < e->g.B; ++b)
     for (int k = 0; k < n_out; ++k) {
@@ -370,13 +366,9 @@ __global__ void __launch_bounds__(256) k_pot_ctrl(int op, lb_pot_ctrl* __restric
 
 namespace {
 struct PotScratch {
+  lb_arena mem;  // owns the buffers below for the length of one call
   double *u2 = nullptr, *v2 = nullptr, *marg = nullptr;
   lb_pot_ctrl *ctrl = nullptr, *host = nullptr;
-  ~PotScratch() {
-    for (void* p : {(void*)u2, (void*)v2, (void*)marg, (void*)ctrl})
-      if (p) (void)hipFree(p);
-    if (host) (void)hipHostFree(host);
-  }
 };
 
 template <int MODE>
@@ -431,11 +423,11 @@ int lbk_sinkhorn_pot(lb_engine* e, const double* pred, int pred_T, const double*
                      int n_out, double reg, int max_it, double thr, double* out_dev, int32_t* info_host) {
   const int N = e->g.N, dim = e->g.dim;
   PotScratch s;
-  LB_HIP(hipMalloc((void**)&s.u2, sizeof(double) * 2 * N));
-  LB_HIP(hipMalloc((void**)&s.v2, sizeof(double) * 2 * N));
-  LB_HIP(hipMalloc((void**)&s.marg, sizeof(double) * N));
-  LB_HIP(hipMalloc((void**)&s.ctrl, sizeof(lb_pot_ctrl)));
-  LB_HIP(hipHostMalloc((void**)&s.host, sizeof(lb_pot_ctrl)));
+  LB_TRY(s.mem.get(&s.u2, (size_t)2 * N));
+  LB_TRY(s.mem.get(&s.v2, (size_t)2 * N));
+  LB_TRY(s.mem.get(&s.marg, (size_t)N));
+  LB_TRY(s.mem.get(&s.ctrl, 1));
+  LB_TRY(s.mem.get_pinned(&s.host, 1));
   std::vector<double> res((size_t)e->g.B * n_out);
   for (int b = 0; b < e->g.B; ++b)
     for (int k = 0; k < n_out; ++k) {

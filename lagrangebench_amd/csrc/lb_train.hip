@@ -71,6 +71,7 @@ struct lb_sgt;  // SEGNN-specific state of a training handle (lb_train_segnn.h)
 struct lb_egt;  // EGNN-specific state of a training handle (lb_train_egnn.h)
 
 struct lb_gns_train {
+  lb_arena mem;           // owns every device / pinned buffer of the handle, those of t->sg / t->eg included
   lb_sgt* sg = nullptr;   // non-null: this handle trains a SEGNN (created by lb_segnn_train_create)
   lb_egt* eg = nullptr;   // non-null: this handle trains an EGNN (created by lb_egnn_train_create)
   lb_gns_desc desc;
@@ -107,10 +108,11 @@ struct lb_gns_train {
   int32_t* cnt_dev = nullptr;  // non-kinematic particles per trajectory
   // sender-sorted view of the edge list (round 4): the transpose of the [n_s | n_r | e] gather sums, per node, the
   // gradient rows of the edges it SENDS - in ascending edge order, no atomics, bit-reproducible
-  int32_t *snd_key = nullptr, *snd_perm = nullptr, *iota = nullptr, *snd_key_in = nullptr, *snd_ptr = nullptr;
+  int32_t *snd_key = nullptr, *snd_perm = nullptr, *iota = nullptr, *snd_ptr = nullptr;
   void* sort_tmp = nullptr;
   size_t sort_tmp_bytes = 0;
-  int64_t sort_cap = 0;
+  int64_t sort_cap = 0;       // entries of snd_perm / snd_ptr, and of snd_key / iota when
+  bool sort_radix = false;    // ... the radix sort's set (snd_key, iota, sort_tmp) is allocated too
   // the operand matrices of k_lin32 in MFMA fragment order (lb_lin32.h): registered at their first use, re-packed from the
   // weight blob at the top of every lb_gns_train_loss_grad (one launch)
   std::vector<lb_pack_ent> pack_tab;
@@ -974,8 +976,8 @@ static int pack_lookup(lb_gns_train* t, const float* W, int NR, int NO, int ldw,
     }
   if (!t->wpack) {
     t->wpack_cap = 4 * t->n_floats + ((int64_t)1 << 21);   // both orientations, in both arithmetics (lb_train_exact_math)
-    LB_TRY(lb_alloc(&t->wpack, (size_t)t->wpack_cap));
-    LB_TRY(lb_alloc(&t->pack_dev, (size_t)LB_PACK_MAX));
+    LB_TRY(t->mem.get(&t->wpack, (size_t)t->wpack_cap));
+    LB_TRY(t->mem.get(&t->pack_dev, (size_t)LB_PACK_MAX));
   }
   lb_pack_ent e{};
   e.src = src; e.dst = t->wpack_floats; e.NR = NR; e.NO = NO; e.ldw = ldw; e.trans = trans;
@@ -1004,12 +1006,12 @@ static int pack_lookup_h(lb_gns_train* t, const float* W, int NR, int NO, int ld
     }
   if (!t->wpack) {
     t->wpack_cap = 4 * t->n_floats + ((int64_t)1 << 21);   // both orientations, in both arithmetics (lb_train_exact_math)
-    LB_TRY(lb_alloc(&t->wpack, (size_t)t->wpack_cap));
-    LB_TRY(lb_alloc(&t->pack_dev, (size_t)LB_PACK_MAX));
+    LB_TRY(t->mem.get(&t->wpack, (size_t)t->wpack_cap));
+    LB_TRY(t->mem.get(&t->pack_dev, (size_t)LB_PACK_MAX));
   }
   if (!t->pack_dev_h) {
-    LB_TRY(lb_alloc(&t->pack_dev_h, (size_t)LB_PACK_MAX));
-    LB_TRY(lb_alloc(&t->wsc, (size_t)LB_PACK_MAX));
+    LB_TRY(t->mem.get(&t->pack_dev_h, (size_t)LB_PACK_MAX));
+    LB_TRY(t->mem.get(&t->wsc, (size_t)LB_PACK_MAX));
   }
   lb_pack_ent_h e{};
   e.src = src; e.dst = t->wpack_floats; e.NR = NR; e.NO = NO; e.ldw = ldw; e.trans = trans;
@@ -1453,34 +1455,27 @@ static int edge_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t E, int64_t B
   return gemm_nt_stack2(t, BN, dPs, (int64_t)BN * TD, Ws, dn);
 }
 
-template <typename T>
-static int tr_alloc(T** p, size_t n) {
-  if (*p) (void)hipFree(*p);
-  return lb_alloc(p, n);
-}
-
 // Scratch for BN nodes and E edges - the frame every model shares: the capacity test, the growth rule (edges with head
 // room: the list changes from step to step) and the training core's own buffers.  model(cn, ce, cm) allocates the model's
 // buffers for cn nodes / ce edges (cm: the larger of the two) and sets t->red_cap, the floats of partial-sum slots its
 // backward pass needs.
 template <typename F>
 static int train_ensure(lb_gns_train* t, int64_t BN, int64_t E, F model) {
-  if (BN <= t->cap_n && E <= t->cap_e && t->loss_part) return LB_OK;
-  LB_HIP(hipStreamSynchronize(t->eng->stream));
+  if (BN <= t->cap_n && E <= t->cap_e) return LB_OK;
   const int64_t cn = std::max(BN, t->cap_n), ce = std::max(E + E / 8 + 1024, t->cap_e), cm = std::max(cn, ce);
-  LB_TRY(model(cn, ce, cm));
-  LB_TRY(tr_alloc(&t->tmax, (size_t)(cm / 16 + 64)));
-  LB_TRY(tr_alloc(&t->dwpart, (size_t)t->red_cap));
-  if (!t->red_dev) {
-    LB_TRY(lb_alloc(&t->red_dev, (size_t)LB_RED_MAX));
-    LB_HIP(hipHostMalloc((void**)&t->red_host, sizeof(lb_red_ent) * (LB_RED_MAX + 1)));   // (+ the step's status words)
-  }
-  LB_TRY(tr_alloc(&t->node_w, (size_t)cn));
-  LB_TRY(tr_alloc(&t->dsave, (size_t)cn * 4));
-  LB_TRY(tr_alloc(&t->loss_part, (size_t)(cn / 64 + 8)));
-  t->cap_n = cn;
-  t->cap_e = ce;
-  return LB_OK;
+  t->cap_e = 0;  // (both capacities are written last: cap_n by lb_regrow, cap_e at the end of its body)
+  return lb_regrow(t->eng->stream, &t->cap_n, cn, [&](int64_t) -> int {
+    LB_TRY(model(cn, ce, cm));
+    LB_TRY(t->mem.get(&t->tmax, (size_t)(cm / 16 + 64)));
+    LB_TRY(t->mem.get(&t->dwpart, (size_t)t->red_cap));
+    if (!t->red_dev) LB_TRY(t->mem.get(&t->red_dev, (size_t)LB_RED_MAX));
+    if (!t->red_host) LB_TRY(t->mem.get_pinned(&t->red_host, (size_t)LB_RED_MAX + 1));   // (+ the step's status words)
+    LB_TRY(t->mem.get(&t->node_w, (size_t)cn));
+    LB_TRY(t->mem.get(&t->dsave, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&t->loss_part, (size_t)(cn / 64 + 8)));
+    t->cap_e = ce;
+    return LB_OK;
+  });
 }
 static int gns_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
   return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t cm) -> int {
@@ -1488,35 +1483,35 @@ static int gns_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
     const size_t nh = (size_t)(t->nlin - 1);   // hidden activations kept per block
     t->hs_n = cn * TD;
     t->hs_e = ce * TD;
-    LB_TRY(tr_alloc(&t->xnode, (size_t)cn * t->kpad));
-    LB_TRY(tr_alloc(&t->a_en, nh * cn * TD));
-    LB_TRY(tr_alloc(&t->z_en, (size_t)cn * TD));
-    LB_TRY(tr_alloc(&t->a_ee, nh * ce * TD));
-    LB_TRY(tr_alloc(&t->z_ee, (size_t)ce * TD));
+    LB_TRY(t->mem.get(&t->xnode, (size_t)cn * t->kpad));
+    LB_TRY(t->mem.get(&t->a_en, nh * cn * TD));
+    LB_TRY(t->mem.get(&t->z_en, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&t->a_ee, nh * ce * TD));
+    LB_TRY(t->mem.get(&t->z_ee, (size_t)ce * TD));
     for (int k = 0; k <= L; ++k) {
-      LB_TRY(tr_alloc(&t->nlat[k], (size_t)cn * TD));
-      LB_TRY(tr_alloc(&t->elat[k], (size_t)ce * TD));
+      LB_TRY(t->mem.get(&t->nlat[k], (size_t)cn * TD));
+      LB_TRY(t->mem.get(&t->elat[k], (size_t)ce * TD));
     }
     for (int k = 0; k < L; ++k) {
-      LB_TRY(tr_alloc(&t->ae[k], nh * ce * TD));
-      LB_TRY(tr_alloc(&t->ze[k], (size_t)ce * TD));
-      LB_TRY(tr_alloc(&t->xn[k], (size_t)cn * 2 * TD));
-      LB_TRY(tr_alloc(&t->an[k], nh * cn * TD));
-      LB_TRY(tr_alloc(&t->zn[k], (size_t)cn * TD));
+      LB_TRY(t->mem.get(&t->ae[k], nh * ce * TD));
+      LB_TRY(t->mem.get(&t->ze[k], (size_t)ce * TD));
+      LB_TRY(t->mem.get(&t->xn[k], (size_t)cn * 2 * TD));
+      LB_TRY(t->mem.get(&t->an[k], nh * cn * TD));
+      LB_TRY(t->mem.get(&t->zn[k], (size_t)cn * TD));
     }
-    LB_TRY(tr_alloc(&t->a_d, nh * cn * TD));
-    LB_TRY(tr_alloc(&t->pred, (size_t)cn * 4));
-    LB_TRY(tr_alloc(&t->dn, (size_t)cn * TD));
-    LB_TRY(tr_alloc(&t->de, (size_t)ce * TD));
-    LB_TRY(tr_alloc(&t->dy, (size_t)cm * TD));
-    LB_TRY(tr_alloc(&t->dz, (size_t)cm * TD));
-    LB_TRY(tr_alloc(&t->da, (size_t)cm * TD));
-    if (t->nlin > 2) LB_TRY(tr_alloc(&t->da2, (size_t)cm * TD));
-    LB_TRY(tr_alloc(&t->dx, (size_t)cn * std::max(3 * TD, t->kpad)));
-    LB_TRY(tr_alloc(&t->dagg, (size_t)cn * TD));
-    LB_TRY(tr_alloc(&t->agg, (size_t)cn * TD));
-    LB_TRY(tr_alloc(&t->proj, (size_t)cn * 2 * TD));
-    LB_TRY(tr_alloc(&t->dxe, (size_t)ce * 8));
+    LB_TRY(t->mem.get(&t->a_d, nh * cn * TD));
+    LB_TRY(t->mem.get(&t->pred, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&t->dn, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&t->de, (size_t)ce * TD));
+    LB_TRY(t->mem.get(&t->dy, (size_t)cm * TD));
+    LB_TRY(t->mem.get(&t->dz, (size_t)cm * TD));
+    LB_TRY(t->mem.get(&t->da, (size_t)cm * TD));
+    if (t->nlin > 2) LB_TRY(t->mem.get(&t->da2, (size_t)cm * TD));
+    LB_TRY(t->mem.get(&t->dx, (size_t)cn * std::max(3 * TD, t->kpad)));
+    LB_TRY(t->mem.get(&t->dagg, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&t->agg, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&t->proj, (size_t)cn * 2 * TD));
+    LB_TRY(t->mem.get(&t->dxe, (size_t)ce * 8));
     t->red_cap = red_capacity(t, cn, ce);
     return LB_OK;
   });
@@ -1571,38 +1566,32 @@ static int train_sender_sort(lb_gns_train* t, int64_t E, int64_t BN) {
   if (!E) return LB_OK;
   static const bool force_cub = getenv("LB_TRAIN_SORT") && getenv("LB_TRAIN_SORT")[0] == 'c';  // LB_TRAIN_SORT=cub: always the fall-back (test)
   if (!t->cub_sort && !force_cub) {
-    if (E > t->sort_cap || BN + 1 > t->sort_cap) {
-      LB_HIP(hipStreamSynchronize(s));
-      for (void* b : {(void*)t->snd_key, (void*)t->snd_perm, (void*)t->iota, (void*)t->snd_ptr, t->sort_tmp})
-        if (b) (void)hipFree(b);
-      t->snd_key = t->iota = nullptr;
-      t->sort_tmp = nullptr;
-      t->sort_tmp_bytes = 0;
-      t->sort_cap = std::max<int64_t>(E + E / 8 + 1024, BN + 2);
-      LB_HIP(hipMalloc((void**)&t->snd_perm, sizeof(int32_t) * t->sort_cap));
-      LB_HIP(hipMalloc((void**)&t->snd_ptr, sizeof(int32_t) * t->sort_cap));
-    }
+    if (E > t->sort_cap || BN + 1 > t->sort_cap)   // the transposition's set: snd_perm, snd_ptr (the radix sort's goes)
+      LB_TRY(lb_regrow(s, &t->sort_cap, std::max<int64_t>(E + E / 8 + 1024, BN + 2), [&](int64_t n) {
+        t->sort_radix = false;
+        t->sort_tmp_bytes = 0;
+        LB_TRY(t->mem.drop(&t->snd_key));
+        LB_TRY(t->mem.drop(&t->iota));
+        LB_TRY(t->mem.drop(&t->sort_tmp));
+        LB_TRY(t->mem.get(&t->snd_perm, (size_t)n));
+        return t->mem.get(&t->snd_ptr, (size_t)n);
+      }));
     hipLaunchKernelGGL(k_sender_transpose, GRID1(std::max(E, BN + 1)), 0, s, e->row_ptr, e->senders, e->receivers, E, BN,
                        t->snd_perm, t->snd_ptr, t->dw_flag);
     return LB_OK;
   }
-  if (E > t->sort_cap || BN + 1 > t->sort_cap || !t->sort_tmp) {
-    LB_HIP(hipStreamSynchronize(s));
-    for (void* b : {(void*)t->snd_key, (void*)t->snd_perm, (void*)t->iota, (void*)t->snd_ptr, t->sort_tmp})
-      if (b) (void)hipFree(b);
-    t->snd_key = t->snd_perm = t->iota = t->snd_ptr = nullptr;
-    t->sort_tmp = nullptr;
-    t->sort_cap = std::max<int64_t>(E + E / 8 + 1024, BN + 2);
-    LB_HIP(hipMalloc((void**)&t->snd_key, sizeof(int32_t) * t->sort_cap));
-    LB_HIP(hipMalloc((void**)&t->snd_perm, sizeof(int32_t) * t->sort_cap));
-    LB_HIP(hipMalloc((void**)&t->iota, sizeof(int32_t) * t->sort_cap));
-    LB_HIP(hipMalloc((void**)&t->snd_ptr, sizeof(int32_t) * t->sort_cap));
-    hipLaunchKernelGGL(k_iota, GRID1(t->sort_cap), 0, s, t->iota, t->sort_cap);
-    t->sort_tmp_bytes = 0;
-    LB_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t->sort_tmp_bytes, e->senders, t->snd_key, t->iota, t->snd_perm,
-                                              (int)t->sort_cap, 0, 32, s));
-    LB_HIP(hipMalloc(&t->sort_tmp, t->sort_tmp_bytes));
-  }
+  if (E > t->sort_cap || BN + 1 > t->sort_cap || !t->sort_radix)   // the radix sort's set: all four arrays and sort_tmp
+    LB_TRY(lb_regrow(s, &t->sort_cap, std::max<int64_t>(E + E / 8 + 1024, BN + 2), [&](int64_t n) {
+      t->sort_radix = false;
+      for (int32_t** p : {&t->snd_key, &t->snd_perm, &t->iota, &t->snd_ptr}) LB_TRY(t->mem.get(p, (size_t)n));
+      hipLaunchKernelGGL(k_iota, GRID1(n), 0, s, t->iota, n);
+      t->sort_tmp_bytes = 0;
+      LB_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, t->sort_tmp_bytes, e->senders, t->snd_key, t->iota, t->snd_perm, (int)n, 0,
+                                                32, s));
+      LB_TRY(t->mem.get(&t->sort_tmp, t->sort_tmp_bytes));
+      t->sort_radix = true;
+      return LB_OK;
+    }));
   size_t bytes = t->sort_tmp_bytes;
   LB_HIP(hipcub::DeviceRadixSort::SortPairs(t->sort_tmp, bytes, e->senders, t->snd_key, t->iota, t->snd_perm, (int)E, 0, 32, s));
   hipLaunchKernelGGL(k_lower_bounds, GRID1(BN + 1), 0, s, t->snd_key, E, BN, t->snd_ptr);
@@ -1710,12 +1699,12 @@ int lb_gns_train_padded_map(const lb_gns_desc* d, std::vector<int64_t>* cmap, in
 static int train_handle_init(lb_gns_train* t, const char* what, const float* w, int64_t n_floats) {
   const int64_t o = t->n_floats, oc = t->n_compact;
   if (oc != n_floats) return lb_fail(LB_ERR_ARG, "%s has %lld floats, expected %lld", what, (long long)n_floats, (long long)oc);
-  for (float** p : {&t->w, &t->g, &t->m, &t->v}) LB_TRY(lb_alloc(p, (size_t)o));
+  for (float** p : {&t->w, &t->g, &t->m, &t->v}) LB_TRY(t->mem.get(p, (size_t)o));
   // the loss and the guard words in ONE allocation, [loss | dw_flag]: one copy brings the loss and dw_flag[0] to the host
-  LB_TRY(lb_alloc(&t->loss_dev, (size_t)(1 + (1 + LB_DW_CALLS + 1) / 2)));
+  LB_TRY(t->mem.get(&t->loss_dev, (size_t)(1 + (1 + LB_DW_CALLS + 1) / 2)));
   t->dw_flag = reinterpret_cast<int32_t*>(t->loss_dev + 1);
   LB_HIP(hipMemset(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS)));
-  LB_TRY(lb_alloc(&t->cnt_dev, (size_t)t->eng->g.B));
+  LB_TRY(t->mem.get(&t->cnt_dev, (size_t)t->eng->g.B));
   std::vector<float> padded;
   const float* src = w;
   if (!t->cmap.empty()) {
@@ -1758,16 +1747,7 @@ extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   if (!t) return;
   sgt_free(t);
   egt_free(t);
-  std::vector<void*> bufs = {t->w, t->g, t->m, t->v, t->xnode, t->a_en, t->z_en, t->a_ee, t->z_ee, t->a_d, t->pred,
-                             t->dn, t->de, t->dy, t->dz, t->da, t->dx, t->dagg, t->agg, t->dwpart, t->red_dev, t->proj, t->node_w,
-                             t->loss_dev, t->da2, t->loss_part, t->cnt_dev, t->snd_key, t->snd_perm, t->iota, t->snd_ptr, t->sort_tmp,
-                             t->wpack, t->pack_dev, t->pack_dev_h, t->wsc, t->tmax, t->dsave, t->dxe};
-  for (auto* v : {&t->nlat, &t->elat, &t->ae, &t->ze, &t->xn, &t->an, &t->zn})
-    for (float* p : *v) bufs.push_back(p);
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (t->red_host) (void)hipHostFree(t->red_host);
-  delete t;
+  delete t;  // (t->mem frees the buffers)
 }
 
 // One training step's loss + gradients with the step's guard flag around it: if a k_dw_part_h block saw activations outside

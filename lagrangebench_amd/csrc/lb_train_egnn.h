@@ -381,11 +381,7 @@ static void egt_free(lb_gns_train* t) {
   lb_egt* g = t->eg;
   if (!g) return;
   if (g->view) lb_egnn_destroy(g->view);
-  for (void* p : {g->tap_h, g->tap_x, g->xin, g->attr2, g->ps, g->pr, g->xn, g->zn0, g->u, g->zv0, g->vv, g->dpsi, g->dh, g->dx,
-                  g->dzn, g->du, g->dagg, g->cdr, g->ea2, g->z0, g->a, g->z1, g->m, g->zx0, g->q, g->phi, g->dphi, g->dcd, g->de1,
-                  g->de2})
-    if (p) (void)hipFree(p);
-  delete g;
+  delete g;  // (its buffers are the handle arena's)
   t->eg = nullptr;
 }
 
@@ -394,21 +390,21 @@ static int egt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
     lb_egt* g = t->eg;
     const int L = g->desc.num_mp_steps, dim = t->eng->g.dim;
     const size_t W = EGT_W;
-    LB_TRY(tr_alloc(&g->tap_h, (size_t)(L + 1) * cn * W));
-    LB_TRY(tr_alloc(&g->tap_x, (size_t)(L + 1) * cn * dim));
-    LB_TRY(tr_alloc(&g->xin, (size_t)cn * EGT_XIN));
-    LB_TRY(tr_alloc(&g->attr2, (size_t)cn * 2));
-    LB_TRY(tr_alloc(&g->xn, (size_t)cn * 2 * W));
-    LB_TRY(tr_alloc(&g->dpsi, (size_t)cn));
-    LB_TRY(tr_alloc(&g->dx, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&g->tap_h, (size_t)(L + 1) * cn * W));
+    LB_TRY(t->mem.get(&g->tap_x, (size_t)(L + 1) * cn * dim));
+    LB_TRY(t->mem.get(&g->xin, (size_t)cn * EGT_XIN));
+    LB_TRY(t->mem.get(&g->attr2, (size_t)cn * 2));
+    LB_TRY(t->mem.get(&g->xn, (size_t)cn * 2 * W));
+    LB_TRY(t->mem.get(&g->dpsi, (size_t)cn));
+    LB_TRY(t->mem.get(&g->dx, (size_t)cn * 4));
     for (float** p : {&g->ps, &g->pr, &g->zn0, &g->u, &g->zv0, &g->vv, &g->dh, &g->dzn, &g->du, &g->dagg})
-      LB_TRY(tr_alloc(p, (size_t)cn * W));
-    LB_TRY(tr_alloc(&g->cdr, (size_t)ce * 4));
-    LB_TRY(tr_alloc(&g->dcd, (size_t)ce * 4));
-    LB_TRY(tr_alloc(&g->ea2, (size_t)ce * 2));
-    LB_TRY(tr_alloc(&g->phi, (size_t)ce));
-    LB_TRY(tr_alloc(&g->dphi, (size_t)ce));
-    for (float** p : {&g->z0, &g->a, &g->z1, &g->m, &g->zx0, &g->q, &g->de1, &g->de2}) LB_TRY(tr_alloc(p, (size_t)ce * W));
+      LB_TRY(t->mem.get(p, (size_t)cn * W));
+    LB_TRY(t->mem.get(&g->cdr, (size_t)ce * 4));
+    LB_TRY(t->mem.get(&g->dcd, (size_t)ce * 4));
+    LB_TRY(t->mem.get(&g->ea2, (size_t)ce * 2));
+    LB_TRY(t->mem.get(&g->phi, (size_t)ce));
+    LB_TRY(t->mem.get(&g->dphi, (size_t)ce));
+    for (float** p : {&g->z0, &g->a, &g->z1, &g->m, &g->zx0, &g->q, &g->de1, &g->de2}) LB_TRY(t->mem.get(p, (size_t)ce * W));
     // partial-sum slots of the step's reductions (mirrors the backward below)
     auto slot = [](int64_t rows, int K) { return (dw_groups_max(std::max<int64_t>(rows, 1)) * (K + 1) * 128 + 63) / 64 * 64; };
     auto narrow = [](int64_t rows) { return (std::min<int64_t>(DW_MAX_G, (rows + 63) / 64 + 1) * 128 + 63) / 64 * 64; };

@@ -247,42 +247,32 @@ __global__ void k_sgt_scatter(const float* __restrict__ A, const float* __restri
 
 // ------------------------------------------------------------------------------------------------------- host
 static void sgt_free(lb_gns_train* t) {
-  lb_sgt* g = t->sg;
-  if (!g) return;
-  std::vector<void*> bufs = {g->xnode, g->nodesv, g->nattr, g->eattr, g->msgsv, g->f, g->agg, g->tn[0], g->tn[1], g->te[0], g->te[1],
-                             g->df, g->dagg, g->dtn[0], g->dtn[1], g->dte[0], g->dte[1], g->dFs, g->dFr, g->draw, g->dZ};
-  for (lb_sgt_block& b : g->blocks) {
-    bufs.push_back(b.Z);
-    bufs.push_back(b.raw);
-  }
-  for (void* p : bufs)
-    if (p) (void)hipFree(p);
-  delete g;
+  delete t->sg;  // (its buffers are the handle arena's)
   t->sg = nullptr;
 }
 
 static int sgt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
   return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t cm) -> int {
     lb_sgt* g = t->sg;
-    LB_TRY(tr_alloc(&g->xnode, (size_t)cn * 32));
-    LB_TRY(tr_alloc(&g->nodesv, (size_t)cn * g->node_stride));
-    LB_TRY(tr_alloc(&g->nattr, (size_t)cn * 4));
-    LB_TRY(tr_alloc(&g->eattr, (size_t)ce * 4));
-    LB_TRY(tr_alloc(&g->msgsv, (size_t)ce * 16));
-    for (float** p : {&g->f, &g->agg, &g->tn[0], &g->tn[1], &g->df, &g->dagg, &g->dtn[0], &g->dtn[1]}) LB_TRY(tr_alloc(p, (size_t)cn * 128));
-    for (float** p : {&g->te[0], &g->te[1], &g->dte[0], &g->dte[1], &g->dFs, &g->dFr}) LB_TRY(tr_alloc(p, (size_t)ce * 128));
-    LB_TRY(tr_alloc(&g->draw, (size_t)4 * cm * 128));
-    LB_TRY(tr_alloc(&g->dZ, (size_t)4 * cm * 256));
+    LB_TRY(t->mem.get(&g->xnode, (size_t)cn * 32));
+    LB_TRY(t->mem.get(&g->nodesv, (size_t)cn * g->node_stride));
+    LB_TRY(t->mem.get(&g->nattr, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&g->eattr, (size_t)ce * 4));
+    LB_TRY(t->mem.get(&g->msgsv, (size_t)ce * 16));
+    for (float** p : {&g->f, &g->agg, &g->tn[0], &g->tn[1], &g->df, &g->dagg, &g->dtn[0], &g->dtn[1]}) LB_TRY(t->mem.get(p, (size_t)cn * 128));
+    for (float** p : {&g->te[0], &g->te[1], &g->dte[0], &g->dte[1], &g->dFs, &g->dFr}) LB_TRY(t->mem.get(p, (size_t)ce * 128));
+    LB_TRY(t->mem.get(&g->draw, (size_t)4 * cm * 128));
+    LB_TRY(t->mem.get(&g->dZ, (size_t)4 * cm * 256));
     int64_t red = 4096;
     for (lb_sgt_block& b : g->blocks) {
       const int64_t R = b.edge ? ce : cn;
-      LB_TRY(tr_alloc(&b.Z, (size_t)4 * R * b.Kp));
-      LB_TRY(tr_alloc(&b.raw, (size_t)4 * R * 128));
+      LB_TRY(t->mem.get(&b.Z, (size_t)4 * R * b.Kp));
+      LB_TRY(t->mem.get(&b.raw, (size_t)4 * R * 128));
       red += (dw_groups_max(4 * R) * (b.Kp + 1) * 128 + 63) / 64 * 64 + (4 * R + 127) / 128 * 128 + 64;
     }
     t->red_cap = red;
-    LB_TRY(tr_alloc(&t->pred, (size_t)cn * 4));
-    LB_TRY(tr_alloc(&t->dy, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&t->pred, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&t->dy, (size_t)cn * 4));
     return LB_OK;
   });
 }
