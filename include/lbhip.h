@@ -290,20 +290,20 @@ int32_t lb_gns_train_sort_fallbacks(lb_gns_train* t);
 
 /* The step split at d loss / d pred, for a loss the CALLER computes.  trainer.py:63-89 takes
  * value_and_grad of _mse only; these two are the halves of that step around any loss: forward with saved activations, then
- * the hand-written backward from the caller's d loss / d pred.  t: a GNS, SEGNN or EGNN training handle.
+ * the hand-written backward from the caller's d loss / d pred.  t: a GNS, SEGNN, EGNN or Linear training handle.
  * lb_train_forward: on the engine's current window + neighbor list; pred_out_dev receives (B*N, dim) fp32 - the normalised
- * accelerations (GNS, SEGNN) or the positions x^L (EGNN) - with the bits lb_*_train_loss_grad reports.  The handle's
+ * accelerations (GNS, SEGNN, Linear) or the positions x^L (EGNN) - with the bits lb_*_train_loss_grad reports.  The handle's
  * forward is then LIVE until the next call on the handle other than lb_gns_train_zero_grad.
  * lb_train_backward: needs a live forward (else LB_ERR_STATE) and ends it.  dpred_dev (B*N, dim) fp32 is copied into the
  * handle (rows of pad particles zeroed); the gradients ACCUMULATE into the gradient blob exactly as in lb_*_train_loss_grad.
  * If the step's guard fires, the repeated attempt re-runs the forward (same weights, same window: the same activations)
  * and starts from the saved copy.  dpos_out_dev: null, or (B, N, isl, dim) fp64 that receives (overwritten) d loss / d window
  * through the feature builder (velocity history and magnitudes, wall distances, edge displacements and distances; the
- * external force counts as constant, the neighbor list as fixed) - GNS only, LB_ERR_UNSUPPORTED for SEGNN / EGNN handles. */
+ * external force counts as constant, the neighbor list as fixed) - GNS only, LB_ERR_UNSUPPORTED for SEGNN / EGNN / Linear handles. */
 int lb_train_forward(lb_gns_train* t, float* pred_out_dev);
 int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double* dpos_out_dev);
 /* The arithmetic of the handle's products from the next forward on: exact != 0 selects the exact-fp32 kernels (what
- * LB_TRAIN_MATH=f32 selects at creation), 0 the handle's default (EGNN handles are always exact).  A live forward stays
+ * LB_TRAIN_MATH=f32 selects at creation), 0 the handle's default (EGNN and Linear handles are always exact).  A live forward stays
  * live: lb_train_forward in one arithmetic may be followed by lb_train_backward in the other.  Why: a ReLU unit within the
  * forward's rounding of zero takes either side of its kink, which moves its particle's gradient by per cent, and the f16x2
  * forward has about ten times as many of them as the exact one.  autograd.DeviceModule therefore runs the forward of a GNS
@@ -485,6 +485,45 @@ int lb_painn_set_tap(lb_painn* painn, float* s_out_dev, float* v_out_dev);
 /* lb_rollout for a PaiNN: the whole step loop on the device, the acceleration integrated as GNS's. */
 int lb_painn_rollout(lb_engine* eng, lb_painn* painn, const double* traj_dev, int32_t T, int32_t n_steps,
                      double* pred_out_dev, int32_t* n_realloc_out);
+
+/* ---- Linear (models/linear.py:13-42) ------------------------------------------------------------
+ * The baseline of the reference's own end-to-end test: acc_i = x_i W + b with x_i = [vel_hist | vel_mag | bound | force |
+ * float(particle_type_i)], each block present when the case has it - the engine's node features followed by the raw type
+ * id as a VALUE (no one-hot).  The output is the normalised acceleration, integrated like GNS's.  fp32 (runner.py:71-72),
+ * sums in a fixed order (bit-reproducible; a particle's result does not depend on the batch). */
+typedef struct lb_linear lb_linear;
+typedef struct lb_linear_desc {
+  int32_t n_in;     /* node features of the engine + 1 (the type column): <= 64 */
+  int32_t out_dim;  /* dim */
+} lb_linear_desc;
+
+/* Linear(dim_out) + params (Haiku names linear/~/linear).  weights_host: w (n_in, out_dim) row-major, then b (out_dim);
+ * n_floats must match exactly.  desc is checked against the engine (LB_ERR_ARG); n_in > 64 is LB_ERR_UNSUPPORTED. */
+int lb_linear_create(lb_engine* eng, const lb_linear_desc* desc, const float* weights_host, int64_t n_floats,
+                     lb_linear** out);
+void lb_linear_destroy(lb_linear* linear);
+/* Linear.__call__ -> {"acc": (B,N,dim) fp32} on the current window.  The model reads no edges: a neighbor list need not
+ * exist.  If the engine's last list build overflowed, every step kernel is a no-op until a re-allocation: nothing is written
+ * and the call returns LB_ERR_STATE.  Host-synchronous. */
+int lb_linear_forward(lb_engine* eng, lb_linear* linear, float* acc_out_dev);
+/* lb_rollout for a Linear: the whole step loop on the device (features, model, integrator).  No step builds the neighbor
+ * list - the positions equal those of the generic loop, which builds one per step, bit for bit - so *n_realloc_out is 0;
+ * like lb_rollout it leaves an allocated list behind (an engine without one, or with an overflowed one, allocates once
+ * before the loop; the latter is counted as one re-allocation). */
+int lb_linear_rollout(lb_engine* eng, lb_linear* linear, const double* traj_dev, int32_t T, int32_t n_steps,
+                      double* pred_out_dev, int32_t* n_realloc_out);
+/* The training step for Linear.  The handle type is lb_gns_train: lb_gns_train_loss_grad (one "acc" target, like SEGNN),
+ * lb_train_forward / lb_train_backward (no gradient with respect to the window: LB_ERR_UNSUPPORTED), lb_gns_train_zero_grad,
+ * lb_adamw_step(_gathered), lb_gns_train_read / _write / _device_blob (flat blob in lb_linear_create's order, no padding),
+ * lb_gns_train_step_count and lb_gns_train_destroy work on it.  The prediction is lb_linear_forward's bit for bit; dW = X^T dY
+ * and db = sum dY in exact fp32, chunks of rows summed in ascending order: gradients bit-reproducible. */
+int lb_linear_train_create(lb_engine* eng, const lb_linear_desc* desc, const float* weights_host, int64_t n_floats,
+                           lb_gns_train** out);
+/* The inference model of a Linear training handle: a view of its device weights, so lb_linear_forward / lb_linear_rollout
+ * on it run on the CURRENT weights.  BORROWED: owned by t, valid until lb_gns_train_destroy(t); never pass it to
+ * lb_linear_destroy.  The view has node rows of its own: a forward or rollout on it between lb_train_forward and
+ * lb_train_backward leaves the handle's saved activations alone (the ENGINE's window is the caller's to restore). */
+int lb_linear_train_model(lb_gns_train* t, lb_linear** out);
 
 /* Arithmetic of the GNS GEMMs.  Default (LB_MATH unset) = mode 1: every fp32 operand is carried as an fp16
  * hi/lo pair on the fp16 MFMA (fp32-class accuracy, ~5x fewer matrix-pipe cycles than the fp32 MFMA) WITH a

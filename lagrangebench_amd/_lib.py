@@ -76,6 +76,12 @@ class PainnDesc(C.Structure):
     ]
 
 
+class LinearDesc(C.Structure):
+    """lb_linear_desc (include/lbhip.h)."""
+
+    _fields_ = [("n_in", C.c_int32), ("out_dim", C.c_int32)]
+
+
 # name -> (restype, argtypes).  Every symbol include/lbhip.h declares must be listed here;
 # tests/test_abi.py checks the two against each other.
 _P = C.c_void_p
@@ -166,6 +172,12 @@ _SIGS = {
     "lb_painn_forward": (C.c_int, [_P, _P, _P]),
     "lb_painn_set_tap": (C.c_int, [_P, _P, _P]),
     "lb_painn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "lb_linear_create": (C.c_int, [_P, C.POINTER(LinearDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "lb_linear_destroy": (None, [_P]),
+    "lb_linear_forward": (C.c_int, [_P, _P, _P]),
+    "lb_linear_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "lb_linear_train_create": (C.c_int, [_P, C.POINTER(LinearDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "lb_linear_train_model": (C.c_int, [_P, C.POINTER(_P)]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -412,6 +412,12 @@ struct lb_egnn_state {
 int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev, lb_egnn** out);
 int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st);
 
+// lb_linear.hip, for the Linear training step (lb_train_linear.h): a model on a caller-owned device blob in lb_linear_create's
+// layout, and one forward on it: node rows into xnode ([BN][64]; null: the model's own buffer), predictions into rows of
+// ldo floats
+int lbk_linear_view_create(lb_engine* e, const lb_linear_desc* d, const float* w_dev, lb_linear** out);
+int lbk_linear_forward(lb_engine* e, lb_linear* m, float* xnode, float* out, int ldo);
+
 // lb_api.hip: the checks every model entry point makes.  lb_model_check: a null engine or model (model_eng = null), or a
 // model created for another engine -> LB_ERR_ARG.  lb_forward_check: the stand-alone forward `name` before
 // lb_nl_allocate, or an LB_FORCE_BUFFER engine without its force -> LB_ERR_STATE.

@@ -69,11 +69,14 @@ static bool lb_train_f16x2_default() {
 
 struct lb_sgt;  // SEGNN-specific state of a training handle (lb_train_segnn.h)
 struct lb_egt;  // EGNN-specific state of a training handle (lb_train_egnn.h)
+struct lb_linear;  // lb_linear.hip
 
 struct lb_gns_train {
   lb_arena mem;           // owns every device / pinned buffer of the handle, those of t->sg / t->eg included
   lb_sgt* sg = nullptr;   // non-null: this handle trains a SEGNN (created by lb_segnn_train_create)
   lb_egt* eg = nullptr;   // non-null: this handle trains an EGNN (created by lb_egnn_train_create)
+  lb_linear* ln = nullptr;  // non-null: this handle trains a Linear (lb_linear_train_create): the inference view of t->w
+  lb_linear_desc ln_desc{};
   lb_gns_desc desc;
   lb_engine* eng;
   int64_t n_floats = 0;   // floats of the DEVICE blobs (latent padded to 128)
@@ -1743,10 +1746,12 @@ extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const flo
 
 static void sgt_free(lb_gns_train* t);
 static void egt_free(lb_gns_train* t);
+static void lnt_free(lb_gns_train* t);
 extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   if (!t) return;
   sgt_free(t);
   egt_free(t);
+  lnt_free(t);
   delete t;  // (t->mem frees the buffers)
 }
 
@@ -1987,6 +1992,8 @@ static int feat_bwd(lb_gns_train* t, double* dpos_out_dev) {
   LB_HIP(hipGetLastError());
   return LB_OK;
 }
+static int linear_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
+                                  float* pred_out_dev);
 static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
   LB_TRY(gns_forward_part(t, "lb_gns_train_loss_grad", pred_out_dev));
   LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));   // loss and d loss / d pred
@@ -1997,6 +2004,7 @@ extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, 
   if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
   if (t->sg) return lb_segnn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
+  if (t->ln) return linear_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
   t->fwd_live = false;
   return train_loss_grad_guarded(t, loss_out, [&] { return gns_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
 }
@@ -2085,7 +2093,7 @@ extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* i
 // The inference images of g re-made on the device from this handle's current weights (lb_gns_repack.hip)
 extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
   if (!t || !g) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->sg || t->eg) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
+  if (t->sg || t->eg || t->ln) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
   if (g->eng != t->eng) return lb_fail(LB_ERR_ARG, "the model was created for another engine");
   const lb_gns_desc &a = t->desc, &b = g->desc;
   if (a.latent_size != b.latent_size || a.blocks_per_step != b.blocks_per_step || a.num_mp_steps != b.num_mp_steps ||
@@ -2101,6 +2109,9 @@ extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
 
 // ------------------------------------------------------------------------------------------------ EGNN
 #include "lb_train_egnn.h"
+
+// ------------------------------------------------------------------------------------------------ Linear
+#include "lb_train_linear.h"
 
 // ------------------------------------------------------------------- the step split for a caller-side loss
 // lb_train_forward / lb_train_backward (include/lbhip.h): the two halves of every model's step around a d loss / d pred the
@@ -2129,12 +2140,13 @@ extern "C" int lb_train_exact_math(lb_gns_train* t, int32_t exact) {
   if (!t) return lb_fail(LB_ERR_ARG, "null argument");
   // (a live forward stays live: saved activations do not depend on the arithmetic that reads them, so a forward in exact
   // products may be followed by a backward in the default ones)
-  t->f16x2 = !exact && !t->eg && lb_train_f16x2_default();
+  t->f16x2 = !exact && !t->eg && !t->ln && lb_train_f16x2_default();
   return LB_OK;
 }
 static int train_forward_part(lb_gns_train* t, float* pred_out_dev) {
   if (t->eg) return egnn_forward_part(t, "lb_train_forward", pred_out_dev);
   if (t->sg) return segnn_forward_part(t, "lb_train_forward", pred_out_dev);
+  if (t->ln) return linear_forward_part(t, "lb_train_forward", pred_out_dev);
   return gns_forward_part(t, "lb_train_forward", pred_out_dev);
 }
 extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
@@ -2151,9 +2163,9 @@ extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double
   if (!t->fwd_live)
     return lb_fail(LB_ERR_STATE, "lb_train_backward needs a live forward: call lb_train_forward first (any other call on the "
                    "handle but lb_gns_train_zero_grad ends it)");
-  if (dpos_out_dev && (t->sg || t->eg))
+  if (dpos_out_dev && (t->sg || t->eg || t->ln))
     return lb_fail(LB_ERR_UNSUPPORTED, "lb_train_backward: the gradient with respect to the window is built for GNS only, "
-                   "not for %s handles", t->sg ? "SEGNN" : "EGNN");
+                   "not for %s handles", t->sg ? "SEGNN" : t->eg ? "EGNN" : "Linear");
   t->fwd_live = false;   // the backward consumes the forward's scratch
   lb_engine* e = t->eng;
   hipStream_t s = e->stream;
@@ -2177,6 +2189,7 @@ extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double
       return egnn_backward_part(t);
     }
     LB_HIP(hipMemcpyAsync(t->dy, t->dsave, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
+    if (t->ln) return linear_backward_part(t);
     return t->sg ? segnn_backward_part(t) : gns_backward_part(t, dpos_out_dev);
   });
 }

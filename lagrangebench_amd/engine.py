@@ -318,6 +318,10 @@ class RolloutEngine:
         """PaiNN normalised accelerations (B, N, dim) fp32."""
         return self._forward("lb_painn_forward", painn, out, torch.float32)
 
+    def linear_forward(self, linear: "LinearHandle", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Linear normalised accelerations (B, N, dim) fp32."""
+        return self._forward("lb_linear_forward", linear, out, torch.float32)
+
     def math_mode(self, set_mode: int = -1) -> Tuple[int, int]:
         """(mode, guard flags): 0 exact fp32 MFMA, 1 guarded f16x2 (default), 2 unguarded f16x2; flags: 1
         large operand, 2 tiny operand tile, 4 non-finite acceleration (include/lbhip.h: lb_math_mode)."""
@@ -657,6 +661,26 @@ class EgnnTrainHandle(GnsTrainHandle):
         super().close()
 
 
+class LinearTrainHandle(GnsTrainHandle):
+    """trainer.py:35-89 for the Linear baseline (csrc/lb_train_linear.h): GnsTrainHandle's calls, one "acc" target."""
+
+    _view: Optional["LinearHandle"] = None
+
+    def model_handle(self) -> "LinearHandle":
+        """The inference model of this handle: a view of its device weights, so engine.linear_forward / rollout on it run
+        on the CURRENT weights.  Borrowed - it is this handle's; closing it frees nothing, closing this handle ends it."""
+        if self._view is None or not self._view._h:
+            h = C.c_void_p()
+            check(self.engine.lib.lb_linear_train_model(self._h, C.byref(h)), "lb_linear_train_model")
+            self._view = _BorrowedLinearHandle(self.engine, h, self.desc, self.n_floats)
+        return self._view
+
+    def close(self):
+        if self._view is not None:
+            self._view._h = None   # the view dies with the handle
+        super().close()
+
+
 class SegnnHandle(_Handle):
     _DESTROY, _ROLLOUT = "lb_segnn_destroy", "lb_segnn_rollout"
     _tap = None
@@ -694,6 +718,17 @@ class EgnnHandle(_Handle):
 
 class _BorrowedEgnnHandle(EgnnHandle):
     """An EgnnHandle whose lb_egnn belongs to a training handle (EgnnTrainHandle.model_handle): close() only lets go."""
+
+    def close(self):
+        self._h = None
+
+
+class LinearHandle(_Handle):
+    _DESTROY, _ROLLOUT = "lb_linear_destroy", "lb_linear_rollout"
+
+
+class _BorrowedLinearHandle(LinearHandle):
+    """A LinearHandle whose lb_linear belongs to a training handle (LinearTrainHandle.model_handle): close() only lets go."""
 
     def close(self):
         self._h = None

@@ -1,7 +1,8 @@
 from .base import BaseModel
 from .egnn import EGNN
 from .gns import GNS
+from .linear import Linear
 from .painn import PaiNN
 from .segnn import SEGNN, node_irreps
 
-__all__ = ["BaseModel", "EGNN", "GNS", "PaiNN", "SEGNN", "node_irreps"]
+__all__ = ["BaseModel", "EGNN", "GNS", "Linear", "PaiNN", "SEGNN", "node_irreps"]

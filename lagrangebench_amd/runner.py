@@ -1,11 +1,11 @@
-"""Runner: mirror of lagrangebench/runner.py for the inference route (`mode: infer`).
+"""Runner: mirror of lagrangebench/runner.py.
 
 ``train_or_infer(cfg)`` (runner.py:25-143), ``setup_data`` (:146-189) and ``setup_model`` (:192-292)
 keep their signatures.  ``cfg`` is a nested mapping with the reference's keys (a dict or anything
 dict-like such as an OmegaConf DictConfig); missing keys fall back to ``defaults``.  `mode: train | all`
-runs ``train.Trainer`` (GNS, SEGNN and EGNN).  Under torchrun (one process per GPU) training is data parallel over
+runs ``train.Trainer`` (GNS, SEGNN, EGNN and the Linear baseline).  Under torchrun (one process per GPU) training is data parallel over
 ``train.batch_size``, the global batch, with no further config key (train/trainer.py); rank 0 alone
-prints and writes checkpoints.  ``train.device_unroll: true`` makes the push-forward unroll of GNS / EGNN run from the
+prints and writes checkpoints.  ``train.device_unroll: true`` makes the push-forward unroll of GNS / EGNN / Linear run from the
 device weights; like ``train.device_data`` it is read by the ``Trainer``, default off.
 """
 from __future__ import annotations
@@ -87,6 +87,8 @@ def setup_model(cfg, metadata: Dict, homogeneous_particles: bool = False, has_ex
             displacement_fn=None, shift_fn=None, normalization_stats=normalization_stats,
             num_mp_steps=cfg.model.num_mp_steps, n_vels=cfg.model.input_seq_length - 1, residual=True)
         return model, models.EGNN
+    if name == "linear":
+        return models.Linear(dim_out=metadata["dim"]), models.Linear   # runner.py:285-286
     raise NotImplementedError(f"model {cfg.model.name!r}: 'gns', 'segnn' and 'egnn' are built (painn/linear are not built)")
 
 
@@ -129,6 +131,18 @@ def train_or_infer(cfg):
             torch.distributed.broadcast_object_list(names, src=0)
             cfg.logging.run_name = names[0]
             store_ckp = os.path.join(cfg.logging.ckp_dir, cfg.logging.run_name) if cfg.logging.ckp_dir else None
+        if store_ckp is not None and rank == 0:
+            # runner.py:83-88: the merged config beside the run's checkpoints and in best/ (`load_ckp=<dir>` reads it)
+            try:
+                from .config import to_yaml
+                text = to_yaml(cfg)
+            except ImportError:
+                text = None
+                say("config.yaml is not written: PyYAML is not installed")
+            for d in (store_ckp, os.path.join(store_ckp, "best")) if text is not None else ():
+                os.makedirs(d, exist_ok=True)
+                with open(os.path.join(d, "config.yaml"), "w") as f:
+                    f.write(text)
         trainer.train(step_max=cfg.train.step_max, load_ckp=cfg.load_ckp, store_ckp=store_ckp)
         if mode == "train":
             return 0

@@ -21,7 +21,8 @@ torch is used for the noise / sampling random streams and as the tensor containe
 two to eight Linears per MLP), since round 5 SEGNN (lmax 1, hidden <= 32x0e+32x1o: ``lb_segnn_train_loss_grad``,
 csrc/lb_train_segnn.h) and EGNN (``lb_egnn_train_loss_grad``, csrc/lb_train_egnn.h: the inference forward, a hand-written
 backward on the exact-fp32 MFMA products; the loss covers every output the model predicts - pos, vel, acc - weighted by
-``loss_weight`` against the case's targets, as _mse does; ``normalize=True`` is refused) - the loop below is the
+``loss_weight`` against the case's targets, as _mse does; ``normalize=True`` is refused) and the Linear baseline
+(csrc/lb_train_linear.h, exact fp32) - the loop below is the
 reference's model-agnostic one; wandb logging is not wired (stdout).
 
 Data parallel (one process per GPU under torchrun, lagrangebench_amd/dist.py): ``train.batch_size``
