@@ -486,6 +486,23 @@ int lb_painn_set_tap(lb_painn* painn, float* s_out_dev, float* v_out_dev);
 int lb_painn_rollout(lb_engine* eng, lb_painn* painn, const double* traj_dev, int32_t T, int32_t n_steps,
                      double* pred_out_dev, int32_t* n_realloc_out);
 
+/* The training step for PaiNN (reference: train/trainer.py:35-89 on PaiNN.__call__).  The handle type is lb_gns_train:
+ * lb_gns_train_loss_grad (one "acc" target, the masked _mse), lb_train_forward / lb_train_backward (weights only: a
+ * non-null dpos_out_dev is LB_ERR_UNSUPPORTED), lb_gns_train_zero_grad, lb_adamw_step(_gathered), lb_gns_train_read /
+ * _write (flat blob in PaiNN.flatten order = lb_painn_create's, n_floats exact), lb_gns_train_step_count,
+ * lb_gns_train_device_blob and lb_gns_train_destroy work on it unchanged; lb_egnn_train_loss_grad on it is LB_ERR_ARG.
+ * The forward is lb_painn_forward's, bit for bit; the backward gives the gradients of every weight, in exact fp32 with
+ * sums in a fixed order (bit-reproducible).  rbf_trainable = 1: ~/widths and ~/offset (the last 2 n_rbf floats) are
+ * parameters, as with gaussian_rbf(trainable=True); 0: they are state - their gradient stays 0 and neither optimiser step
+ * touches them, so lb_gns_train_read returns the bits that were written.  Built for 64 <= hidden <= 128 and
+ * num_mp_steps <= 32 (LB_ERR_UNSUPPORTED otherwise). */
+int lb_painn_train_create(lb_engine* eng, const lb_painn_desc* desc, const float* weights_host, int64_t n_floats,
+                          int32_t rbf_trainable, lb_gns_train** out);
+/* The inference model of a PaiNN training handle: a view of its device weights, so lb_painn_forward / lb_painn_rollout on
+ * it run on the CURRENT weights (bit-identical to a model created from lb_gns_train_read(t, 0)).  BORROWED: owned by t,
+ * valid until lb_gns_train_destroy(t); never pass it to lb_painn_destroy. */
+int lb_painn_train_model(lb_gns_train* t, lb_painn** out);
+
 /* ---- Linear (models/linear.py:13-42) ------------------------------------------------------------
  * The baseline of the reference's own end-to-end test: acc_i = x_i W + b with x_i = [vel_hist | vel_mag | bound | force |
  * float(particle_type_i)], each block present when the case has it - the engine's node features followed by the raw type

@@ -172,6 +172,8 @@ _SIGS = {
     "lb_painn_forward": (C.c_int, [_P, _P, _P]),
     "lb_painn_set_tap": (C.c_int, [_P, _P, _P]),
     "lb_painn_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "lb_painn_train_create": (C.c_int, [_P, C.POINTER(PainnDesc), C.POINTER(C.c_float), C.c_int64, C.c_int32, C.POINTER(_P)]),
+    "lb_painn_train_model": (C.c_int, [_P, C.POINTER(_P)]),
     "lb_linear_create": (C.c_int, [_P, C.POINTER(LinearDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_linear_destroy": (None, [_P]),
     "lb_linear_forward": (C.c_int, [_P, _P, _P]),

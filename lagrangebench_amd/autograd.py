@@ -3,7 +3,7 @@
 The reference user wraps ``jax.grad`` around ``model.apply`` and ``case.integrate`` (trainer.py:63-89 does so for ``_mse``
 only).  Here ``DeviceModule`` is the ``torch.nn.Module`` with that role: its forward is the training handle's forward with
 saved activations (``lb_train_forward``), its backward the handle's backward from the ``d loss / d pred`` autograd hands
-over (``lb_train_backward``).  Gradients flow to ``weights`` (GNS, SEGNN, EGNN) and to the input window (GNS), so losses
+over (``lb_train_backward``).  Gradients flow to ``weights`` (GNS, SEGNN, EGNN, PaiNN) and to the input window (GNS), so losses
 other than the MSE, gradients with respect to positions and unrolls with gradients through time are a few lines of torch.
 ``Trainer`` keeps its fused ``_mse`` step; this is a second road beside it.
 
@@ -77,7 +77,7 @@ class _Step(torch.autograd.Function):
 
 
 class DeviceModule(torch.nn.Module):
-    """``model`` (GNS, SEGNN or EGNN) on the device as a differentiable torch module.
+    """``model`` (GNS, SEGNN, EGNN or PaiNN) on the device as a differentiable torch module.
 
     ``weights``: an ``nn.Parameter`` that ALIASES the training handle's device weight blob (device layout: latents padded to
     128, the padding zero): an optimiser that steps it in place trains the handle.  ``params()`` reads the current

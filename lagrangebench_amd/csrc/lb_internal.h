@@ -412,6 +412,19 @@ struct lb_egnn_state {
 int lbk_egnn_view_create(lb_engine* e, const lb_egnn_desc* d, const float* w_dev, lb_egnn** out);
 int lbk_egnn_train_forward(lb_engine* e, lb_egnn* m, lb_egnn_state* st);
 
+// lb_painn.hip, for the PaiNN training step (lb_train_painn.h): a model on a caller-owned device blob in lb_painn_create's
+// layout (its fragment images are re-made from the blob by every forward), and one forward on it (taps through
+// lb_painn_set_tap; the prediction in e->acc, rows of 4) that hands back the state the backward reads
+struct lb_painn_state {
+  const float* xnode;    // [BN][64] raw node features
+  const int32_t* rev;    // [n_edges_total] slot of each edge's transpose, -1 if none
+  const int32_t* orph;   // orphan count and slots (lbk_edge_rev)
+  const f32x4* geo;      // [n_edges_total] direction (3), filter scale (0 on a dead edge)
+  const float* nrm;      // [n_edges_total] norm, -1 on a dead edge
+};
+int lbk_painn_view_create(lb_engine* e, const lb_painn_desc* d, const float* w_dev, int64_t n_floats, lb_painn** out);
+int lbk_painn_train_forward(lb_engine* e, lb_painn* m, lb_painn_state* st);
+
 // lb_linear.hip, for the Linear training step (lb_train_linear.h): a model on a caller-owned device blob in lb_linear_create's
 // layout, and one forward on it: node rows into xnode ([BN][64]; null: the model's own buffer), predictions into rows of
 // ldo floats

@@ -64,7 +64,7 @@ struct lb_painn {
   lb_engine* eng;
   int n_scal, n_vec, c_frc, c_bnd;  // scalar inputs, vector channels, raw-row columns of force / bound (-1: absent)
   int n_sets, n_filt;               // parameter sets of the layers, filter blocks
-  float* blob = nullptr;            // the weights as given
+  float* blob = nullptr;            // the weights as given (a view: the caller's device blob)
   f32x4* packed = nullptr;          // MFMA fragment images
   const float *w_se = nullptr, *b_se = nullptr, *w_ve = nullptr, *w_f = nullptr, *b_f = nullptr;
   const float *w_rbf = nullptr, *o_rbf = nullptr;
@@ -87,6 +87,10 @@ struct lb_painn {
   float* nrm = nullptr;    // [e_alloc]: norm, or -1 on a dead edge
   float* tap_s = nullptr;
   float* tap_v = nullptr;
+  // a view (lbk_painn_view_create): blob belongs to the caller, the fragment images are re-made from it by every forward
+  struct pack_job { int64_t src, dst; int K, NO; };  // float offsets into blob / packed
+  pack_job* jobs_dev = nullptr;
+  int n_jobs = 0;   // > 0: a view
 };
 
 __device__ __forceinline__ float pn_silu(float x) { return x / (1.f + expf(-x)); }
@@ -418,6 +422,23 @@ static void pn_pack(const float* W, int K, int NO, float* dst) {
         }
 }
 
+// the same on the device, for a view: one job per blockIdx.y
+__global__ void __launch_bounds__(256) k_pn_pack(const float* __restrict__ blob, float* __restrict__ packed,
+                                                 const lb_painn::pack_job* __restrict__ jobs) {
+  const lb_painn::pack_job jb = jobs[blockIdx.y];
+  const int NJ = (jb.K + 15) / 16, NOB = (jb.NO + 63) / 64 * 4;
+  const int64_t total = (int64_t)NJ * NOB * 256;
+  const float* W = blob + jb.src;
+  float* dst = packed + jb.dst;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int i = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
+    const int64_t q = idx >> 8;
+    const int mb = (int)(q % NOB), j = (int)(q / NOB);
+    const int k = 16 * j + 4 * (lane >> 4) + i, m = 16 * mb + (lane & 15);
+    dst[idx] = (k < jb.K && m < jb.NO) ? W[(int64_t)k * jb.NO + m] : 0.f;
+  }
+}
+
 static int pn_ensure_edges(lb_painn* m) {
   lb_engine* e = m->eng;
   if (m->e_alloc >= e->e_alloc) return LB_OK;
@@ -444,9 +465,10 @@ static int64_t pn_n_floats(const lb_painn_desc* d, int n_scal, int n_vec) {
   return n_scal * H + H + n_vec * H + R * filt * 3 * H + filt * 3 * H + sets * layer + ro0 + ro1 + 2 * R;
 }
 
-extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float* w, int64_t n_floats,
-                               lb_painn** out) {
-  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
+// w: the caller's host blob (a model), or null with w_dev: a view of a device blob in the same layout that the caller owns
+static int pn_create(lb_engine* e, const lb_painn_desc* d, const float* w, const float* w_dev, int64_t n_floats,
+                     lb_painn** out) {
+  if (!e || !d || (!w && !w_dev) || !out) return lb_fail(LB_ERR_ARG, "null argument");
   *out = nullptr;
   if (d->hidden < 16 || d->hidden > 128 || d->hidden % 16)
     return lb_fail(LB_ERR_UNSUPPORTED, "PaiNN hidden size %d: a multiple of 16 up to 128 is built", d->hidden);
@@ -479,10 +501,14 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
   auto step = [&](int r) {
     if (!rc) rc = r;
   };
-  step(m->mem.get(&m->blob, (size_t)n_floats));
-  if (!rc) {
-    const hipError_t he = hipMemcpy(m->blob, w, sizeof(float) * n_floats, hipMemcpyHostToDevice);
-    if (he != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he));
+  if (w) {
+    step(m->mem.get(&m->blob, (size_t)n_floats));
+    if (!rc) {
+      const hipError_t he = hipMemcpy(m->blob, w, sizeof(float) * n_floats, hipMemcpyHostToDevice);
+      if (he != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he));
+    }
+  } else {
+    m->blob = const_cast<float*>(w_dev);   // (not the arena's: never freed here)
   }
   step(m->mem.get(&m->xnode, (size_t)BN * PN_KPAD));
   step(m->mem.get(&m->s, (size_t)BN * H));
@@ -496,11 +522,12 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
     lb_painn_destroy(m);
     return rc;
   }
-  // carve the blob (include/lbhip.h: lb_painn_create); h_* point into the host copy for packing
+  // carve the blob (include/lbhip.h: lb_painn_create); h_* point into the host copy for packing (a view: into the device blob, read for their offsets only)
   int64_t o = 0;
+  const float* const hbase = w ? w : m->blob;
   auto take = [&](int64_t n, const float** h) {
     const float* r = m->blob + o;
-    *h = w + o;
+    *h = hbase + o;
     o += n;
     return r;
   };
@@ -563,16 +590,26 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
   m->o_rbf = take(d->n_rbf, &hd);
   int64_t pf = 0;
   for (auto& j : jobs) pf += pn_frag_floats(j.K, j.NO);
-  std::vector<float> img((size_t)pf);
+  std::vector<float> img(w ? (size_t)pf : 0);
   int64_t po = 0;
   std::vector<int64_t> offs;
+  std::vector<lb_painn::pack_job> pj;
   for (auto& j : jobs) {
-    pn_pack(j.host, j.K, j.NO, img.data() + po);
+    if (w) pn_pack(j.host, j.K, j.NO, img.data() + po);
+    else pj.push_back({(int64_t)(j.host - hbase), po, j.K, j.NO});
     offs.push_back(po);
     po += pn_frag_floats(j.K, j.NO);
   }
   if (m->mem.get(&m->packed, (size_t)pf / 4) == LB_OK) {
-    const hipError_t he = hipMemcpy(m->packed, img.data(), sizeof(float) * pf, hipMemcpyHostToDevice);
+    hipError_t he = hipSuccess;
+    if (w) {
+      he = hipMemcpy(m->packed, img.data(), sizeof(float) * pf, hipMemcpyHostToDevice);
+    } else if (m->mem.get(&m->jobs_dev, pj.size()) == LB_OK) {
+      he = hipMemcpy(m->jobs_dev, pj.data(), sizeof(lb_painn::pack_job) * pj.size(), hipMemcpyHostToDevice);
+      m->n_jobs = (int)pj.size();
+    } else {
+      rc = LB_ERR_HIP;
+    }
     if (he != hipSuccess) rc = lb_fail(LB_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he));
   } else {
     rc = LB_ERR_HIP;
@@ -591,6 +628,18 @@ extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float
   }
   *out = m;
   return LB_OK;
+}
+
+extern "C" int lb_painn_create(lb_engine* e, const lb_painn_desc* d, const float* w, int64_t n_floats,
+                               lb_painn** out) {
+  if (!w) return lb_fail(LB_ERR_ARG, "null argument");
+  return pn_create(e, d, w, nullptr, n_floats, out);
+}
+
+// the training handle's view (lb_train_painn.h): a model on the caller's device blob w_dev (lb_painn_create's layout)
+int lbk_painn_view_create(lb_engine* e, const lb_painn_desc* d, const float* w_dev, int64_t n_floats, lb_painn** out) {
+  if (!w_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  return pn_create(e, d, nullptr, w_dev, n_floats, out);
 }
 
 extern "C" int lb_painn_set_tap(lb_painn* m, float* s_out_dev, float* v_out_dev) {
@@ -613,6 +662,9 @@ static int lbk_painn_forward(lb_engine* e, lb_painn* m) {
   const int64_t BN = e->BN;
   const int H = m->desc.hidden, dim = e->g.dim, Hh = H / 2;
   LB_TRY(pn_ensure_edges(m));
+  if (m->n_jobs)   // a view: the weights may have moved since the last forward
+    hipLaunchKernelGGL(k_pn_pack, dim3(16, (unsigned)m->n_jobs), dim3(256), 0, st, m->blob, reinterpret_cast<float*>(m->packed),
+                       m->jobs_dev);
   const int64_t ecap = (int64_t)e->e_cap * e->g.B;
   const unsigned nb_t = (unsigned)((BN + PN_TN - 1) / PN_TN), nb_e = (unsigned)((ecap + 255) / 256);
   float* v = m->va;
@@ -698,6 +750,17 @@ extern "C" int lb_painn_forward(lb_engine* e, lb_painn* m, float* acc_out_dev) {
   LB_TRY(lbk_painn_forward(e, m));
   if (acc_out_dev) LB_TRY(lb_export_rows(e, e->acc, acc_out_dev, true));
   LB_HIP(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+// one forward of the view for the training step: the state its backward reads
+int lbk_painn_train_forward(lb_engine* e, lb_painn* m, lb_painn_state* st) {
+  LB_TRY(lbk_painn_forward(e, m));
+  st->xnode = m->xnode;
+  st->rev = m->rev;
+  st->orph = m->orph;
+  st->geo = m->geo;
+  st->nrm = m->nrm;
   return LB_OK;
 }
 

@@ -57,7 +57,9 @@ struct lb_red_ent {
   int64_t stride;   // floats between the partials of consecutive g
   int64_t dst0, dst1;  // float offsets into the gradient blob (dst1 unused when n1 == 0)
   int G, n0, n1, off1;
-  int blk0, pad;    // first block of this reduction in the flat grid (RED_OUT = 256 outputs per block)
+  int blk0;         // first block of this reduction in the flat grid (RED_OUT = 256 outputs per block)
+  int ld0;          // 0: the n0 outputs are consecutive floats at dst0; else rows of 128 with this row stride (a column
+                    // block of a wider row-major matrix: lb_train_painn.h)
 };
 
 // LB_TRAIN_MATH=f32: the exact-fp32 product kernels (k_lin32f); default: f16x2 (k_lin32h)
@@ -70,6 +72,7 @@ static bool lb_train_f16x2_default() {
 struct lb_sgt;  // SEGNN-specific state of a training handle (lb_train_segnn.h)
 struct lb_egt;  // EGNN-specific state of a training handle (lb_train_egnn.h)
 struct lb_linear;  // lb_linear.hip
+struct lb_pnt;  // PaiNN-specific state of a training handle (lb_train_painn.h)
 
 struct lb_gns_train {
   lb_arena mem;           // owns every device / pinned buffer of the handle, those of t->sg / t->eg included
@@ -77,10 +80,13 @@ struct lb_gns_train {
   lb_egt* eg = nullptr;   // non-null: this handle trains an EGNN (created by lb_egnn_train_create)
   lb_linear* ln = nullptr;  // non-null: this handle trains a Linear (lb_linear_train_create): the inference view of t->w
   lb_linear_desc ln_desc{};
+  lb_pnt* pa = nullptr;   // non-null: this handle trains a PaiNN (created by lb_painn_train_create)
   lb_gns_desc desc;
   lb_engine* eng;
   int64_t n_floats = 0;   // floats of the DEVICE blobs (latent padded to 128)
   int64_t n_compact = 0;  // floats of the caller's blob (GNS.flatten with the model's latent size)
+  int64_t n_frozen = 0;   // the last n_frozen floats of the blobs are not parameters: AdamW leaves them alone (PaiNN's
+                          // radial basis with gaussian_rbf(trainable=False))
   int lat = TD;           // the model's latent size (<= 128)
   std::vector<int64_t> cmap;  // caller index -> device index (empty: identity, latent 128)
   float *w = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;  // weights, gradients, AdamW moments
@@ -588,7 +594,7 @@ __global__ void __launch_bounds__(1024) k_part_reduce(const float* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int e = e0 + j;
-      if (e < n0) grad[d.dst0 + e] += v[j];
+      if (e < n0) grad[d.dst0 + (d.ld0 ? (int64_t)(e >> 7) * d.ld0 + (e & 127) : (int64_t)e)] += v[j];
       else if (e < n_all) grad[d.dst1 + (e - n0)] += v[j];
     }
   }
@@ -924,7 +930,7 @@ __device__ __forceinline__ void adamw_elem(float gi, float& wk, float& mk, float
   wk -= lr * (mh / (sqrtf(vh) + eps) + wd * wk);
 }
 __global__ void __launch_bounds__(256) k_adamw_gathered(float* __restrict__ w, float* g, float* __restrict__ m,
-                                                         float* __restrict__ v, const float* gath, int64_t n, int world,
+                                                         float* __restrict__ v, const float* gath, int64_t n, int64_t ld, int world,
                                                          float scale, float lr, float b1, float b2, float eps, float wd,
                                                          float c1, float c2) {
   const int64_t nv = n / 4, stride = (int64_t)gridDim.x * blockDim.x;
@@ -933,7 +939,7 @@ __global__ void __launch_bounds__(256) k_adamw_gathered(float* __restrict__ w, f
     lb_f4u acc = *reinterpret_cast<const lb_f4u*>(gath + 4 * i);
 #pragma unroll 4
     for (int r = 1; r < world; ++r) {
-      const lb_f4u row = *reinterpret_cast<const lb_f4u*>(gath + (int64_t)r * n + 4 * i);
+      const lb_f4u row = *reinterpret_cast<const lb_f4u*>(gath + (int64_t)r * ld + 4 * i);
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc.f[k] = acc.f[k] + row.f[k];
     }
@@ -954,7 +960,7 @@ __global__ void __launch_bounds__(256) k_adamw_gathered(float* __restrict__ w, f
   const int64_t j = 4 * nv + tid;   // the n % 4 parameters after the last whole vector
   if (j < n) {
     float acc = gath[j];
-    for (int r = 1; r < world; ++r) acc = acc + gath[(int64_t)r * n + j];
+    for (int r = 1; r < world; ++r) acc = acc + gath[(int64_t)r * ld + j];
     const float gi = acc * scale;
     float wk = w[j], mk = m[j], vk = v[j];
     adamw_elem(gi, wk, mk, vk, lr, b1, b2, eps, wd, c1, c2);
@@ -1747,11 +1753,13 @@ extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const flo
 static void sgt_free(lb_gns_train* t);
 static void egt_free(lb_gns_train* t);
 static void lnt_free(lb_gns_train* t);
+static void pnt_free(lb_gns_train* t);
 extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   if (!t) return;
   sgt_free(t);
   egt_free(t);
   lnt_free(t);
+  pnt_free(t);
   delete t;  // (t->mem frees the buffers)
 }
 
@@ -1994,6 +2002,8 @@ static int feat_bwd(lb_gns_train* t, double* dpos_out_dev) {
 }
 static int linear_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                   float* pred_out_dev);
+static int painn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
+                                 float* pred_out_dev);
 static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
   LB_TRY(gns_forward_part(t, "lb_gns_train_loss_grad", pred_out_dev));
   LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));   // loss and d loss / d pred
@@ -2005,6 +2015,7 @@ extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, 
   if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
   if (t->sg) return lb_segnn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
   if (t->ln) return linear_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
+  if (t->pa) return painn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
   t->fwd_live = false;
   return train_loss_grad_guarded(t, loss_out, [&] { return gns_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
 }
@@ -2022,8 +2033,9 @@ extern "C" int lb_adamw_step(lb_gns_train* t, float lr, float b1, float b2, floa
   t->fwd_live = false;
   t->step += 1;
   const float c1 = 1.f - powf(b1, (float)t->step), c2 = 1.f - powf(b2, (float)t->step);
-  hipLaunchKernelGGL(k_adamw, GRID1(t->n_floats), 0, t->eng->stream, t->w, t->g, t->m, t->v, t->n_floats, lr, b1, b2, eps,
-                     weight_decay, c1, c2);
+  const int64_t n_opt = t->n_floats - t->n_frozen;   // (the frozen tail keeps its bits: weight decay alone would shrink it)
+  if (n_opt > 0)
+    hipLaunchKernelGGL(k_adamw, GRID1(n_opt), 0, t->eng->stream, t->w, t->g, t->m, t->v, n_opt, lr, b1, b2, eps, weight_decay, c1, c2);
   LB_HIP(hipGetLastError());
   return LB_OK;
 }
@@ -2047,12 +2059,13 @@ extern "C" int lb_adamw_step_gathered(lb_gns_train* t, const float* gathered_dev
   if (world > 1 && gathered_dev < t->g + n && t->g < gathered_dev + (int64_t)world * n)
     return lb_fail(LB_ERR_ARG, "the gathered rows overlap the handle's gradient blob");
   t->fwd_live = false;
-  if (n <= 0) return LB_OK;
+  const int64_t n_opt = n - t->n_frozen;   // rows are n floats apart; the frozen tail of each is not summed, nor stepped
+  if (n_opt <= 0) return LB_OK;
   t->step += 1;
   const float c1 = 1.f - powf(b1, (float)t->step), c2 = 1.f - powf(b2, (float)t->step);
   // one lane per four parameters; 256 CUs x 8 blocks at most, grid-stride the rest; >= 1 block for the n % 4 tail
-  const unsigned blocks = (unsigned)std::min<int64_t>((n / 4 + 255) / 256 + (n < 4 ? 1 : 0), 2048);
-  hipLaunchKernelGGL(k_adamw_gathered, dim3(blocks), dim3(256), 0, t->eng->stream, t->w, t->g, t->m, t->v, gathered_dev, n,
+  const unsigned blocks = (unsigned)std::min<int64_t>((n_opt / 4 + 255) / 256 + (n_opt < 4 ? 1 : 0), 2048);
+  hipLaunchKernelGGL(k_adamw_gathered, dim3(blocks), dim3(256), 0, t->eng->stream, t->w, t->g, t->m, t->v, gathered_dev, n_opt, n,
                      (int)world, grad_scale, lr, b1, b2, eps, weight_decay, c1, c2);
   LB_HIP(hipGetLastError());
   return LB_OK;
@@ -2093,7 +2106,7 @@ extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* i
 // The inference images of g re-made on the device from this handle's current weights (lb_gns_repack.hip)
 extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
   if (!t || !g) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->sg || t->eg || t->ln) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
+  if (t->sg || t->eg || t->ln || t->pa) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
   if (g->eng != t->eng) return lb_fail(LB_ERR_ARG, "the model was created for another engine");
   const lb_gns_desc &a = t->desc, &b = g->desc;
   if (a.latent_size != b.latent_size || a.blocks_per_step != b.blocks_per_step || a.num_mp_steps != b.num_mp_steps ||
@@ -2112,6 +2125,9 @@ extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
 
 // ------------------------------------------------------------------------------------------------ Linear
 #include "lb_train_linear.h"
+
+// ------------------------------------------------------------------------------------------------ PaiNN
+#include "lb_train_painn.h"
 
 // ------------------------------------------------------------------- the step split for a caller-side loss
 // lb_train_forward / lb_train_backward (include/lbhip.h): the two halves of every model's step around a d loss / d pred the
@@ -2140,13 +2156,14 @@ extern "C" int lb_train_exact_math(lb_gns_train* t, int32_t exact) {
   if (!t) return lb_fail(LB_ERR_ARG, "null argument");
   // (a live forward stays live: saved activations do not depend on the arithmetic that reads them, so a forward in exact
   // products may be followed by a backward in the default ones)
-  t->f16x2 = !exact && !t->eg && !t->ln && lb_train_f16x2_default();
+  t->f16x2 = !exact && !t->eg && !t->ln && !t->pa && lb_train_f16x2_default();
   return LB_OK;
 }
 static int train_forward_part(lb_gns_train* t, float* pred_out_dev) {
   if (t->eg) return egnn_forward_part(t, "lb_train_forward", pred_out_dev);
   if (t->sg) return segnn_forward_part(t, "lb_train_forward", pred_out_dev);
   if (t->ln) return linear_forward_part(t, "lb_train_forward", pred_out_dev);
+  if (t->pa) return painn_forward_part(t, "lb_train_forward", pred_out_dev);
   return gns_forward_part(t, "lb_train_forward", pred_out_dev);
 }
 extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
@@ -2163,9 +2180,9 @@ extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double
   if (!t->fwd_live)
     return lb_fail(LB_ERR_STATE, "lb_train_backward needs a live forward: call lb_train_forward first (any other call on the "
                    "handle but lb_gns_train_zero_grad ends it)");
-  if (dpos_out_dev && (t->sg || t->eg || t->ln))
+  if (dpos_out_dev && (t->sg || t->eg || t->ln || t->pa))
     return lb_fail(LB_ERR_UNSUPPORTED, "lb_train_backward: the gradient with respect to the window is built for GNS only, "
-                   "not for %s handles", t->sg ? "SEGNN" : t->eg ? "EGNN" : "Linear");
+                   "not for %s handles", t->sg ? "SEGNN" : t->eg ? "EGNN" : t->ln ? "Linear" : "PaiNN");
   t->fwd_live = false;   // the backward consumes the forward's scratch
   lb_engine* e = t->eng;
   hipStream_t s = e->stream;
@@ -2190,6 +2207,7 @@ extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double
     }
     LB_HIP(hipMemcpyAsync(t->dy, t->dsave, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
     if (t->ln) return linear_backward_part(t);
+    if (t->pa) return painn_backward_part(t);
     return t->sg ? segnn_backward_part(t) : gns_backward_part(t, dpos_out_dev);
   });
 }

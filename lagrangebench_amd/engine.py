@@ -289,13 +289,13 @@ class RolloutEngine:
         return {"rel_disp": rd, "rel_dist": rr}
 
     # ------------------------------------------------------------------ model
-    def _new_handle(self, cls, symbol: str, desc, blob: np.ndarray):
-        """A new `cls` handle from the C entry point `symbol`(engine, desc, blob, n_floats, &handle): one model
-        (models/*.py `_create`) or its training state (`_train_create`) on this engine."""
+    def _new_handle(self, cls, symbol: str, desc, blob: np.ndarray, *extra):
+        """A new `cls` handle from the C entry point `symbol`(engine, desc, blob, n_floats, [extra ...,] &handle): one
+        model (models/*.py `_create`) or its training state (`_train_create`) on this engine."""
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         h = C.c_void_p()
         check(getattr(self.lib, symbol)(self._h, C.byref(desc), blob.ctypes.data_as(C.POINTER(C.c_float)),
-                                        C.c_int64(blob.size), C.byref(h)), symbol)
+                                        C.c_int64(blob.size), *extra, C.byref(h)), symbol)
         return cls(self, h, desc, blob.size)
 
     def _forward(self, symbol: str, model, out: Optional[torch.Tensor], dtype) -> torch.Tensor:
@@ -681,6 +681,26 @@ class LinearTrainHandle(GnsTrainHandle):
         super().close()
 
 
+class PainnTrainHandle(GnsTrainHandle):
+    """trainer.py:35-89 for PaiNN (csrc/lb_train_painn.h): GnsTrainHandle's calls, one "acc" target."""
+
+    _view: Optional["PainnHandle"] = None
+
+    def model_handle(self) -> "PainnHandle":
+        """The inference model of this handle: a view of its device weights, so engine.painn_forward / rollout on it run
+        on the CURRENT weights.  Borrowed - it is this handle's; closing it frees nothing, closing this handle ends it."""
+        if self._view is None or not self._view._h:
+            h = C.c_void_p()
+            check(self.engine.lib.lb_painn_train_model(self._h, C.byref(h)), "lb_painn_train_model")
+            self._view = _BorrowedPainnHandle(self.engine, h, self.desc, self.n_floats)
+        return self._view
+
+    def close(self):
+        if self._view is not None:
+            self._view._h = None   # the view dies with the handle
+        super().close()
+
+
 class SegnnHandle(_Handle):
     _DESTROY, _ROLLOUT = "lb_segnn_destroy", "lb_segnn_rollout"
     _tap = None
@@ -750,3 +770,10 @@ class PainnHandle(_Handle):
             self._tap = None
             check(e.lib.lb_painn_set_tap(self._h, None, None), "lb_painn_set_tap")
         return self._tap
+
+
+class _BorrowedPainnHandle(PainnHandle):
+    """A PainnHandle whose lb_painn belongs to a training handle (PainnTrainHandle.model_handle): close() only lets go."""
+
+    def close(self):
+        self._h = None

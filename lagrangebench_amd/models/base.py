@@ -124,7 +124,7 @@ class BaseModel(ABC):
     def check_trainable(self) -> None:
         """Raise NotImplementedError unless the device training step is built for this configuration."""
         raise NotImplementedError("Trainer: the model has no device training step (GNS: csrc/lb_train.hip, SEGNN: "
-                                  "csrc/lb_train_segnn.h, EGNN: csrc/lb_train_egnn.h)")
+                                  "csrc/lb_train_segnn.h, EGNN: csrc/lb_train_egnn.h, PaiNN: csrc/lb_train_painn.h)")
 
     def train_handle(self, engine, params):
         """Device-resident training state (weights, gradients, AdamW moments) for `params` on `engine`."""

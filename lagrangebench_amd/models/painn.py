@@ -13,7 +13,8 @@ rollout integrates it with the case's integrator, as it does GNS's.
   (the reference's runner asserts it).
 * Not built (``NotImplementedError``): an activation other than SiLU, ``output_size != 1``,
   ``gaussian_rbf(centered=True)`` (broken in the reference: it reads an undefined ``width``) and a hidden size
-  that is not a multiple of 16 or exceeds 128.
+  that is not a multiple of 16 or exceeds 128; training (``train_handle``, csrc/lb_train_painn.h) with a hidden
+  size below 64.
 
 Parameters: ``{"scalar_embedding": {"w", "b"}, "vector_embedding": {"w"}, "filter_net": {"w", "b"},
 "layer_{p}/interaction_{0,1}", "layer_{p}/mixing_{0,1}": {"w", "b"}, "layer_{p}/vector_mixing": {"w"},
@@ -30,7 +31,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from .._lib import PainnDesc
-from ..engine import PainnHandle
+from ..engine import PainnHandle, PainnTrainHandle
 from ..utils import NodeType, painn_params_from_haiku, painn_params_to_haiku
 from .base import BaseModel
 from .egnn import _is_silu
@@ -187,9 +188,17 @@ class PaiNN(BaseModel):
             raise ValueError(f"PaiNN radial basis: expected {R} widths and offsets, got {w.size}, {o.size}")
         return np.concatenate(out + [w, o])
 
-    def unflatten(self, blob, has_force: bool, has_bound: bool = False) -> Tuple[Dict, Dict]:
-        """Inverse of flatten -> (params, state)."""
+    def unflatten(self, blob, has_force=None, has_bound: bool = False, like=None):
+        """Inverse of flatten.  ``unflatten(blob, has_force, has_bound)`` -> (params, state).  With a parameter tree of
+        the model's shapes as the second argument (or ``like=``), as the Trainer and DeviceModule call every model:
+        -> the parameter tree alone (a frozen radial basis, which flatten takes from the state, is not part of it)."""
         blob = np.asarray(blob, np.float32)
+        if isinstance(has_force, dict):
+            has_force, like = None, has_force
+        if like is not None:
+            return self.unflatten(blob, *self._io(like))[0]
+        if has_force is None:
+            raise TypeError("PaiNN.unflatten: give has_force (and has_bound), or a parameter tree to take them from")
         out, o = {}, 0
         for mod, leaf, shape in self.leaves(has_force, has_bound):
             n = int(np.prod(shape))
@@ -229,3 +238,29 @@ class PaiNN(BaseModel):
 
     def _to_haiku(self, params):
         return painn_params_to_haiku(params, self)
+
+    # ------------------------------------------------------------------ training
+    MIN_TRAIN_HIDDEN = 64
+
+    def check_trainable(self) -> None:
+        if self._hidden_size < self.MIN_TRAIN_HIDDEN:
+            raise NotImplementedError(f"PaiNN with hidden_size {self._hidden_size}: the model has no device training step "
+                                      f"(csrc/lb_train_painn.h is built for {self.MIN_TRAIN_HIDDEN} <= hidden_size <= 128)")
+
+    def train_handle(self, engine, params, state=None):
+        """Device-resident training state for `params`; `state` carries a frozen radial basis (gaussian_rbf(trainable=
+        False)), else the basis' initial values are taken."""
+        self.check_trainable()
+        self._check_padded(engine)
+        return self._train_create(engine, params, state)
+
+    def _train_create(self, engine, params, state=None):
+        """csrc/lb_train_painn.h: a GnsTrainHandle (one "acc" target).  The radial basis is the blob's tail: parameters
+        with gaussian_rbf(trainable=True), otherwise frozen - zero gradient, untouched by AdamW."""
+        return engine._new_handle(PainnTrainHandle, "lb_painn_train_create", self._desc(), self.flatten(params, state),
+                                  int(bool(self.radial_basis_fn.trainable)))
+
+    def unroll_handle(self, engine, th, params_like):
+        """The training handle's own inference view (csrc/lb_train_painn.h): it reads th's weight blob, nothing to refresh."""
+        self._check_padded(engine)
+        return th.model_handle()

@@ -21,7 +21,9 @@ torch is used for the noise / sampling random streams and as the tensor containe
 two to eight Linears per MLP), since round 5 SEGNN (lmax 1, hidden <= 32x0e+32x1o: ``lb_segnn_train_loss_grad``,
 csrc/lb_train_segnn.h) and EGNN (``lb_egnn_train_loss_grad``, csrc/lb_train_egnn.h: the inference forward, a hand-written
 backward on the exact-fp32 MFMA products; the loss covers every output the model predicts - pos, vel, acc - weighted by
-``loss_weight`` against the case's targets, as _mse does; ``normalize=True`` is refused) and the Linear baseline
+``loss_weight`` against the case's targets, as _mse does; ``normalize=True`` is refused), PaiNN of hidden size 64 to 128
+(csrc/lb_train_painn.h: the inference forward, a hand-written backward on the same exact-fp32 products, the radial basis
+trained or frozen as ``gaussian_rbf(trainable=...)`` says) and the Linear baseline
 (csrc/lb_train_linear.h, exact fp32) - the loop below is the
 reference's model-agnostic one; wandb logging is not wired (stdout).
 
@@ -37,9 +39,9 @@ sample of a step - window, random-walk noise, shift, targets - is made by one HI
 of on the host.  Permutation and unroll count still come from the common stream; the noise is keyed by (seed, step, global
 slot), so a rank's shard gets the single-process noise of its slots.  With the key off nothing below changes.
 
-``train.device_unroll`` (default off): the push-forward unroll of GNS and EGNN runs on an inference
-handle fed from the training handle's device weights (``model.unroll_handle``: ``lb_gns_train_sync_model`` re-packs the GNS
-images in HIP, EGNN lends its view) instead of ``th.read("weights")`` + a host repack; same bits, every rank does the same.
+``train.device_unroll`` (default off): the push-forward unroll of GNS, EGNN and PaiNN runs on an
+inference handle fed from the training handle's device weights (``model.unroll_handle``: ``lb_gns_train_sync_model`` re-packs
+the GNS images in HIP, EGNN and PaiNN lend their views) instead of ``th.read("weights")`` + a host repack; same bits, every rank does the same.
 """
 from __future__ import annotations
 
