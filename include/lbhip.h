@@ -542,6 +542,16 @@ int lb_linear_train_create(lb_engine* eng, const lb_linear_desc* desc, const flo
  * lb_train_backward leaves the handle's saved activations alone (the ENGINE's window is the caller's to restore). */
 int lb_linear_train_model(lb_gns_train* t, lb_linear** out);
 
+/* ---- a training handle that is only optimiser state ----------------------
+ * For a model the CALLER evaluates and differentiates (models.TorchModel: a torch.nn.Module on the engine's features and
+ * graph ops): w / g / m / v blobs of exactly n_floats floats, initialised from weights_host / 0 / 0 / 0 - no padding, nothing
+ * frozen, step counter 0.  lb_gns_train_zero_grad, lb_adamw_step, lb_adamw_step_gathered, lb_gns_train_read / _write /
+ * _device_blob, lb_gns_train_step_count and lb_gns_train_destroy work on it unchanged (the caller's autograd accumulates into
+ * the gradient blob through lb_gns_train_device_blob).  lb_gns_train_loss_grad, lb_segnn_train_loss_grad,
+ * lb_egnn_train_loss_grad, lb_train_forward, lb_train_backward and lb_gns_train_sync_model return LB_ERR_UNSUPPORTED with a
+ * message that names the blob handle: there is no model in it. */
+int lb_blob_train_create(lb_engine* eng, const float* weights_host, int64_t n_floats, lb_gns_train** out);
+
 /* Arithmetic of the GNS GEMMs.  Default (LB_MATH unset) = mode 1: every fp32 operand is carried as an fp16
  * hi/lo pair on the fp16 MFMA (fp32-class accuracy, ~5x fewer matrix-pipe cycles than the fp32 MFMA) WITH a
  * range guard: operands >= 2^15 (sampled), operand ROWS whose values all sit below 2^-11 (tested on every tile of the
@@ -645,6 +655,26 @@ int lb_kernel_names(lb_engine* eng, char* out, int32_t cap);
  * msg (E_total,D) fp32 in engine edge order -> out (B*N,D) fp32.  Used by tests and by the
  * aggregation-roofline leg of bench.py. */
 int lb_segment_sum(lb_engine* eng, const float* msg_dev, float* out_dev, int32_t D);
+
+/* ---- graph primitives for a network written outside the library --------
+ * x[senders], x[receivers] and jraph.segment_sum(msg, receivers | senders, N) on the engine's CURRENT list, each other's
+ * adjoints (the backward of one is the other).  role: 0 receivers, 1 senders.  All tensors fp32, row-major, on the engine's
+ * device, in the PADDED layout of lb_nl_read_idx: edge slot (b, j), j < n_edges[b], is the j-th edge of trajectory b in
+ * canonical (receiver, sender) order.  C >= 1 columns, no upper limit; 16-byte accesses when C % 4 == 0 and both pointers
+ * are 16-byte aligned.  Asynchronous on the engine's stream, except the first call after a list build, which reads the
+ * list's status back (and, for the sender sum, builds the sender-ordered view: per sender its edges in ascending slot
+ * order, by transposing the receiver rows, or by a stable radix sort when an edge has no transpose).  LB_ERR_STATE
+ * without a list or with an overflowed one.
+ * lb_graph_gather: real slots get a copy of the node row, pad slots (j >= n_edges[b]) +0.0.
+ * lb_graph_segment_sum: out[b, i, :] = the fp32 sum of the real slots whose role index is i, taken one term after the other
+ * in ASCENDING SLOT ORDER starting from the first term - bit for bit a float32 loop; pad slots are never read (they may
+ * hold NaN); a node with no such edge gets +0.0.  No float atomics: two calls give the same bits. */
+int lb_graph_gather(lb_engine* eng, int32_t role, const float* x_dev /*(B*N,C)*/, float* out_dev /*(B*E_cap,C)*/, int32_t C);
+int lb_graph_segment_sum(lb_engine* eng, int32_t role, const float* msg_dev /*(B*E_cap,C)*/, float* out_dev /*(B*N,C)*/,
+                         int32_t C);
+/* Test support / diagnostics, like lb_gns_train_sort_fallbacks: sender views built by the radix sort since the engine was
+ * created (a list with an edge in one direction only).  Nothing in the package depends on it. */
+int32_t lb_graph_sender_sorts(lb_engine* eng);
 
 #ifdef __cplusplus
 }

@@ -180,6 +180,10 @@ _SIGS = {
     "lb_linear_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "lb_linear_train_create": (C.c_int, [_P, C.POINTER(LinearDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_linear_train_model": (C.c_int, [_P, C.POINTER(_P)]),
+    "lb_blob_train_create": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
+    "lb_graph_gather": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
+    "lb_graph_segment_sum": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
+    "lb_graph_sender_sorts": (C.c_int32, [_P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -808,10 +808,12 @@ int lb_rollout_generic(lb_engine* e, int (*forward)(lb_engine*, void*), void* mo
         (void)hipGraphDestroy(graph);
         if (ie != hipSuccess) return lb_fail(LB_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
       }
-      if (exec)
+      if (exec) {
+        e->nl_gen += 1;   // (the replayed step builds a list without passing through lbk_nl_build)
         LB_HIP(hipGraphLaunch(exec, e->stream));
-      else
+      } else {
         LB_TRY(lb_enqueue_step(e, forward, model, traj_dev, T, pred_out_dev, n_steps));
+      }
       warm = true;
       LB_HIP(hipEventRecord(e->step_ev[s & 3], e->stream));
     }

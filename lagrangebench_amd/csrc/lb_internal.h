@@ -175,6 +175,23 @@ struct lb_engine {
   int32_t* overflow;   // [B] did_buffer_overflow
   int32_t* nedges_b;   // [B]
 
+  // graph ops on the current list (lb_graph.hip).  nl_gen counts the list builds enqueued so far (lbk_nl_build, a replayed
+  // rollout graph); what the ops read back about a build and the sender-sorted view are cached per build.
+  uint64_t nl_gen = 0;
+  bool graph_seen = false, graph_bad = false;  // a build was read back; it overflowed (or a trajectory outgrew E_cap)
+  uint64_t graph_gen = 0;                      // ... the build that was
+  int32_t graph_ecap = 0, graph_E = 0;         // ... under this E_cap, with this many edges (n_edges_total)
+  bool snd_seen = false;                       // the sender view below is that of build snd_gen
+  uint64_t snd_gen = 0;
+  int32_t *snd_perm = nullptr, *snd_ptr = nullptr;   // [snd_cap] compact edges grouped by sender, row starts (BN + 1)
+  int32_t *snd_key = nullptr, *snd_iota = nullptr;   // [snd_cap] the radix sort's set, with snd_tmp, when snd_radix
+  int32_t* snd_flag = nullptr;                       // [1] bit 4: k_sender_transpose met an edge without its transpose
+  void* snd_tmp = nullptr;
+  size_t snd_tmp_bytes = 0;
+  int64_t snd_cap = 0;
+  bool snd_radix = false;
+  int32_t snd_sorts = 0;                             // sender views built by the radix sort
+
   // network scratch (allocated by lb_gns_create / regrown with e_alloc)
   float* xnode;        // [BN][kpad]
   float* nlat;         // [BN][D]

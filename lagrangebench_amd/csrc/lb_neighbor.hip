@@ -1828,6 +1828,7 @@ static void lb_launch_one_traj(lb_engine* e, bool mid, int nb, int threads, size
 }
 
 int lbk_nl_build(lb_engine* e, bool want_efeat64) {
+  e->nl_gen += 1;   // (what lb_graph.hip caches per list is stale from here on)
   const lb_geom& g = e->g;
   const int64_t BN = e->BN;
   const int ncell_tot = g.B * g.ncells;

@@ -39,6 +39,7 @@
 #include "lb_device.h"
 #include "lb_lin32.h"
 #include "lb_gns_repack.h"
+#include "lb_sender_view.h"
 
 #include <hipcub/hipcub.hpp>  // header-only device radix sort (the sender-sorted edge permutation of the gather's transpose)
 
@@ -81,6 +82,7 @@ struct lb_gns_train {
   lb_linear* ln = nullptr;  // non-null: this handle trains a Linear (lb_linear_train_create): the inference view of t->w
   lb_linear_desc ln_desc{};
   lb_pnt* pa = nullptr;   // non-null: this handle trains a PaiNN (created by lb_painn_train_create)
+  bool blob = false;      // lb_blob_train_create: optimiser state only (w / g / m / v of n_floats), no model behind it
   lb_gns_desc desc;
   lb_engine* eng;
   int64_t n_floats = 0;   // floats of the DEVICE blobs (latent padded to 128)
@@ -767,21 +769,6 @@ __global__ void k_edge_dP(const float* __restrict__ da, const int32_t* __restric
   for (int k = k0; k < k1; ++k) ar = ar + reinterpret_cast<const f32x4*>(da)[(int64_t)k * 32 + q];
   reinterpret_cast<f32x4*>(dPs)[i] = as;
   reinterpret_cast<f32x4*>(dPr)[i] = ar;
-}
-__global__ void k_iota(int32_t* __restrict__ x, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] = (int32_t)i;
-}
-// snd_ptr[s] = first position of key >= s in the sorted sender keys (lower bound), s = 0 .. N
-__global__ void k_lower_bounds(const int32_t* __restrict__ keys, int64_t E, int64_t N, int32_t* __restrict__ ptr) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s > N) return;
-  int64_t lo = 0, hi = E;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < (int32_t)s) lo = mid + 1; else hi = mid;
-  }
-  ptr[s] = (int32_t)lo;
 }
 // jraph.segment_sum on the receiver-sorted CSR (rows are contiguous edge ranges): agg[r] = sum_e msg[e]
 // xn != null (the GNS node block): the sum goes straight into the right half of the node MLP's input row [n | agg] and the
@@ -1540,33 +1527,6 @@ static int train_loss(lb_gns_train* t, const float* pred, const float* target_de
   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, s, t->loss_part, (int64_t)((BN + 255) / 256) * 4, t->loss_dev);
   return LB_OK;
 }
-// Sender-sorted view of the step's edge list WITHOUT a sort (round 6; hipcub::DeviceRadixSort until then: three rocprim
-// kernels + a lower-bound pass per step).  The neighbor relation is symmetric - (r, s) is an edge iff (s, r) is - and the list
-// is sorted by (receiver, sender): the edges SENT by node s are the transposes of row s, so s sends as many edges as it
-// receives (snd_ptr == row_ptr) and, among the edges sent by s in ascending edge order (= ascending receiver), edge (r, s)
-// has the rank that r has among the senders of row s.  One thread per edge: a bisection of row s (a dozen L2-resident
-// integers) for r, then snd_perm[row_ptr[s] + rank] = edge.  The periodic displacement is antisymmetric only up to one
-// rounding of (x + L/2), so a pair within ~1e-16 of the cutoff CAN be an edge in one direction only: a thread that does
-// not find its transpose raises bit 4 of the step's guard flag - the reductions then add nothing and the step is repeated
-// with the radix sort below (train_loss_grad_guarded).
-__global__ void k_sender_transpose(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ senders,
-                                   const int32_t* __restrict__ receivers, int64_t E, int64_t BN, int32_t* __restrict__ snd_perm,
-                                   int32_t* __restrict__ snd_ptr, int32_t* __restrict__ flag) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i <= BN) snd_ptr[i] = row_ptr[i];
-  if (i >= E) return;
-  const int r = receivers[i], s = senders[i];
-  int lo = row_ptr[s], hi = row_ptr[s + 1];   // first position of row s whose sender is >= r
-  const int end = hi;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (senders[mid] < r) lo = mid + 1; else hi = mid;
-  }
-  if (lo < end && senders[lo] == r)
-    snd_perm[lo] = (int32_t)i;
-  else
-    atomicOr(flag, 4);
-}
 // the same view by a stable radix sort of (sender, edge index) - the fall-back for a step whose list is not symmetric
 // -> t->snd_perm (E), t->snd_ptr (BN + 1)
 static int train_sender_sort(lb_gns_train* t, int64_t E, int64_t BN) {
@@ -1748,6 +1708,33 @@ extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const flo
   }
   *out = t;
   return LB_OK;
+}
+
+// A training handle with no model in it (lagrangebench_amd/models/torch_model.py: the network and its loss are torch's):
+// the four blobs of exactly n_floats floats - no padding, cmap empty, nothing frozen - for lb_gns_train_zero_grad,
+// lb_adamw_step(_gathered), lb_gns_train_read / _write / _device_blob, lb_gns_train_step_count and lb_gns_train_destroy.
+// Every entry that runs a model refuses it (blob_refuse).
+extern "C" int lb_blob_train_create(lb_engine* e, const float* w, int64_t n_floats, lb_gns_train** out) {
+  if (!e || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (n_floats < 1) return lb_fail(LB_ERR_ARG, "lb_blob_train_create: %lld floats", (long long)n_floats);
+  lb_gns_train* t = new lb_gns_train();
+  t->eng = e;
+  t->blob = true;
+  t->f16x2 = false;
+  t->desc = lb_gns_desc{};
+  t->n_floats = t->n_compact = n_floats;
+  const int rc = train_handle_init(t, "weight blob", w, n_floats);
+  if (rc) {
+    lb_gns_train_destroy(t);
+    return rc;
+  }
+  *out = t;
+  return LB_OK;
+}
+static int blob_refuse(const char* entry) {
+  return lb_fail(LB_ERR_UNSUPPORTED, "%s: a blob training handle (lb_blob_train_create) holds optimiser state only - the model, "
+                 "its forward and its loss are the caller's", entry);
 }
 
 static void sgt_free(lb_gns_train* t);
@@ -2012,6 +1999,7 @@ static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, fl
 extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                       float* pred_out_dev) {
   if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->blob) return blob_refuse("lb_gns_train_loss_grad");
   if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
   if (t->sg) return lb_segnn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
   if (t->ln) return linear_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
@@ -2106,6 +2094,7 @@ extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* i
 // The inference images of g re-made on the device from this handle's current weights (lb_gns_repack.hip)
 extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
   if (!t || !g) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->blob) return blob_refuse("lb_gns_train_sync_model");
   if (t->sg || t->eg || t->ln || t->pa) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
   if (g->eng != t->eng) return lb_fail(LB_ERR_ARG, "the model was created for another engine");
   const lb_gns_desc &a = t->desc, &b = g->desc;
@@ -2156,7 +2145,7 @@ extern "C" int lb_train_exact_math(lb_gns_train* t, int32_t exact) {
   if (!t) return lb_fail(LB_ERR_ARG, "null argument");
   // (a live forward stays live: saved activations do not depend on the arithmetic that reads them, so a forward in exact
   // products may be followed by a backward in the default ones)
-  t->f16x2 = !exact && !t->eg && !t->ln && !t->pa && lb_train_f16x2_default();
+  t->f16x2 = !exact && !t->eg && !t->ln && !t->pa && !t->blob && lb_train_f16x2_default();
   return LB_OK;
 }
 static int train_forward_part(lb_gns_train* t, float* pred_out_dev) {
@@ -2168,6 +2157,7 @@ static int train_forward_part(lb_gns_train* t, float* pred_out_dev) {
 }
 extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
   if (!t || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->blob) return blob_refuse("lb_train_forward");
   t->fwd_live = false;
   LB_TRY(train_forward_part(t, pred_out_dev));
   LB_HIP(hipGetLastError());
@@ -2177,6 +2167,7 @@ extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
 }
 extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double* dpos_out_dev) {
   if (!t || !dpred_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->blob) return blob_refuse("lb_train_backward");
   if (!t->fwd_live)
     return lb_fail(LB_ERR_STATE, "lb_train_backward needs a live forward: call lb_train_forward first (any other call on the "
                    "handle but lb_gns_train_zero_grad ends it)");

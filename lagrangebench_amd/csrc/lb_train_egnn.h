@@ -637,6 +637,7 @@ static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, con
 // value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h)
 extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
                                        float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev) {
+  if (t && t->blob) return blob_refuse("lb_egnn_train_loss_grad");
   if (!t || !t->eg) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");
   if ((w_pos != 0.f && !tgt_pos) || (w_vel != 0.f && !tgt_vel) || (w_acc != 0.f && !tgt_acc))
     return lb_fail(LB_ERR_ARG, "egnn training: a target with a non-zero loss weight is null");

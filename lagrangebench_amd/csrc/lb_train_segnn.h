@@ -540,6 +540,7 @@ static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, 
 // value_and_grad of _mse for SEGNN on the engine's CURRENT window / neighbor list: same contract as lb_gns_train_loss_grad
 extern "C" int lb_segnn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                         float* pred_out_dev) {
+  if (t && t->blob) return blob_refuse("lb_segnn_train_loss_grad");
   if (!t || !t->sg || !target_dev) return lb_fail(LB_ERR_ARG, "null argument / not a SEGNN training handle");
   t->fwd_live = false;
   return train_loss_grad_guarded(t, loss_out, [&] { return segnn_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });

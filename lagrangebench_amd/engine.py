@@ -117,6 +117,7 @@ class RolloutEngine:
         self.e_cap = 0
         self.version = 0  # bumped whenever window / list change: ties FeatureDicts to a state
         self.has_pads = False  # the current particle types hold NodeType.PAD_VALUE (set_particle_type)
+        self.particle_type: Optional[torch.Tensor] = None  # the (B, N) int32 device tensor last handed to the engine
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -150,6 +151,7 @@ class RolloutEngine:
         self.has_pads = bool((src == -1).any())
         t = self._t(src, torch.int32).reshape(self.B, self.N)
         check(self.lib.lb_set_particle_type(self._h, ptr(t)), "lb_set_particle_type")
+        self.particle_type = t
 
     def train_batch(self, dd, trajs: Sequence[int], t0s: Sequence[int], slots: Sequence[int], seed: int, step: int,
                     noise_std: float, unroll_steps: int = 0, want_normals: bool = False):
@@ -184,6 +186,7 @@ class RolloutEngine:
         self.has_pads = bool(has_pads)
         self._t(ptype, torch.int32)
         check(self.lib.lb_set_particle_type(self._h, ptr(ptype)), "lb_set_particle_type")
+        self.particle_type = ptype
 
     def prepare_traj(self, pos) -> torch.Tensor:
         """(B,N,T,dim) or (N,T,dim) positions -> fp64 contiguous device tensor."""
@@ -429,6 +432,38 @@ class RolloutEngine:
             return out, np.frombuffer(info, dtype=np.int32).reshape(self.B, n_out, 6).copy()
         return out
 
+    def blob_train_handle(self, blob: np.ndarray) -> "BlobTrainHandle":
+        """A training handle that is only optimiser state - weights (from `blob`), gradients and the AdamW moments of
+        blob.size floats - for a model the caller evaluates (include/lbhip.h: lb_blob_train_create)."""
+        blob = np.ascontiguousarray(blob, dtype=np.float32).reshape(-1)
+        h = C.c_void_p()
+        check(self.lib.lb_blob_train_create(self._h, blob.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(blob.size),
+                                            C.byref(h)), "lb_blob_train_create")
+        return BlobTrainHandle(self, h, None, blob.size)
+
+    def _graph_op(self, symbol: str, role: int, src: torch.Tensor, rows_in: int, rows_out: int) -> torch.Tensor:
+        if src.dtype != torch.float32 or src.device != self.device or not src.is_contiguous() or src.dim() != 2 \
+                or src.shape[0] != rows_in or src.shape[1] < 1:
+            raise ValueError(f"{symbol}: expected a contiguous ({rows_in}, C >= 1) float32 tensor on {self.device}, got "
+                             f"{tuple(src.shape)} {src.dtype} on {src.device}")
+        out = torch.empty((rows_out, src.shape[1]), dtype=torch.float32, device=self.device)
+        check(getattr(self.lib, symbol)(self._h, int(role), ptr(src), ptr(out), int(src.shape[1])), symbol)
+        return out
+
+    def graph_gather(self, role: int, x: torch.Tensor) -> torch.Tensor:
+        """x (B*N, C) float32 -> (B*E_cap, C): the node row of every real edge slot of the current list in the padded
+        layout of nl_idx(), +0.0 in the pad slots.  role: 0 receivers, 1 senders (include/lbhip.h: lb_graph_gather)."""
+        return self._graph_op("lb_graph_gather", role, x, self.B * self.N, self.B * self.e_cap)
+
+    def graph_segment_sum(self, role: int, msg: torch.Tensor) -> torch.Tensor:
+        """msg (B*E_cap, C) float32 -> (B*N, C): per node the sum of its real edge slots in ascending slot order, one fp32
+        add after the other; no atomics (include/lbhip.h: lb_graph_segment_sum)."""
+        return self._graph_op("lb_graph_segment_sum", role, msg, self.B * self.e_cap, self.B * self.N)
+
+    def graph_sender_sorts(self) -> int:
+        """Sender-ordered views the graph ops built by the radix sort (a list with an edge in one direction only)."""
+        return int(self.lib.lb_graph_sender_sorts(self._h))
+
     def segment_sum(self, msg: torch.Tensor) -> torch.Tensor:
         msg = _dev(msg, torch.float32, self.device)
         out = torch.empty((self.B * self.N, msg.shape[1]), dtype=torch.float32, device=self.device)
@@ -557,15 +592,16 @@ class GnsTrainHandle(_Handle):
         check(self.engine.lib.lb_adamw_step(self._h, C.c_float(lr), C.c_float(b1), C.c_float(b2), C.c_float(eps),
                                             C.c_float(weight_decay)), "lb_adamw_step")
 
-    def device_blob(self, which: str = "grads") -> torch.Tensor:
+    def device_blob(self, which: str = "grads", keep_alive: bool = True) -> torch.Tensor:
         """The device memory of a blob as a 1-D float32 tensor - a view, no copy - in the DEVICE layout (latents padded
         to 128, so it can be longer than read(which); every rank of a data-parallel run has the same layout).  Valid
-        until close()."""
+        until close().  keep_alive: the tensor references this handle; False is for a tensor the handle itself keeps
+        (BlobTrainHandle.module), which must not hold its owner in a reference cycle."""
         idx = {"weights": 0, "grads": 1, "m": 2, "v": 3}[which]
         p, n = C.c_void_p(), C.c_int64()
         check(self.engine.lib.lb_gns_train_device_blob(self._h, idx, C.byref(p), C.byref(n)), "lb_gns_train_device_blob")
         self._dev_floats = n.value
-        return torch.as_tensor(_DeviceSpan(self, p.value, n.value), device=self.engine.device)
+        return torch.as_tensor(_DeviceSpan(self if keep_alive else None, p.value, n.value), device=self.engine.device)
 
     def device_floats(self) -> int:
         """Floats of a blob in the device layout (the length of device_blob)."""
@@ -678,6 +714,27 @@ class LinearTrainHandle(GnsTrainHandle):
     def close(self):
         if self._view is not None:
             self._view._h = None   # the view dies with the handle
+        super().close()
+
+
+class BlobTrainHandle(GnsTrainHandle):
+    """Optimiser state with no model in it (include/lbhip.h: lb_blob_train_create): zero_grad, adamw_step(_gathered), read /
+    write / device_blob and step_count are GnsTrainHandle's; loss_grad, forward, backward and sync_model are refused by the
+    library.  models.TorchModel keeps its device module here: `module`, whose parameters and gradients alias the weight
+    and gradient blobs, and `view`, the inference handle on that module.  Those aliases do not reference the handle (no
+    cycle: dropping the last reference to the handle frees it at once, like the other handles); close() - also run by
+    __del__ - empties the module's parameters before the blobs are freed, so a module kept beyond its handle holds no
+    dangling memory."""
+
+    module = None
+    view = None
+
+    def close(self):
+        if self.module is not None:   # the parameters alias memory that is about to be freed: let go of it first
+            for p in self.module.parameters():
+                p.grad = None
+                p.data = torch.empty(0, dtype=p.dtype, device=p.device)
+        self.module = self.view = None
         super().close()
 
 

@@ -53,7 +53,7 @@ def _gns_of(model_apply) -> Optional[BaseModel]:
     while isinstance(fn, partial):
         fn = fn.func
     owner = getattr(fn, "__self__", None)
-    return owner if isinstance(owner, BaseModel) else None
+    return owner if isinstance(owner, BaseModel) and owner._FUSED_ROLLOUT else None
 
 
 def _eval_batched_rollout(forward_eval_vmap: Callable, preprocess_eval_vmap: Callable, case, params, state,

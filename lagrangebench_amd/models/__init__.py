@@ -4,5 +4,6 @@ from .gns import GNS
 from .linear import Linear
 from .painn import PaiNN
 from .segnn import SEGNN, node_irreps
+from .torch_model import TorchModel
 
-__all__ = ["BaseModel", "EGNN", "GNS", "Linear", "PaiNN", "SEGNN", "node_irreps"]
+__all__ = ["BaseModel", "EGNN", "GNS", "Linear", "PaiNN", "SEGNN", "TorchModel", "node_irreps"]

@@ -24,6 +24,8 @@ class BaseModel(ABC):
     _HAIKU_KEY = ""
     _PADDED_OK = False  # runs on padded trajectories (particles of type NodeType.PAD_VALUE): GNS only
     _EXACT_FORWARD = False  # autograd.DeviceModule runs the forward in exact-fp32 products: networks with ReLU kinks (GNS)
+    _FUSED_ROLLOUT = True  # evaluate.rollout runs the model's handle through the device loop (engine.rollout); False: the
+    #                        generic Python loop drives apply + case.integrate step by step (models.TorchModel)
     _WINDOW_GRAD = False  # the training handle's backward also gives d loss / d window (autograd.DeviceModule): GNS only
     _MAX_HANDLES = 4  # device copies kept per model object (LRU): a training loop that hands over a fresh
     #                   parameter tree every step must not accumulate one packed weight blob per step
