@@ -672,6 +672,44 @@ int lb_segment_sum(lb_engine* eng, const float* msg_dev, float* out_dev, int32_t
 int lb_graph_gather(lb_engine* eng, int32_t role, const float* x_dev /*(B*N,C)*/, float* out_dev /*(B*E_cap,C)*/, int32_t C);
 int lb_graph_segment_sum(lb_engine* eng, int32_t role, const float* msg_dev /*(B*E_cap,C)*/, float* out_dev /*(B*N,C)*/,
                          int32_t C);
+/* ---- graph ops for attention and pooling layers ------------------------
+ * The rules of the segment sum hold for all of them: fp32, the padded layout, role 0 receivers / 1 senders (the cached sender
+ * view), pad slots never read (they may hold NaN), every pad slot of an edge-shaped output +0.0, no float atomics, two calls
+ * give the same bits, int64 addresses.  LB_ERR_ARG on a null pointer, a role other than 0 / 1, or C, H, D < 1; LB_ERR_STATE as
+ * above.  "Slot order" is ascending slot j within the trajectory, over the real slots whose role index is the node.
+ * degree: out[b, i] = the number of those slots (int32).
+ * segment_max: out[b, i, c] starts from the node's first slot; each further slot in slot order replaces it only if it is
+ *   strictly greater (ties keep the earlier slot, -0.0 then +0.0 stays -0.0); a NaN wins and stays.  segment_min: strictly
+ *   smaller.  A node without a slot gets +0.0 (not -/+inf).  win[b, i, c] (int32) is the slot j that won, -1 for such a node.
+ * segment_max_backward (max and min): d_msg[slot, c] = d_out[node, c] where the slot is win[node, c], +0.0 in every other
+ *   slot, pads included; every slot is written.
+ * segment_softmax: per node and column m = the maximum as above, e_j = expf(x_j - m) (the accurate expf), s = e of the first
+ *   slot + e of each further slot in slot order, y_j = e_j / s.
+ * segment_softmax_backward: d_x_j = y_j (d_y_j - sum_k d_y_k y_k), the sum in slot order from its first term.
+ * attend: out[b, i, h, :] = sum_j alpha[j, h] values[j, h, :] with alpha = e / s exactly as segment_softmax computes it from
+ *   logits (B*E_cap, H); each product is rounded to fp32, the sum starts from the first product and adds in slot order, without
+ *   FMA contraction - bit for bit segment_sum(segment_softmax(logits)[..., None] * values).  m, s (B*N, H): the maximum and the
+ *   sum used (0 and 1 for a node without a slot), for the backward.
+ * attend_backward: d_values[j, h, :] = alpha[j, h] d_out[node, h, :] (one multiplication: the composition's bits);
+ *   d_logits[j, h] = alpha[j, h] (t[j, h] - sum_k alpha[k, h] t[k, h]), t[j, h] = sum_d d_out[node, h, d] values[j, h, d] with d
+ *   ascending in one lane, the sum over k in slot order.  alpha is recomputed from logits, m and s: the forward's bits. */
+int lb_graph_degree(lb_engine* eng, int32_t role, int32_t* out_dev /*(B*N)*/);
+int lb_graph_segment_max(lb_engine* eng, int32_t role, const float* msg_dev /*(B*E_cap,C)*/, float* out_dev /*(B*N,C)*/,
+                         int32_t* win_dev /*(B*N,C)*/, int32_t C);
+int lb_graph_segment_min(lb_engine* eng, int32_t role, const float* msg_dev /*(B*E_cap,C)*/, float* out_dev /*(B*N,C)*/,
+                         int32_t* win_dev /*(B*N,C)*/, int32_t C);
+int lb_graph_segment_max_backward(lb_engine* eng, int32_t role, const float* d_out_dev /*(B*N,C)*/,
+                                  const int32_t* win_dev /*(B*N,C)*/, float* d_msg_dev /*(B*E_cap,C)*/, int32_t C);
+int lb_graph_segment_softmax(lb_engine* eng, int32_t role, const float* logits_dev /*(B*E_cap,C)*/,
+                             float* out_dev /*(B*E_cap,C)*/, int32_t C);
+int lb_graph_segment_softmax_backward(lb_engine* eng, int32_t role, const float* y_dev /*(B*E_cap,C)*/,
+                                      const float* d_y_dev /*(B*E_cap,C)*/, float* d_x_dev /*(B*E_cap,C)*/, int32_t C);
+int lb_graph_attend(lb_engine* eng, int32_t role, const float* logits_dev /*(B*E_cap,H)*/,
+                    const float* values_dev /*(B*E_cap,H*D)*/, float* out_dev /*(B*N,H*D)*/, float* m_dev /*(B*N,H)*/,
+                    float* s_dev /*(B*N,H)*/, int32_t H, int32_t D);
+int lb_graph_attend_backward(lb_engine* eng, int32_t role, const float* logits_dev, const float* values_dev, const float* m_dev,
+                             const float* s_dev, const float* d_out_dev /*(B*N,H*D)*/, float* d_logits_dev /*(B*E_cap,H)*/,
+                             float* d_values_dev /*(B*E_cap,H*D)*/, int32_t H, int32_t D);
 /* Test support / diagnostics, like lb_gns_train_sort_fallbacks: sender views built by the radix sort since the engine was
  * created (a list with an edge in one direction only).  Nothing in the package depends on it. */
 int32_t lb_graph_sender_sorts(lb_engine* eng);

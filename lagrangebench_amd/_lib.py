@@ -184,6 +184,14 @@ _SIGS = {
     "lb_graph_gather": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
     "lb_graph_segment_sum": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
     "lb_graph_sender_sorts": (C.c_int32, [_P]),
+    "lb_graph_degree": (C.c_int, [_P, C.c_int32, _P]),
+    "lb_graph_segment_max": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "lb_graph_segment_min": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "lb_graph_segment_max_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "lb_graph_segment_softmax": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32]),
+    "lb_graph_segment_softmax_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
+    "lb_graph_attend": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_attend_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,12 +1,15 @@
-// lb_graph.hip - the two graph primitives a message-passing network written OUTSIDE this library needs on the engine's
+// lb_graph.hip - the graph primitives a message-passing network written OUTSIDE this library needs on the engine's
 // current neighbor list (lagrangebench_amd/graph.py wraps them as torch autograd functions):
 //
 //   lb_graph_gather(role, x (B*N, C))         -> out (B*E_cap, C)   out[slot] = x[role index of the slot], pads +0.0
 //   lb_graph_segment_sum(role, msg (B*E_cap, C)) -> out (B*N, C)    out[i]    = sum of the real slots whose role index is i
 //
-// in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
-// receiver-sorted list.  They are each other's adjoints, so the backward of either is the other one: the same kernels,
-// the same bits.
+// and, for attention and pooling layers (further down: "attention ops"), lb_graph_degree, lb_graph_segment_max / _min,
+// lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries.
+//
+// All work in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
+// receiver-sorted list.  Gather and segment_sum are each other's adjoints, so the backward of either is the other one: the
+// same kernels, the same bits.
 //
 // Order contract of the sum: the first term, then one fp32 add per further term in ASCENDING SLOT ORDER - a numpy float32
 // loop gives the same bits.  Receivers: the slots of node i are the contiguous CSR row of i.  Senders: the slots come from
@@ -116,6 +119,404 @@ __global__ void __launch_bounds__(256) k_graph_segment_sum(const int32_t* __rest
       }
       for (; p < p1; ++p) s = s + ms[edge(p) * U + u];
       os[i * U + u] = s;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ attention ops
+// degree, segment max / min, segment softmax and the fused attend, forward and backward (the contracts
+// are in include/lbhip.h).  The node-parallel kernels walk a row exactly as k_graph_segment_sum does (lb_row: the same caps and
+// clamps), the edge-parallel ones address a slot as k_graph_gather does.  A unit is W = 4 floats (one 16-byte access) or W = 1.
+// -ffp-contract=off holds for this file (build.py); the attend sum spells its roundings out with __fmul_rn / __fadd_rn anyway.
+typedef int32_t lb_i32x4 __attribute__((ext_vector_type(4)));
+
+template <int W>
+__device__ __forceinline__ void lb_ld(const float* p, float (&a)[W]) {
+  if constexpr (W == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    a[0] = t[0], a[1] = t[1], a[2] = t[2], a[3] = t[3];
+  } else {
+    a[0] = *p;
+  }
+}
+template <int W>
+__device__ __forceinline__ void lb_st(float* p, const float (&a)[W]) {
+  if constexpr (W == 4)
+    *reinterpret_cast<f32x4*>(p) = f32x4{a[0], a[1], a[2], a[3]};
+  else
+    *p = a[0];
+}
+template <int W>
+__device__ __forceinline__ void lb_ldi(const int32_t* p, int32_t (&a)[W]) {
+  if constexpr (W == 4) {
+    const lb_i32x4 t = *reinterpret_cast<const lb_i32x4*>(p);
+    a[0] = t[0], a[1] = t[1], a[2] = t[2], a[3] = t[3];
+  } else {
+    a[0] = *p;
+  }
+}
+template <int W>
+__device__ __forceinline__ void lb_sti(int32_t* p, const int32_t (&a)[W]) {
+  if constexpr (W == 4)
+    *reinterpret_cast<lb_i32x4*>(p) = lb_i32x4{a[0], a[1], a[2], a[3]};
+  else
+    *p = a[0];
+}
+
+// Row i of (seg_ptr, perm): positions p0 .. p1 - 1; edge(p) is the padded slot (flat over the batch) of position p, clamped
+// into the trajectory's own E_cap slots; first is the trajectory's slot 0, so edge(p) - first is the slot j within it.
+struct lb_row {
+  const int32_t* perm;
+  int base, last, p0, p1;
+  int64_t slot0, first;
+  __device__ __forceinline__ int64_t edge(int p) const {
+    int k = perm ? perm[p] : p;
+    k = k < base ? base : k;
+    k = k >= last ? last - 1 : k;
+    return slot0 + k;
+  }
+};
+__device__ __forceinline__ lb_row graph_row(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                            const int32_t* __restrict__ perm, int64_t i, int N, int e_cap, int E) {
+  lb_row R;
+  const int64_t b = i / N;
+  R.perm = perm;
+  R.base = row_ptr[b * N];
+  int last = row_ptr[(b + 1) * N];
+  last = last < E ? last : E;
+  R.last = last - R.base < e_cap ? last : R.base + e_cap;
+  int p0 = seg_ptr[i], p1 = seg_ptr[i + 1];
+  R.p0 = p0 < E ? p0 : E;
+  R.p1 = p1 < E ? p1 : E;
+  if (R.last <= R.base || R.p1 < R.p0) R.p1 = R.p0;
+  R.first = b * e_cap;
+  R.slot0 = R.first - R.base;
+  return R;
+}
+
+// a replaces the running s: strictly greater (MIN: smaller), or a is the first NaN (np.maximum / np.minimum keep a NaN)
+template <bool MIN>
+__device__ __forceinline__ bool lb_beats(float a, float s) {
+  return (MIN ? a < s : a > s) || (a != a && s == s);
+}
+
+__global__ void __launch_bounds__(256) k_graph_degree(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                                      int32_t* __restrict__ out, int64_t BN, int N, int e_cap, int E) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= BN) return;
+  const lb_row R = graph_row(row_ptr, seg_ptr, nullptr, i, N, e_cap, E);
+  out[i] = R.p1 - R.p0;
+}
+
+// out[i][c] = the first real slot's value, replaced by each further slot in ascending slot order that beats it; win[i][c] = the
+// slot j (within the trajectory) that won, -1 and +0.0 for an empty row.
+template <bool VEC, bool MIN>
+__global__ void __launch_bounds__(256) k_graph_segment_max(const int32_t* __restrict__ row_ptr,
+                                                           const int32_t* __restrict__ seg_ptr,
+                                                           const int32_t* __restrict__ perm, const float* __restrict__ msg,
+                                                           float* __restrict__ out, int32_t* __restrict__ win, int64_t BN, int N,
+                                                           int e_cap, int E, int U, int lpr_shift) {
+  constexpr int W = VEC ? 4 : 1;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
+    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    for (int u = lane; u < U; u += lpr) {
+      float s[W], a[W];
+      int32_t w[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) s[k] = 0.f, w[k] = -1;
+      int p = R.p0;
+      if (p < R.p1) {
+        const int64_t e = R.edge(p++);
+        lb_ld<W>(msg + (e * U + u) * W, s);
+#pragma unroll
+        for (int k = 0; k < W; ++k) w[k] = (int32_t)(e - R.first);
+      }
+#pragma unroll 4
+      for (; p < R.p1; ++p) {
+        const int64_t e = R.edge(p);
+        lb_ld<W>(msg + (e * U + u) * W, a);
+#pragma unroll
+        for (int k = 0; k < W; ++k)
+          if (lb_beats<MIN>(a[k], s[k])) s[k] = a[k], w[k] = (int32_t)(e - R.first);
+      }
+      lb_st<W>(out + (i * U + u) * W, s);
+      lb_sti<W>(win + (i * U + u) * W, w);
+    }
+  }
+}
+
+// d_msg[slot][c] = d_out[node][c] where the slot won column c of its node, +0.0 in every other real slot and in the pads.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_graph_segment_max_bwd(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
+                                                               const float* __restrict__ d_out, const int32_t* __restrict__ win,
+                                                               float* __restrict__ d_msg, int64_t BN, int N, int B, int e_cap,
+                                                               int E, int U, int lpr_shift) {
+  constexpr int W = VEC ? 4 : 1;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
+    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
+    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
+    const bool real = j < nb && base + j < E;
+    int64_t node = real ? idx[base + j] : 0;
+    node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
+    for (int u = lane; u < U; u += lpr) {
+      float d[W], g[W];
+      int32_t w[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) d[k] = 0.f;
+      if (real) {
+        lb_ld<W>(d_out + (node * U + u) * W, g);
+        lb_ldi<W>(win + (node * U + u) * W, w);
+#pragma unroll
+        for (int k = 0; k < W; ++k) d[k] = w[k] == j ? g[k] : 0.f;
+      }
+      lb_st<W>(d_msg + (r * U + u) * W, d);
+    }
+  }
+}
+
+// y[slot][c] = expf(x[slot][c] - m) / s over the slots of node i: m the maximum as in k_graph_segment_max, s the ordered sum of
+// the exponentials.  The group that owns the node writes the node's slots; the pad slots were zeroed before the launch.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_graph_softmax(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                                       const int32_t* __restrict__ perm, const float* __restrict__ x,
+                                                       float* __restrict__ y, int64_t BN, int N, int e_cap, int E, int U,
+                                                       int lpr_shift) {
+  constexpr int W = VEC ? 4 : 1;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
+    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    if (R.p0 >= R.p1) continue;
+    for (int u = lane; u < U; u += lpr) {
+      float m[W], s[W], a[W];
+      lb_ld<W>(x + (R.edge(R.p0) * U + u) * W, m);
+#pragma unroll 4
+      for (int p = R.p0 + 1; p < R.p1; ++p) {
+        lb_ld<W>(x + (R.edge(p) * U + u) * W, a);
+#pragma unroll
+        for (int k = 0; k < W; ++k)
+          if (lb_beats<false>(a[k], m[k])) m[k] = a[k];
+      }
+      lb_ld<W>(x + (R.edge(R.p0) * U + u) * W, a);
+#pragma unroll
+      for (int k = 0; k < W; ++k) s[k] = expf(a[k] - m[k]);
+#pragma unroll 4
+      for (int p = R.p0 + 1; p < R.p1; ++p) {
+        lb_ld<W>(x + (R.edge(p) * U + u) * W, a);
+#pragma unroll
+        for (int k = 0; k < W; ++k) s[k] = __fadd_rn(s[k], expf(a[k] - m[k]));
+      }
+#pragma unroll 4
+      for (int p = R.p0; p < R.p1; ++p) {
+        const int64_t o = (R.edge(p) * U + u) * W;
+        lb_ld<W>(x + o, a);
+#pragma unroll
+        for (int k = 0; k < W; ++k) a[k] = expf(a[k] - m[k]) / s[k];
+        lb_st<W>(y + o, a);
+      }
+    }
+  }
+}
+
+// d_x[slot][c] = y (d_y - sum_k d_y[k] y[k]) over the slots of node i, the sum ordered; the pads were zeroed before the launch.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_graph_softmax_bwd(const int32_t* __restrict__ row_ptr,
+                                                           const int32_t* __restrict__ seg_ptr,
+                                                           const int32_t* __restrict__ perm, const float* __restrict__ y,
+                                                           const float* __restrict__ d_y, float* __restrict__ d_x, int64_t BN,
+                                                           int N, int e_cap, int E, int U, int lpr_shift) {
+  constexpr int W = VEC ? 4 : 1;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
+    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    if (R.p0 >= R.p1) continue;
+    for (int u = lane; u < U; u += lpr) {
+      float dot[W], a[W], g[W];
+      {
+        const int64_t o = (R.edge(R.p0) * U + u) * W;
+        lb_ld<W>(y + o, a);
+        lb_ld<W>(d_y + o, g);
+#pragma unroll
+        for (int k = 0; k < W; ++k) dot[k] = __fmul_rn(g[k], a[k]);
+      }
+#pragma unroll 4
+      for (int p = R.p0 + 1; p < R.p1; ++p) {
+        const int64_t o = (R.edge(p) * U + u) * W;
+        lb_ld<W>(y + o, a);
+        lb_ld<W>(d_y + o, g);
+#pragma unroll
+        for (int k = 0; k < W; ++k) dot[k] = __fadd_rn(dot[k], __fmul_rn(g[k], a[k]));
+      }
+#pragma unroll 4
+      for (int p = R.p0; p < R.p1; ++p) {
+        const int64_t o = (R.edge(p) * U + u) * W;
+        lb_ld<W>(y + o, a);
+        lb_ld<W>(d_y + o, g);
+#pragma unroll
+        for (int k = 0; k < W; ++k) a[k] = __fmul_rn(a[k], g[k] - dot[k]);
+        lb_st<W>(d_x + o, a);
+      }
+    }
+  }
+}
+
+// out[i][h][:] = sum over the slots of node i of alpha[slot][h] v[slot][h][:], alpha = expf(l - m) / s as k_graph_softmax computes
+// it: the product rounded, the adds in ascending slot order from the first term.  A lane owns units of the H D row and runs the
+// max and the sum pass over its head's logits itself; the lane of a head's first unit stores that head's m and s.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_graph_attend(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                                      const int32_t* __restrict__ perm, const float* __restrict__ logits,
+                                                      const float* __restrict__ values, float* __restrict__ out,
+                                                      float* __restrict__ m_out, float* __restrict__ s_out, int64_t BN, int N,
+                                                      int e_cap, int E, int H, int D, int U, int lpr_shift) {
+  constexpr int W = VEC ? 4 : 1;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
+    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    int hc = -1;
+    float m = 0.f, s = 1.f;
+    for (int u = lane; u < U; u += lpr) {
+      const int h = (u * W) / D;
+      float acc[W], v[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) acc[k] = 0.f;
+      if (R.p0 < R.p1) {
+        if (h != hc) {
+          hc = h;
+          m = logits[R.edge(R.p0) * H + h];
+#pragma unroll 4
+          for (int p = R.p0 + 1; p < R.p1; ++p) {
+            const float a = logits[R.edge(p) * H + h];
+            if (lb_beats<false>(a, m)) m = a;
+          }
+          s = expf(logits[R.edge(R.p0) * H + h] - m);
+#pragma unroll 4
+          for (int p = R.p0 + 1; p < R.p1; ++p) s = __fadd_rn(s, expf(logits[R.edge(p) * H + h] - m));
+        }
+        {
+          const int64_t e = R.edge(R.p0);
+          const float al = expf(logits[e * H + h] - m) / s;
+          lb_ld<W>(values + (e * U + u) * W, v);
+#pragma unroll
+          for (int k = 0; k < W; ++k) acc[k] = __fmul_rn(al, v[k]);
+        }
+#pragma unroll 4
+        for (int p = R.p0 + 1; p < R.p1; ++p) {
+          const int64_t e = R.edge(p);
+          const float al = expf(logits[e * H + h] - m) / s;
+          lb_ld<W>(values + (e * U + u) * W, v);
+#pragma unroll
+          for (int k = 0; k < W; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(al, v[k]));
+        }
+      }
+      lb_st<W>(out + (i * U + u) * W, acc);
+      if ((u * W) % D == 0) m_out[i * H + h] = m, s_out[i * H + h] = s;
+    }
+  }
+}
+
+// d_values[slot][h][:] = alpha[slot][h] d_out[node][h][:] (one multiplication), +0.0 in the pads; alpha recomputed from the
+// saved m and s of the node.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_graph_attend_dvalues(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
+                                                              const float* __restrict__ logits, const float* __restrict__ m_in,
+                                                              const float* __restrict__ s_in, const float* __restrict__ d_out,
+                                                              float* __restrict__ d_values, int64_t BN, int N, int B, int e_cap,
+                                                              int E, int H, int D, int U, int lpr_shift) {
+  constexpr int W = VEC ? 4 : 1;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
+    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
+    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
+    const bool real = j < nb && base + j < E;
+    int64_t node = real ? idx[base + j] : 0;
+    node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
+    for (int u = lane; u < U; u += lpr) {
+      float d[W], g[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) d[k] = 0.f;
+      if (real) {
+        const int h = (u * W) / D;
+        const float al = expf(logits[r * H + h] - m_in[node * H + h]) / s_in[node * H + h];
+        lb_ld<W>(d_out + (node * U + u) * W, g);
+#pragma unroll
+        for (int k = 0; k < W; ++k) d[k] = __fmul_rn(al, g[k]);
+      }
+      lb_st<W>(d_values + (r * U + u) * W, d);
+    }
+  }
+}
+
+// t[slot][h] = sum_d d_out[node][h][d] v[slot][h][d], one lane per (slot, head), d ascending; +0.0 in the pads.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_graph_attend_t(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
+                                                        const float* __restrict__ values, const float* __restrict__ d_out,
+                                                        float* __restrict__ t, int64_t BN, int N, int B, int e_cap, int E, int H,
+                                                        int D) {
+  constexpr int W = VEC ? 4 : 1;
+  const int64_t total = (int64_t)B * e_cap * H, stride = (int64_t)gridDim.x * 256;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
+    const int64_t r = q / H;
+    const int h = (int)(q - r * H);
+    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
+    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
+    const bool real = j < nb && base + j < E;
+    float acc = 0.f;
+    if (real) {
+      int64_t node = idx[base + j];
+      node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
+      const float* __restrict__ vp = values + (r * H + h) * D;
+      const float* __restrict__ gp = d_out + (node * H + h) * D;
+      float v[W], g[W];
+      bool first = true;
+      for (int d = 0; d < D; d += W) {
+        lb_ld<W>(vp + d, v);
+        lb_ld<W>(gp + d, g);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          const float pr = __fmul_rn(g[k], v[k]);
+          acc = first ? pr : __fadd_rn(acc, pr);
+          first = false;
+        }
+      }
+    }
+    t[q] = acc;
+  }
+}
+
+// In place on t (B E_cap, H): d_logits[slot][h] = alpha (t[slot][h] - sum_k alpha[k] t[k][h]) over the slots of node i, the sum
+// ordered; one lane per (node, head).  The pad slots hold the +0.0 k_graph_attend_t wrote.
+__global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __restrict__ row_ptr,
+                                                              const int32_t* __restrict__ seg_ptr,
+                                                              const int32_t* __restrict__ perm, const float* __restrict__ logits,
+                                                              const float* __restrict__ m_in, const float* __restrict__ s_in,
+                                                              float* t, int64_t BN, int N, int e_cap, int E, int H) {
+  const int64_t total = BN * H, stride = (int64_t)gridDim.x * 256;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
+    const int64_t i = q / H;
+    const int h = (int)(q - i * H);
+    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    if (R.p0 >= R.p1) continue;
+    const float m = m_in[q], s = s_in[q];
+    float dot;
+    {
+      const int64_t o = R.edge(R.p0) * H + h;
+      dot = __fmul_rn(expf(logits[o] - m) / s, t[o]);
+    }
+    for (int p = R.p0 + 1; p < R.p1; ++p) {
+      const int64_t o = R.edge(p) * H + h;
+      dot = __fadd_rn(dot, __fmul_rn(expf(logits[o] - m) / s, t[o]));
+    }
+    for (int p = R.p0; p < R.p1; ++p) {
+      const int64_t o = R.edge(p) * H + h;
+      t[o] = __fmul_rn(expf(logits[o] - m) / s, t[o] - dot);
     }
   }
 }
@@ -245,3 +646,129 @@ extern "C" int lb_graph_segment_sum(lb_engine* e, int32_t role, const float* msg
 }
 
 extern "C" int32_t lb_graph_sender_sorts(lb_engine* e) { return e ? e->snd_sorts : -1; }
+
+// ---- the attention ops' entries.  graph_entry: the checks every entry makes, the list's status, the sender view for role 1.
+static bool graph_aligned(std::initializer_list<const void*> ptrs) {
+  uintptr_t a = 0;
+  for (const void* p : ptrs) a |= (uintptr_t)p;
+  return a % 16 == 0;
+}
+static unsigned graph_blocks1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65536)); }
+static int graph_entry(lb_engine* e, const char* entry, int32_t role, bool ptrs_ok, int32_t c0, int32_t c1) {
+  if (!e || !ptrs_ok) return lb_fail(LB_ERR_ARG, "null argument");
+  if ((role != 0 && role != 1) || c0 < 1 || c1 < 1)
+    return lb_fail(LB_ERR_ARG, "%s: role %d (0 receivers, 1 senders), columns %d x %d", entry, role, c0, c1);
+  LB_TRY(graph_begin(e, entry));
+  if (role) LB_TRY(graph_sender_view(e));
+  return LB_OK;
+}
+#define GRAPH_LAUNCH(kernel, blocks, ...)                                                    \
+  do {                                                                                       \
+    if (vec)                                                                                 \
+      hipLaunchKernelGGL(kernel<true>, dim3(blocks), dim3(256), 0, e->stream, __VA_ARGS__);  \
+    else                                                                                     \
+      hipLaunchKernelGGL(kernel<false>, dim3(blocks), dim3(256), 0, e->stream, __VA_ARGS__); \
+    LB_HIP(hipGetLastError());                                                               \
+  } while (0)
+
+extern "C" int lb_graph_degree(lb_engine* e, int32_t role, int32_t* out_dev) {
+  LB_TRY(graph_entry(e, "lb_graph_degree", role, out_dev != nullptr, 1, 1));
+  hipLaunchKernelGGL(k_graph_degree, GRID1(e->BN), 0, e->stream, e->row_ptr, role ? e->snd_ptr : e->row_ptr, out_dev, e->BN,
+                     e->g.N, e->e_cap, (int)e->graph_E);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+
+template <bool MIN>
+static int graph_segment_max(lb_engine* e, const char* entry, int32_t role, const float* msg, float* out, int32_t* win, int32_t C) {
+  LB_TRY(graph_entry(e, entry, role, msg && out && win, C, 1));
+  const int32_t* seg = role ? e->snd_ptr : e->row_ptr;
+  const int32_t* perm = role ? e->snd_perm : nullptr;
+  const bool vec = C % 4 == 0 && graph_aligned({msg, out, win});
+  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
+  const unsigned blocks = graph_blocks(e->BN, sh);
+  if (vec)
+    hipLaunchKernelGGL((k_graph_segment_max<true, MIN>), dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, seg, perm, msg, out,
+                       win, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  else
+    hipLaunchKernelGGL((k_graph_segment_max<false, MIN>), dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, seg, perm, msg, out,
+                       win, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+extern "C" int lb_graph_segment_max(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t* win_dev, int32_t C) {
+  return graph_segment_max<false>(e, "lb_graph_segment_max", role, msg_dev, out_dev, win_dev, C);
+}
+extern "C" int lb_graph_segment_min(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t* win_dev, int32_t C) {
+  return graph_segment_max<true>(e, "lb_graph_segment_min", role, msg_dev, out_dev, win_dev, C);
+}
+
+extern "C" int lb_graph_segment_max_backward(lb_engine* e, int32_t role, const float* d_out_dev, const int32_t* win_dev,
+                                             float* d_msg_dev, int32_t C) {
+  LB_TRY(graph_entry(e, "lb_graph_segment_max_backward", role, d_out_dev && win_dev && d_msg_dev, C, 1));
+  const int32_t* idx = role ? e->senders : e->receivers;
+  const bool vec = C % 4 == 0 && graph_aligned({d_out_dev, win_dev, d_msg_dev});
+  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
+  GRAPH_LAUNCH(k_graph_segment_max_bwd, graph_blocks((int64_t)e->g.B * e->e_cap, sh), e->row_ptr, idx, d_out_dev, win_dev,
+               d_msg_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_segment_softmax(lb_engine* e, int32_t role, const float* logits_dev, float* out_dev, int32_t C) {
+  LB_TRY(graph_entry(e, "lb_graph_segment_softmax", role, logits_dev && out_dev, C, 1));
+  const bool vec = C % 4 == 0 && graph_aligned({logits_dev, out_dev});
+  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
+  LB_HIP(hipMemsetAsync(out_dev, 0, sizeof(float) * (size_t)e->g.B * e->e_cap * C, e->stream));   // the pad slots: +0.0
+  GRAPH_LAUNCH(k_graph_softmax, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+               role ? e->snd_perm : nullptr, logits_dev, out_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_segment_softmax_backward(lb_engine* e, int32_t role, const float* y_dev, const float* d_y_dev,
+                                                 float* d_x_dev, int32_t C) {
+  LB_TRY(graph_entry(e, "lb_graph_segment_softmax_backward", role, y_dev && d_y_dev && d_x_dev, C, 1));
+  const bool vec = C % 4 == 0 && graph_aligned({y_dev, d_y_dev, d_x_dev});
+  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
+  LB_HIP(hipMemsetAsync(d_x_dev, 0, sizeof(float) * (size_t)e->g.B * e->e_cap * C, e->stream));
+  GRAPH_LAUNCH(k_graph_softmax_bwd, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+               role ? e->snd_perm : nullptr, y_dev, d_y_dev, d_x_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_attend(lb_engine* e, int32_t role, const float* logits_dev, const float* values_dev, float* out_dev,
+                               float* m_dev, float* s_dev, int32_t H, int32_t D) {
+  LB_TRY(graph_entry(e, "lb_graph_attend", role, logits_dev && values_dev && out_dev && m_dev && s_dev, H, D));
+  if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_attend: H %d x D %d columns", H, D);
+  const bool vec = D % 4 == 0 && graph_aligned({values_dev, out_dev});
+  const int U = vec ? H * D / 4 : H * D, sh = graph_lpr_shift(U);
+  GRAPH_LAUNCH(k_graph_attend, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+               role ? e->snd_perm : nullptr, logits_dev, values_dev, out_dev, m_dev, s_dev, e->BN, e->g.N, e->e_cap,
+               (int)e->graph_E, H, D, U, sh);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_attend_backward(lb_engine* e, int32_t role, const float* logits_dev, const float* values_dev,
+                                        const float* m_dev, const float* s_dev, const float* d_out_dev, float* d_logits_dev,
+                                        float* d_values_dev, int32_t H, int32_t D) {
+  LB_TRY(graph_entry(e, "lb_graph_attend_backward", role,
+                     logits_dev && values_dev && m_dev && s_dev && d_out_dev && d_logits_dev && d_values_dev, H, D));
+  if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_attend_backward: H %d x D %d columns", H, D);
+  const int32_t* idx = role ? e->senders : e->receivers;
+  const int64_t slots = (int64_t)e->g.B * e->e_cap;
+  {
+    const bool vec = D % 4 == 0 && graph_aligned({d_out_dev, d_values_dev});
+    const int U = vec ? H * D / 4 : H * D, sh = graph_lpr_shift(U);
+    GRAPH_LAUNCH(k_graph_attend_dvalues, graph_blocks(slots, sh), e->row_ptr, idx, logits_dev, m_dev, s_dev, d_out_dev,
+                 d_values_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, H, D, U, sh);
+  }
+  {
+    const bool vec = D % 4 == 0 && graph_aligned({values_dev, d_out_dev});
+    GRAPH_LAUNCH(k_graph_attend_t, graph_blocks1(slots * H), e->row_ptr, idx, values_dev, d_out_dev, d_logits_dev, e->BN, e->g.N,
+                 e->g.B, e->e_cap, (int)e->graph_E, H, D);
+  }
+  hipLaunchKernelGGL(k_graph_attend_dlogits, dim3(graph_blocks1(e->BN * H)), dim3(256), 0, e->stream, e->row_ptr,
+                     role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, logits_dev, m_dev, s_dev, d_logits_dev, e->BN,
+                     e->g.N, e->e_cap, (int)e->graph_E, H);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}

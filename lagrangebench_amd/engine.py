@@ -460,6 +460,96 @@ class RolloutEngine:
         add after the other; no atomics (include/lbhip.h: lb_graph_segment_sum)."""
         return self._graph_op("lb_graph_segment_sum", role, msg, self.B * self.e_cap, self.B * self.N)
 
+    def _graph_arg(self, symbol: str, t: torch.Tensor, shape, dtype=torch.float32) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() \
+                or tuple(t.shape) != tuple(shape) or t.numel() == 0:
+            raise ValueError(f"{symbol}: expected a contiguous {tuple(shape)} {dtype} tensor on {self.device}, got "
+                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', None)}")
+        return t
+
+    def _graph_cols(self, symbol: str, t: torch.Tensor, rows: int) -> int:
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < 1:
+            raise ValueError(f"{symbol}: expected a ({rows}, C >= 1) tensor, got {tuple(getattr(t, 'shape', ()))}")
+        return int(t.shape[1])
+
+    def graph_degree(self, role: int) -> torch.Tensor:
+        """-> (B*N,) int32: the real edge slots of the current list whose role index is the node (lb_graph_degree)."""
+        out = torch.empty((self.B * self.N,), dtype=torch.int32, device=self.device)
+        check(self.lib.lb_graph_degree(self._h, int(role), ptr(out)), "lb_graph_degree")
+        return out
+
+    def graph_segment_max(self, role: int, msg: torch.Tensor, minimum: bool = False):
+        """msg (B*E_cap, C) float32 -> (out (B*N, C), win (B*N, C) int32): per node and column the first real slot's value,
+        replaced in ascending slot order by a strictly greater (minimum: smaller) one, and the slot that won (-1 and +0.0 for
+        a node without edges) (include/lbhip.h: lb_graph_segment_max / _min)."""
+        symbol = "lb_graph_segment_min" if minimum else "lb_graph_segment_max"
+        C_ = self._graph_cols(symbol, msg, self.B * self.e_cap)
+        self._graph_arg(symbol, msg, (self.B * self.e_cap, C_))
+        out = torch.empty((self.B * self.N, C_), dtype=torch.float32, device=self.device)
+        win = torch.empty((self.B * self.N, C_), dtype=torch.int32, device=self.device)
+        check(getattr(self.lib, symbol)(self._h, int(role), ptr(msg), ptr(out), ptr(win), C_), symbol)
+        return out, win
+
+    def graph_segment_max_backward(self, role: int, d_out: torch.Tensor, win: torch.Tensor) -> torch.Tensor:
+        """d_out (B*N, C), win (B*N, C) int32 -> d_msg (B*E_cap, C): d_out in the winning slots, +0.0 elsewhere."""
+        symbol = "lb_graph_segment_max_backward"
+        C_ = self._graph_cols(symbol, d_out, self.B * self.N)
+        self._graph_arg(symbol, d_out, (self.B * self.N, C_))
+        self._graph_arg(symbol, win, (self.B * self.N, C_), torch.int32)
+        d_msg = torch.empty((self.B * self.e_cap, C_), dtype=torch.float32, device=self.device)
+        check(self.lib.lb_graph_segment_max_backward(self._h, int(role), ptr(d_out), ptr(win), ptr(d_msg), C_), symbol)
+        return d_msg
+
+    def graph_segment_softmax(self, role: int, logits: torch.Tensor) -> torch.Tensor:
+        """logits (B*E_cap, C) float32 -> (B*E_cap, C): per node and column the softmax over the node's real slots, shifted by
+        their maximum, the denominator summed in ascending slot order; +0.0 in the pad slots (lb_graph_segment_softmax)."""
+        return self._graph_op("lb_graph_segment_softmax", role, logits, self.B * self.e_cap, self.B * self.e_cap)
+
+    def graph_segment_softmax_backward(self, role: int, y: torch.Tensor, d_y: torch.Tensor) -> torch.Tensor:
+        """y, d_y (B*E_cap, C) -> d_logits (B*E_cap, C) = y (d_y - the node's ordered sum of d_y y)."""
+        symbol = "lb_graph_segment_softmax_backward"
+        C_ = self._graph_cols(symbol, y, self.B * self.e_cap)
+        self._graph_arg(symbol, y, (self.B * self.e_cap, C_))
+        self._graph_arg(symbol, d_y, (self.B * self.e_cap, C_))
+        d_x = torch.empty_like(y)
+        check(self.lib.lb_graph_segment_softmax_backward(self._h, int(role), ptr(y), ptr(d_y), ptr(d_x), C_), symbol)
+        return d_x
+
+    def _graph_attend_args(self, symbol: str, logits: torch.Tensor, values: torch.Tensor):
+        slots = self.B * self.e_cap
+        H = self._graph_cols(symbol, logits, slots)
+        if not isinstance(values, torch.Tensor) or values.dim() != 3 or values.shape[2] < 1:
+            raise ValueError(f"{symbol}: expected values ({slots}, {H}, D >= 1), got {tuple(getattr(values, 'shape', ()))}")
+        D = int(values.shape[2])
+        self._graph_arg(symbol, logits, (slots, H))
+        self._graph_arg(symbol, values, (slots, H, D))
+        return H, D
+
+    def graph_attend(self, role: int, logits: torch.Tensor, values: torch.Tensor):
+        """logits (B*E_cap, H), values (B*E_cap, H, D) float32 -> (out (B*N, H, D), m (B*N, H), s (B*N, H)): the softmax of the
+        logits over each node's slots times the values, summed per node in ascending slot order - the bits of
+        graph_segment_sum(graph_segment_softmax(logits)[..., None] * values) in one launch; m and s are the maximum and the
+        denominator it used (include/lbhip.h: lb_graph_attend)."""
+        H, D = self._graph_attend_args("lb_graph_attend", logits, values)
+        out = torch.empty((self.B * self.N, H, D), dtype=torch.float32, device=self.device)
+        m = torch.empty((self.B * self.N, H), dtype=torch.float32, device=self.device)
+        s = torch.empty_like(m)
+        check(self.lib.lb_graph_attend(self._h, int(role), ptr(logits), ptr(values), ptr(out), ptr(m), ptr(s), H, D), "lb_graph_attend")
+        return out, m, s
+
+    def graph_attend_backward(self, role: int, logits: torch.Tensor, values: torch.Tensor, m: torch.Tensor, s: torch.Tensor,
+                              d_out: torch.Tensor):
+        """-> (d_logits (B*E_cap, H), d_values (B*E_cap, H, D)) of graph_attend (include/lbhip.h: lb_graph_attend_backward)."""
+        symbol = "lb_graph_attend_backward"
+        H, D = self._graph_attend_args(symbol, logits, values)
+        self._graph_arg(symbol, m, (self.B * self.N, H))
+        self._graph_arg(symbol, s, (self.B * self.N, H))
+        self._graph_arg(symbol, d_out, (self.B * self.N, H, D))
+        d_logits, d_values = torch.empty_like(logits), torch.empty_like(values)
+        check(self.lib.lb_graph_attend_backward(self._h, int(role), ptr(logits), ptr(values), ptr(m), ptr(s), ptr(d_out),
+                                                ptr(d_logits), ptr(d_values), H, D), symbol)
+        return d_logits, d_values
+
     def graph_sender_sorts(self) -> int:
         """Sender-ordered views the graph ops built by the radix sort (a list with an edge in one direction only)."""
         return int(self.lib.lb_graph_sender_sorts(self._h))

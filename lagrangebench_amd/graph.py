@@ -9,12 +9,34 @@ describes, in the padded layout of ``features["senders"]`` / ``["receivers"]`` (
     agg = g.segment_sum(msg, "receivers")    # (B, E_cap, C) -> (B, N, C); pad slots are never read
     g.n_edges, g.senders, g.receivers        # (B,), (B, E_cap), (B, E_cap)
 
-(with un-batched features the leading B is dropped: (N, C) -> (E_cap, C)).  Trailing dimensions beyond C are folded into C.
+    g.degree("receivers")                    # (B, N) int32: the node's real slots
+    g.segment_mean(msg, "receivers")         # segment_sum / max(degree, 1)
+    g.segment_max(msg, "senders")            # (B, E_cap, C) -> (B, N, C); segment_min likewise
+    a = g.segment_softmax(logits, "receivers")          # (B, E_cap, C) -> (B, E_cap, C): a softmax per node and column
+    out = g.attend(logits, values, "receivers")         # (B, E_cap, H), (B, E_cap, H, D) -> (B, N, H, D), one launch
+
+(with un-batched features the leading B is dropped: (N, C) -> (E_cap, C)).  Trailing dimensions beyond C are folded into C
+where the op is column-wise (all but ``attend``).
 
 The sum is ordered: per node its real slots in ascending slot order, one float32 add after the other, no atomics - the
 result equals a numpy float32 loop bit for bit and two calls give the same bits (torch's ``index_add_`` on the GPU uses
 float atomics and does not).  The two ops are each other's adjoints - gather's backward is ``segment_sum`` over the same
 role, ``segment_sum``'s backward is ``gather`` - so forward and backward are the same two kernels with the same bits.
+
+The attention ops keep these contracts - pad slots are never read (they may hold NaN), every pad slot of an edge-shaped
+result or gradient is +0.0, no float atomics, two calls give the same bits:
+
+* ``segment_max`` starts from the node's first real slot; a further slot, in ascending slot order, replaces it only if it is
+  strictly greater (ties keep the earlier slot, -0.0 then +0.0 stays -0.0; a NaN wins and stays, as ``np.maximum``).  The
+  gradient goes to the winning slot alone.  ``segment_min`` mirrors it.  A node without edges gets +0.0 - jraph gives -inf /
+  +inf there; like ``segment_sum`` we keep what such a node feeds onward finite.
+* ``segment_mean`` is the ordered sum followed by one correctly rounded float32 division by ``max(degree, 1)``.
+* ``segment_softmax`` per node and column: m = the maximum as above, e_j = expf(x_j - m), s = the ordered sum of the e_j,
+  y_j = e_j / s.  Backward: y_j (d_y_j - sum_k d_y_k y_k), the sum ordered.
+* ``attend(logits, values, role)`` equals ``segment_sum(segment_softmax(logits, role)[..., None] * values, role)`` bit for
+  bit - the same weights, each product rounded to float32, added in ascending slot order - without the (E_cap, H, D)
+  intermediate.  Its ``d_values`` has the composition's bits too; ``d_logits`` reduces over D in another order and agrees
+  to rounding.
 
 Tensors are float32 on the engine's device (``TypeError`` otherwise) and are made contiguous here.  A forward or a
 backward after the engine's list moved on raises ``RuntimeError``: the staleness rule of ``FeatureDict``.  The ops are once
@@ -47,8 +69,73 @@ class _Op(torch.autograd.Function):
         return ctx.graph._run(1 - ctx.kind, ctx.role, d), None, None, None
 
 
+class _SegmentMax(torch.autograd.Function):
+    """segment_max / segment_min over `role`; the forward's winning slots route the gradient."""
+
+    @staticmethod
+    def forward(ctx, msg, graph, role, minimum):
+        name = "segment_min" if minimum else "segment_max"
+        flat, rest = graph._flat(name, msg, graph.engine.e_cap)
+        out, win = graph.engine.graph_segment_max(role, flat, minimum)
+        ctx.graph, ctx.role, ctx.name, ctx.rest = graph, role, name, rest
+        ctx.save_for_backward(win)
+        return out.reshape(graph._shape(graph.engine.N) + rest)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        flat, _ = g._flat(ctx.name, d, e.N)
+        d_msg = e.graph_segment_max_backward(ctx.role, flat, ctx.saved_tensors[0])
+        return d_msg.reshape(g._shape(e.e_cap) + ctx.rest), None, None, None
+
+
+class _SegmentSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, graph, role):
+        flat, rest = graph._flat("segment_softmax", logits, graph.engine.e_cap)
+        y = graph.engine.graph_segment_softmax(role, flat)
+        ctx.graph, ctx.role, ctx.rest = graph, role, rest
+        ctx.save_for_backward(y)
+        return y.reshape(graph._shape(graph.engine.e_cap) + rest)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        flat, _ = g._flat("segment_softmax", d, e.e_cap)
+        d_x = e.graph_segment_softmax_backward(ctx.role, ctx.saved_tensors[0], flat)
+        return d_x.reshape(g._shape(e.e_cap) + ctx.rest), None, None
+
+
+class _Attend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, values, graph, role):
+        e = graph.engine
+        lf, heads = graph._flat("attend", logits, e.e_cap)
+        vf, hd = graph._flat("attend", values, e.e_cap)
+        if len(heads) != 1 or len(hd) != 2 or hd[0] != heads[0]:
+            raise ValueError(f"graph.attend: expected logits {graph._shape(e.e_cap) + ('H',)} and values "
+                             f"{graph._shape(e.e_cap) + ('H', 'D')}, got {tuple(logits.shape)} and {tuple(values.shape)}")
+        vf = vf.reshape(e.B * e.e_cap, hd[0], hd[1])
+        out, m, s = e.graph_attend(role, lf, vf)
+        ctx.graph, ctx.role, ctx.hd = graph, role, hd
+        ctx.save_for_backward(lf, vf, m, s)
+        return out.reshape(graph._shape(e.N) + hd)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        flat, _ = g._flat("attend", d, e.N)
+        lf, vf, m, s = ctx.saved_tensors
+        d_l, d_v = e.graph_attend_backward(ctx.role, lf, vf, m, s, flat.reshape(e.B * e.N, *ctx.hd))
+        return d_l.reshape(g._shape(e.e_cap) + ctx.hd[:1]), d_v.reshape(g._shape(e.e_cap) + ctx.hd), None, None
+
+
 class Graph:
-    """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum.
+    """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum and the attention
+    ops (degree, segment_mean / max / min / softmax, attend).
     `batched`: whether the tensors carry the leading B (default: as the features do)."""
 
     def __init__(self, features, batched: Optional[bool] = None):
@@ -96,23 +183,28 @@ class Graph:
             raise ValueError(f"role must be 'senders' or 'receivers', got {role!r}")
         return _ROLES[role]
 
-    def _run(self, kind: int, role: int, t: torch.Tensor) -> torch.Tensor:
-        name = "segment_sum" if kind == _SEGMENT_SUM else "gather"
+    def _shape(self, rows: int) -> tuple:
+        return (self.engine.B, rows) if self.batched else (rows,)
+
+    def _flat(self, name: str, t: torch.Tensor, rows: int):
+        """The checks every op makes on a (B, rows, ...) tensor -> (its detached contiguous (B * rows, C) view, the trailing
+        dimensions)."""
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
             raise TypeError(f"graph.{name}: float32 tensors only, got {getattr(t, 'dtype', type(t))}")
         e = self.engine
         if t.device != e.device:
             raise TypeError(f"graph.{name}: the tensor is on {t.device}, the engine on {e.device}")
         self._check_fresh(name)
-        rows = e.e_cap if kind == _SEGMENT_SUM else e.N
-        lead = (e.B, rows) if self.batched else (rows,)
+        lead = self._shape(rows)
         if tuple(t.shape[:len(lead)]) != lead or t.dim() <= len(lead) or t.numel() == 0:
             raise ValueError(f"graph.{name}: expected {lead + ('C',)} (C >= 1), got {tuple(t.shape)}")
-        rest = tuple(t.shape[len(lead):])
-        flat = t.detach().contiguous().reshape(e.B * rows, -1)
+        return t.detach().contiguous().reshape(e.B * rows, -1), tuple(t.shape[len(lead):])
+
+    def _run(self, kind: int, role: int, t: torch.Tensor) -> torch.Tensor:
+        e = self.engine
+        flat, rest = self._flat("segment_sum" if kind == _SEGMENT_SUM else "gather", t, e.e_cap if kind == _SEGMENT_SUM else e.N)
         out = (e.graph_segment_sum if kind == _SEGMENT_SUM else e.graph_gather)(role, flat)
-        out_rows = e.N if kind == _SEGMENT_SUM else e.e_cap
-        return out.reshape(((e.B, out_rows) if self.batched else (out_rows,)) + rest)
+        return out.reshape(self._shape(e.N if kind == _SEGMENT_SUM else e.e_cap) + rest)
 
     def gather(self, x: torch.Tensor, role: str) -> torch.Tensor:
         """x (B, N, C) -> (B, E_cap, C): x[b, role index of slot (b, j)] in the real slots, +0.0 in the pad slots."""
@@ -121,3 +213,38 @@ class Graph:
     def segment_sum(self, msg: torch.Tensor, role: str) -> torch.Tensor:
         """msg (B, E_cap, C) -> (B, N, C): per node the ordered float32 sum of the real slots whose role index it is."""
         return _Op.apply(msg, self, self._role(role), _SEGMENT_SUM)
+
+    def degree(self, role: str) -> torch.Tensor:
+        """-> (B, N) int32: the number of real slots whose role index is the node.  No autograd."""
+        r = self._role(role)
+        self._check_fresh("degree")
+        return self.engine.graph_degree(r).reshape(self._shape(self.engine.N))
+
+    def segment_mean(self, msg: torch.Tensor, role: str) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, N, C): segment_sum divided by max(degree, 1) as float32 - the ordered sum, then one
+        correctly rounded division; +0.0 for a node without edges."""
+        total = self.segment_sum(msg, role)
+        deg = self.degree(role).clamp(min=1).to(torch.float32)
+        return total / deg.reshape(deg.shape + (1,) * (total.dim() - deg.dim()))
+
+    def segment_max(self, msg: torch.Tensor, role: str) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, N, C): per node and column the first real slot's value, replaced in ascending slot order
+        only by a strictly greater one (ties keep the earlier slot; a NaN wins and stays).  A node without edges gets +0.0
+        where jraph gives -inf, as segment_sum does, so that it feeds finite values onward.  The gradient goes to the
+        winning slot; every other slot of it, pads included, is +0.0."""
+        return _SegmentMax.apply(msg, self, self._role(role), False)
+
+    def segment_min(self, msg: torch.Tensor, role: str) -> torch.Tensor:
+        """segment_max with "strictly smaller"; a node without edges gets +0.0 (jraph: +inf)."""
+        return _SegmentMax.apply(msg, self, self._role(role), True)
+
+    def segment_softmax(self, logits: torch.Tensor, role: str) -> torch.Tensor:
+        """logits (B, E_cap, C) -> (B, E_cap, C): one softmax per node and column over the node's real slots, shifted by
+        their maximum, the denominator summed in ascending slot order; +0.0 in the pad slots."""
+        return _SegmentSoftmax.apply(logits, self, self._role(role))
+
+    def attend(self, logits: torch.Tensor, values: torch.Tensor, role: str) -> torch.Tensor:
+        """logits (B, E_cap, H), values (B, E_cap, H, D) -> (B, N, H, D): bit for bit
+        segment_sum(segment_softmax(logits, role)[..., None] * values, role), in one kernel that reads the values once and
+        writes nothing of their size."""
+        return _Attend.apply(logits, values, self, self._role(role))
