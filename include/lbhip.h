@@ -710,6 +710,27 @@ int lb_graph_attend(lb_engine* eng, int32_t role, const float* logits_dev /*(B*E
 int lb_graph_attend_backward(lb_engine* eng, int32_t role, const float* logits_dev, const float* values_dev, const float* m_dev,
                              const float* s_dev, const float* d_out_dev /*(B*N,H*D)*/, float* d_logits_dev /*(B*E_cap,H)*/,
                              float* d_values_dev /*(B*E_cap,H*D)*/, int32_t H, int32_t D);
+/* d loss / d window from the cotangents of the features a TorchModel module receives (graph.differentiable_features), on the
+ * engine's CURRENT window and list: the transpose of the feature builder.  Every input may be NULL (= zero).  fp32 inputs in the
+ * layouts of TorchModel's feature dict; the edge-shaped ones in the padded slot layout of lb_nl_read_idx, whose pad slots are
+ * never read (they may hold NaN).  vel_hist: g / std to the later frame of each velocity, -g / std to the earlier (the periodic
+ * displacement has derivative 1); vel_mag: the same path with g = d_vel_mag vn / |vn| (0 where |vn| = 0); bound: +-d / r_c on
+ * the newest frame where the feature lies strictly inside (-1, 1); per edge h = (d_rel_disp + d_rel_dist rel_disp / rel_dist) /
+ * r_c (second term 0 where rel_dist = 0), +h to the receiver's newest frame, -h to the sender's (the cached sender view); the
+ * external force is a constant of the positions; d_abs_pos is added term by term; rows of pad particles are 0.  Forward values:
+ * rel_disp / rel_dist from the engine's fp32 edge features, the node values recomputed from the fp64 window and rounded to
+ * fp32.  Every sum in fp64 over terms formed from the fp32 inputs, in a fixed order - frames ascending (velocities, then
+ * d_abs_pos); on the newest frame the walls, the receiver row in ascending slot order, the sent edges in ascending sender-view
+ * order - without atomics: two calls give the same bits, and a call with every input NULL writes +0.0 everywhere.
+ * LB_ERR_UNSUPPORTED on an engine with float32 geometry; LB_ERR_STATE as for the other graph ops. */
+int lb_graph_features_backward(lb_engine* eng,
+    const float* d_abs_pos,   /* (B*N, isl, dim)            identity                                    */
+    const float* d_vel_hist,  /* (B*N, (isl-1)*dim)                                                     */
+    const float* d_vel_mag,   /* (B*N, isl-1)      LB_ERR_ARG if non-null and the engine has no vel_mag */
+    const float* d_bound,     /* (B*N, 2*dim)      LB_ERR_ARG if non-null and the engine has no bound   */
+    const float* d_rel_disp,  /* (B*E_cap, dim)    padded slot layout of lb_nl_read_idx                 */
+    const float* d_rel_dist,  /* (B*E_cap, 1)                                                           */
+    double* d_window_out);    /* (B*N, isl, dim) fp64, overwritten                                      */
 /* Test support / diagnostics, like lb_gns_train_sort_fallbacks: sender views built by the radix sort since the engine was
  * created (a list with an edge in one direction only).  Nothing in the package depends on it. */
 int32_t lb_graph_sender_sorts(lb_engine* eng);

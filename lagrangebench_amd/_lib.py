@@ -192,6 +192,7 @@ _SIGS = {
     "lb_graph_segment_softmax_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32]),
     "lb_graph_attend": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32]),
     "lb_graph_attend_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_features_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -13,6 +13,16 @@ other than the MSE, gradients with respect to positions and unrolls with gradien
     torch.nn.functional.huber_loss(pred[mask], target[mask]).backward()
     opt.step()
 
+``TorchModule`` plays the same role for a user's own network behind ``models.TorchModel``: torch holds the network and its
+autograd, the graph ops are HIP (``graph.Graph``), and the window's gradient comes from ``graph.differentiable_features``
+(``lb_graph_features_backward``).  ``advance_window`` is ``case.integrate`` plus the window shift in differentiable torch, so
+an unroll through time is
+
+    mod = TorchModule(model, case, params, batch=1)
+    p1 = mod(w1, particle_type)["acc"]
+    p2 = mod(advance_window(case, w1, p1, "acc"))["acc"]
+    (loss(p1, t1) + loss(p2, t2)).backward()                  # gradients to mod.parameters() and to w1
+
 Arithmetic: the forward of a GNS runs in exact-fp32 products (its backward's ReLU masks are the forward's signs, and the
 default f16x2 forward leaves ten times as many units on the wrong side of a kink), the backward in the handle's default
 ones - unless the window's gradient is asked for, which is per particle and runs exact throughout.
@@ -26,9 +36,10 @@ from __future__ import annotations
 
 from typing import Dict, Optional
 
+import numpy as np
 import torch
 
-__all__ = ["DeviceModule", "non_kinematic_mask"]
+__all__ = ["DeviceModule", "TorchModule", "advance_window", "non_kinematic_mask"]
 
 
 def non_kinematic_mask(particle_type: torch.Tensor) -> torch.Tensor:
@@ -168,3 +179,181 @@ class DeviceModule(torch.nn.Module):
         """Forget every saved window (graphs that will not be differentiated any more)."""
         self._saved.clear()
         self._live = None
+
+
+class _Restore(torch.autograd.Function):
+    """Identity on one step's output.  Every op of the step lies upstream of it, so its backward runs first for that step:
+    the place to bring the engine back to the step's window and list."""
+
+    @staticmethod
+    def forward(ctx, out, mod, ticket):
+        ctx.mod, ctx.ticket = mod, ticket
+        return out.view_as(out)
+
+    @staticmethod
+    def backward(ctx, d):
+        ctx.mod._restore(ctx.ticket)
+        return d, None, None
+
+
+class TorchModule(torch.nn.Module):
+    """``model`` (a ``models.TorchModel``) on the device as a differentiable torch module: the role ``DeviceModule`` plays
+    for the device models.
+
+    The network is a device copy of the wrapped module holding `params` (and `state`, default: the wrapped module's
+    buffers), registered as ``self.module``: ``parameters()``, any torch optimiser and ``state_dict()`` work.  With
+    ``handle=`` (from ``model.train_handle``) it runs on ``handle.module`` instead: gradients accumulate in the handle's
+    gradient blob and ``handle.adamw_step`` trains it.
+
+    ``mod(window, particle_type=None, features=None) -> {"acc" | "vel" | "pos": (B, N, dim) float32 with a grad_fn}``.
+    `window`: (B, N, isl, dim) float64 on the device.  Without `features` the module loads the window into the engine and
+    updates the neighbor list (sized before by ``case.allocate*``); with the ``FeatureDict`` that ``case.preprocess*`` just
+    made for this window it skips that.  Gradients flow to the parameters and, when ``window.requires_grad``, to the window
+    (``graph.differentiable_features``: the neighbor list is held fixed, the external force is a constant).
+
+    Several graphs may be alive at once (an unroll through time, two backward calls).  Each forward saves its window and
+    particle types (64 at most).  A backward whose step is no longer the engine's live one reloads them and rebuilds the list -
+    the same positions under frozen capacities and a deterministic search give the same list; a different edge count raises -
+    and makes the step's ``FeatureDict`` and ``Graph`` fresh again (``restored`` counts these).  Nothing of the network is
+    recomputed: torch holds the activations.
+    """
+
+    def __init__(self, model, case, params, batch: int, state=None, handle=None):
+        super().__init__()
+        from .models.torch_model import TorchModel
+        if not isinstance(model, TorchModel):
+            raise TypeError(f"TorchModule wraps a models.TorchModel, not {type(model).__name__}; the device models (GNS, SEGNN, "
+                            "EGNN, PaiNN) go through DeviceModule")
+        self.model, self.case, self.batch = model, case, int(batch)
+        self.engine = case.engine(self.batch)
+        model._check_padded(self.engine)
+        self.handle = handle
+        if handle is not None:
+            if handle.engine is not self.engine or getattr(handle, "module", None) is None:
+                raise ValueError("TorchModule: `handle` must be an open handle of model.train_handle on the case's engine of "
+                                 "this batch size")
+            self.module = handle.module
+        else:
+            model._check_state(state)
+            self.module = model._device_module(self.engine, params, model.state_of() if state is None else state)
+        self._ticket = 0
+        self._live: Optional[int] = None
+        self._saved: Dict[int, tuple] = {}
+        self.restored = 0   # backward calls that had to reload their window and rebuild the list
+
+    # ------------------------------------------------------------------ engine state
+    def _load(self, window: torch.Tensor, particle_type: Optional[torch.Tensor]) -> None:
+        eng = self.engine
+        if eng.e_cap <= 0:
+            raise RuntimeError("TorchModule: the engine has no neighbor list yet - size it through the case first "
+                               "(case.allocate / allocate_eval on a sample of this batch size)")
+        if particle_type is not None:
+            eng.set_particle_type(particle_type)
+        eng.load_window(window, t0=0, step=0)
+        eng.nl_update()
+        if bool(eng.nl_flags().any()):
+            raise RuntimeError("TorchModule: the neighbor list overflowed its capacity for this window - re-allocate "
+                               "through the case (case.allocate / allocate_eval) and call the module again")
+
+    def _restore(self, ticket: int) -> None:
+        eng = self.engine
+        saved = self._saved.get(ticket)
+        if saved is None:
+            raise RuntimeError("TorchModule: this graph's window is gone (more than 64 forwards since, or the module was reset)")
+        window, pt, features, graph, n_edges = saved
+        if self._live == ticket and features.version == eng.version:
+            return
+        self._load(window, pt)
+        if not torch.equal(eng.nl_idx()[1], n_edges):
+            raise RuntimeError("TorchModule: the neighbor list rebuilt for this graph's backward has another edge count than "
+                               "its forward's (were the capacities changed in between?)")
+        features.version = graph.version = eng.version
+        self._live = ticket
+        self.restored += 1
+
+    def forward(self, window: torch.Tensor, particle_type=None, features=None):
+        from .case_setup.features import FeatureDict
+        from .graph import Graph, _plain, differentiable_features
+        eng = self.engine
+        if tuple(window.shape) != (eng.B, eng.N, eng.isl, eng.dim) or window.dtype != torch.float64:
+            raise ValueError(f"TorchModule: window must be ({eng.B}, {eng.N}, {eng.isl}, {eng.dim}) float64, got "
+                             f"{tuple(window.shape)} {window.dtype}")
+        w = window.detach()
+        pt = None if particle_type is None else torch.as_tensor(particle_type).detach().clone()
+        if features is None:
+            self._load(w, pt)
+            features = FeatureDict(eng, w, True)
+        elif self.model._engine_of((features, particle_type)) is not eng:
+            raise ValueError("TorchModule: the features belong to another engine than the module's")
+        self.model._check_padded(eng)
+        types = pt if pt is not None else eng.particle_type
+        if types is None:
+            raise RuntimeError("TorchModule: the engine has no particle types yet - pass particle_type")
+        types = types.to(device=eng.device, dtype=torch.int64).reshape(eng.B, eng.N)
+        if window.requires_grad:
+            fd = differentiable_features(features, window)
+        else:
+            fd = {k: _plain(features, k) for k in features.keys()}
+        graph = Graph(features, batched=True)
+        out = self.module(fd, types, graph)
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (eng.B, eng.N, eng.dim) or out.dtype != torch.float32:
+            raise ValueError(f"TorchModule: the module must return a ({eng.B}, {eng.N}, {eng.dim}) float32 tensor, got "
+                             f"{tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__} "
+                             f"{getattr(out, 'dtype', '')}")
+        self._ticket += 1
+        ticket = self._ticket
+        if torch.is_grad_enabled():
+            self._saved[ticket] = (w.clone(), pt, features, graph, graph.n_edges.clone())
+            while len(self._saved) > 64:   # graphs that never ran a backward must not pile up windows
+                self._saved.pop(next(iter(self._saved)))
+            out = _Restore.apply(out, self, ticket)
+        self._live = ticket
+        return {self.model._OUTPUT: out}
+
+    # ------------------------------------------------------------------ weights
+    def params(self) -> Dict:
+        """The current parameters as the model's parameter tree (a host copy)."""
+        return self.model.params_of(self.module)
+
+    def reset(self) -> None:
+        """Forget every saved window (graphs that will not be differentiated any more)."""
+        self._saved.clear()
+        self._live = None
+
+
+def advance_window(case, window: torch.Tensor, pred: torch.Tensor, output: str = "acc", particle_type=None,
+                   target_pos=None) -> torch.Tensor:
+    """``case.integrate`` (case.py:230-259) plus the window shift, in differentiable float64 torch: the window of the next step.
+
+    `window` (..., N, isl, dim) float64, `pred` (..., N, dim) the model's output under key `output`: "acc" (normalised
+    acceleration: new = shift(newest, displacement(newest, previous) + mean + pred std)), "vel" (normalised velocity) or "pos"
+    (the position itself), with the case's normalisation statistics; displacement and shift are the case's, periodic with
+    derivative 1.  With `target_pos` (..., N, dim), kinematic and pad particles (`particle_type` 1, 2, -1) take their targets,
+    detached.  Gradients flow to `window` and `pred`."""
+    if output not in ("acc", "vel", "pos"):
+        raise ValueError(f"advance_window: output {output!r} must be 'acc', 'vel' or 'pos'")
+    if not isinstance(window, torch.Tensor) or window.dtype != torch.float64 or window.dim() < 3 or window.shape[-2] < 2:
+        raise ValueError(f"advance_window: window must be (..., N, isl >= 2, dim) float64, got "
+                         f"{tuple(getattr(window, 'shape', ()))} {getattr(window, 'dtype', type(window))}")
+    if tuple(pred.shape) != tuple(window.shape[:-2]) + (window.shape[-1],):
+        raise ValueError(f"advance_window: pred must be {tuple(window.shape[:-2]) + (window.shape[-1],)}, got {tuple(pred.shape)}")
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64), dtype=torch.float64, device=window.device)
+    p = pred.to(torch.float64)
+    newest = window[..., -1, :]
+    if output == "pos":
+        new = p
+    else:
+        if output == "vel":
+            s = case.normalization_stats["velocity"]
+            vel = t(s["mean"]) + p * t(s["std"])
+        else:
+            s = case.normalization_stats["acceleration"]
+            vel = case.displacement(newest, window[..., -2, :]) + (t(s["mean"]) + p * t(s["std"]))
+        new = case.shift(newest, vel)
+    if target_pos is not None:
+        if particle_type is None:
+            raise ValueError("advance_window: target_pos needs particle_type (which particles are kinematic)")
+        fixed = ~non_kinematic_mask(torch.as_tensor(particle_type)).to(window.device)
+        tgt = torch.as_tensor(target_pos).detach().to(device=window.device, dtype=torch.float64)
+        new = torch.where(fixed[..., None], tgt, new)
+    return torch.cat([window[..., 1:, :], new[..., None, :]], dim=-2)

@@ -5,7 +5,8 @@
 //   lb_graph_segment_sum(role, msg (B*E_cap, C)) -> out (B*N, C)    out[i]    = sum of the real slots whose role index is i
 //
 // and, for attention and pooling layers (further down: "attention ops"), lb_graph_degree, lb_graph_segment_max / _min,
-// lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries.
+// lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries; and lb_graph_features_backward
+// ("feature transpose"): d loss / d window from the cotangents of the features such a network was handed.
 //
 // All work in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
 // receiver-sorted list.  Gather and segment_sum are each other's adjoints, so the backward of either is the other one: the
@@ -27,6 +28,7 @@
 #include <algorithm>
 
 #include "lb_device.h"
+#include "lb_features.h"
 #include "lb_sender_view.h"
 
 #include <hipcub/hipcub.hpp>  // header-only device radix sort (the sender view of a list with one-directional edges)
@@ -521,6 +523,105 @@ __global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __r
   }
 }
 
+// ------------------------------------------------------------------------------------------------ feature transpose
+// d loss / d window (B N, isl, dim) fp64 from the cotangents of the features a TorchModel module receives: the transpose of the
+// feature builder as the comment above k_feat_bwd (lb_train.hip) states it, on the engine's current window and list, in the
+// layouts of the module's feature dict (node arrays (B N, .), edge arrays in the padded slots).  One lane per (particle, axis),
+// axis minor: the lanes of a particle read neighbouring floats of an edge row, the per-axis sums are independent and share only
+// the scalar d_rel_dist / rel_dist.  Every sum in fp64 over terms formed from the fp32 inputs, in a fixed order: frames
+// ascending (velocity terms, then d_abs_pos); on the newest frame the walls, the particle's receiver row in ascending slot
+// order, the edges it sends in ascending sender-view order.  No atomics.  Forward values: rel_disp / rel_dist are read from the
+// engine's fp32 edge features (as k_feat_bwd does); the engine holds no fp32 node features outside a GNS handle, so the
+// normalised velocities, their magnitudes and the wall distances are recomputed from the fp64 window by the operations of
+// lb_node_features_body and rounded to fp32 - the values the module was handed.  Null cotangents are zero and skip their reads.
+struct lb_gfb_args {
+  int64_t BN;
+  int e_cap, E;
+  const double* win;
+  const lb_ctrl* ctrl;
+  const int32_t *ptype, *row_ptr, *snd_ptr, *snd_perm;
+  const float* efeat;
+  const float *d_abs, *d_vh, *d_vm, *d_bd, *d_rd, *d_rr;
+  double* out;
+};
+__device__ __forceinline__ double lb_gfb_nvel(const lb_geom& g, int64_t BN, const double* __restrict__ win, int step, int f,
+                                              int d, int64_t i, double box, double half, double mean, double sd) {
+  const double v = lb_disp1(lb_pos(win, g, BN, step, f + 1, d, i), lb_pos(win, g, BN, step, f, d, i), box, half, g.periodic);
+  return (v - mean) / sd;
+}
+// h_e along axis d of the edge in padded slot `slot` (compact edge slot - slot0)
+__device__ __forceinline__ double lb_gfb_edge(const lb_gfb_args& a, int dim, int d, int64_t slot, int64_t slot0, double rc) {
+  const float* __restrict__ f = a.efeat + (slot - slot0) * 8;
+  const float dist = f[dim];
+  const double w = (a.d_rr && dist != 0.f) ? (double)a.d_rr[slot] / (double)dist : 0.0;
+  const double dd = a.d_rd ? (double)a.d_rd[slot * dim + d] : 0.0;
+  return (dd + w * (double)f[d]) / rc;
+}
+__global__ void __launch_bounds__(256) k_graph_features_bwd(lb_geom g, lb_gfb_args a) {
+  const int dim = g.dim, isl = g.isl, K = g.isl - 1;
+  const int64_t total = a.BN * dim, stride = (int64_t)gridDim.x * 256;
+  int step = a.ctrl->step;
+  step = step < 0 ? 0 : step;
+  const bool edges = a.d_rd || a.d_rr;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
+    const int64_t i = q / dim;
+    const int d = (int)(q - i * dim);
+    double* __restrict__ out = a.out + i * isl * dim + d;
+    if (a.ptype[i] == LB_PAD_TYPE) {
+      for (int f = 0; f <= K; ++f) out[f * dim] = 0.0;
+      continue;
+    }
+    // this lane's axis constants (selected with compares: a run-time index into the by-value geometry would go to scratch)
+    const double box = lb_sel3(d, g.box[0], g.box[1], g.box[2]), half = lb_sel3(d, g.half_box[0], g.half_box[1], g.half_box[2]);
+    const double mean = lb_sel3(d, g.vel_mean[0], g.vel_mean[1], g.vel_mean[2]);
+    const double sd = lb_sel3(d, g.vel_std[0], g.vel_std[1], g.vel_std[2]), inv_std = 1.0 / sd;
+    double prev = 0.0;   // what velocity f - 1 sends to its later frame f
+    for (int f = 0; f <= K; ++f) {
+      double cur = 0.0;
+      if (f < K && (a.d_vh || a.d_vm)) {
+        const float gv = a.d_vh ? a.d_vh[(i * K + f) * dim + d] : 0.f;
+        double wm = 0.0;
+        float x = 0.f;
+        if (a.d_vm) {
+          double s2 = 0.0, nd = 0.0;
+#pragma nounroll   // (one copy of the periodic displacement's fmod; c is uniform, so g.box[c] is a scalar load)
+          for (int c = 0; c < dim; ++c) {
+            const double nv = lb_gfb_nvel(g, a.BN, a.win, step, f, c, i, g.box[c], g.half_box[c], g.vel_mean[c], g.vel_std[c]);
+            s2 = c == 0 ? nv * nv : s2 + nv * nv;
+            nd = c == d ? nv : nd;
+          }
+          const float m = (float)sqrt(s2);
+          x = (float)nd;
+          wm = m != 0.f ? (double)a.d_vm[i * K + f] / (double)m : 0.0;
+        }
+        cur = ((double)gv + wm * (double)x) * inv_std;
+      }
+      double acc = prev - cur;
+      prev = cur;
+      if (a.d_abs) acc += (double)a.d_abs[(i * isl + f) * dim + d];
+      if (f == K) {
+        if (a.d_bd) {
+          const double p = lb_pos(a.win, g, a.BN, step, K, d, i);
+          const double b_lo = lb_sel3(d, g.bound_lo[0], g.bound_lo[1], g.bound_lo[2]);
+          const double b_hi = lb_sel3(d, g.bound_hi[0], g.bound_hi[1], g.bound_hi[2]);
+          const float lo = (float)fmin(fmax((p - b_lo) / g.rc, -1.0), 1.0), hi = (float)fmin(fmax((b_hi - p) / g.rc, -1.0), 1.0);
+          if (lo > -1.f && lo < 1.f) acc += (double)a.d_bd[i * 2 * dim + d] / g.rc;
+          if (hi > -1.f && hi < 1.f) acc -= (double)a.d_bd[i * 2 * dim + dim + d] / g.rc;
+        }
+        if (edges) {
+          const lb_row R = graph_row(a.row_ptr, a.row_ptr, nullptr, i, g.N, a.e_cap, a.E);
+#pragma unroll 4
+          for (int p = R.p0; p < R.p1; ++p) acc += lb_gfb_edge(a, dim, d, R.edge(p), R.slot0, g.rc);
+          const lb_row S = graph_row(a.row_ptr, a.snd_ptr, a.snd_perm, i, g.N, a.e_cap, a.E);
+#pragma unroll 4
+          for (int p = S.p0; p < S.p1; ++p) acc -= lb_gfb_edge(a, dim, d, S.edge(p), S.slot0, g.rc);
+        }
+      }
+      out[f * dim] = acc;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host
 // What the ops need to know about the current list, read back ONCE per list build (one stream synchronisation): whether
 // it overflowed, its edge count, and that every trajectory's edges fit its E_cap slots.
@@ -769,6 +870,27 @@ extern "C" int lb_graph_attend_backward(lb_engine* e, int32_t role, const float*
   hipLaunchKernelGGL(k_graph_attend_dlogits, dim3(graph_blocks1(e->BN * H)), dim3(256), 0, e->stream, e->row_ptr,
                      role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, logits_dev, m_dev, s_dev, d_logits_dev, e->BN,
                      e->g.N, e->e_cap, (int)e->graph_E, H);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+
+extern "C" int lb_graph_features_backward(lb_engine* e, const float* d_abs_pos, const float* d_vel_hist, const float* d_vel_mag,
+                                          const float* d_bound, const float* d_rel_disp, const float* d_rel_dist,
+                                          double* d_window_out) {
+  if (!e || !d_window_out) return lb_fail(LB_ERR_ARG, "null argument");
+  if (d_vel_mag && !e->g.has_vel_mag) return lb_fail(LB_ERR_ARG, "lb_graph_features_backward: d_vel_mag on an engine without vel_mag");
+  if (d_bound && !e->g.has_bound) return lb_fail(LB_ERR_ARG, "lb_graph_features_backward: d_bound on an engine without bound");
+  if (e->g.f32) return lb_fail(LB_ERR_UNSUPPORTED, "lb_graph_features_backward: float32 geometry");
+  const bool edges = d_rel_disp || d_rel_dist;   // (only these need the sender view)
+  LB_TRY(graph_entry(e, "lb_graph_features_backward", edges ? 1 : 0, true, 1, 1));
+  lb_gfb_args a{};
+  a.BN = e->BN; a.e_cap = e->e_cap; a.E = (int)e->graph_E;
+  a.win = e->win; a.ctrl = e->ctrl; a.ptype = e->ptype; a.row_ptr = e->row_ptr;
+  a.snd_ptr = edges ? e->snd_ptr : e->row_ptr; a.snd_perm = edges ? e->snd_perm : nullptr;
+  a.efeat = e->efeat;
+  a.d_abs = d_abs_pos; a.d_vh = d_vel_hist; a.d_vm = d_vel_mag; a.d_bd = d_bound; a.d_rd = d_rel_disp; a.d_rr = d_rel_dist;
+  a.out = d_window_out;
+  hipLaunchKernelGGL(k_graph_features_bwd, dim3(graph_blocks(e->BN * e->g.dim, 0)), dim3(256), 0, e->stream, e->g, a);
   LB_HIP(hipGetLastError());
   return LB_OK;
 }

@@ -550,6 +550,25 @@ class RolloutEngine:
                                                 ptr(d_logits), ptr(d_values), H, D), symbol)
         return d_logits, d_values
 
+    def graph_features_backward(self, d_abs_pos=None, d_vel_hist=None, d_vel_mag=None, d_bound=None, d_rel_disp=None,
+                                d_rel_dist=None) -> torch.Tensor:
+        """-> d loss / d window (B, N, isl, dim) float64 from the float32 cotangents of the features a TorchModel module
+        receives, on the current window and list; None = zero.  Shapes: d_abs_pos (B*N, isl, dim), d_vel_hist (B*N, (isl-1)*dim),
+        d_vel_mag (B*N, isl-1), d_bound (B*N, 2*dim), d_rel_disp (B*E_cap, dim), d_rel_dist (B*E_cap, 1); the pad slots of the
+        last two are never read.  fp64 sums in a fixed order, no atomics (include/lbhip.h: lb_graph_features_backward)."""
+        symbol = "lb_graph_features_backward"
+        BN, slots, K = self.B * self.N, self.B * self.e_cap, self.isl - 1
+        if d_vel_mag is not None and not self.has_vel_mag:
+            raise ValueError(f"{symbol}: d_vel_mag given, but the engine has no vel_mag feature")
+        if d_bound is not None and not self.has_bound:
+            raise ValueError(f"{symbol}: d_bound given, but the engine has no bound feature")
+        shapes = ((d_abs_pos, (BN, self.isl, self.dim)), (d_vel_hist, (BN, K * self.dim)), (d_vel_mag, (BN, K)),
+                  (d_bound, (BN, 2 * self.dim)), (d_rel_disp, (slots, self.dim)), (d_rel_dist, (slots, 1)))
+        args = [None if t is None else self._graph_arg(symbol, t, shape) for t, shape in shapes]
+        out = torch.empty((self.B, self.N, self.isl, self.dim), dtype=torch.float64, device=self.device)
+        check(self.lib.lb_graph_features_backward(self._h, *[ptr(t) for t in args], ptr(out)), symbol)
+        return out
+
     def graph_sender_sorts(self) -> int:
         """Sender-ordered views the graph ops built by the radix sort (a list with an edge in one direction only)."""
         return int(self.lib.lb_graph_sender_sorts(self._h))

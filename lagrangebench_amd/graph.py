@@ -41,6 +41,10 @@ result or gradient is +0.0, no float atomics, two calls give the same bits:
 Tensors are float32 on the engine's device (``TypeError`` otherwise) and are made contiguous here.  A forward or a
 backward after the engine's list moved on raises ``RuntimeError``: the staleness rule of ``FeatureDict``.  The ops are once
 differentiable: a double backward through them (``create_graph=True``) raises.
+
+``differentiable_features(features, window)`` gives the feature dict a ``TorchModel`` module receives as one autograd node
+over the position window, so that a loss on the module's output has a gradient with respect to the positions
+(``autograd.TorchModule`` uses it); its backward is one HIP launch under the same rules.
 """
 from __future__ import annotations
 
@@ -49,7 +53,7 @@ from typing import Optional
 import torch
 from torch.autograd.function import once_differentiable
 
-__all__ = ["Graph"]
+__all__ = ["Graph", "differentiable_features"]
 
 _ROLES = {"receivers": 0, "senders": 1}
 _GATHER, _SEGMENT_SUM = 0, 1
@@ -131,6 +135,76 @@ class _Attend(torch.autograd.Function):
         lf, vf, m, s = ctx.saved_tensors
         d_l, d_v = e.graph_attend_backward(ctx.role, lf, vf, m, s, flat.reshape(e.B * e.N, *ctx.hd))
         return d_l.reshape(g._shape(e.e_cap) + ctx.hd[:1]), d_v.reshape(g._shape(e.e_cap) + ctx.hd), None, None
+
+
+_FLOAT_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "force", "rel_disp", "rel_dist")
+_GRAD_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "rel_disp", "rel_dist")   # ("force" is a constant of the positions)
+
+
+def _plain(features, key: str) -> torch.Tensor:
+    """One value of a FeatureDict as a TorchModel module receives it: batched, float32 (indices int64)."""
+    v = features[key]
+    v = v if features.batched else v[None]
+    return v.to(torch.int64 if key in ("senders", "receivers") else torch.float32)
+
+
+class _Features(torch.autograd.Function):
+    """The float features of a FeatureDict as functions of the window; the backward is one lb_graph_features_backward."""
+
+    @staticmethod
+    def forward(ctx, window, features, keys):
+        ctx.features, ctx.keys = features, keys
+        outs = [_plain(features, k) for k in keys]
+        ctx.mark_non_differentiable(*[o for k, o in zip(keys, outs) if k not in _GRAD_KEYS])
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        f, e = ctx.features, ctx.features.engine
+        if e.version != f.version:
+            raise RuntimeError("graph.differentiable_features: the engine's neighbor list changed since these features were "
+                               "produced (features are stale)")
+        rows = {"rel_disp": e.B * e.e_cap, "rel_dist": e.B * e.e_cap}
+        args = {}
+        for k, g in zip(ctx.keys, grads):
+            if g is None or k not in _GRAD_KEYS:
+                continue
+            if g.dtype != torch.float32 or g.device != e.device:
+                raise TypeError(f"graph.differentiable_features: the gradient of {k!r} is {g.dtype} on {g.device}, expected "
+                                f"float32 on {e.device}")
+            g = g.detach().contiguous()
+            args["d_" + k] = g.reshape((rows.get(k, e.B * e.N),) + tuple(g.shape[2:]))
+        return e.graph_features_backward(**args), None, None
+
+
+def differentiable_features(features, window: torch.Tensor) -> dict:
+    """The plain batched dict a ``TorchModel`` module receives - the float keys as float32 with the bits of
+    ``features[k].to(torch.float32)``, ``senders`` / ``receivers`` as int64 - with the float keys as ONE autograd node over
+    `window` ((B, N, isl, dim) float64: the window `features` describes).  Its backward is one HIP launch
+    (``lb_graph_features_backward``): the transpose of the feature builder on the engine's current window and list - velocity
+    history and magnitudes, wall distances, relative displacements and distances; the neighbor list is held fixed and
+    ``force`` carries no gradient.  Once differentiable; a backward after the engine moved on raises ``RuntimeError``."""
+    engine = getattr(features, "engine", None)
+    if engine is None:
+        raise TypeError("graph.differentiable_features needs the FeatureDict returned by case.preprocess* / allocate* (it "
+                        "names the engine and the list to run on)")
+    if engine.geometry_f32:
+        raise NotImplementedError("graph.differentiable_features: the window gradient is built for float64 geometry only "
+                                  "(the case was made with dtype=float32)")
+    shape = (engine.B, engine.N, engine.isl, engine.dim)
+    if not isinstance(window, torch.Tensor) or tuple(window.shape) != shape or window.dtype != torch.float64:
+        raise ValueError(f"graph.differentiable_features: window must be {shape} float64, got "
+                         f"{tuple(getattr(window, 'shape', ()))} {getattr(window, 'dtype', type(window))}")
+    if window.device != engine.device:
+        raise TypeError(f"graph.differentiable_features: the window is on {window.device}, the engine on {engine.device}")
+    if engine.version != features.version:
+        raise RuntimeError("graph.differentiable_features: the engine's neighbor list changed since these features were "
+                           "produced (features are stale)")
+    keys = tuple(k for k in features.keys() if k in _FLOAT_KEYS)
+    out = dict(zip(keys, _Features.apply(window, features, keys)))
+    return {k: out[k] if k in out else _plain(features, k) for k in features.keys()}
 
 
 class Graph:

@@ -25,6 +25,9 @@ device copy of the module at its slice of the handle's weight blob and every ``.
 without a copy.  ``loss_grad`` is the reference's ``_mse`` in torch; its ``backward()`` accumulates straight into the gradient
 blob, and the library's AdamW kernels (``lb_adamw_step``, ``lb_adamw_step_gathered``) update the weights in place.  There is
 no fused rollout: ``evaluate.rollout`` drives ``apply`` step by step through its generic loop.
+
+Losses and training schemes of the user's own - gradients with respect to the input window, unrolls through time - go through
+``autograd.TorchModule``, which runs the same module as a differentiable torch module on the engine.
 """
 from __future__ import annotations
 
