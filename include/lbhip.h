@@ -577,6 +577,56 @@ int32_t lb_math_fallbacks(lb_engine* eng);
  * path on healthy weights and compare the result with the oracle.  No reference counterpart. */
 int lb_debug_inject_guard(lb_engine* eng, int32_t flags, int32_t step);
 
+/* ---- test hooks of the training step's gradient reductions -----------------
+ * TEST ONLY: no product code calls them.  They run the launchers of csrc/lb_train.hip - the host code that decides a
+ * kernel's grid, row chunks and partial-sum slots - on arrays the caller supplies, so that a test compares each producer
+ * kernel and the ordered reduce with a float64 reference without restating that geometry.  Both change no state of a
+ * model-backed handle: the plan query takes no handle, and lb_train_probe accepts a blob handle (lb_blob_train_create)
+ * only and is LB_ERR_ARG on every other one.
+ *
+ * lb_train_probe_plan: host only.  What the weight-gradient launcher does with `rows` rows and K columns of X in
+ * arithmetic `math` (0 exact fp32, 1 f16x2): out[0] = G workgroups, out[1] = chunk (rows per workgroup), out[2] = 1 if
+ * k_dw_part_h runs, else out[3] = NA and out[4] = DEPTH of k_dw_part<NA, DEPTH>.  The launcher itself chooses through
+ * the same function. */
+int lb_train_probe_plan(int64_t rows, int32_t K, int32_t math, int64_t* out5);
+
+#define LB_PROBE_DW 0          /* dW[K x 128] += X^T dY, db[nb] += column sums of dY (k_dw_part / k_dw_part_h)             */
+#define LB_PROBE_DW_NARROW 1   /* dW[K x M] += X^T dY, M <= 4, K <= 128 (k_dw_narrow)                                       */
+#define LB_PROBE_COLSUM 2      /* out[M] += column sums of x (rows x M, row stride ldx) (k_colsum_part)                     */
+#define LB_PROBE_LN_BWD 3      /* LayerNorm backward with its parameter gradients (k_ln_bwd2)                               */
+#define LB_PROBE_REDUCE 4      /* the ordered reduce alone, on partials the caller wrote (k_part_reduce)                    */
+#define LB_PROBE_EMBED_GRAD 5  /* gembed[ntypes x emb] += per-type row sums of x[:, col0 : col0 + emb] (k_embed_grad)       */
+/* One call of lb_train_probe.  Pointers are DEVICE pointers; a field an op does not name is ignored.  dst0 / dst1 /
+ * dst_b are float offsets into the handle's GRADIENT blob (lb_gns_train_device_blob, which = 1), -1 = none; the op's whole
+ * destination must lie inside the blob.
+ *   DW           x (rows x K, row stride ldx), dy (rows x 128), rows, K, ldx, dst0 = dW, dst1 = db or -1, nb (columns of db),
+ *                tmax (largest |dy| per 16-row tile, ceil(rows / 16) floats) or NULL, dy_b / dst_b = the second product of a
+ *                paired launch or NULL / -1, math (0 exact fp32, 1 f16x2), xexp (the site's X exponent, |xexp| <= 126), xdyn
+ *   DW_NARROW    x, ldx, K, dy (rows x M, row stride ldy), M, rows, dst0
+ *   COLSUM       x (rows x M, row stride ldx), M, rows, dst0
+ *   LN_BWD       z, b1, scale (128 floats each, zero beyond d), dy, dz (out, rows x 128), rows, d, gth / idx (the gathered
+ *                term dy[r] + gth[idx[r]]) or NULL, dst0 = d scale, dst1 = d offset
+ *   REDUCE       x = G partials (G * stride floats; copied to float offset part_off of the partial buffer), G, stride, n0, n1,
+ *                off1, ld0, dst0, dst1 (the descriptor of csrc/lb_train.hip: lb_red_ent), skip (nonzero: the guard word is
+ *                raised before the launch, which then adds nothing)
+ *   EMBED_GRAD   x (rows x ldx), col0, emb, idx = particle types (rows), ntypes, rows, dst0, skip
+ * Out: guard = the step's guard word after the call (bit 1 / 2: k_dw_part_h saw |X| above / below its fp16 window; the
+ * reduce then added nothing), slot = the site's slot (the bit pattern of the largest raw |X| when the guard fired). */
+typedef struct lb_train_probe_args {
+  const float *x, *dy, *dy_b, *tmax, *z, *b1, *scale, *gth;
+  float* dz;
+  const int32_t* idx;
+  int64_t rows, dst0, dst1, dst_b, part_off, stride;
+  int32_t K, ldx, M, ldy, nb, math, xexp, xdyn, d, G, n0, n1, off1, ld0, skip, col0, emb, ntypes;
+  int32_t guard, slot;
+} lb_train_probe_args;
+/* Runs launcher `op` and the ordered reduce on the handle's stream and waits for them.  The partial buffer, descriptor
+ * table and guard words come from the handle's arena and grow to what the call needs; the arithmetic, the site's X
+ * exponent and its per-chunk switch hold for this call only.  LB_ERR_ARG with a reason in lb_last_error: a null
+ * pointer, K > 384, an odd K with ldx <= K, a paired launch outside f16x2 (math 0 or K < 32), a destination outside
+ * the blob, a handle that is not a blob handle.  The arguments are checked before the handle is looked at. */
+int lb_train_probe(lb_gns_train* t, int32_t op, lb_train_probe_args* args);
+
 /* Debug/parity tap: hidden node state after the embedding and after each layer,
  * ((num_mp_steps+1), B*N, lb_segnn_row_floats) fp32 rows, or NULL.  Layout (1): 128 floats [s(32) | vx(32) | vy(32) | vz(32)];
  * layout (2): e3nn's own layout (n scalars, n x 3, n x 5), padded to a multiple of 4 floats. */

@@ -82,6 +82,27 @@ class LinearDesc(C.Structure):
     _fields_ = [("n_in", C.c_int32), ("out_dim", C.c_int32)]
 
 
+class TrainProbeArgs(C.Structure):
+    """lb_train_probe_args (include/lbhip.h): one call of the test hook lb_train_probe."""
+
+    _fields_ = (
+        [(k, C.c_void_p) for k in ("x", "dy", "dy_b", "tmax", "z", "b1", "scale", "gth", "dz", "idx")]
+        + [(k, C.c_int64) for k in ("rows", "dst0", "dst1", "dst_b", "part_off", "stride")]
+        + [(k, C.c_int32) for k in ("K", "ldx", "M", "ldy", "nb", "math", "xexp", "xdyn", "d", "G", "n0", "n1", "off1", "ld0",
+                                    "skip", "col0", "emb", "ntypes", "guard", "slot")]
+    )
+
+
+PROBE_OPS = {"dw": 0, "dw_narrow": 1, "colsum": 2, "ln_bwd": 3, "reduce": 4, "embed_grad": 5}
+
+
+def train_probe_plan(rows: int, K: int, math: int) -> dict:
+    """Test hook (include/lbhip.h: lb_train_probe_plan): the row split and the kernel of a weight-gradient launch."""
+    out = (C.c_int64 * 5)()
+    check(load().lb_train_probe_plan(int(rows), int(K), int(math), out), "lb_train_probe_plan")
+    return {"G": out[0], "chunk": out[1], "h": out[2], "NA": out[3], "DEPTH": out[4]}
+
+
 # name -> (restype, argtypes).  Every symbol include/lbhip.h declares must be listed here;
 # tests/test_abi.py checks the two against each other.
 _P = C.c_void_p
@@ -113,6 +134,8 @@ _SIGS = {
     "lb_math_mode": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lb_math_fallbacks": (C.c_int32, [_P]),
     "lb_debug_inject_guard": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "lb_train_probe_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "lb_train_probe": (C.c_int, [_P, C.c_int32, C.POINTER(TrainProbeArgs)]),
     "lb_integrate": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "lb_case_integrate": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P]),
     "lb_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),

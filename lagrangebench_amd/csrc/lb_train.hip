@@ -714,8 +714,9 @@ __global__ void __launch_bounds__(256) k_ln_bwd2(const float* __restrict__ z, co
     f32x4 oA, oB;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {   // (u is 0 in the padded columns: they add nothing to a, b)
-      oA[j] = keepA[j] * (rs * (uA[j] - a - hA[j] * b));
-      oB[j] = keepB[j] * (rs * (uB[j] - a - hB[j] * b));
+      // a select, not a product with keep: 0 x a negative value is -0.0, and the padding holds +0.0 everywhere else
+      oA[j] = keepA[j] != 0.f ? rs * (uA[j] - a - hA[j] * b) : 0.f;
+      oB[j] = keepB[j] != 0.f ? rs * (uB[j] - a - hB[j] * b) : 0.f;
     }
     f32x4* dr = reinterpret_cast<f32x4*>(dz + r * TD) + 2 * cl;
     dr[0] = oA;
@@ -1196,6 +1197,23 @@ static int dw_groups(int64_t rows, int64_t* chunk_out) {
 }
 // upper bound of dw_groups over every row count <= rows_cap (dw_groups is not monotonic: the chunk is rounded up to 4 rows)
 static int64_t dw_groups_max(int64_t rows_cap) { return std::min<int64_t>(DW_MAX_G, (rows_cap + 63) / 64 + 1); }
+// What a weight-gradient launch of `rows` rows and K X columns runs: the row split and the kernel - k_dw_part_h (h), or
+// k_dw_part<NA, DEPTH> (narrower operands than 32 columns - the encoders' raw features - stay on the fp32 kernel; the deep
+// pipelines belong to chunks of 192 rows and more).  dw_acc launches by it, lb_train_probe_plan reports it.
+struct lb_dw_plan {
+  int G, h, NA, DEPTH;
+  int64_t chunk;
+};
+static lb_dw_plan dw_plan(int64_t rows, int K, bool f16x2) {
+  lb_dw_plan p{};
+  p.G = dw_groups(rows, &p.chunk);
+  const bool deep = p.chunk >= 192;
+  if (f16x2 && K >= 32) p.h = 1;
+  else if (K <= 128) { p.NA = 1; p.DEPTH = deep ? 12 : 6; }
+  else if (K <= 256) { p.NA = 2; p.DEPTH = deep ? 8 : 6; }
+  else { p.NA = 3; p.DEPTH = 4; }
+  return p;
+}
 static float* red_slot(lb_gns_train* t, int64_t floats, int64_t* off) {
   floats = (floats + 63) / 64 * 64;
   if (t->red_off + floats > t->red_cap || t->red_tab.size() >= LB_RED_MAX) {
@@ -1255,8 +1273,10 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
     (void)lb_fail(LB_ERR_STATE, "dw_acc: K = %d (<= 384) / rows = %lld (> 0) out of range", K, (long long)rows);
     return false;
   }
-  int64_t chunk = 0, off = 0;
-  const int G = dw_groups(rows, &chunk);
+  const lb_dw_plan pl = dw_plan(rows, K, t->f16x2);
+  const int64_t chunk = pl.chunk;
+  int64_t off = 0;
+  const int G = pl.G;
   hipStream_t s = t->eng->stream;
   if ((K & 1) && ldx <= K) {  // (the pair load of an odd K reads the row's padding column: never stored)
     (void)lb_fail(LB_ERR_STATE, "dw_acc: odd K = %d needs a padded row (ldx = %d)", K, ldx);
@@ -1267,7 +1287,7 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
   int64_t off_b = 0;
   float* part_b = nullptr;
   if (dY_b) {
-    if (!(t->f16x2 && K >= 32)) {
+    if (!pl.h) {
       (void)lb_fail(LB_ERR_STATE, "dw_acc: paired products run on the f16x2 kernel only");
       return false;
     }
@@ -1275,8 +1295,7 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
     if (!part_b) return false;
   }
 #define DW_GO(NA, DEPTH) hipLaunchKernelGGL((k_dw_part<NA, DEPTH>), dim3(G), dim3(512), 0, s, X, ldx, K, dY, rows, chunk, part)
-  const bool deep = chunk >= 192;
-  if (t->f16x2 && K >= 32) {   // (narrower operands - the encoders' raw features - stay on the fp32 kernel)
+  if (pl.h) {
     const int64_t site = dW - t->g;   // (no two launches of a step produce the same matrix's gradient: GNS splits w0 by rows)
     int c = (int)(std::find(t->dw_site.begin(), t->dw_site.end(), site) - t->dw_site.begin());
     if (c == (int)t->dw_site.size() && c < LB_DW_CALLS - 1) t->dw_site.push_back(site);   // (past the cap: the shared last slot)
@@ -1284,8 +1303,8 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
     hipLaunchKernelGGL(k_dw_part_h, dim3((unsigned)G, (unsigned)((K + 127) / 128), part_b ? 2u : 1u), dim3(512), 0, s, X, ldx, K, dY,
                        rows, chunk, part, tmax, t->dw_flag, t->dw_flag + 1 + c, (int)t->dw_xexp[c], (int)t->dw_xdyn[c], dY_b, part_b);
   }
-  else if (K <= 128) { if (deep) DW_GO(1, 12); else DW_GO(1, 6); }
-  else if (K <= 256) { if (deep) DW_GO(2, 8); else DW_GO(2, 6); }
+  else if (pl.NA == 1) { if (pl.DEPTH == 12) DW_GO(1, 12); else DW_GO(1, 6); }
+  else if (pl.NA == 2) { if (pl.DEPTH == 8) DW_GO(2, 8); else DW_GO(2, 6); }
   else DW_GO(3, 4);
 #undef DW_GO
   red_push(t, off, G, (int64_t)(K + 1) * 128, K * 128, db ? nb : 0, K * 128, dW, db);
@@ -1296,7 +1315,7 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
 static bool dw_acc_pair(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx, const float* dY_a, float* dW_a,
                         const float* dY_b, float* dW_b) {
 #ifndef LB_NO_PAIR
-  if (t->f16x2 && K >= 32) return dw_acc(t, rows, K, X, ldx, dY_a, dW_a, nullptr, 128, nullptr, dY_b, dW_b);
+  if (dw_plan(rows, K, t->f16x2).h) return dw_acc(t, rows, K, X, ldx, dY_a, dW_a, nullptr, 128, nullptr, dY_b, dW_b);
 #endif
   return dw_acc(t, rows, K, X, ldx, dY_a, dW_a, nullptr, 128, nullptr, nullptr, nullptr) &&
          dw_acc(t, rows, K, X, ldx, dY_b, dW_b, nullptr, 128, nullptr, nullptr, nullptr);
@@ -1324,6 +1343,13 @@ static int colsum_add(lb_gns_train* t, const float* x, int64_t rows, int cols, i
   hipLaunchKernelGGL(k_colsum_part, dim3(nb), dim3(128), 0, t->eng->stream, x, rows, cols, ld, part);
   red_push(t, off, nb, 128, cols, 0, 0, out, nullptr);
   return LB_OK;
+}
+
+// gembed[type][emb] += the rows of dx[:, col0 : col0 + emb] of that type (k_embed_grad: adds nothing under a raised guard)
+static void embed_grad_acc(lb_gns_train* t, const float* dx, int ld, int col0, int emb, const int32_t* ptype, int ntypes,
+                           int64_t BN, float* gembed) {
+  hipLaunchKernelGGL(k_embed_grad, dim3(ntypes), dim3(1024), 0, t->eng->stream, dx, ld, col0, emb, ptype, ntypes, BN, gembed,
+                     t->dw_flag);
 }
 
 static int mlp_fwd_tail(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, float* a, float* z, const float* resid, float* y,
@@ -1388,24 +1414,31 @@ static int mlp_fwd_tail(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, fl
   lb_ln_epi ln{t->w + p.lns, t->w + p.lno, resid, y, y2, t->lat};
   return gemm_nn(t, rows, TD, TD, a, TD, t->w + p.w1, z, TD, 0.f, t->w + p.b1, 0, &ln);
 }
+// LayerNorm backward of `rows` rows of width d (k_ln_bwd2): dz = d loss / d z from dy (+ gth[gidx], the gathered aggregate
+// gradient), the scale / offset gradients accumulated into g_lns / g_lno through the ordered reduce
+static int ln_bwd_acc(lb_gns_train* t, int64_t rows, const float* z, const float* b1, const float* sc, const float* dy, float* dz,
+                      int d, const float* gth, const int32_t* gidx, float* g_lns, float* g_lno) {
+  hipStream_t s = t->eng->stream;
+  const int nb = (int)((rows + LNB_ROWS - 1) / LNB_ROWS);
+  int64_t off = 0;
+  float* part = red_slot(t, (int64_t)nb * 256, &off);
+  if (!part) return LB_ERR_STATE;
+  if (gth)
+    hipLaunchKernelGGL(k_ln_bwd2<true>, dim3(nb), dim3(256), 0, s, z, b1, sc, dy, dz, rows, part, d, gth, gidx);
+  else
+    hipLaunchKernelGGL(k_ln_bwd2<false>, dim3(nb), dim3(256), 0, s, z, b1, sc, dy, dz, rows, part, d, gth, gidx);
+  red_push(t, off, nb, 256, 128, 128, 128, g_lns, g_lno);
+  return LB_OK;
+}
 // backward of one MLP block.  dy: gradient w.r.t. the block's output BEFORE the residual add (rows x out);
 // produces parameter gradients (accumulated) and, if dX != null, dX (rows x in, ld = ldx).  Scratch: t->dz, t->da.
 // first part (shared with the edge block): LayerNorm and second Linear backward, ReLU mask -> t->da = d loss / d (X W0 + b0)
 static int mlp_bwd_head(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* a, const float* z, const float* dy,
                         const float* gth = nullptr, const int32_t* gidx = nullptr) {
-  hipStream_t s = t->eng->stream;
   if (rows == 0) return LB_OK;
   const float* dzz = dy;
   if (p.ln) {
-    const int nb = (int)((rows + LNB_ROWS - 1) / LNB_ROWS);
-    int64_t off = 0;
-    float* part = red_slot(t, (int64_t)nb * 256, &off);
-    if (!part) return LB_ERR_STATE;
-    if (gth)
-      hipLaunchKernelGGL(k_ln_bwd2<true>, dim3(nb), dim3(256), 0, s, z, t->w + p.b1, t->w + p.lns, dy, t->dz, rows, part, t->lat, gth, gidx);
-    else
-      hipLaunchKernelGGL(k_ln_bwd2<false>, dim3(nb), dim3(256), 0, s, z, t->w + p.b1, t->w + p.lns, dy, t->dz, rows, part, t->lat, gth, gidx);
-    red_push(t, off, nb, 256, 128, 128, 128, t->g + p.lns, t->g + p.lno);
+    LB_TRY(ln_bwd_acc(t, rows, z, t->w + p.b1, t->w + p.lns, dy, t->dz, t->lat, gth, gidx, t->g + p.lns, t->g + p.lno));
     dzz = t->dz;
   }
   // dX first: k_lin32h leaves the row-tile maxima of dzz behind, which the weight-gradient kernel scales by
@@ -1889,9 +1922,7 @@ static int gns_backward_part(lb_gns_train* t, double* dpos_out_dev) {
   // (d efeat: [E][8] like efeat, rel_disp in the first dim columns, rel_dist in column dim - a 128 x (dim + 1) operand)
   LB_TRY(mlp_bwd(t, t->enc_edge, E, e->efeat, 8, t->a_ee, t->z_ee, t->de, want_dx ? t->dxe : nullptr, t->hs_e));
   LB_TRY(mlp_bwd(t, t->enc_node, BN, t->xnode, t->kpad, t->a_en, t->z_en, t->dn, has_emb || want_dx ? t->dx : nullptr, t->hs_n));
-  if (has_emb)
-    hipLaunchKernelGGL(k_embed_grad, dim3(t->desc.num_particle_types), dim3(1024), 0, s, t->dx, t->kpad, t->desc.node_in, emb,
-                       e->ptype, t->desc.num_particle_types, BN, t->g + t->off_embed, t->dw_flag);
+  if (has_emb) embed_grad_acc(t, t->dx, t->kpad, t->desc.node_in, emb, e->ptype, t->desc.num_particle_types, BN, t->g + t->off_embed);
   if (want_dx) LB_TRY(feat_bwd(t, dpos_out_dev));
   return train_step_end(t);
 }
@@ -2201,4 +2232,166 @@ extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double
     if (t->pa) return painn_backward_part(t);
     return t->sg ? segnn_backward_part(t) : gns_backward_part(t, dpos_out_dev);
   });
+}
+
+// ---------------------------------------------------------------------------------------------- test hooks
+// lb_train_probe_plan / lb_train_probe (include/lbhip.h): the launchers above on the caller's arrays, for
+// tests/test_train_kernels*.py.  Nothing in the product calls them.
+extern "C" int lb_train_probe_plan(int64_t rows, int32_t K, int32_t math, int64_t* out) {
+  if (!out) return lb_fail(LB_ERR_ARG, "null argument");
+  if (rows < 1 || K < 1 || K > 384) return lb_fail(LB_ERR_ARG, "lb_train_probe_plan: rows = %lld (> 0), K = %d (1 ... 384)", (long long)rows, (int)K);
+  const lb_dw_plan p = dw_plan(rows, K, math != 0);
+  out[0] = p.G; out[1] = p.chunk; out[2] = p.h; out[3] = p.NA; out[4] = p.DEPTH;
+  return LB_OK;
+}
+// the argument checks that need no handle: 0, or the refusal
+static int probe_check(int32_t op, const lb_train_probe_args* a) {
+  const char* w = "lb_train_probe";
+  if (a->rows < 1 && op != LB_PROBE_REDUCE) return lb_fail(LB_ERR_ARG, "%s: rows = %lld (> 0)", w, (long long)a->rows);
+  switch (op) {
+    case LB_PROBE_DW: {
+      if (!a->x || !a->dy) return lb_fail(LB_ERR_ARG, "%s: null argument (dw: x, dy)", w);
+      if (a->K < 1 || a->K > 384) return lb_fail(LB_ERR_ARG, "%s: dw: K = %d (1 ... 384) out of range", w, (int)a->K);
+      if (a->ldx < a->K || ((a->K & 1) && a->ldx <= a->K))
+        return lb_fail(LB_ERR_ARG, "%s: dw: odd K = %d needs a padded row, and every K ldx >= K (ldx = %d)", w, (int)a->K, (int)a->ldx);
+      const bool h = dw_plan(a->rows, a->K, a->math != 0).h != 0;   // (the launcher's own choice of kernel)
+      if (!h && ((a->ldx & 1) || ((uintptr_t)a->x & 7)))
+        return lb_fail(LB_ERR_ARG, "%s: dw: the fp32 kernel loads X in aligned pairs (ldx = %d)", w, (int)a->ldx);
+      if ((uintptr_t)a->dy & 15 || (a->dy_b && ((uintptr_t)a->dy_b & 15))) return lb_fail(LB_ERR_ARG, "%s: dw: dy is not 16-byte aligned", w);
+      if ((a->dy_b != nullptr) != (a->dst_b >= 0)) return lb_fail(LB_ERR_ARG, "%s: dw: dy_b and dst_b go together", w);
+      if (a->dy_b && !h) return lb_fail(LB_ERR_ARG, "%s: dw: paired products run on the f16x2 kernel only", w);
+      if (a->dst0 < 0 || a->nb < 0 || a->nb > 128) return lb_fail(LB_ERR_ARG, "%s: dw: dst0 = %lld, nb = %d (0 ... 128)", w, (long long)a->dst0, (int)a->nb);
+      if (a->xexp < -126 || a->xexp > 126) return lb_fail(LB_ERR_ARG, "%s: dw: xexp = %d (-126 ... 126)", w, (int)a->xexp);
+      return LB_OK;
+    }
+    case LB_PROBE_DW_NARROW:
+      if (!a->x || !a->dy) return lb_fail(LB_ERR_ARG, "%s: null argument (dw_narrow: x, dy)", w);
+      if (a->M < 1 || a->M > 4 || a->K < 1 || a->K > 128 || a->ldx < a->K || a->ldy < a->M || a->dst0 < 0)
+        return lb_fail(LB_ERR_ARG, "%s: dw_narrow: K = %d (<= 128, ldx = %d), M = %d (<= 4, ldy = %d)", w, (int)a->K, (int)a->ldx, (int)a->M, (int)a->ldy);
+      return LB_OK;
+    case LB_PROBE_COLSUM:
+      if (!a->x) return lb_fail(LB_ERR_ARG, "%s: null argument (colsum: x)", w);
+      if (a->M < 1 || a->M > 128 || a->ldx < a->M || a->dst0 < 0) return lb_fail(LB_ERR_ARG, "%s: colsum: %d columns (1 ... 128, ldx = %d)", w, (int)a->M, (int)a->ldx);
+      return LB_OK;
+    case LB_PROBE_LN_BWD:
+      if (!a->z || !a->b1 || !a->scale || !a->dy || !a->dz) return lb_fail(LB_ERR_ARG, "%s: null argument (ln_bwd: z, b1, scale, dy, dz)", w);
+      if ((a->gth != nullptr) != (a->idx != nullptr)) return lb_fail(LB_ERR_ARG, "%s: ln_bwd: gth and idx go together", w);
+      if (a->d < 1 || a->d > 128 || a->dst0 < 0 || a->dst1 < 0) return lb_fail(LB_ERR_ARG, "%s: ln_bwd: d = %d (1 ... 128), two destinations", w, (int)a->d);
+      return LB_OK;
+    case LB_PROBE_REDUCE:
+      if (!a->x) return lb_fail(LB_ERR_ARG, "%s: null argument (reduce: x)", w);
+      if (a->G < 1 || a->stride < 1 || a->n0 < 0 || a->n1 < 0 || a->n0 + a->n1 < 1 || a->n0 > a->stride || a->off1 < 0 ||
+          a->off1 + a->n1 > a->stride || a->part_off < 0 || a->dst0 < 0 || (a->n1 && a->dst1 < 0))
+        return lb_fail(LB_ERR_ARG, "%s: reduce: G = %d, stride = %lld, n0 = %d, n1 = %d at %d do not describe partials", w, (int)a->G,
+                       (long long)a->stride, (int)a->n0, (int)a->n1, (int)a->off1);
+      if (a->ld0 && (a->ld0 < 128 || (a->n0 & 127))) return lb_fail(LB_ERR_ARG, "%s: reduce: ld0 = %d takes rows of 128", w, (int)a->ld0);
+      return LB_OK;
+    case LB_PROBE_EMBED_GRAD:
+      if (!a->x || !a->idx) return lb_fail(LB_ERR_ARG, "%s: null argument (embed_grad: x, idx)", w);
+      if (a->emb < 1 || a->emb > 1024 || a->ntypes < 1 || a->col0 < 0 || a->col0 + a->emb > a->ldx || a->dst0 < 0)
+        return lb_fail(LB_ERR_ARG, "%s: embed_grad: emb = %d, %d types, columns from %d of %d", w, (int)a->emb, (int)a->ntypes, (int)a->col0, (int)a->ldx);
+      return LB_OK;
+  }
+  return lb_fail(LB_ERR_ARG, "%s: op = %d", w, (int)op);
+}
+extern "C" int lb_train_probe(lb_gns_train* t, int32_t op, lb_train_probe_args* a) {
+  if (!a) return lb_fail(LB_ERR_ARG, "lb_train_probe: null argument");
+  a->guard = a->slot = 0;
+  LB_TRY(probe_check(op, a));
+  if (!t) return lb_fail(LB_ERR_ARG, "lb_train_probe: null handle");
+  if (!t->blob) return lb_fail(LB_ERR_ARG, "lb_train_probe: a test hook for blob handles (lb_blob_train_create) only");
+  // the destinations inside the gradient blob, the floats of partial sums the call takes
+  const int64_t n = t->n_floats;
+  auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n; };
+  auto r64 = [](int64_t f) { return (f + 63) / 64 * 64; };
+  int64_t need = 0;
+  bool ok = true;
+  switch (op) {
+    case LB_PROBE_DW: {
+      const lb_dw_plan pl = dw_plan(a->rows, a->K, a->math != 0);
+      need = r64((int64_t)pl.G * (a->K + 1) * 128) * (a->dy_b ? 2 : 1);
+      ok = inside(a->dst0, (int64_t)a->K * 128) && (a->dst1 < 0 || inside(a->dst1, a->nb)) && (a->dst_b < 0 || inside(a->dst_b, (int64_t)a->K * 128));
+      break;
+    }
+    case LB_PROBE_DW_NARROW:
+      need = r64(dw_groups_max(a->rows) * a->K * a->M);
+      ok = inside(a->dst0, (int64_t)a->K * a->M);
+      break;
+    case LB_PROBE_COLSUM:
+      need = r64((a->rows + 127) / 128 * 128);
+      ok = inside(a->dst0, a->M);
+      break;
+    case LB_PROBE_LN_BWD:
+      need = r64((a->rows + LNB_ROWS - 1) / LNB_ROWS * 256);
+      ok = inside(a->dst0, 128) && inside(a->dst1, 128);
+      break;
+    case LB_PROBE_REDUCE:
+      need = a->part_off + (int64_t)a->G * a->stride;
+      ok = inside(a->dst0, a->ld0 ? (int64_t)(a->n0 / 128 - 1) * a->ld0 + (a->n0 ? 128 : 0) : (int64_t)a->n0) && (!a->n1 || inside(a->dst1, a->n1));
+      break;
+    case LB_PROBE_EMBED_GRAD:
+      ok = inside(a->dst0, (int64_t)a->ntypes * a->emb);
+      break;
+  }
+  if (!ok) return lb_fail(LB_ERR_ARG, "lb_train_probe: a destination lies outside the gradient blob of %lld floats", (long long)n);
+  hipStream_t s = t->eng->stream;
+  if (!t->red_dev) LB_TRY(t->mem.get(&t->red_dev, (size_t)LB_RED_MAX));
+  if (!t->red_host) LB_TRY(t->mem.get_pinned(&t->red_host, (size_t)LB_RED_MAX + 1));
+  need += 64;
+  if (need > t->red_cap)
+    LB_TRY(lb_regrow(s, &t->red_cap, need, [&](int64_t want) -> int { return t->mem.get(&t->dwpart, (size_t)want); }));
+  // this call's arithmetic and X scale: the site takes slot 0 of an empty table; put back below
+  const bool f16x2_was = t->f16x2;
+  std::vector<int64_t> site_was;
+  std::vector<int8_t> xexp_was;
+  std::vector<uint8_t> xdyn_was;
+  site_was.swap(t->dw_site); xexp_was.swap(t->dw_xexp); xdyn_was.swap(t->dw_xdyn);
+  auto run = [&]() -> int {
+    LB_HIP(hipMemsetAsync(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS), s));
+    if (a->skip && (op == LB_PROBE_REDUCE || op == LB_PROBE_EMBED_GRAD)) LB_HIP(hipMemsetAsync(t->dw_flag, 1, 1, s));   // (word 0 = 1)
+    switch (op) {
+      case LB_PROBE_DW:
+        t->f16x2 = a->math != 0;
+        t->dw_site.assign(1, a->dst0);
+        t->dw_xexp.assign(1, (int8_t)a->xexp);
+        t->dw_xdyn.assign(1, (uint8_t)(a->xdyn != 0));
+        if (!dw_acc(t, a->rows, a->K, a->x, a->ldx, a->dy, t->g + a->dst0, a->dst1 >= 0 ? t->g + a->dst1 : nullptr, a->nb, a->tmax,
+                    a->dy_b, a->dy_b ? t->g + a->dst_b : nullptr))
+          return LB_ERR_STATE;
+        break;
+      case LB_PROBE_DW_NARROW:
+        LB_TRY(dw_narrow(t, a->rows, a->M, a->K, a->x, a->ldx, a->dy, a->ldy, t->g + a->dst0));
+        break;
+      case LB_PROBE_COLSUM:
+        LB_TRY(colsum_add(t, a->x, a->rows, a->M, a->ldx, t->g + a->dst0));
+        break;
+      case LB_PROBE_LN_BWD:
+        LB_TRY(ln_bwd_acc(t, a->rows, a->z, a->b1, a->scale, a->dy, a->dz, a->d, a->gth, a->idx, t->g + a->dst0, t->g + a->dst1));
+        break;
+      case LB_PROBE_REDUCE:
+        LB_HIP(hipMemcpyAsync(t->dwpart + a->part_off, a->x, sizeof(float) * (size_t)a->G * a->stride, hipMemcpyDeviceToDevice, s));
+        red_push(t, a->part_off, a->G, a->stride, a->n0, a->n1, a->off1, t->g + a->dst0, a->n1 ? t->g + a->dst1 : nullptr);
+        t->red_tab.back().ld0 = a->ld0;
+        break;
+      case LB_PROBE_EMBED_GRAD:
+        embed_grad_acc(t, a->x, a->ldx, a->col0, a->emb, a->idx, a->ntypes, a->rows, t->g + a->dst0);
+        break;
+    }
+    LB_TRY(red_flush(t));
+    LB_HIP(hipGetLastError());
+    int32_t fl[2] = {0, 0};
+    LB_HIP(hipMemcpyAsync(fl, t->dw_flag, sizeof(fl), hipMemcpyDeviceToHost, s));
+    LB_HIP(hipMemsetAsync(t->dw_flag, 0, sizeof(int32_t) * (1 + LB_DW_CALLS), s));
+    LB_HIP(hipStreamSynchronize(s));
+    a->guard = fl[0];
+    a->slot = fl[1];
+    return LB_OK;
+  };
+  const int rc = run();
+  t->f16x2 = f16x2_was;
+  t->dw_site.swap(site_was); t->dw_xexp.swap(xexp_was); t->dw_xdyn.swap(xdyn_was);
+  t->red_tab.clear();
+  t->red_off = 0;
+  t->red_blocks = 0;
+  return rc;
 }

@@ -847,6 +847,22 @@ class BlobTrainHandle(GnsTrainHandle):
         super().close()
 
 
+    def probe(self, op: str, **kw) -> Tuple[int, int]:
+        """Test hook (include/lbhip.h: lb_train_probe): one gradient-reduction launcher of the training step on the
+        caller's device tensors, accumulated into this handle's gradient blob at float offsets dst0 / dst1 / dst_b.
+        Tensors are passed by pointer - keep them alive and synchronised.  Returns (guard word, site slot)."""
+        from ._lib import PROBE_OPS, TrainProbeArgs
+        a = TrainProbeArgs()
+        a.dst0 = a.dst1 = a.dst_b = -1
+        for k, v in kw.items():
+            if not hasattr(a, k):
+                raise TypeError(f"probe: no argument {k!r}")
+            setattr(a, k, ptr(v) if isinstance(v, torch.Tensor) else v)
+        torch.cuda.synchronize(self.engine.device)   # the launch runs on the engine's stream
+        check(self.engine.lib.lb_train_probe(self._h, PROBE_OPS[op], C.byref(a)), "lb_train_probe")
+        return int(a.guard), int(a.slot)
+
+
 class PainnTrainHandle(GnsTrainHandle):
     """trainer.py:35-89 for PaiNN (csrc/lb_train_painn.h): GnsTrainHandle's calls, one "acc" target."""
 
