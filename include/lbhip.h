@@ -708,7 +708,8 @@ int lb_segment_sum(lb_engine* eng, const float* msg_dev, float* out_dev, int32_t
 
 /* ---- graph primitives for a network written outside the library --------
  * x[senders], x[receivers] and jraph.segment_sum(msg, receivers | senders, N) on the engine's CURRENT list, each other's
- * adjoints (the backward of one is the other).  role: 0 receivers, 1 senders.  All tensors fp32, row-major, on the engine's
+ * adjoints (the backward of one is the other).  role: 0 receivers, 1 senders.  All tensors fp32 (bfloat16: the _t entries
+ * further down), row-major, on the engine's
  * device, in the PADDED layout of lb_nl_read_idx: edge slot (b, j), j < n_edges[b], is the j-th edge of trajectory b in
  * canonical (receiver, sender) order.  C >= 1 columns, no upper limit; 16-byte accesses when C % 4 == 0 and both pointers
  * are 16-byte aligned.  Asynchronous on the engine's stream, except the first call after a list build, which reads the
@@ -760,6 +761,43 @@ int lb_graph_attend(lb_engine* eng, int32_t role, const float* logits_dev /*(B*E
 int lb_graph_attend_backward(lb_engine* eng, int32_t role, const float* logits_dev, const float* values_dev, const float* m_dev,
                              const float* s_dev, const float* d_out_dev /*(B*N,H*D)*/, float* d_logits_dev /*(B*E_cap,H)*/,
                              float* d_values_dev /*(B*E_cap,H*D)*/, int32_t H, int32_t D);
+/* ---- the same ops on float32 OR bfloat16 tensors ("bfloat16") ----------
+ * Each entry has the arguments of its fp32 entry above, with void* data pointers and the element type of every data tensor of
+ * the call: dtype LB_DTYPE_F32 or LB_DTYPE_BF16 (anything else is LB_ERR_ARG).  win stays int32, m and s of attend stay fp32.
+ * The fp32 entries above ARE these with LB_DTYPE_F32.  The contract of LB_DTYPE_BF16, for every op and every backward:
+ *
+ *     bf16 op  ==  round_to_bf16( fp32 op( upcast(inputs) ) )      bit for bit
+ *
+ * upcast is the exact bf16 -> fp32 widening; the fp32 op is the arithmetic stated above, unchanged - the same order of adds,
+ * the same m, expf, s, division and roundings of products; round_to_bf16 is ONE round-to-nearest-even per stored element
+ * (a NaN stays a NaN, payload unspecified; beyond the bf16 range -> +-inf; bf16 subnormals are kept; -0.0 stays -0.0 where
+ * the fp32 op keeps it).  So: gather is a bit copy; segment_sum adds the upcast terms in fp32 from the first term in ascending
+ * slot order and rounds once - no partial sum is ever held in bf16; segment_max / _min return one of the inputs and
+ * the backward copies d_out into the winning slot; segment_softmax stores y = round(e / s), and its backward works on the
+ * stored (rounded) y; attend forms alpha in fp32 from the upcast logits, rounds each alpha v to fp32, adds in slot order and
+ * rounds once - it does NOT round alpha to bf16 as the composition segment_sum(segment_softmax(l) v) does, and is the more
+ * accurate of the two; attend_backward recomputes alpha from m, s and the upcast logits, d_values = round(alpha d_out),
+ * d_logits = round(alpha (t - sum alpha t)) with t held in fp32 (a buffer of the engine's).  Pad slots are never read and every
+ * pad slot of an edge-shaped output is +0.0 (bf16 bits 0x0000).  16-byte accesses (8 bf16) when C % 8 == 0 and the pointers
+ * are 16-byte aligned, single elements otherwise; attend: 16 bytes when D % 8 == 0, 8 bytes when D % 4 == 0. */
+#define LB_DTYPE_F32 0
+#define LB_DTYPE_BF16 1
+int lb_graph_gather_t(lb_engine* eng, int32_t role, const void* x_dev, void* out_dev, int32_t C, int32_t dtype);
+int lb_graph_segment_sum_t(lb_engine* eng, int32_t role, const void* msg_dev, void* out_dev, int32_t C, int32_t dtype);
+int lb_graph_segment_max_t(lb_engine* eng, int32_t role, const void* msg_dev, void* out_dev, int32_t* win_dev, int32_t C,
+                           int32_t dtype);
+int lb_graph_segment_min_t(lb_engine* eng, int32_t role, const void* msg_dev, void* out_dev, int32_t* win_dev, int32_t C,
+                           int32_t dtype);
+int lb_graph_segment_max_backward_t(lb_engine* eng, int32_t role, const void* d_out_dev, const int32_t* win_dev,
+                                    void* d_msg_dev, int32_t C, int32_t dtype);
+int lb_graph_segment_softmax_t(lb_engine* eng, int32_t role, const void* logits_dev, void* out_dev, int32_t C, int32_t dtype);
+int lb_graph_segment_softmax_backward_t(lb_engine* eng, int32_t role, const void* y_dev, const void* d_y_dev, void* d_x_dev,
+                                        int32_t C, int32_t dtype);
+int lb_graph_attend_t(lb_engine* eng, int32_t role, const void* logits_dev, const void* values_dev, void* out_dev,
+                      float* m_dev, float* s_dev, int32_t H, int32_t D, int32_t dtype);
+int lb_graph_attend_backward_t(lb_engine* eng, int32_t role, const void* logits_dev, const void* values_dev,
+                               const float* m_dev, const float* s_dev, const void* d_out_dev, void* d_logits_dev,
+                               void* d_values_dev, int32_t H, int32_t D, int32_t dtype);
 /* d loss / d window from the cotangents of the features a TorchModel module receives (graph.differentiable_features), on the
  * engine's CURRENT window and list: the transpose of the feature builder.  Every input may be NULL (= zero).  fp32 inputs in the
  * layouts of TorchModel's feature dict; the edge-shaped ones in the padded slot layout of lb_nl_read_idx, whose pad slots are

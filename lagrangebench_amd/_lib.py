@@ -216,6 +216,16 @@ _SIGS = {
     "lb_graph_attend": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32]),
     "lb_graph_attend_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32]),
     "lb_graph_features_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    # the same ops on float32 or bfloat16 tensors: the float32 entry's arguments and a trailing dtype (0 float32, 1 bfloat16)
+    "lb_graph_gather_t": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_segment_sum_t": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_segment_max_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_segment_min_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_segment_max_backward_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_segment_softmax_t": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_segment_softmax_backward_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
+    "lb_graph_attend_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_graph_attend_backward_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -209,7 +209,8 @@ class TorchModule(torch.nn.Module):
     `window`: (B, N, isl, dim) float64 on the device.  Without `features` the module loads the window into the engine and
     updates the neighbor list (sized before by ``case.allocate*``); with the ``FeatureDict`` that ``case.preprocess*`` just
     made for this window it skips that.  Gradients flow to the parameters and, when ``window.requires_grad``, to the window
-    (``graph.differentiable_features``: the neighbor list is held fixed, the external force is a constant).
+    (``graph.differentiable_features``: the neighbor list is held fixed, the external force is a constant).  A model made
+    with ``autocast=torch.bfloat16`` runs its module under that autocast context here too; the output is float32 either way.
 
     Several graphs may be alive at once (an unroll through time, two backward calls).  Each forward saves its window and
     particle types (64 at most).  A backward whose step is no longer the engine's live one reloads them and rebuilds the list -
@@ -295,11 +296,7 @@ class TorchModule(torch.nn.Module):
         else:
             fd = {k: _plain(features, k) for k in features.keys()}
         graph = Graph(features, batched=True)
-        out = self.module(fd, types, graph)
-        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (eng.B, eng.N, eng.dim) or out.dtype != torch.float32:
-            raise ValueError(f"TorchModule: the module must return a ({eng.B}, {eng.N}, {eng.dim}) float32 tensor, got "
-                             f"{tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__} "
-                             f"{getattr(out, 'dtype', '')}")
+        out = self.model._call_module(self.module, eng, "TorchModule", fd, types, graph)   # (the model's autocast setting)
         self._ticket += 1
         ticket = self._ticket
         if torch.is_grad_enabled():

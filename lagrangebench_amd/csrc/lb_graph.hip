@@ -25,6 +25,10 @@
 // of k_segment_sum (lb_gns.hip) - so a row's slots are read as whole 512-byte lines.  Four independent loads are in flight
 // per lane; the adds stay sequential.  Rows of one output are summed by ONE lane per column: no cross-lane step, no LDS.
 // Grids are capped at 2048 workgroups of 256 threads and stride over the rows.  Addresses are int64 throughout.
+//
+// Element types.  The text above and the kernels' comments speak of float32; every op also runs on bfloat16 tensors (the
+// lb_graph_*_t entries) through the same kernels - "element types" below: a 16-byte unit is then 8 elements (C % 8 == 0), the
+// arithmetic stays fp32 and each stored element is rounded once.
 #include <algorithm>
 
 #include "lb_device.h"
@@ -35,31 +39,99 @@
 
 #define GRID1(n) dim3((unsigned)(((n) + 255) / 256)), dim3(256)
 
-template <bool VEC>
-struct lb_unit {
-  typedef float type;
-};
-template <>
-struct lb_unit<true> {
-  typedef f32x4 type;
-};
-template <typename T>
-__device__ __forceinline__ T lb_zero_unit();
-template <>
-__device__ __forceinline__ float lb_zero_unit<float>() {
-  return 0.f;
+// ---- element types.  Every op runs on float32 or bfloat16 tensors (include/lbhip.h: the lb_graph_*_t entries); the kernels are
+// templates over the element type E (float, or lb_bf16: the 16 bits of a bfloat16) and the elements W of one access - 16
+// bytes (4 floats, 8 bf16), 8 bytes (4 bf16, attend only) or one element.  Only the load and the store of a unit differ: the
+// load widens to fp32 registers (exact), the store rounds to nearest even ONCE; everything between them is the fp32 arithmetic.
+// So a bf16 op is round(fp32 op(upcast inputs)) bit for bit, and no partial result is ever held in bf16.
+typedef uint16_t lb_bf16;
+typedef uint32_t lb_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t lb_u32x2 __attribute__((ext_vector_type(2)));
+typedef int32_t lb_i32x4 __attribute__((ext_vector_type(4)));
+typedef float lb_f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 lb_bf16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float lb_widen(uint32_t bits16) { return __uint_as_float(bits16 << 16); }
+// two fp32 -> two bf16 in one word (lo in bits 0..15): the compiler's conversion, v_cvt_pk_bf16_f32 on gfx950 - round to
+// nearest even, NaN stays NaN, overflow to inf, subnormals kept (the kernel mode keeps fp32 subnormals)
+__device__ __forceinline__ uint32_t lb_round2(float lo, float hi) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(lb_f32x2{lo, hi}, lb_bf16x2));
 }
-template <>
-__device__ __forceinline__ f32x4 lb_zero_unit<f32x4>() {
-  return f32x4{0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ lb_bf16 lb_round1(float f) { return __builtin_bit_cast(lb_bf16, (__bf16)f); }
+
+template <typename E>
+__device__ __forceinline__ float lb_ld1(const E* p) {
+  if constexpr (sizeof(E) == 4)
+    return *p;
+  else
+    return lb_widen(*p);
+}
+template <typename E>
+__device__ __forceinline__ void lb_st1(E* p, float f) {
+  if constexpr (sizeof(E) == 4)
+    *p = f;
+  else
+    *p = lb_round1(f);
+}
+template <typename E, int W>
+__device__ __forceinline__ void lb_ld(const E* p, float (&a)[W]) {
+  static_assert(sizeof(E) == 4 ? (W == 4 || W == 1) : (W == 8 || W == 4 || W == 1), "unit width");
+  if constexpr (W == 1) {
+    a[0] = lb_ld1<E>(p);
+  } else if constexpr (sizeof(E) == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+    a[0] = t[0], a[1] = t[1], a[2] = t[2], a[3] = t[3];
+  } else if constexpr (W == 8) {
+    const lb_u32x4 t = *reinterpret_cast<const lb_u32x4*>(p);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[2 * k] = lb_widen(t[k]), a[2 * k + 1] = __uint_as_float(t[k] & 0xffff0000u);
+  } else {
+    const lb_u32x2 t = *reinterpret_cast<const lb_u32x2*>(p);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) a[2 * k] = lb_widen(t[k]), a[2 * k + 1] = __uint_as_float(t[k] & 0xffff0000u);
+  }
+}
+template <typename E, int W>
+__device__ __forceinline__ void lb_st(E* p, const float (&a)[W]) {
+  if constexpr (W == 1)
+    lb_st1<E>(p, a[0]);
+  else if constexpr (sizeof(E) == 4)
+    *reinterpret_cast<f32x4*>(p) = f32x4{a[0], a[1], a[2], a[3]};
+  else if constexpr (W == 8)
+    *reinterpret_cast<lb_u32x4*>(p) =
+        lb_u32x4{lb_round2(a[0], a[1]), lb_round2(a[2], a[3]), lb_round2(a[4], a[5]), lb_round2(a[6], a[7])};
+  else
+    *reinterpret_cast<lb_u32x2*>(p) = lb_u32x2{lb_round2(a[0], a[1]), lb_round2(a[2], a[3])};
+}
+// W int32 (the winning slots of segment_max): 16-byte accesses when W > 1
+template <int W>
+__device__ __forceinline__ void lb_ldi(const int32_t* p, int32_t (&a)[W]) {
+  if constexpr (W == 1) {
+    a[0] = *p;
+  } else {
+#pragma unroll
+    for (int q = 0; q < W; q += 4) {
+      const lb_i32x4 t = *reinterpret_cast<const lb_i32x4*>(p + q);
+      a[q] = t[0], a[q + 1] = t[1], a[q + 2] = t[2], a[q + 3] = t[3];
+    }
+  }
+}
+template <int W>
+__device__ __forceinline__ void lb_sti(int32_t* p, const int32_t (&a)[W]) {
+  if constexpr (W == 1) {
+    *p = a[0];
+  } else {
+#pragma unroll
+    for (int q = 0; q < W; q += 4) *reinterpret_cast<lb_i32x4*>(p + q) = lb_i32x4{a[q], a[q + 1], a[q + 2], a[q + 3]};
+  }
 }
 
-// out[slot][:] = x[idx[compact edge of the slot]][:] for the real slots, +0.0 for the pads.  U units per row.
-template <bool VEC>
+// out[slot][:] = x[idx[compact edge of the slot]][:] for the real slots, +0.0 for the pads: a bit copy of U units of type T per
+// row - f32x4 (16 bytes of either element type), float, or lb_bf16; all bits zero is +0.0 in both.
+template <typename T>
 __global__ void __launch_bounds__(256) k_graph_gather(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
-                                                      const float* __restrict__ x, float* __restrict__ out, int64_t BN, int N,
+                                                      const void* __restrict__ x, void* __restrict__ out, int64_t BN, int N,
                                                       int B, int e_cap, int E, int U, int lpr_shift) {
-  typedef typename lb_unit<VEC>::type T;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   const T* __restrict__ xs = reinterpret_cast<const T*>(x);
@@ -70,23 +142,21 @@ __global__ void __launch_bounds__(256) k_graph_gather(const int32_t* __restrict_
     const bool real = j < nb && base + j < E;
     int64_t node = real ? idx[base + j] : 0;
     node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);   // (an index of the list is a node of the batch: never clamps)
-    for (int u = lane; u < U; u += lpr) os[r * U + u] = real ? xs[node * U + u] : lb_zero_unit<T>();
+    for (int u = lane; u < U; u += lpr) os[r * U + u] = real ? xs[node * U + u] : T{};
   }
 }
 
 // out[i][:] = msg[slot of p0][:] + msg[slot of p0 + 1][:] + ... over the positions p of row i of (seg_ptr, perm): compact edge
 // k = perm ? perm[p] : p, padded slot = b E_cap + k - row_ptr[b N].  +0.0 for an empty row.  Pad slots are never read.
-template <bool VEC>
+// The adds are fp32 on the widened terms; the sum is rounded to E once, at the store.
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_segment_sum(const int32_t* __restrict__ row_ptr,
                                                            const int32_t* __restrict__ seg_ptr,
-                                                           const int32_t* __restrict__ perm, const float* __restrict__ msg,
-                                                           float* __restrict__ out, int64_t BN, int N, int e_cap, int E, int U,
+                                                           const int32_t* __restrict__ perm, const T* __restrict__ ms,
+                                                           T* __restrict__ os, int64_t BN, int N, int e_cap, int E, int U,
                                                            int lpr_shift) {
-  typedef typename lb_unit<VEC>::type T;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  const T* __restrict__ ms = reinterpret_cast<const T*>(msg);
-  T* __restrict__ os = reinterpret_cast<T*>(out);
   for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
     const int64_t b = i / N;
     const int base = row_ptr[b * N];
@@ -106,21 +176,30 @@ __global__ void __launch_bounds__(256) k_graph_segment_sum(const int32_t* __rest
     };
     if (last <= base) p1 = p0;   // (a trajectory without edges has empty rows)
     for (int u = lane; u < U; u += lpr) {
-      T s = lb_zero_unit<T>();
+      float s[W], a0[W], a1[W], a2[W], a3[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) s[k] = 0.f;
       int p = p0;
-      if (p < p1) s = ms[edge(p++) * U + u];   // the sum STARTS from the first term (-0.0 stays -0.0)
+      if (p < p1) lb_ld<T, W>(ms + (edge(p++) * U + u) * W, s);   // the sum STARTS from the first term (-0.0 stays -0.0)
       for (; p + 4 <= p1; p += 4) {
-        const T a0 = ms[edge(p + 0) * U + u];
-        const T a1 = ms[edge(p + 1) * U + u];
-        const T a2 = ms[edge(p + 2) * U + u];
-        const T a3 = ms[edge(p + 3) * U + u];
-        s = s + a0;
-        s = s + a1;
-        s = s + a2;
-        s = s + a3;
+        lb_ld<T, W>(ms + (edge(p + 0) * U + u) * W, a0);
+        lb_ld<T, W>(ms + (edge(p + 1) * U + u) * W, a1);
+        lb_ld<T, W>(ms + (edge(p + 2) * U + u) * W, a2);
+        lb_ld<T, W>(ms + (edge(p + 3) * U + u) * W, a3);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          s[k] = s[k] + a0[k];
+          s[k] = s[k] + a1[k];
+          s[k] = s[k] + a2[k];
+          s[k] = s[k] + a3[k];
+        }
       }
-      for (; p < p1; ++p) s = s + ms[edge(p) * U + u];
-      os[i * U + u] = s;
+      for (; p < p1; ++p) {
+        lb_ld<T, W>(ms + (edge(p) * U + u) * W, a0);
+#pragma unroll
+        for (int k = 0; k < W; ++k) s[k] = s[k] + a0[k];
+      }
+      lb_st<T, W>(os + (i * U + u) * W, s);
     }
   }
 }
@@ -130,41 +209,6 @@ __global__ void __launch_bounds__(256) k_graph_segment_sum(const int32_t* __rest
 // are in include/lbhip.h).  The node-parallel kernels walk a row exactly as k_graph_segment_sum does (lb_row: the same caps and
 // clamps), the edge-parallel ones address a slot as k_graph_gather does.  A unit is W = 4 floats (one 16-byte access) or W = 1.
 // -ffp-contract=off holds for this file (build.py); the attend sum spells its roundings out with __fmul_rn / __fadd_rn anyway.
-typedef int32_t lb_i32x4 __attribute__((ext_vector_type(4)));
-
-template <int W>
-__device__ __forceinline__ void lb_ld(const float* p, float (&a)[W]) {
-  if constexpr (W == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    a[0] = t[0], a[1] = t[1], a[2] = t[2], a[3] = t[3];
-  } else {
-    a[0] = *p;
-  }
-}
-template <int W>
-__device__ __forceinline__ void lb_st(float* p, const float (&a)[W]) {
-  if constexpr (W == 4)
-    *reinterpret_cast<f32x4*>(p) = f32x4{a[0], a[1], a[2], a[3]};
-  else
-    *p = a[0];
-}
-template <int W>
-__device__ __forceinline__ void lb_ldi(const int32_t* p, int32_t (&a)[W]) {
-  if constexpr (W == 4) {
-    const lb_i32x4 t = *reinterpret_cast<const lb_i32x4*>(p);
-    a[0] = t[0], a[1] = t[1], a[2] = t[2], a[3] = t[3];
-  } else {
-    a[0] = *p;
-  }
-}
-template <int W>
-__device__ __forceinline__ void lb_sti(int32_t* p, const int32_t (&a)[W]) {
-  if constexpr (W == 4)
-    *reinterpret_cast<lb_i32x4*>(p) = lb_i32x4{a[0], a[1], a[2], a[3]};
-  else
-    *p = a[0];
-}
-
 // Row i of (seg_ptr, perm): positions p0 .. p1 - 1; edge(p) is the padded slot (flat over the batch) of position p, clamped
 // into the trajectory's own E_cap slots; first is the trajectory's slot 0, so edge(p) - first is the slot j within it.
 struct lb_row {
@@ -212,13 +256,11 @@ __global__ void __launch_bounds__(256) k_graph_degree(const int32_t* __restrict_
 
 // out[i][c] = the first real slot's value, replaced by each further slot in ascending slot order that beats it; win[i][c] = the
 // slot j (within the trajectory) that won, -1 and +0.0 for an empty row.
-template <bool VEC, bool MIN>
-__global__ void __launch_bounds__(256) k_graph_segment_max(const int32_t* __restrict__ row_ptr,
-                                                           const int32_t* __restrict__ seg_ptr,
-                                                           const int32_t* __restrict__ perm, const float* __restrict__ msg,
-                                                           float* __restrict__ out, int32_t* __restrict__ win, int64_t BN, int N,
-                                                           int e_cap, int E, int U, int lpr_shift) {
-  constexpr int W = VEC ? 4 : 1;
+template <typename T, int W, bool MIN>
+__device__ __forceinline__ void graph_segment_max_body(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                                       const int32_t* __restrict__ perm, const T* __restrict__ msg,
+                                                       T* __restrict__ out, int32_t* __restrict__ win, int64_t BN, int N,
+                                                       int e_cap, int E, int U, int lpr_shift) {
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
@@ -231,31 +273,41 @@ __global__ void __launch_bounds__(256) k_graph_segment_max(const int32_t* __rest
       int p = R.p0;
       if (p < R.p1) {
         const int64_t e = R.edge(p++);
-        lb_ld<W>(msg + (e * U + u) * W, s);
+        lb_ld<T, W>(msg + (e * U + u) * W, s);
 #pragma unroll
         for (int k = 0; k < W; ++k) w[k] = (int32_t)(e - R.first);
       }
 #pragma unroll 4
       for (; p < R.p1; ++p) {
         const int64_t e = R.edge(p);
-        lb_ld<W>(msg + (e * U + u) * W, a);
+        lb_ld<T, W>(msg + (e * U + u) * W, a);
 #pragma unroll
         for (int k = 0; k < W; ++k)
           if (lb_beats<MIN>(a[k], s[k])) s[k] = a[k], w[k] = (int32_t)(e - R.first);
       }
-      lb_st<W>(out + (i * U + u) * W, s);
+      lb_st<T, W>(out + (i * U + u) * W, s);
       lb_sti<W>(win + (i * U + u) * W, w);
     }
   }
 }
+#define LB_SEGMENT_MAX_KERNEL(name, MIN)                                                                                  \
+  template <typename T, int W>                                                                                            \
+  __global__ void __launch_bounds__(256) name(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,  \
+                                              const int32_t* __restrict__ perm, const T* __restrict__ msg,               \
+                                              T* __restrict__ out, int32_t* __restrict__ win, int64_t BN, int N,         \
+                                              int e_cap, int E, int U, int lpr_shift) {                                  \
+    graph_segment_max_body<T, W, MIN>(row_ptr, seg_ptr, perm, msg, out, win, BN, N, e_cap, E, U, lpr_shift);             \
+  }
+LB_SEGMENT_MAX_KERNEL(k_graph_segment_max, false)
+LB_SEGMENT_MAX_KERNEL(k_graph_segment_min, true)
+#undef LB_SEGMENT_MAX_KERNEL
 
 // d_msg[slot][c] = d_out[node][c] where the slot won column c of its node, +0.0 in every other real slot and in the pads.
-template <bool VEC>
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_segment_max_bwd(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
-                                                               const float* __restrict__ d_out, const int32_t* __restrict__ win,
-                                                               float* __restrict__ d_msg, int64_t BN, int N, int B, int e_cap,
+                                                               const T* __restrict__ d_out, const int32_t* __restrict__ win,
+                                                               T* __restrict__ d_msg, int64_t BN, int N, int B, int e_cap,
                                                                int E, int U, int lpr_shift) {
-  constexpr int W = VEC ? 4 : 1;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
@@ -270,24 +322,23 @@ __global__ void __launch_bounds__(256) k_graph_segment_max_bwd(const int32_t* __
 #pragma unroll
       for (int k = 0; k < W; ++k) d[k] = 0.f;
       if (real) {
-        lb_ld<W>(d_out + (node * U + u) * W, g);
+        lb_ld<T, W>(d_out + (node * U + u) * W, g);
         lb_ldi<W>(win + (node * U + u) * W, w);
 #pragma unroll
         for (int k = 0; k < W; ++k) d[k] = w[k] == j ? g[k] : 0.f;
       }
-      lb_st<W>(d_msg + (r * U + u) * W, d);
+      lb_st<T, W>(d_msg + (r * U + u) * W, d);
     }
   }
 }
 
 // y[slot][c] = expf(x[slot][c] - m) / s over the slots of node i: m the maximum as in k_graph_segment_max, s the ordered sum of
 // the exponentials.  The group that owns the node writes the node's slots; the pad slots were zeroed before the launch.
-template <bool VEC>
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_softmax(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                       const int32_t* __restrict__ perm, const float* __restrict__ x,
-                                                       float* __restrict__ y, int64_t BN, int N, int e_cap, int E, int U,
+                                                       const int32_t* __restrict__ perm, const T* __restrict__ x,
+                                                       T* __restrict__ y, int64_t BN, int N, int e_cap, int E, int U,
                                                        int lpr_shift) {
-  constexpr int W = VEC ? 4 : 1;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
@@ -295,43 +346,42 @@ __global__ void __launch_bounds__(256) k_graph_softmax(const int32_t* __restrict
     if (R.p0 >= R.p1) continue;
     for (int u = lane; u < U; u += lpr) {
       float m[W], s[W], a[W];
-      lb_ld<W>(x + (R.edge(R.p0) * U + u) * W, m);
+      lb_ld<T, W>(x + (R.edge(R.p0) * U + u) * W, m);
 #pragma unroll 4
       for (int p = R.p0 + 1; p < R.p1; ++p) {
-        lb_ld<W>(x + (R.edge(p) * U + u) * W, a);
+        lb_ld<T, W>(x + (R.edge(p) * U + u) * W, a);
 #pragma unroll
         for (int k = 0; k < W; ++k)
           if (lb_beats<false>(a[k], m[k])) m[k] = a[k];
       }
-      lb_ld<W>(x + (R.edge(R.p0) * U + u) * W, a);
+      lb_ld<T, W>(x + (R.edge(R.p0) * U + u) * W, a);
 #pragma unroll
       for (int k = 0; k < W; ++k) s[k] = expf(a[k] - m[k]);
 #pragma unroll 4
       for (int p = R.p0 + 1; p < R.p1; ++p) {
-        lb_ld<W>(x + (R.edge(p) * U + u) * W, a);
+        lb_ld<T, W>(x + (R.edge(p) * U + u) * W, a);
 #pragma unroll
         for (int k = 0; k < W; ++k) s[k] = __fadd_rn(s[k], expf(a[k] - m[k]));
       }
 #pragma unroll 4
       for (int p = R.p0; p < R.p1; ++p) {
         const int64_t o = (R.edge(p) * U + u) * W;
-        lb_ld<W>(x + o, a);
+        lb_ld<T, W>(x + o, a);
 #pragma unroll
         for (int k = 0; k < W; ++k) a[k] = expf(a[k] - m[k]) / s[k];
-        lb_st<W>(y + o, a);
+        lb_st<T, W>(y + o, a);
       }
     }
   }
 }
 
 // d_x[slot][c] = y (d_y - sum_k d_y[k] y[k]) over the slots of node i, the sum ordered; the pads were zeroed before the launch.
-template <bool VEC>
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_softmax_bwd(const int32_t* __restrict__ row_ptr,
                                                            const int32_t* __restrict__ seg_ptr,
-                                                           const int32_t* __restrict__ perm, const float* __restrict__ y,
-                                                           const float* __restrict__ d_y, float* __restrict__ d_x, int64_t BN,
+                                                           const int32_t* __restrict__ perm, const T* __restrict__ y,
+                                                           const T* __restrict__ d_y, T* __restrict__ d_x, int64_t BN,
                                                            int N, int e_cap, int E, int U, int lpr_shift) {
-  constexpr int W = VEC ? 4 : 1;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
@@ -341,27 +391,27 @@ __global__ void __launch_bounds__(256) k_graph_softmax_bwd(const int32_t* __rest
       float dot[W], a[W], g[W];
       {
         const int64_t o = (R.edge(R.p0) * U + u) * W;
-        lb_ld<W>(y + o, a);
-        lb_ld<W>(d_y + o, g);
+        lb_ld<T, W>(y + o, a);
+        lb_ld<T, W>(d_y + o, g);
 #pragma unroll
         for (int k = 0; k < W; ++k) dot[k] = __fmul_rn(g[k], a[k]);
       }
 #pragma unroll 4
       for (int p = R.p0 + 1; p < R.p1; ++p) {
         const int64_t o = (R.edge(p) * U + u) * W;
-        lb_ld<W>(y + o, a);
-        lb_ld<W>(d_y + o, g);
+        lb_ld<T, W>(y + o, a);
+        lb_ld<T, W>(d_y + o, g);
 #pragma unroll
         for (int k = 0; k < W; ++k) dot[k] = __fadd_rn(dot[k], __fmul_rn(g[k], a[k]));
       }
 #pragma unroll 4
       for (int p = R.p0; p < R.p1; ++p) {
         const int64_t o = (R.edge(p) * U + u) * W;
-        lb_ld<W>(y + o, a);
-        lb_ld<W>(d_y + o, g);
+        lb_ld<T, W>(y + o, a);
+        lb_ld<T, W>(d_y + o, g);
 #pragma unroll
         for (int k = 0; k < W; ++k) a[k] = __fmul_rn(a[k], g[k] - dot[k]);
-        lb_st<W>(d_x + o, a);
+        lb_st<T, W>(d_x + o, a);
       }
     }
   }
@@ -370,13 +420,12 @@ __global__ void __launch_bounds__(256) k_graph_softmax_bwd(const int32_t* __rest
 // out[i][h][:] = sum over the slots of node i of alpha[slot][h] v[slot][h][:], alpha = expf(l - m) / s as k_graph_softmax computes
 // it: the product rounded, the adds in ascending slot order from the first term.  A lane owns units of the H D row and runs the
 // max and the sum pass over its head's logits itself; the lane of a head's first unit stores that head's m and s.
-template <bool VEC>
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_attend(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                      const int32_t* __restrict__ perm, const float* __restrict__ logits,
-                                                      const float* __restrict__ values, float* __restrict__ out,
+                                                      const int32_t* __restrict__ perm, const T* __restrict__ logits,
+                                                      const T* __restrict__ values, T* __restrict__ out,
                                                       float* __restrict__ m_out, float* __restrict__ s_out, int64_t BN, int N,
                                                       int e_cap, int E, int H, int D, int U, int lpr_shift) {
-  constexpr int W = VEC ? 4 : 1;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
@@ -391,33 +440,33 @@ __global__ void __launch_bounds__(256) k_graph_attend(const int32_t* __restrict_
       if (R.p0 < R.p1) {
         if (h != hc) {
           hc = h;
-          m = logits[R.edge(R.p0) * H + h];
+          m = lb_ld1<T>(logits + R.edge(R.p0) * H + h);
 #pragma unroll 4
           for (int p = R.p0 + 1; p < R.p1; ++p) {
-            const float a = logits[R.edge(p) * H + h];
+            const float a = lb_ld1<T>(logits + R.edge(p) * H + h);
             if (lb_beats<false>(a, m)) m = a;
           }
-          s = expf(logits[R.edge(R.p0) * H + h] - m);
+          s = expf(lb_ld1<T>(logits + R.edge(R.p0) * H + h) - m);
 #pragma unroll 4
-          for (int p = R.p0 + 1; p < R.p1; ++p) s = __fadd_rn(s, expf(logits[R.edge(p) * H + h] - m));
+          for (int p = R.p0 + 1; p < R.p1; ++p) s = __fadd_rn(s, expf(lb_ld1<T>(logits + R.edge(p) * H + h) - m));
         }
         {
           const int64_t e = R.edge(R.p0);
-          const float al = expf(logits[e * H + h] - m) / s;
-          lb_ld<W>(values + (e * U + u) * W, v);
+          const float al = expf(lb_ld1<T>(logits + e * H + h) - m) / s;
+          lb_ld<T, W>(values + (e * U + u) * W, v);
 #pragma unroll
           for (int k = 0; k < W; ++k) acc[k] = __fmul_rn(al, v[k]);
         }
 #pragma unroll 4
         for (int p = R.p0 + 1; p < R.p1; ++p) {
           const int64_t e = R.edge(p);
-          const float al = expf(logits[e * H + h] - m) / s;
-          lb_ld<W>(values + (e * U + u) * W, v);
+          const float al = expf(lb_ld1<T>(logits + e * H + h) - m) / s;
+          lb_ld<T, W>(values + (e * U + u) * W, v);
 #pragma unroll
           for (int k = 0; k < W; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(al, v[k]));
         }
       }
-      lb_st<W>(out + (i * U + u) * W, acc);
+      lb_st<T, W>(out + (i * U + u) * W, acc);
       if ((u * W) % D == 0) m_out[i * H + h] = m, s_out[i * H + h] = s;
     }
   }
@@ -425,13 +474,12 @@ __global__ void __launch_bounds__(256) k_graph_attend(const int32_t* __restrict_
 
 // d_values[slot][h][:] = alpha[slot][h] d_out[node][h][:] (one multiplication), +0.0 in the pads; alpha recomputed from the
 // saved m and s of the node.
-template <bool VEC>
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_attend_dvalues(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
-                                                              const float* __restrict__ logits, const float* __restrict__ m_in,
-                                                              const float* __restrict__ s_in, const float* __restrict__ d_out,
-                                                              float* __restrict__ d_values, int64_t BN, int N, int B, int e_cap,
+                                                              const T* __restrict__ logits, const float* __restrict__ m_in,
+                                                              const float* __restrict__ s_in, const T* __restrict__ d_out,
+                                                              T* __restrict__ d_values, int64_t BN, int N, int B, int e_cap,
                                                               int E, int H, int D, int U, int lpr_shift) {
-  constexpr int W = VEC ? 4 : 1;
   const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
   const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
   for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
@@ -446,23 +494,24 @@ __global__ void __launch_bounds__(256) k_graph_attend_dvalues(const int32_t* __r
       for (int k = 0; k < W; ++k) d[k] = 0.f;
       if (real) {
         const int h = (u * W) / D;
-        const float al = expf(logits[r * H + h] - m_in[node * H + h]) / s_in[node * H + h];
-        lb_ld<W>(d_out + (node * U + u) * W, g);
+        const float al = expf(lb_ld1<T>(logits + r * H + h) - m_in[node * H + h]) / s_in[node * H + h];
+        lb_ld<T, W>(d_out + (node * U + u) * W, g);
 #pragma unroll
         for (int k = 0; k < W; ++k) d[k] = __fmul_rn(al, g[k]);
       }
-      lb_st<W>(d_values + (r * U + u) * W, d);
+      lb_st<T, W>(d_values + (r * U + u) * W, d);
     }
   }
 }
 
-// t[slot][h] = sum_d d_out[node][h][d] v[slot][h][d], one lane per (slot, head), d ascending; +0.0 in the pads.
-template <bool VEC>
+// t[slot][h] = sum_d d_out[node][h][d] v[slot][h][d], one lane per (slot, head), d ascending; +0.0 in the pads.  t is fp32:
+// for float tensors it IS the d_logits buffer; for bf16 ones it is the engine's buffer, and every slot of d_logits gets +0.0
+// here (k_graph_attend_dlogits then writes the real slots).
+template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_attend_t(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
-                                                        const float* __restrict__ values, const float* __restrict__ d_out,
-                                                        float* __restrict__ t, int64_t BN, int N, int B, int e_cap, int E, int H,
-                                                        int D) {
-  constexpr int W = VEC ? 4 : 1;
+                                                        const T* __restrict__ values, const T* __restrict__ d_out,
+                                                        float* __restrict__ t, T* d_logits, int64_t BN, int N, int B,
+                                                        int e_cap, int E, int H, int D) {
   const int64_t total = (int64_t)B * e_cap * H, stride = (int64_t)gridDim.x * 256;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
     const int64_t r = q / H;
@@ -474,13 +523,13 @@ __global__ void __launch_bounds__(256) k_graph_attend_t(const int32_t* __restric
     if (real) {
       int64_t node = idx[base + j];
       node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
-      const float* __restrict__ vp = values + (r * H + h) * D;
-      const float* __restrict__ gp = d_out + (node * H + h) * D;
+      const T* __restrict__ vp = values + (r * H + h) * D;
+      const T* __restrict__ gp = d_out + (node * H + h) * D;
       float v[W], g[W];
       bool first = true;
       for (int d = 0; d < D; d += W) {
-        lb_ld<W>(vp + d, v);
-        lb_ld<W>(gp + d, g);
+        lb_ld<T, W>(vp + d, v);
+        lb_ld<T, W>(gp + d, g);
 #pragma unroll
         for (int k = 0; k < W; ++k) {
           const float pr = __fmul_rn(g[k], v[k]);
@@ -490,16 +539,20 @@ __global__ void __launch_bounds__(256) k_graph_attend_t(const int32_t* __restric
       }
     }
     t[q] = acc;
+    if constexpr (sizeof(T) != 4) d_logits[q] = 0;
   }
 }
 
-// In place on t (B E_cap, H): d_logits[slot][h] = alpha (t[slot][h] - sum_k alpha[k] t[k][h]) over the slots of node i, the sum
-// ordered; one lane per (node, head).  The pad slots hold the +0.0 k_graph_attend_t wrote.
+// d_logits[slot][h] = alpha (t[slot][h] - sum_k alpha[k] t[k][h]) over the slots of node i, t (B E_cap, H) fp32, the sum ordered;
+// one lane per (node, head).  In place on t for float tensors (d_logits == t); rounded once into d_logits for bf16 ones.  The
+// pad slots hold the +0.0 k_graph_attend_t wrote.
+template <typename T>
 __global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __restrict__ row_ptr,
                                                               const int32_t* __restrict__ seg_ptr,
-                                                              const int32_t* __restrict__ perm, const float* __restrict__ logits,
+                                                              const int32_t* __restrict__ perm, const T* __restrict__ logits,
                                                               const float* __restrict__ m_in, const float* __restrict__ s_in,
-                                                              float* t, int64_t BN, int N, int e_cap, int E, int H) {
+                                                              const float* t, T* d_logits, int64_t BN, int N, int e_cap,
+                                                              int E, int H) {
   const int64_t total = BN * H, stride = (int64_t)gridDim.x * 256;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
     const int64_t i = q / H;
@@ -510,15 +563,15 @@ __global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __r
     float dot;
     {
       const int64_t o = R.edge(R.p0) * H + h;
-      dot = __fmul_rn(expf(logits[o] - m) / s, t[o]);
+      dot = __fmul_rn(expf(lb_ld1<T>(logits + o) - m) / s, t[o]);
     }
     for (int p = R.p0 + 1; p < R.p1; ++p) {
       const int64_t o = R.edge(p) * H + h;
-      dot = __fadd_rn(dot, __fmul_rn(expf(logits[o] - m) / s, t[o]));
+      dot = __fadd_rn(dot, __fmul_rn(expf(lb_ld1<T>(logits + o) - m) / s, t[o]));
     }
     for (int p = R.p0; p < R.p1; ++p) {
       const int64_t o = R.edge(p) * H + h;
-      t[o] = __fmul_rn(expf(logits[o] - m) / s, t[o] - dot);
+      lb_st1<T>(d_logits + o, __fmul_rn(expf(lb_ld1<T>(logits + o) - m) / s, t[o] - dot));
     }
   }
 }
@@ -699,179 +752,270 @@ static int graph_lpr_shift(int U) {
   while (sh < 6 && (1 << sh) < U) ++sh;
   return sh;
 }
-static bool graph_vec(const void* a, const void* b, int C) {
-  return C % 4 == 0 && ((uintptr_t)a | (uintptr_t)b) % 16 == 0;
-}
 static unsigned graph_blocks(int64_t rows, int lpr_shift) {
   const int64_t per_block = 256 >> lpr_shift;
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + per_block - 1) / per_block, 2048));
 }
-
-extern "C" int lb_graph_gather(lb_engine* e, int32_t role, const float* x_dev, float* out_dev, int32_t C) {
-  if (!e || !x_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if ((role != 0 && role != 1) || C < 1) return lb_fail(LB_ERR_ARG, "lb_graph_gather: role %d (0 receivers, 1 senders), C %d", role, C);
-  LB_TRY(graph_begin(e, "lb_graph_gather"));
-  const int32_t* idx = role ? e->senders : e->receivers;
-  const bool vec = graph_vec(x_dev, out_dev, C);
-  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
-  const unsigned blocks = graph_blocks((int64_t)e->g.B * e->e_cap, sh);
-  if (vec)
-    hipLaunchKernelGGL(k_graph_gather<true>, dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, idx, x_dev, out_dev, e->BN,
-                       e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, sh);
-  else
-    hipLaunchKernelGGL(k_graph_gather<false>, dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, idx, x_dev, out_dev, e->BN,
-                       e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, sh);
-  LB_HIP(hipGetLastError());
-  return LB_OK;
-}
-
-extern "C" int lb_graph_segment_sum(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t C) {
-  if (!e || !msg_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if ((role != 0 && role != 1) || C < 1)
-    return lb_fail(LB_ERR_ARG, "lb_graph_segment_sum: role %d (0 receivers, 1 senders), C %d", role, C);
-  LB_TRY(graph_begin(e, "lb_graph_segment_sum"));
-  if (role) LB_TRY(graph_sender_view(e));
-  const int32_t* seg = role ? e->snd_ptr : e->row_ptr;
-  const int32_t* perm = role ? e->snd_perm : nullptr;
-  const bool vec = graph_vec(msg_dev, out_dev, C);
-  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
-  const unsigned blocks = graph_blocks(e->BN, sh);
-  if (vec)
-    hipLaunchKernelGGL(k_graph_segment_sum<true>, dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, seg, perm, msg_dev, out_dev,
-                       e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
-  else
-    hipLaunchKernelGGL(k_graph_segment_sum<false>, dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, seg, perm, msg_dev, out_dev,
-                       e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
-  LB_HIP(hipGetLastError());
-  return LB_OK;
-}
-
-extern "C" int32_t lb_graph_sender_sorts(lb_engine* e) { return e ? e->snd_sorts : -1; }
-
-// ---- the attention ops' entries.  graph_entry: the checks every entry makes, the list's status, the sender view for role 1.
+static unsigned graph_blocks1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65536)); }
 static bool graph_aligned(std::initializer_list<const void*> ptrs) {
   uintptr_t a = 0;
   for (const void* p : ptrs) a |= (uintptr_t)p;
   return a % 16 == 0;
 }
-static unsigned graph_blocks1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65536)); }
-static int graph_entry(lb_engine* e, const char* entry, int32_t role, bool ptrs_ok, int32_t c0, int32_t c1) {
+static size_t graph_esize(int32_t dtype) { return dtype == LB_DTYPE_BF16 ? 2 : 4; }
+// Elements of one access for rows whose units must divide `span` columns (C; D for attend, where a unit lies in one head):
+// 16 bytes - 4 floats, 8 bf16 - when span allows it and every pointer is 16-byte aligned; for bf16 and `half_units` (attend)
+// 8 bytes when span % 4 == 0; one element otherwise.
+static int graph_width(int32_t dtype, int span, bool half_units, std::initializer_list<const void*> ptrs) {
+  if (!graph_aligned(ptrs)) return 1;
+  if (dtype == LB_DTYPE_F32) return span % 4 == 0 ? 4 : 1;
+  return span % 8 == 0 ? 8 : (half_units && span % 4 == 0 ? 4 : 1);
+}
+// The checks every entry makes, the list's status, the sender view for role 1 (`view`: the op walks rows of the role).
+static int graph_entry(lb_engine* e, const char* entry, int32_t role, int32_t dtype, bool ptrs_ok, int32_t c0, int32_t c1,
+                       bool view = true) {
   if (!e || !ptrs_ok) return lb_fail(LB_ERR_ARG, "null argument");
   if ((role != 0 && role != 1) || c0 < 1 || c1 < 1)
     return lb_fail(LB_ERR_ARG, "%s: role %d (0 receivers, 1 senders), columns %d x %d", entry, role, c0, c1);
+  if (dtype != LB_DTYPE_F32 && dtype != LB_DTYPE_BF16)
+    return lb_fail(LB_ERR_ARG, "%s: dtype %d (0 float32, 1 bfloat16)", entry, dtype);
   LB_TRY(graph_begin(e, entry));
-  if (role) LB_TRY(graph_sender_view(e));
+  if (role && view) LB_TRY(graph_sender_view(e));
   return LB_OK;
 }
-#define GRAPH_LAUNCH(kernel, blocks, ...)                                                    \
-  do {                                                                                       \
-    if (vec)                                                                                 \
-      hipLaunchKernelGGL(kernel<true>, dim3(blocks), dim3(256), 0, e->stream, __VA_ARGS__);  \
-    else                                                                                     \
-      hipLaunchKernelGGL(kernel<false>, dim3(blocks), dim3(256), 0, e->stream, __VA_ARGS__); \
-    LB_HIP(hipGetLastError());                                                               \
+// kernel<GT, W> for the call's dtype and W (both in scope); the arguments name the element type as GT.  GRAPH_LAUNCH_HD also
+// has the 8-byte bf16 units of attend.
+#define GRAPH_LAUNCH_ONE(kernel, T_, W_, blocks, ...)                                         \
+  {                                                                                           \
+    typedef T_ GT;                                                                            \
+    hipLaunchKernelGGL((kernel<GT, W_>), dim3(blocks), dim3(256), 0, e->stream, __VA_ARGS__); \
+  }
+#define GRAPH_LAUNCH_ANY(kernel, HALF, blocks, ...)                                     \
+  do {                                                                                  \
+    if (dtype == LB_DTYPE_F32 && W == 4)                                                \
+      GRAPH_LAUNCH_ONE(kernel, float, 4, blocks, __VA_ARGS__)                           \
+    else if (dtype == LB_DTYPE_F32)                                                     \
+      GRAPH_LAUNCH_ONE(kernel, float, 1, blocks, __VA_ARGS__)                           \
+    else if (W == 8)                                                                    \
+      GRAPH_LAUNCH_ONE(kernel, lb_bf16, 8, blocks, __VA_ARGS__)                         \
+    HALF(kernel, blocks, __VA_ARGS__)                                                   \
+    else GRAPH_LAUNCH_ONE(kernel, lb_bf16, 1, blocks, __VA_ARGS__)                      \
+    LB_HIP(hipGetLastError());                                                          \
   } while (0)
+#define GRAPH_NO_HALF(kernel, blocks, ...)
+#define GRAPH_HALF(kernel, blocks, ...) else if (W == 4) GRAPH_LAUNCH_ONE(kernel, lb_bf16, 4, blocks, __VA_ARGS__)
+#define GRAPH_LAUNCH(kernel, blocks, ...) GRAPH_LAUNCH_ANY(kernel, GRAPH_NO_HALF, blocks, __VA_ARGS__)
+#define GRAPH_LAUNCH_HD(kernel, blocks, ...) GRAPH_LAUNCH_ANY(kernel, GRAPH_HALF, blocks, __VA_ARGS__)
 
+static int graph_gather(lb_engine* e, const char* entry, int32_t role, const void* x, void* out, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, x && out, C, 1, false));
+  const int32_t* idx = role ? e->senders : e->receivers;
+  // a bit copy: 16-byte units (4 floats, 8 bf16) when the row is made of them and the pointers are aligned, elements otherwise
+  const int W = graph_width(dtype, C, false, {x, out});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  const unsigned blocks = graph_blocks((int64_t)e->g.B * e->e_cap, sh);
+#define GRAPH_GATHER(T_)                                                                                                 \
+  hipLaunchKernelGGL(k_graph_gather<T_>, dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, idx, x, out, e->BN, e->g.N, \
+                     e->g.B, e->e_cap, (int)e->graph_E, U, sh)
+  if (W > 1)
+    GRAPH_GATHER(f32x4);
+  else if (dtype == LB_DTYPE_F32)
+    GRAPH_GATHER(float);
+  else
+    GRAPH_GATHER(lb_bf16);
+#undef GRAPH_GATHER
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+extern "C" int lb_graph_gather_t(lb_engine* e, int32_t role, const void* x_dev, void* out_dev, int32_t C, int32_t dtype) {
+  return graph_gather(e, "lb_graph_gather_t", role, x_dev, out_dev, C, dtype);
+}
+extern "C" int lb_graph_gather(lb_engine* e, int32_t role, const float* x_dev, float* out_dev, int32_t C) {
+  return graph_gather(e, "lb_graph_gather", role, x_dev, out_dev, C, LB_DTYPE_F32);
+}
+
+static int graph_segment_sum(lb_engine* e, const char* entry, int32_t role, const void* msg, void* out, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, msg && out, C, 1));
+  const int W = graph_width(dtype, C, false, {msg, out});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  GRAPH_LAUNCH(k_graph_segment_sum, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+               role ? e->snd_perm : nullptr, (const GT*)msg, (GT*)out, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+extern "C" int lb_graph_segment_sum_t(lb_engine* e, int32_t role, const void* msg_dev, void* out_dev, int32_t C, int32_t dtype) {
+  return graph_segment_sum(e, "lb_graph_segment_sum_t", role, msg_dev, out_dev, C, dtype);
+}
+extern "C" int lb_graph_segment_sum(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t C) {
+  return graph_segment_sum(e, "lb_graph_segment_sum", role, msg_dev, out_dev, C, LB_DTYPE_F32);
+}
+
+extern "C" int32_t lb_graph_sender_sorts(lb_engine* e) { return e ? e->snd_sorts : -1; }
+
+// ---- the attention ops' entries
 extern "C" int lb_graph_degree(lb_engine* e, int32_t role, int32_t* out_dev) {
-  LB_TRY(graph_entry(e, "lb_graph_degree", role, out_dev != nullptr, 1, 1));
+  LB_TRY(graph_entry(e, "lb_graph_degree", role, LB_DTYPE_F32, out_dev != nullptr, 1, 1));
   hipLaunchKernelGGL(k_graph_degree, GRID1(e->BN), 0, e->stream, e->row_ptr, role ? e->snd_ptr : e->row_ptr, out_dev, e->BN,
                      e->g.N, e->e_cap, (int)e->graph_E);
   LB_HIP(hipGetLastError());
   return LB_OK;
 }
 
-template <bool MIN>
-static int graph_segment_max(lb_engine* e, const char* entry, int32_t role, const float* msg, float* out, int32_t* win, int32_t C) {
-  LB_TRY(graph_entry(e, entry, role, msg && out && win, C, 1));
+static int graph_segment_max(lb_engine* e, const char* entry, bool minimum, int32_t role, const void* msg, void* out, int32_t* win,
+                             int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, msg && out && win, C, 1));
   const int32_t* seg = role ? e->snd_ptr : e->row_ptr;
   const int32_t* perm = role ? e->snd_perm : nullptr;
-  const bool vec = C % 4 == 0 && graph_aligned({msg, out, win});
-  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
+  const int W = graph_width(dtype, C, false, {msg, out, win});
+  const int U = C / W, sh = graph_lpr_shift(U);
   const unsigned blocks = graph_blocks(e->BN, sh);
-  if (vec)
-    hipLaunchKernelGGL((k_graph_segment_max<true, MIN>), dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, seg, perm, msg, out,
-                       win, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  if (minimum)
+    GRAPH_LAUNCH(k_graph_segment_min, blocks, e->row_ptr, seg, perm, (const GT*)msg, (GT*)out, win, e->BN, e->g.N, e->e_cap,
+                 (int)e->graph_E, U, sh);
   else
-    hipLaunchKernelGGL((k_graph_segment_max<false, MIN>), dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, seg, perm, msg, out,
-                       win, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+    GRAPH_LAUNCH(k_graph_segment_max, blocks, e->row_ptr, seg, perm, (const GT*)msg, (GT*)out, win, e->BN, e->g.N, e->e_cap,
+                 (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+extern "C" int lb_graph_segment_max_t(lb_engine* e, int32_t role, const void* msg_dev, void* out_dev, int32_t* win_dev, int32_t C,
+                                      int32_t dtype) {
+  return graph_segment_max(e, "lb_graph_segment_max_t", false, role, msg_dev, out_dev, win_dev, C, dtype);
+}
+extern "C" int lb_graph_segment_min_t(lb_engine* e, int32_t role, const void* msg_dev, void* out_dev, int32_t* win_dev, int32_t C,
+                                      int32_t dtype) {
+  return graph_segment_max(e, "lb_graph_segment_min_t", true, role, msg_dev, out_dev, win_dev, C, dtype);
+}
+extern "C" int lb_graph_segment_max(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t* win_dev, int32_t C) {
+  return graph_segment_max(e, "lb_graph_segment_max", false, role, msg_dev, out_dev, win_dev, C, LB_DTYPE_F32);
+}
+extern "C" int lb_graph_segment_min(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t* win_dev, int32_t C) {
+  return graph_segment_max(e, "lb_graph_segment_min", true, role, msg_dev, out_dev, win_dev, C, LB_DTYPE_F32);
+}
+
+static int graph_segment_max_backward(lb_engine* e, const char* entry, int32_t role, const void* d_out, const int32_t* win,
+                                      void* d_msg, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, d_out && win && d_msg, C, 1));
+  const int32_t* idx = role ? e->senders : e->receivers;
+  const int W = graph_width(dtype, C, false, {d_out, win, d_msg});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  GRAPH_LAUNCH(k_graph_segment_max_bwd, graph_blocks((int64_t)e->g.B * e->e_cap, sh), e->row_ptr, idx, (const GT*)d_out, win,
+               (GT*)d_msg, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+extern "C" int lb_graph_segment_max_backward_t(lb_engine* e, int32_t role, const void* d_out_dev, const int32_t* win_dev,
+                                               void* d_msg_dev, int32_t C, int32_t dtype) {
+  return graph_segment_max_backward(e, "lb_graph_segment_max_backward_t", role, d_out_dev, win_dev, d_msg_dev, C, dtype);
+}
+extern "C" int lb_graph_segment_max_backward(lb_engine* e, int32_t role, const float* d_out_dev, const int32_t* win_dev,
+                                             float* d_msg_dev, int32_t C) {
+  return graph_segment_max_backward(e, "lb_graph_segment_max_backward", role, d_out_dev, win_dev, d_msg_dev, C, LB_DTYPE_F32);
+}
+
+static int graph_segment_softmax(lb_engine* e, const char* entry, int32_t role, const void* logits, void* out, int32_t C,
+                                 int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, logits && out, C, 1));
+  const int W = graph_width(dtype, C, false, {logits, out});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  LB_HIP(hipMemsetAsync(out, 0, graph_esize(dtype) * (size_t)e->g.B * e->e_cap * C, e->stream));   // the pad slots: +0.0
+  GRAPH_LAUNCH(k_graph_softmax, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+               role ? e->snd_perm : nullptr, (const GT*)logits, (GT*)out, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
+}
+extern "C" int lb_graph_segment_softmax_t(lb_engine* e, int32_t role, const void* logits_dev, void* out_dev, int32_t C,
+                                          int32_t dtype) {
+  return graph_segment_softmax(e, "lb_graph_segment_softmax_t", role, logits_dev, out_dev, C, dtype);
+}
+extern "C" int lb_graph_segment_softmax(lb_engine* e, int32_t role, const float* logits_dev, float* out_dev, int32_t C) {
+  return graph_segment_softmax(e, "lb_graph_segment_softmax", role, logits_dev, out_dev, C, LB_DTYPE_F32);
+}
+
+static int graph_segment_softmax_backward(lb_engine* e, const char* entry, int32_t role, const void* y, const void* d_y, void* d_x,
+                                          int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, y && d_y && d_x, C, 1));
+  const int W = graph_width(dtype, C, false, {y, d_y, d_x});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  LB_HIP(hipMemsetAsync(d_x, 0, graph_esize(dtype) * (size_t)e->g.B * e->e_cap * C, e->stream));
+  GRAPH_LAUNCH(k_graph_softmax_bwd, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+               role ? e->snd_perm : nullptr, (const GT*)y, (const GT*)d_y, (GT*)d_x, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U,
+               sh);
+  return LB_OK;
+}
+extern "C" int lb_graph_segment_softmax_backward_t(lb_engine* e, int32_t role, const void* y_dev, const void* d_y_dev,
+                                                   void* d_x_dev, int32_t C, int32_t dtype) {
+  return graph_segment_softmax_backward(e, "lb_graph_segment_softmax_backward_t", role, y_dev, d_y_dev, d_x_dev, C, dtype);
+}
+extern "C" int lb_graph_segment_softmax_backward(lb_engine* e, int32_t role, const float* y_dev, const float* d_y_dev,
+                                                 float* d_x_dev, int32_t C) {
+  return graph_segment_softmax_backward(e, "lb_graph_segment_softmax_backward", role, y_dev, d_y_dev, d_x_dev, C, LB_DTYPE_F32);
+}
+
+static int graph_attend(lb_engine* e, const char* entry, int32_t role, const void* logits, const void* values, void* out,
+                        float* m, float* s, int32_t H, int32_t D, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, logits && values && out && m && s, H, D));
+  if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "%s: H %d x D %d columns", entry, H, D);
+  const int W = graph_width(dtype, D, true, {values, out});
+  const int U = H * D / W, sh = graph_lpr_shift(U);
+  GRAPH_LAUNCH_HD(k_graph_attend, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
+                  role ? e->snd_perm : nullptr, (const GT*)logits, (const GT*)values, (GT*)out, m, s, e->BN, e->g.N, e->e_cap,
+                  (int)e->graph_E, H, D, U, sh);
+  return LB_OK;
+}
+extern "C" int lb_graph_attend_t(lb_engine* e, int32_t role, const void* logits_dev, const void* values_dev, void* out_dev,
+                                 float* m_dev, float* s_dev, int32_t H, int32_t D, int32_t dtype) {
+  return graph_attend(e, "lb_graph_attend_t", role, logits_dev, values_dev, out_dev, m_dev, s_dev, H, D, dtype);
+}
+extern "C" int lb_graph_attend(lb_engine* e, int32_t role, const float* logits_dev, const float* values_dev, float* out_dev,
+                               float* m_dev, float* s_dev, int32_t H, int32_t D) {
+  return graph_attend(e, "lb_graph_attend", role, logits_dev, values_dev, out_dev, m_dev, s_dev, H, D, LB_DTYPE_F32);
+}
+
+static int graph_attend_backward(lb_engine* e, const char* entry, int32_t role, const void* logits, const void* values,
+                                 const float* m, const float* s, const void* d_out, void* d_logits, void* d_values, int32_t H,
+                                 int32_t D, int32_t dtype) {
+  LB_TRY(graph_entry(e, entry, role, dtype, logits && values && m && s && d_out && d_logits && d_values, H, D));
+  if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "%s: H %d x D %d columns", entry, H, D);
+  const int32_t* idx = role ? e->senders : e->receivers;
+  const int64_t slots = (int64_t)e->g.B * e->e_cap;
+  // t (slots, H) fp32: the d_logits buffer itself for float tensors, the engine's buffer for bf16 ones (t is never rounded)
+  float* t = (float*)d_logits;
+  if (dtype != LB_DTYPE_F32) {
+    if (slots * H > e->graph_t_cap)
+      LB_TRY(lb_regrow(e->stream, &e->graph_t_cap, slots * H + slots * H / 8, [&](int64_t n) { return e->mem.get(&e->graph_t, (size_t)n); }));
+    t = e->graph_t;
+  }
+  {
+    const int W = graph_width(dtype, D, true, {d_out, d_values});
+    const int U = H * D / W, sh = graph_lpr_shift(U);
+    GRAPH_LAUNCH_HD(k_graph_attend_dvalues, graph_blocks(slots, sh), e->row_ptr, idx, (const GT*)logits, m, s, (const GT*)d_out,
+                    (GT*)d_values, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, H, D, U, sh);
+  }
+  {
+    const int W = graph_width(dtype, D, true, {values, d_out});
+    GRAPH_LAUNCH_HD(k_graph_attend_t, graph_blocks1(slots * H), e->row_ptr, idx, (const GT*)values, (const GT*)d_out, t,
+                    (GT*)d_logits, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, H, D);
+  }
+#define GRAPH_DLOGITS(T_)                                                                                                    \
+  hipLaunchKernelGGL(k_graph_attend_dlogits<T_>, dim3(graph_blocks1(e->BN * H)), dim3(256), 0, e->stream, e->row_ptr,      \
+                     role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, (const T_*)logits, m, s, t, (T_*)d_logits, \
+                     e->BN, e->g.N, e->e_cap, (int)e->graph_E, H)
+  if (dtype == LB_DTYPE_F32)
+    GRAPH_DLOGITS(float);
+  else
+    GRAPH_DLOGITS(lb_bf16);
+#undef GRAPH_DLOGITS
   LB_HIP(hipGetLastError());
   return LB_OK;
 }
-extern "C" int lb_graph_segment_max(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t* win_dev, int32_t C) {
-  return graph_segment_max<false>(e, "lb_graph_segment_max", role, msg_dev, out_dev, win_dev, C);
+extern "C" int lb_graph_attend_backward_t(lb_engine* e, int32_t role, const void* logits_dev, const void* values_dev,
+                                          const float* m_dev, const float* s_dev, const void* d_out_dev, void* d_logits_dev,
+                                          void* d_values_dev, int32_t H, int32_t D, int32_t dtype) {
+  return graph_attend_backward(e, "lb_graph_attend_backward_t", role, logits_dev, values_dev, m_dev, s_dev, d_out_dev,
+                               d_logits_dev, d_values_dev, H, D, dtype);
 }
-extern "C" int lb_graph_segment_min(lb_engine* e, int32_t role, const float* msg_dev, float* out_dev, int32_t* win_dev, int32_t C) {
-  return graph_segment_max<true>(e, "lb_graph_segment_min", role, msg_dev, out_dev, win_dev, C);
-}
-
-extern "C" int lb_graph_segment_max_backward(lb_engine* e, int32_t role, const float* d_out_dev, const int32_t* win_dev,
-                                             float* d_msg_dev, int32_t C) {
-  LB_TRY(graph_entry(e, "lb_graph_segment_max_backward", role, d_out_dev && win_dev && d_msg_dev, C, 1));
-  const int32_t* idx = role ? e->senders : e->receivers;
-  const bool vec = C % 4 == 0 && graph_aligned({d_out_dev, win_dev, d_msg_dev});
-  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
-  GRAPH_LAUNCH(k_graph_segment_max_bwd, graph_blocks((int64_t)e->g.B * e->e_cap, sh), e->row_ptr, idx, d_out_dev, win_dev,
-               d_msg_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
-}
-
-extern "C" int lb_graph_segment_softmax(lb_engine* e, int32_t role, const float* logits_dev, float* out_dev, int32_t C) {
-  LB_TRY(graph_entry(e, "lb_graph_segment_softmax", role, logits_dev && out_dev, C, 1));
-  const bool vec = C % 4 == 0 && graph_aligned({logits_dev, out_dev});
-  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
-  LB_HIP(hipMemsetAsync(out_dev, 0, sizeof(float) * (size_t)e->g.B * e->e_cap * C, e->stream));   // the pad slots: +0.0
-  GRAPH_LAUNCH(k_graph_softmax, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-               role ? e->snd_perm : nullptr, logits_dev, out_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
-}
-
-extern "C" int lb_graph_segment_softmax_backward(lb_engine* e, int32_t role, const float* y_dev, const float* d_y_dev,
-                                                 float* d_x_dev, int32_t C) {
-  LB_TRY(graph_entry(e, "lb_graph_segment_softmax_backward", role, y_dev && d_y_dev && d_x_dev, C, 1));
-  const bool vec = C % 4 == 0 && graph_aligned({y_dev, d_y_dev, d_x_dev});
-  const int U = vec ? C / 4 : C, sh = graph_lpr_shift(U);
-  LB_HIP(hipMemsetAsync(d_x_dev, 0, sizeof(float) * (size_t)e->g.B * e->e_cap * C, e->stream));
-  GRAPH_LAUNCH(k_graph_softmax_bwd, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-               role ? e->snd_perm : nullptr, y_dev, d_y_dev, d_x_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
-}
-
-extern "C" int lb_graph_attend(lb_engine* e, int32_t role, const float* logits_dev, const float* values_dev, float* out_dev,
-                               float* m_dev, float* s_dev, int32_t H, int32_t D) {
-  LB_TRY(graph_entry(e, "lb_graph_attend", role, logits_dev && values_dev && out_dev && m_dev && s_dev, H, D));
-  if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_attend: H %d x D %d columns", H, D);
-  const bool vec = D % 4 == 0 && graph_aligned({values_dev, out_dev});
-  const int U = vec ? H * D / 4 : H * D, sh = graph_lpr_shift(U);
-  GRAPH_LAUNCH(k_graph_attend, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-               role ? e->snd_perm : nullptr, logits_dev, values_dev, out_dev, m_dev, s_dev, e->BN, e->g.N, e->e_cap,
-               (int)e->graph_E, H, D, U, sh);
-  return LB_OK;
-}
-
 extern "C" int lb_graph_attend_backward(lb_engine* e, int32_t role, const float* logits_dev, const float* values_dev,
                                         const float* m_dev, const float* s_dev, const float* d_out_dev, float* d_logits_dev,
                                         float* d_values_dev, int32_t H, int32_t D) {
-  LB_TRY(graph_entry(e, "lb_graph_attend_backward", role,
-                     logits_dev && values_dev && m_dev && s_dev && d_out_dev && d_logits_dev && d_values_dev, H, D));
-  if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_attend_backward: H %d x D %d columns", H, D);
-  const int32_t* idx = role ? e->senders : e->receivers;
-  const int64_t slots = (int64_t)e->g.B * e->e_cap;
-  {
-    const bool vec = D % 4 == 0 && graph_aligned({d_out_dev, d_values_dev});
-    const int U = vec ? H * D / 4 : H * D, sh = graph_lpr_shift(U);
-    GRAPH_LAUNCH(k_graph_attend_dvalues, graph_blocks(slots, sh), e->row_ptr, idx, logits_dev, m_dev, s_dev, d_out_dev,
-                 d_values_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, H, D, U, sh);
-  }
-  {
-    const bool vec = D % 4 == 0 && graph_aligned({values_dev, d_out_dev});
-    GRAPH_LAUNCH(k_graph_attend_t, graph_blocks1(slots * H), e->row_ptr, idx, values_dev, d_out_dev, d_logits_dev, e->BN, e->g.N,
-                 e->g.B, e->e_cap, (int)e->graph_E, H, D);
-  }
-  hipLaunchKernelGGL(k_graph_attend_dlogits, dim3(graph_blocks1(e->BN * H)), dim3(256), 0, e->stream, e->row_ptr,
-                     role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, logits_dev, m_dev, s_dev, d_logits_dev, e->BN,
-                     e->g.N, e->e_cap, (int)e->graph_E, H);
-  LB_HIP(hipGetLastError());
-  return LB_OK;
+  return graph_attend_backward(e, "lb_graph_attend_backward", role, logits_dev, values_dev, m_dev, s_dev, d_out_dev, d_logits_dev,
+                               d_values_dev, H, D, LB_DTYPE_F32);
 }
 
 extern "C" int lb_graph_features_backward(lb_engine* e, const float* d_abs_pos, const float* d_vel_hist, const float* d_vel_mag,
@@ -882,7 +1026,7 @@ extern "C" int lb_graph_features_backward(lb_engine* e, const float* d_abs_pos, 
   if (d_bound && !e->g.has_bound) return lb_fail(LB_ERR_ARG, "lb_graph_features_backward: d_bound on an engine without bound");
   if (e->g.f32) return lb_fail(LB_ERR_UNSUPPORTED, "lb_graph_features_backward: float32 geometry");
   const bool edges = d_rel_disp || d_rel_dist;   // (only these need the sender view)
-  LB_TRY(graph_entry(e, "lb_graph_features_backward", edges ? 1 : 0, true, 1, 1));
+  LB_TRY(graph_entry(e, "lb_graph_features_backward", edges ? 1 : 0, LB_DTYPE_F32, true, 1, 1));
   lb_gfb_args a{};
   a.BN = e->BN; a.e_cap = e->e_cap; a.E = (int)e->graph_E;
   a.win = e->win; a.ctrl = e->ctrl; a.ptype = e->ptype; a.row_ptr = e->row_ptr;

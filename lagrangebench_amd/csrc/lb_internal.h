@@ -191,6 +191,8 @@ struct lb_engine {
   int64_t snd_cap = 0;
   bool snd_radix = false;
   int32_t snd_sorts = 0;                             // sender views built by the radix sort
+  float* graph_t = nullptr;                          // [graph_t_cap] fp32 t (B E_cap, H) of a bf16 lb_graph_attend_backward_t
+  int64_t graph_t_cap = 0;
 
   // network scratch (allocated by lb_gns_create / regrown with e_alloc)
   float* xnode;        // [BN][kpad]

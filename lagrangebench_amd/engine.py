@@ -441,23 +441,38 @@ class RolloutEngine:
                                             C.byref(h)), "lb_blob_train_create")
         return BlobTrainHandle(self, h, None, blob.size)
 
+    # The graph ops run on float32 or bfloat16 tensors - every data tensor of one call the same dtype (win stays int32, m and s
+    # of attend float32), outputs in that dtype - through the typed entries (include/lbhip.h: lb_graph_*_t).  The bfloat16
+    # contract: round_to_bf16(float32 op(upcast inputs)) bit for bit.
+    _GRAPH_DTYPES = {torch.float32: 0, torch.bfloat16: 1}   # LB_DTYPE_F32, LB_DTYPE_BF16
+
+    def _graph_dtype(self, symbol: str, t) -> torch.dtype:
+        dtype = getattr(t, "dtype", None)
+        if dtype not in self._GRAPH_DTYPES:
+            raise ValueError(f"{symbol}: expected a float32 or bfloat16 tensor on {self.device}, got "
+                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', None)}")
+        return dtype
+
     def _graph_op(self, symbol: str, role: int, src: torch.Tensor, rows_in: int, rows_out: int) -> torch.Tensor:
-        if src.dtype != torch.float32 or src.device != self.device or not src.is_contiguous() or src.dim() != 2 \
-                or src.shape[0] != rows_in or src.shape[1] < 1:
-            raise ValueError(f"{symbol}: expected a contiguous ({rows_in}, C >= 1) float32 tensor on {self.device}, got "
-                             f"{tuple(src.shape)} {src.dtype} on {src.device}")
-        out = torch.empty((rows_out, src.shape[1]), dtype=torch.float32, device=self.device)
-        check(getattr(self.lib, symbol)(self._h, int(role), ptr(src), ptr(out), int(src.shape[1])), symbol)
+        if getattr(src, "dtype", None) not in self._GRAPH_DTYPES or src.device != self.device or not src.is_contiguous() \
+                or src.dim() != 2 or src.shape[0] != rows_in or src.shape[1] < 1:
+            raise ValueError(f"{symbol}: expected a contiguous ({rows_in}, C >= 1) float32 or bfloat16 tensor on {self.device}, "
+                             f"got {tuple(src.shape)} {src.dtype} on {src.device}")
+        out = torch.empty((rows_out, src.shape[1]), dtype=src.dtype, device=self.device)
+        check(getattr(self.lib, symbol + "_t")(self._h, int(role), ptr(src), ptr(out), int(src.shape[1]),
+                                               self._GRAPH_DTYPES[src.dtype]), symbol)
         return out
 
     def graph_gather(self, role: int, x: torch.Tensor) -> torch.Tensor:
-        """x (B*N, C) float32 -> (B*E_cap, C): the node row of every real edge slot of the current list in the padded
-        layout of nl_idx(), +0.0 in the pad slots.  role: 0 receivers, 1 senders (include/lbhip.h: lb_graph_gather)."""
+        """x (B*N, C) float32 or bfloat16 -> (B*E_cap, C): the node row of every real edge slot of the current list in the
+        padded layout of nl_idx(), +0.0 in the pad slots; a bit copy.  role: 0 receivers, 1 senders (include/lbhip.h:
+        lb_graph_gather_t)."""
         return self._graph_op("lb_graph_gather", role, x, self.B * self.N, self.B * self.e_cap)
 
     def graph_segment_sum(self, role: int, msg: torch.Tensor) -> torch.Tensor:
-        """msg (B*E_cap, C) float32 -> (B*N, C): per node the sum of its real edge slots in ascending slot order, one fp32
-        add after the other; no atomics (include/lbhip.h: lb_graph_segment_sum)."""
+        """msg (B*E_cap, C) float32 or bfloat16 -> (B*N, C): per node the sum of its real edge slots in ascending slot order, one
+        fp32 add after the other; no atomics.  bfloat16: the terms are widened, the fp32 sum is rounded once (include/lbhip.h:
+        lb_graph_segment_sum_t)."""
         return self._graph_op("lb_graph_segment_sum", role, msg, self.B * self.e_cap, self.B * self.N)
 
     def _graph_arg(self, symbol: str, t: torch.Tensor, shape, dtype=torch.float32) -> torch.Tensor:
@@ -479,40 +494,46 @@ class RolloutEngine:
         return out
 
     def graph_segment_max(self, role: int, msg: torch.Tensor, minimum: bool = False):
-        """msg (B*E_cap, C) float32 -> (out (B*N, C), win (B*N, C) int32): per node and column the first real slot's value,
-        replaced in ascending slot order by a strictly greater (minimum: smaller) one, and the slot that won (-1 and +0.0 for
-        a node without edges) (include/lbhip.h: lb_graph_segment_max / _min)."""
+        """msg (B*E_cap, C) float32 or bfloat16 -> (out (B*N, C), win (B*N, C) int32): per node and column the first real slot's
+        value, replaced in ascending slot order by a strictly greater (minimum: smaller) one, and the slot that won (-1 and +0.0
+        for a node without edges) (include/lbhip.h: lb_graph_segment_max_t / _min_t)."""
         symbol = "lb_graph_segment_min" if minimum else "lb_graph_segment_max"
         C_ = self._graph_cols(symbol, msg, self.B * self.e_cap)
-        self._graph_arg(symbol, msg, (self.B * self.e_cap, C_))
-        out = torch.empty((self.B * self.N, C_), dtype=torch.float32, device=self.device)
+        dt = self._graph_dtype(symbol, msg)
+        self._graph_arg(symbol, msg, (self.B * self.e_cap, C_), dt)
+        out = torch.empty((self.B * self.N, C_), dtype=dt, device=self.device)
         win = torch.empty((self.B * self.N, C_), dtype=torch.int32, device=self.device)
-        check(getattr(self.lib, symbol)(self._h, int(role), ptr(msg), ptr(out), ptr(win), C_), symbol)
+        check(getattr(self.lib, symbol + "_t")(self._h, int(role), ptr(msg), ptr(out), ptr(win), C_, self._GRAPH_DTYPES[dt]), symbol)
         return out, win
 
     def graph_segment_max_backward(self, role: int, d_out: torch.Tensor, win: torch.Tensor) -> torch.Tensor:
-        """d_out (B*N, C), win (B*N, C) int32 -> d_msg (B*E_cap, C): d_out in the winning slots, +0.0 elsewhere."""
+        """d_out (B*N, C), win (B*N, C) int32 -> d_msg (B*E_cap, C) in d_out's dtype: d_out in the winning slots, +0.0 elsewhere."""
         symbol = "lb_graph_segment_max_backward"
         C_ = self._graph_cols(symbol, d_out, self.B * self.N)
-        self._graph_arg(symbol, d_out, (self.B * self.N, C_))
+        dt = self._graph_dtype(symbol, d_out)
+        self._graph_arg(symbol, d_out, (self.B * self.N, C_), dt)
         self._graph_arg(symbol, win, (self.B * self.N, C_), torch.int32)
-        d_msg = torch.empty((self.B * self.e_cap, C_), dtype=torch.float32, device=self.device)
-        check(self.lib.lb_graph_segment_max_backward(self._h, int(role), ptr(d_out), ptr(win), ptr(d_msg), C_), symbol)
+        d_msg = torch.empty((self.B * self.e_cap, C_), dtype=dt, device=self.device)
+        check(self.lib.lb_graph_segment_max_backward_t(self._h, int(role), ptr(d_out), ptr(win), ptr(d_msg), C_,
+                                                       self._GRAPH_DTYPES[dt]), symbol)
         return d_msg
 
     def graph_segment_softmax(self, role: int, logits: torch.Tensor) -> torch.Tensor:
-        """logits (B*E_cap, C) float32 -> (B*E_cap, C): per node and column the softmax over the node's real slots, shifted by
-        their maximum, the denominator summed in ascending slot order; +0.0 in the pad slots (lb_graph_segment_softmax)."""
+        """logits (B*E_cap, C) float32 or bfloat16 -> (B*E_cap, C): per node and column the softmax over the node's real slots,
+        shifted by their maximum, the denominator summed in ascending slot order; +0.0 in the pad slots
+        (lb_graph_segment_softmax_t)."""
         return self._graph_op("lb_graph_segment_softmax", role, logits, self.B * self.e_cap, self.B * self.e_cap)
 
     def graph_segment_softmax_backward(self, role: int, y: torch.Tensor, d_y: torch.Tensor) -> torch.Tensor:
-        """y, d_y (B*E_cap, C) -> d_logits (B*E_cap, C) = y (d_y - the node's ordered sum of d_y y)."""
+        """y, d_y (B*E_cap, C), one dtype -> d_logits (B*E_cap, C) = y (d_y - the node's ordered sum of d_y y)."""
         symbol = "lb_graph_segment_softmax_backward"
         C_ = self._graph_cols(symbol, y, self.B * self.e_cap)
-        self._graph_arg(symbol, y, (self.B * self.e_cap, C_))
-        self._graph_arg(symbol, d_y, (self.B * self.e_cap, C_))
+        dt = self._graph_dtype(symbol, y)
+        self._graph_arg(symbol, y, (self.B * self.e_cap, C_), dt)
+        self._graph_arg(symbol, d_y, (self.B * self.e_cap, C_), dt)
         d_x = torch.empty_like(y)
-        check(self.lib.lb_graph_segment_softmax_backward(self._h, int(role), ptr(y), ptr(d_y), ptr(d_x), C_), symbol)
+        check(self.lib.lb_graph_segment_softmax_backward_t(self._h, int(role), ptr(y), ptr(d_y), ptr(d_x), C_,
+                                                           self._GRAPH_DTYPES[dt]), symbol)
         return d_x
 
     def _graph_attend_args(self, symbol: str, logits: torch.Tensor, values: torch.Tensor):
@@ -521,33 +542,38 @@ class RolloutEngine:
         if not isinstance(values, torch.Tensor) or values.dim() != 3 or values.shape[2] < 1:
             raise ValueError(f"{symbol}: expected values ({slots}, {H}, D >= 1), got {tuple(getattr(values, 'shape', ()))}")
         D = int(values.shape[2])
-        self._graph_arg(symbol, logits, (slots, H))
-        self._graph_arg(symbol, values, (slots, H, D))
-        return H, D
+        dt = self._graph_dtype(symbol, logits)
+        self._graph_arg(symbol, logits, (slots, H), dt)
+        self._graph_arg(symbol, values, (slots, H, D), dt)
+        return H, D, dt
 
     def graph_attend(self, role: int, logits: torch.Tensor, values: torch.Tensor):
-        """logits (B*E_cap, H), values (B*E_cap, H, D) float32 -> (out (B*N, H, D), m (B*N, H), s (B*N, H)): the softmax of the
-        logits over each node's slots times the values, summed per node in ascending slot order - the bits of
-        graph_segment_sum(graph_segment_softmax(logits)[..., None] * values) in one launch; m and s are the maximum and the
-        denominator it used (include/lbhip.h: lb_graph_attend)."""
-        H, D = self._graph_attend_args("lb_graph_attend", logits, values)
-        out = torch.empty((self.B * self.N, H, D), dtype=torch.float32, device=self.device)
+        """logits (B*E_cap, H), values (B*E_cap, H, D), both float32 or both bfloat16 -> (out (B*N, H, D) in that dtype,
+        m (B*N, H), s (B*N, H) float32): the softmax of the logits over each node's slots times the values, summed per node in
+        ascending slot order.  float32: the bits of graph_segment_sum(graph_segment_softmax(logits)[..., None] * values) in one
+        launch.  bfloat16: that float32 result on the widened inputs, rounded once - the weights are not rounded to bfloat16
+        on the way, as the composition's are.  m and s are the maximum and the denominator it used (include/lbhip.h:
+        lb_graph_attend_t)."""
+        H, D, dt = self._graph_attend_args("lb_graph_attend", logits, values)
+        out = torch.empty((self.B * self.N, H, D), dtype=dt, device=self.device)
         m = torch.empty((self.B * self.N, H), dtype=torch.float32, device=self.device)
         s = torch.empty_like(m)
-        check(self.lib.lb_graph_attend(self._h, int(role), ptr(logits), ptr(values), ptr(out), ptr(m), ptr(s), H, D), "lb_graph_attend")
+        check(self.lib.lb_graph_attend_t(self._h, int(role), ptr(logits), ptr(values), ptr(out), ptr(m), ptr(s), H, D,
+                                         self._GRAPH_DTYPES[dt]), "lb_graph_attend")
         return out, m, s
 
     def graph_attend_backward(self, role: int, logits: torch.Tensor, values: torch.Tensor, m: torch.Tensor, s: torch.Tensor,
                               d_out: torch.Tensor):
-        """-> (d_logits (B*E_cap, H), d_values (B*E_cap, H, D)) of graph_attend (include/lbhip.h: lb_graph_attend_backward)."""
+        """-> (d_logits (B*E_cap, H), d_values (B*E_cap, H, D)) of graph_attend, in the dtype of logits, values and d_out
+        (include/lbhip.h: lb_graph_attend_backward_t)."""
         symbol = "lb_graph_attend_backward"
-        H, D = self._graph_attend_args(symbol, logits, values)
+        H, D, dt = self._graph_attend_args(symbol, logits, values)
         self._graph_arg(symbol, m, (self.B * self.N, H))
         self._graph_arg(symbol, s, (self.B * self.N, H))
-        self._graph_arg(symbol, d_out, (self.B * self.N, H, D))
+        self._graph_arg(symbol, d_out, (self.B * self.N, H, D), dt)
         d_logits, d_values = torch.empty_like(logits), torch.empty_like(values)
-        check(self.lib.lb_graph_attend_backward(self._h, int(role), ptr(logits), ptr(values), ptr(m), ptr(s), ptr(d_out),
-                                                ptr(d_logits), ptr(d_values), H, D), symbol)
+        check(self.lib.lb_graph_attend_backward_t(self._h, int(role), ptr(logits), ptr(values), ptr(m), ptr(s), ptr(d_out),
+                                                  ptr(d_logits), ptr(d_values), H, D, self._GRAPH_DTYPES[dt]), symbol)
         return d_logits, d_values
 
     def graph_features_backward(self, d_abs_pos=None, d_vel_hist=None, d_vel_mag=None, d_bound=None, d_rel_disp=None,

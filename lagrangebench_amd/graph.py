@@ -38,7 +38,25 @@ result or gradient is +0.0, no float atomics, two calls give the same bits:
   intermediate.  Its ``d_values`` has the composition's bits too; ``d_logits`` reduces over D in another order and agrees
   to rounding.
 
-Tensors are float32 on the engine's device (``TypeError`` otherwise) and are made contiguous here.  A forward or a
+bfloat16.  Every op takes float32 or bfloat16 tensors (what ``torch.autocast(dtype=torch.bfloat16)`` hands a module) and
+returns the dtype it was given.  One contract for every op and every backward:
+
+    the bfloat16 op  ==  round_to_bf16( the float32 op( upcast(inputs) ) )        bit for bit
+
+upcast is the exact widening, the float32 op is the arithmetic stated above - the same order of adds, the same m, expf, s
+and division - and round_to_bf16 is one round-to-nearest-even per stored element (NaN stays NaN, beyond the range +-inf,
+subnormals kept, -0.0 kept where the float32 op keeps it).  So ``gather`` is a bit copy; ``segment_sum`` adds the widened
+terms in float32 in slot order and rounds once - no partial sum is ever held in bfloat16, which is what ``index_add_`` on
+bfloat16 (atomics on 8 significant bits, in any order) cannot give; ``segment_max`` / ``segment_min`` return one of the
+inputs; ``segment_mean`` is ``(segment_sum(msg).float() / max(degree, 1)).to(bfloat16)``; ``segment_softmax`` saves the
+rounded y and differentiates that.  ``attend`` on bfloat16 is NOT the composition of the bfloat16 ops: the composition rounds
+the weights to bfloat16 before it multiplies, ``attend`` forms them in float32 from the widened logits and rounds the sum
+once - it is the more accurate of the two; ``m`` and ``s`` stay float32.  The engine's features stay float32, so
+``torch.cat([h_bf16, features["rel_disp"]], -1)`` promotes to float32 unless the features are cast.  float16, float64 and
+integer tensors are refused.
+
+Tensors are float32 or bfloat16 on the engine's device (``TypeError`` otherwise; the logits and values of one ``attend`` the
+same dtype; a cotangent in another dtype than its forward's is a ``TypeError`` too) and are made contiguous here.  A forward or a
 backward after the engine's list moved on raises ``RuntimeError``: the staleness rule of ``FeatureDict``.  The ops are once
 differentiable: a double backward through them (``create_graph=True``) raises.
 
@@ -64,13 +82,13 @@ class _Op(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, graph, role, kind):
-        ctx.graph, ctx.role, ctx.kind = graph, role, kind
+        ctx.graph, ctx.role, ctx.kind, ctx.dtype = graph, role, kind, getattr(x, "dtype", None)
         return graph._run(kind, role, x)
 
     @staticmethod
     @once_differentiable   # (the backward runs the kernel on detached data: a double backward raises instead of giving zeros)
     def backward(ctx, d):
-        return ctx.graph._run(1 - ctx.kind, ctx.role, d), None, None, None
+        return ctx.graph._run(1 - ctx.kind, ctx.role, d, ctx.dtype), None, None, None
 
 
 class _SegmentMax(torch.autograd.Function):
@@ -81,7 +99,7 @@ class _SegmentMax(torch.autograd.Function):
         name = "segment_min" if minimum else "segment_max"
         flat, rest = graph._flat(name, msg, graph.engine.e_cap)
         out, win = graph.engine.graph_segment_max(role, flat, minimum)
-        ctx.graph, ctx.role, ctx.name, ctx.rest = graph, role, name, rest
+        ctx.graph, ctx.role, ctx.name, ctx.rest, ctx.dtype = graph, role, name, rest, flat.dtype
         ctx.save_for_backward(win)
         return out.reshape(graph._shape(graph.engine.N) + rest)
 
@@ -89,7 +107,7 @@ class _SegmentMax(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, d):
         g, e = ctx.graph, ctx.graph.engine
-        flat, _ = g._flat(ctx.name, d, e.N)
+        flat, _ = g._flat(ctx.name, d, e.N, ctx.dtype)
         d_msg = e.graph_segment_max_backward(ctx.role, flat, ctx.saved_tensors[0])
         return d_msg.reshape(g._shape(e.e_cap) + ctx.rest), None, None, None
 
@@ -107,7 +125,7 @@ class _SegmentSoftmax(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, d):
         g, e = ctx.graph, ctx.graph.engine
-        flat, _ = g._flat("segment_softmax", d, e.e_cap)
+        flat, _ = g._flat("segment_softmax", d, e.e_cap, ctx.saved_tensors[0].dtype)
         d_x = e.graph_segment_softmax_backward(ctx.role, ctx.saved_tensors[0], flat)
         return d_x.reshape(g._shape(e.e_cap) + ctx.rest), None, None
 
@@ -116,6 +134,9 @@ class _Attend(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, values, graph, role):
         e = graph.engine
+        if isinstance(logits, torch.Tensor) and isinstance(values, torch.Tensor) and logits.dtype != values.dtype:
+            raise TypeError(f"graph.attend: logits and values must have one dtype (float32 or bfloat16), got {logits.dtype} and "
+                            f"{values.dtype}")
         lf, heads = graph._flat("attend", logits, e.e_cap)
         vf, hd = graph._flat("attend", values, e.e_cap)
         if len(heads) != 1 or len(hd) != 2 or hd[0] != heads[0]:
@@ -131,8 +152,8 @@ class _Attend(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, d):
         g, e = ctx.graph, ctx.graph.engine
-        flat, _ = g._flat("attend", d, e.N)
         lf, vf, m, s = ctx.saved_tensors
+        flat, _ = g._flat("attend", d, e.N, lf.dtype)
         d_l, d_v = e.graph_attend_backward(ctx.role, lf, vf, m, s, flat.reshape(e.B * e.N, *ctx.hd))
         return d_l.reshape(g._shape(e.e_cap) + ctx.hd[:1]), d_v.reshape(g._shape(e.e_cap) + ctx.hd), None, None
 
@@ -260,11 +281,13 @@ class Graph:
     def _shape(self, rows: int) -> tuple:
         return (self.engine.B, rows) if self.batched else (rows,)
 
-    def _flat(self, name: str, t: torch.Tensor, rows: int):
+    def _flat(self, name: str, t: torch.Tensor, rows: int, forward_dtype=None):
         """The checks every op makes on a (B, rows, ...) tensor -> (its detached contiguous (B * rows, C) view, the trailing
-        dimensions)."""
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"graph.{name}: float32 tensors only, got {getattr(t, 'dtype', type(t))}")
+        dimensions).  `forward_dtype`: t is a cotangent of a forward that ran in this dtype."""
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"graph.{name}: float32 or bfloat16 tensors only, got {getattr(t, 'dtype', type(t))}")
+        if forward_dtype is not None and t.dtype != forward_dtype:
+            raise TypeError(f"graph.{name}: the cotangent is {t.dtype}, the forward ran in {forward_dtype}")
         e = self.engine
         if t.device != e.device:
             raise TypeError(f"graph.{name}: the tensor is on {t.device}, the engine on {e.device}")
@@ -274,9 +297,10 @@ class Graph:
             raise ValueError(f"graph.{name}: expected {lead + ('C',)} (C >= 1), got {tuple(t.shape)}")
         return t.detach().contiguous().reshape(e.B * rows, -1), tuple(t.shape[len(lead):])
 
-    def _run(self, kind: int, role: int, t: torch.Tensor) -> torch.Tensor:
+    def _run(self, kind: int, role: int, t: torch.Tensor, forward_dtype=None) -> torch.Tensor:
         e = self.engine
-        flat, rest = self._flat("segment_sum" if kind == _SEGMENT_SUM else "gather", t, e.e_cap if kind == _SEGMENT_SUM else e.N)
+        flat, rest = self._flat("segment_sum" if kind == _SEGMENT_SUM else "gather", t, e.e_cap if kind == _SEGMENT_SUM else e.N,
+                                forward_dtype)
         out = (e.graph_segment_sum if kind == _SEGMENT_SUM else e.graph_gather)(role, flat)
         return out.reshape(self._shape(e.N if kind == _SEGMENT_SUM else e.e_cap) + rest)
 
@@ -285,7 +309,8 @@ class Graph:
         return _Op.apply(x, self, self._role(role), _GATHER)
 
     def segment_sum(self, msg: torch.Tensor, role: str) -> torch.Tensor:
-        """msg (B, E_cap, C) -> (B, N, C): per node the ordered float32 sum of the real slots whose role index it is."""
+        """msg (B, E_cap, C) -> (B, N, C): per node the ordered float32 sum of the real slots whose role index it is; for
+        bfloat16 the terms are widened and that float32 sum is rounded once."""
         return _Op.apply(msg, self, self._role(role), _SEGMENT_SUM)
 
     def degree(self, role: str) -> torch.Tensor:
@@ -296,10 +321,11 @@ class Graph:
 
     def segment_mean(self, msg: torch.Tensor, role: str) -> torch.Tensor:
         """msg (B, E_cap, C) -> (B, N, C): segment_sum divided by max(degree, 1) as float32 - the ordered sum, then one
-        correctly rounded division; +0.0 for a node without edges."""
+        correctly rounded division; +0.0 for a node without edges.  bfloat16: the rounded ordered sum, widened, one float32
+        division, one rounding."""
         total = self.segment_sum(msg, role)
         deg = self.degree(role).clamp(min=1).to(torch.float32)
-        return total / deg.reshape(deg.shape + (1,) * (total.dim() - deg.dim()))
+        return (total.float() / deg.reshape(deg.shape + (1,) * (total.dim() - deg.dim()))).to(total.dtype)
 
     def segment_max(self, msg: torch.Tensor, role: str) -> torch.Tensor:
         """msg (B, E_cap, C) -> (B, N, C): per node and column the first real slot's value, replaced in ascending slot order
@@ -320,5 +346,7 @@ class Graph:
     def attend(self, logits: torch.Tensor, values: torch.Tensor, role: str) -> torch.Tensor:
         """logits (B, E_cap, H), values (B, E_cap, H, D) -> (B, N, H, D): bit for bit
         segment_sum(segment_softmax(logits, role)[..., None] * values, role), in one kernel that reads the values once and
-        writes nothing of their size."""
+        writes nothing of their size.  On bfloat16 (logits and values alike) it is that float32 result on the widened inputs,
+        rounded once: not the composition of the bfloat16 ops, which rounds the weights to bfloat16 first, and the more
+        accurate of the two."""
         return _Attend.apply(logits, values, self, self._role(role))

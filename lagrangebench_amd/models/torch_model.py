@@ -26,6 +26,15 @@ without a copy.  ``loss_grad`` is the reference's ``_mse`` in torch; its ``backw
 blob, and the library's AdamW kernels (``lb_adamw_step``, ``lb_adamw_step_gathered``) update the weights in place.  There is
 no fused rollout: ``evaluate.rollout`` drives ``apply`` step by step through its generic loop.
 
+Mixed precision: ``TorchModel(module, autocast=torch.bfloat16)`` runs the module under
+``torch.autocast(device, dtype=torch.bfloat16)`` wherever the model runs it - ``apply``, ``loss_grad``, the push-forward
+unroll, ``eval_rollout``, ``infer``, ``autograd.TorchModule``.  The parameters, the training handle's blob, AdamW and the
+checkpoints stay float32, as autocast expects; ``Linear`` and the like then return bfloat16, the graph ops take and return
+bfloat16 (``graph.py`` states their contract), and the module's (B, N, dim) output may be bfloat16: it is widened to float32
+before the loss and the integrator.  The features the module receives stay float32 - ``torch.cat([h, features["rel_disp"]],
+-1)`` with a bfloat16 ``h`` promotes to float32 unless the module casts the features.  A module written for float32 runs
+unchanged.  float16 is not offered (it would need loss scaling).
+
 Losses and training schemes of the user's own - gradients with respect to the input window, unrolls through time - go through
 ``autograd.TorchModule``, which runs the same module as a differentiable torch module on the engine.
 """
@@ -65,12 +74,15 @@ class TorchModel(BaseModel):
     _FUSED_ROLLOUT = False   # no device rollout: evaluate.rollout's generic loop
     _PADDED_OK = False
 
-    def __init__(self, module: torch.nn.Module, output: str = "acc"):
+    def __init__(self, module: torch.nn.Module, output: str = "acc", autocast=None):
         if not isinstance(module, torch.nn.Module):
             raise TypeError(f"TorchModel wraps a torch.nn.Module, got {type(module).__name__}")
         if output not in ("acc", "vel", "pos"):
             raise ValueError(f"TorchModel: output {output!r} must be 'acc', 'vel' or 'pos'")
+        if autocast is not None and autocast is not torch.bfloat16:
+            raise ValueError(f"TorchModel: autocast {autocast!r} must be None or torch.bfloat16")
         self._OUTPUT = output
+        self.autocast = autocast
         self._module = copy.deepcopy(module).to("cpu")   # the template: shapes, names, buffers; init() resets it
         self._names: List[str] = [n for n, _ in self._module.named_parameters()]
         bad = [n for n, p in self._module.named_parameters() if p.dtype != torch.float32]
@@ -182,12 +194,23 @@ class TorchModel(BaseModel):
             fd[k] = v.to(torch.int64) if k in ("senders", "receivers") else v.to(torch.float32)
         pt = torch.as_tensor(np.asarray(particle_type) if not isinstance(particle_type, torch.Tensor) else particle_type)
         pt = pt.to(device=engine.device, dtype=torch.int64).reshape(engine.B, engine.N)
-        out = module(fd, pt, Graph(features, batched=True))
-        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (engine.B, engine.N, engine.dim) or out.dtype != torch.float32:
-            raise ValueError(f"TorchModel: the module must return a ({engine.B}, {engine.N}, {engine.dim}) float32 tensor, got "
+        return self._call_module(module, engine, "TorchModel", fd, pt, Graph(features, batched=True))
+
+    def _call_module(self, module, engine, who: str, fd, pt, graph) -> torch.Tensor:
+        """module(fd, pt, graph) under the model's autocast setting -> its (B, N, dim) output as float32 (a bfloat16 output is
+        accepted under autocast only)."""
+        if self.autocast is None:
+            out = module(fd, pt, graph)
+        else:
+            with torch.autocast(engine.device.type, dtype=self.autocast):
+                out = module(fd, pt, graph)
+        dtypes = (torch.float32,) if self.autocast is None else (torch.float32, self.autocast)
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (engine.B, engine.N, engine.dim) or out.dtype not in dtypes:
+            raise ValueError(f"{who}: the module must return a ({engine.B}, {engine.N}, {engine.dim}) float32 tensor"
+                             f"{'' if self.autocast is None else ' (or bfloat16 under autocast)'}, got "
                              f"{tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__} "
                              f"{getattr(out, 'dtype', '')}")
-        return out
+        return out.float()
 
     def apply_handle(self, handle, state, sample):
         engine = self._engine_of(sample)

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """The graph ops of csrc/lb_graph.hip beside torch's index_select / index_add_ on the same tensors.
 
-    python tools/graph_ops_bench.py [--repeats 20] [--inner 50] [--only rpf2d] [--columns 128] [--out FILE]
+    python tools/graph_ops_bench.py [--dtype f32|bf16] [--repeats 20] [--inner 50] [--only rpf2d] [--columns 128] [--out FILE]
 
 Workloads: RPF2D-3.2k and TGV3D-8k, B = 1 (synthetic cases of lagrangebench_amd.data, seeded), C = 128 columns.  Per
 workload and role (receivers, senders): lb_graph_gather and lb_graph_segment_sum - the forward and the backward of
 graph.Graph.gather are these two launches in this order, of graph.Graph.segment_sum the same two in the other order, so
 "forward plus backward" of either op is their sum - beside torch.index_select (pad slots read row 0) and zero_ +
 index_add_ over the REAL slots only, with the same indices; index_add_ is also timed alone, accumulating into a warm
-buffer.  Each figure is the median of `--repeats` windows of `--inner` launches between two device events (after one
+buffer.  `--dtype bf16` runs every line, torch's included, on bfloat16 tensors (bytes from the 2-byte element).  One more
+line per role: the fused lb_graph_attend at H = 8, D = 16 (logits (E_cap, 8), values (E_cap, 8, 16); it reads both once per
+real slot and writes the node rows, m and s).  Each figure is the median of `--repeats` windows of `--inner` launches between two device events (after one
 warm-up window), with the spread (min .. max) of the windows.
 
 Bytes are those the op has to move, from the shapes: gather reads one C-row per real slot and writes every slot (pads are
@@ -55,8 +57,9 @@ def line(tag, ms, nbytes):
             f"{nbytes / 1e6:8.2f} MB  {nbytes / (med * 1e-3) / 1e12:5.2f} TB/s = {100 * nbytes / (med * 1e-3) / HBM_PEAK:5.1f} % of HBM peak"), med
 
 
-def run(case, C, repeats, inner):
+def run(case, C, repeats, inner, dtype="f32"):
     import torch
+    dt, esize = {"f32": (torch.float32, 4), "bf16": (torch.bfloat16, 2)}[dtype]
     from lagrangebench_amd.case_setup import case_builder
     from lagrangebench_amd.data import make_case
     ds = make_case(case, n_trajs=1, extra_seq_length=1)
@@ -69,10 +72,13 @@ def run(case, C, repeats, inner):
     idx, ne = eng.nl_idx()
     E = int(ne[0])
     gen = torch.Generator(device=eng.device).manual_seed(0)
-    x = torch.randn((N, C), device=eng.device, generator=gen)
-    msg = torch.randn((E_cap, C), device=eng.device, generator=gen)
-    out = [f"{WORKLOADS[case]}: N = {N}, E = {E} real slots of E_cap = {E_cap}, C = {C}"]
-    row = 4 * C
+    x = torch.randn((N, C), device=eng.device, generator=gen).to(dt)
+    msg = torch.randn((E_cap, C), device=eng.device, generator=gen).to(dt)
+    H, D = 8, 16
+    logits = torch.randn((E_cap, H), device=eng.device, generator=gen).to(dt)
+    values = torch.randn((E_cap, H, D), device=eng.device, generator=gen).to(dt)
+    out = [f"{WORKLOADS[case]}: N = {N}, E = {E} real slots of E_cap = {E_cap}, C = {C}, {dtype}"]
+    row = esize * C
     for role, r in (("receivers", 0), ("senders", 1)):
         flat = idx[0, r].long()
         real = torch.arange(E_cap, device=eng.device) < E
@@ -80,12 +86,15 @@ def run(case, C, repeats, inner):
         # index_add_ over the REAL slots only (at B = 1 they are a prefix): what a torch user would write.  Sending the pad
         # slots into one spare row would serialise a fifth of the atomics on one row and measure that row, not torch.
         add, msg_real = flat[:E].contiguous(), msg[:E]
-        acc = torch.zeros((N, C), device=eng.device)
+        acc = torch.zeros((N, C), device=eng.device, dtype=dt)
         b_gather = E * row + E_cap * row + 4 * (E + 2)
         b_sum = E * row + N * row + 4 * (N + 1) + (4 * (E + N + 1) if r else 0)
         # the ops agree before they are timed (the ordered sum and the atomic one differ in the last bits only)
         ours, theirs = eng.graph_segment_sum(r, msg), acc.zero_().index_add_(0, add, msg_real)
-        assert torch.allclose(ours, theirs, rtol=1e-4, atol=1e-4)
+        if dtype == "f32":
+            assert torch.allclose(ours, theirs, rtol=1e-4, atol=1e-4)
+        else:   # (the atomic bfloat16 sum keeps 8 bits along the way: only the float32 ordered sum is held to anything)
+            assert torch.equal(ours, eng.graph_segment_sum(r, msg.float()).to(dt))
         assert torch.equal(eng.graph_gather(r, x)[:E], x.index_select(0, sel)[:E])
         l1, g_ms = line(f"lb_graph_gather({role})", windows(lambda: eng.graph_gather(r, x), repeats, inner), b_gather)
         l2, s_ms = line(f"lb_graph_segment_sum({role})", windows(lambda: eng.graph_segment_sum(r, msg), repeats, inner), b_sum)
@@ -94,7 +103,9 @@ def run(case, C, repeats, inner):
                          windows(lambda: acc.zero_().index_add_(0, add, msg_real), repeats, inner), b_sum + N * row)
         l5, ta_ms = line(f"torch index_add_ alone({role})",
                          windows(lambda: acc.index_add_(0, add, msg_real), repeats, inner), b_sum + N * row)
-        out += [l1, l2, l3, l4, l5,
+        b_att = E * esize * H * (D + 1) + N * esize * H * D + 8 * N * H + 4 * (N + 1) + (4 * (E + N + 1) if r else 0)
+        l6, _ = line(f"lb_graph_attend({role}, {H}x{D})", windows(lambda: eng.graph_attend(r, logits, values), repeats, inner), b_att)
+        out += [l1, l2, l3, l4, l5, l6,
                 f"  forward + backward of gather or segment_sum over {role}: ours {1e3 * (g_ms + s_ms):.2f} us, torch "
                 f"{1e3 * (tg_ms + ts_ms):.2f} us (ordered sum / atomic sum = {s_ms / ts_ms:.2f}x, gather / index_select = "
                 f"{g_ms / tg_ms:.2f}x)"]
@@ -107,6 +118,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--inner", type=int, default=50)
     ap.add_argument("--columns", type=int, default=128)
+    ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--only", choices=sorted(WORKLOADS), default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -115,7 +127,7 @@ def main():
         sys.exit("graph_ops_bench: needs a HIP device (no CPU timing)")
     lines = [f"graph ops, {torch.cuda.get_device_name(0)}; median of {a.repeats} windows of {a.inner} launches (device events)"]
     for case in ([a.only] if a.only else list(WORKLOADS)):
-        lines += run(case, a.columns, a.repeats, a.inner)
+        lines += run(case, a.columns, a.repeats, a.inner, a.dtype)
     print("\n".join(lines), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
