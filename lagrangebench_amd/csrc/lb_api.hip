@@ -869,8 +869,9 @@ int lb_rollout_generic(lb_engine* e, int (*forward)(lb_engine*, void*), void* mo
 
 extern "C" int lb_ekin(lb_engine* e, const double* rollout_dev, int32_t T, int32_t stride, double dt,
                        double dx, double* out_dev, int32_t n_out) {
-  if (!e || !rollout_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
+  // the shape first: a caller that sized out_dev by a bad stride or T holds an empty (null) buffer
   if (stride < 1 || T < 2) return lb_fail(LB_ERR_ARG, "need stride >= 1 and T >= 2");
+  if (!e || !rollout_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   const int expect = (T - 1 + stride - 1) / stride;  // len(x[1::stride]) == len(x[0:-1:stride])
   if (n_out != expect) return lb_fail(LB_ERR_ARG, "n_out must be ceil((T-1)/stride) = %d", expect);
   return lbk_ekin(e, rollout_dev, T, stride, n_out, dt, dx, out_dev);
@@ -879,8 +880,8 @@ extern "C" int lb_ekin(lb_engine* e, const double* rollout_dev, int32_t T, int32
 extern "C" int lb_sinkhorn(lb_engine* e, const double* pred_dev, int32_t pred_T, const double* target_dev,
                            int32_t target_T, int32_t stride, double threshold, double* out_dev, int32_t n_out,
                            int32_t* iters_out_host) {
-  if (!e || !pred_dev || !target_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (stride < 1 || pred_T < 1 || target_T < 1) return lb_fail(LB_ERR_ARG, "need stride >= 1 and T >= 1");
+  if (!e || !pred_dev || !target_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (!(threshold > 0)) return lb_fail(LB_ERR_ARG, "threshold must be > 0");
   const int T = pred_T < target_T ? pred_T : target_T;
   const int expect = (T + stride - 1) / stride;  // len(x[0::stride])
@@ -891,8 +892,8 @@ extern "C" int lb_sinkhorn(lb_engine* e, const double* pred_dev, int32_t pred_T,
 extern "C" int lb_sinkhorn_pot(lb_engine* e, const double* pred_dev, int32_t pred_T, const double* target_dev,
                                int32_t target_T, int32_t stride, double reg, int32_t num_iter_max, double stop_thr,
                                double* out_dev, int32_t n_out, int32_t* info_out_host) {
-  if (!e || !pred_dev || !target_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (stride < 1 || pred_T < 1 || target_T < 1) return lb_fail(LB_ERR_ARG, "need stride >= 1 and T >= 1");
+  if (!e || !pred_dev || !target_dev || !out_dev) return lb_fail(LB_ERR_ARG, "null argument");
   if (!(reg > 0) || num_iter_max < 1 || !(stop_thr >= 0)) return lb_fail(LB_ERR_ARG, "need reg > 0, numItermax >= 1, stopThr >= 0");
   const int T = pred_T < target_T ? pred_T : target_T;
   const int expect = (T + stride - 1) / stride;  // len(x[0::stride])

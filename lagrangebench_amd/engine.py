@@ -27,6 +27,11 @@ def _dev(t: torch.Tensor, dtype, device) -> torch.Tensor:
     return t.to(device=device, dtype=dtype).contiguous()
 
 
+def _n_strided(n: int, stride: int) -> int:
+    """len(range(0, n, stride)); 0 for a stride or length the library refuses, so that the refusal is the library's."""
+    return (n + stride - 1) // stride if stride >= 1 and n >= 1 else 0
+
+
 class ForceSpec:
     """How external_force_fn(position) (features.py:105-107) is evaluated on the device.
 
@@ -396,7 +401,7 @@ class RolloutEngine:
         """Kinetic energy of strided frames of (B,T,N,dim) (or (T,N,dim)) positions -> (B, n_out)."""
         r = _dev(rollout if rollout.dim() == 4 else rollout[None], torch.float64, self.device)
         T = r.shape[1]
-        n_out = (T - 1 + stride - 1) // stride
+        n_out = _n_strided(T - 1, stride)
         out = torch.empty((self.B, n_out), dtype=torch.float64, device=self.device)
         check(self.lib.lb_ekin(self._h, ptr(r), T, int(stride), float(dt), float(dx), ptr(out), n_out), "lb_ekin")
         return out
@@ -407,7 +412,7 @@ class RolloutEngine:
         p = _dev(pred if pred.dim() == 4 else pred[None], torch.float64, self.device)
         t = _dev(target if target.dim() == 4 else target[None], torch.float64, self.device)
         T = min(p.shape[1], t.shape[1])
-        n_out = (T + stride - 1) // stride
+        n_out = _n_strided(T, stride)
         out = torch.empty((self.B, n_out), dtype=torch.float64, device=self.device)
         iters = (C.c_int32 * (self.B * n_out * 3))()
         check(self.lib.lb_sinkhorn(self._h, ptr(p), p.shape[1], ptr(t), t.shape[1], int(stride), float(threshold),
@@ -423,7 +428,7 @@ class RolloutEngine:
         p = _dev(pred if pred.dim() == 4 else pred[None], torch.float64, self.device)
         t = _dev(target if target.dim() == 4 else target[None], torch.float64, self.device)
         T = min(p.shape[1], t.shape[1])
-        n_out = (T + stride - 1) // stride
+        n_out = _n_strided(T, stride)
         out = torch.empty((self.B, n_out), dtype=torch.float64, device=self.device)
         info = (C.c_int32 * (self.B * n_out * 6))()
         check(self.lib.lb_sinkhorn_pot(self._h, ptr(p), p.shape[1], ptr(t), t.shape[1], int(stride), float(reg),

@@ -28,7 +28,7 @@ pin the solver against the closed form of the 2 x 2 entropic problem.
 """
 from __future__ import annotations
 
-from typing import Callable, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
@@ -46,8 +46,10 @@ def _lse(z: np.ndarray, axis: int) -> np.ndarray:
 
 def sinkhorn_solve(C: np.ndarray, a: np.ndarray, b: np.ndarray, eps: float, threshold: float = 1e-4,
                    parallel: bool = False, momentum: float = 1.0, inner_iterations: int = 10,
-                   max_iterations: int = 2000) -> Tuple[float, int, float]:
-    """-> (reg_ot_cost, iterations run, last error).  C float32 (n, m); everything else float64."""
+                   max_iterations: int = 2000, trace: Optional[List[float]] = None) -> Tuple[float, int, float]:
+    """-> (reg_ot_cost, iterations run, last error).  C float32 (n, m); everything else float64.
+    ``trace``: a list that receives the error of every check (every ``inner_iterations``-th iteration), in order -
+    a test that asks for equal iteration counts uses it to see that no check lands on the threshold."""
     C = C.astype(np.float64)
     f, g = np.zeros(len(a)), np.zeros(len(b))
     la, lb = np.log(a), np.log(b)
@@ -70,6 +72,8 @@ def sinkhorn_solve(C: np.ndarray, a: np.ndarray, b: np.ndarray, eps: float, thre
             err = np.abs(mb - b).sum()
             if parallel:
                 err += np.abs(ma - a).sum()
+            if trace is not None:
+                trace.append(float(err))
             if err < threshold:
                 break
     ma, mb = marginals(f, g)
@@ -86,12 +90,14 @@ def sinkhorn_divergence(displacement_fn: Callable, pred: np.ndarray, target: np.
     a = np.ones(len(pred)) / len(pred)
     b = np.ones(len(target)) / len(target)
     eps = 0.05 * float(Cxy.astype(np.float64).mean())
-    rxy, ixy, exy = sinkhorn_solve(Cxy, a, b, eps, threshold)
-    rxx, ixx, exx = sinkhorn_solve(Cxx, a, a, eps, threshold, parallel=True, momentum=0.5)
-    ryy, iyy, eyy = sinkhorn_solve(Cyy, b, b, eps, threshold, parallel=True, momentum=0.5)
+    txy, txx, tyy = ([], [], []) if return_info else (None, None, None)
+    rxy, ixy, exy = sinkhorn_solve(Cxy, a, b, eps, threshold, trace=txy)
+    rxx, ixx, exx = sinkhorn_solve(Cxx, a, a, eps, threshold, parallel=True, momentum=0.5, trace=txx)
+    ryy, iyy, eyy = sinkhorn_solve(Cyy, b, b, eps, threshold, parallel=True, momentum=0.5, trace=tyy)
     div = rxy - 0.5 * (rxx + ryy) + 0.5 * eps * (a.sum() - b.sum()) ** 2
     if return_info:
-        return div, {"eps": eps, "iters": (ixy, ixx, iyy), "errors": (exy, exx, eyy), "reg": (rxy, rxx, ryy)}
+        return div, {"eps": eps, "iters": (ixy, ixx, iyy), "errors": (exy, exx, eyy), "reg": (rxy, rxx, ryy),
+                     "traces": (txy, txx, tyy)}
     return div
 
 
