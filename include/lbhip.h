@@ -798,6 +798,34 @@ int lb_graph_attend_t(lb_engine* eng, int32_t role, const void* logits_dev, cons
 int lb_graph_attend_backward_t(lb_engine* eng, int32_t role, const void* logits_dev, const void* values_dev,
                                const float* m_dev, const float* s_dev, const void* d_out_dev, void* d_logits_dev,
                                void* d_values_dev, int32_t H, int32_t D, int32_t dtype);
+/* ---- edge messages: filter x neighbour without edge-shaped intermediates -----
+ * The rules above hold: the padded layout, role 0 receivers / 1 senders, pad slots never read (they may hold NaN), every pad
+ * slot of an edge-shaped output +0.0, no float atomics, two calls give the same bits, int64 addresses; dtype LB_DTYPE_F32 or
+ * LB_DTYPE_BF16 for every data tensor of the call (there are no fp32-only twins).  other(role) is the opposite role; a slot's
+ * two nodes are its entries of the engine's compact sender and receiver lists.  Node tensors are (B*N, K, C), K >= 1 rows of C
+ * per node; w and the edge-shaped outputs are (B*E_cap, C).  16-byte accesses when C % 4 == 0 (bf16: C % 8 == 0) and the
+ * pointers are 16-byte aligned: a unit never crosses a k boundary.  LB_ERR_ARG on a null pointer, a role other than 0 / 1, a
+ * dtype other than the two, K < 1 or C < 1; LB_ERR_STATE without a list or with an overflowed one.
+ * conv: out[i, k, c] = the sum over the real slots j whose `role` index is i, in ascending slot order (the CSR row for
+ *   receivers, the sender view for senders), of fl32(x[other(role) index of j, k, c] * w[j, c]): each product rounded to fp32,
+ *   the first product starts the sum, one fp32 add per further one, no FMA contraction; +0.0 for a node without a slot.  With
+ *   fp32 tensors bit for bit segment_sum(gather(x, other(role)) * w[:, None, :], role).  Its adjoints: d_x = conv(d_out, w,
+ *   other(role)); d_w = pair_mul(other(role), x, d_out) with the K of the call.  Only role 1 builds (or reuses) the sender view.
+ * pair_mul: out[j, c] = fl32(a[a_role index of j, 0, c] * b[other(a_role) index of j, 0, c]) + ... over k = 0 .. K-1 ascending,
+ *   the first product starts the sum; +0.0 in the pad slots.  K = 1 is the plain product.  Adjoints at K = 1 and a_role 1:
+ *   d_a = conv(b, d, 1), d_b = conv(a, d, 0).
+ * pair_add: out[j, c] = fl32(a[a_role index of j, c] + b[other(a_role) index of j, c]), a and b (B*N, C); +0.0 in the pad
+ *   slots.  Adjoints: the segment sums of d over the two roles.
+ * LB_DTYPE_BF16: round_to_bf16(the fp32 op(upcast inputs)), one rounding per stored element.  A product of two bf16 values is
+ *   exact in fp32 (8 + 8 significant bits), so conv sums exact products in fp32 and rounds once - it is NOT the composition of
+ *   the bf16 ops, which rounds each product to bf16 before it adds; pair_mul's k-sum likewise.  pair_mul at K = 1 and pair_add
+ *   equal bf16 arithmetic on the gathered rows. */
+int lb_graph_conv(lb_engine* eng, int32_t role, const void* x_dev /*(B*N,K,C)*/, const void* w_dev /*(B*E_cap,C)*/,
+                  void* out_dev /*(B*N,K,C)*/, int32_t K, int32_t C, int32_t dtype);
+int lb_graph_pair_mul(lb_engine* eng, int32_t a_role, const void* a_dev /*(B*N,K,C)*/, const void* b_dev /*(B*N,K,C)*/,
+                      void* out_dev /*(B*E_cap,C)*/, int32_t K, int32_t C, int32_t dtype);
+int lb_graph_pair_add(lb_engine* eng, int32_t a_role, const void* a_dev /*(B*N,C)*/, const void* b_dev /*(B*N,C)*/,
+                      void* out_dev /*(B*E_cap,C)*/, int32_t C, int32_t dtype);
 /* d loss / d window from the cotangents of the features a TorchModel module receives (graph.differentiable_features), on the
  * engine's CURRENT window and list: the transpose of the feature builder.  Every input may be NULL (= zero).  fp32 inputs in the
  * layouts of TorchModel's feature dict; the edge-shaped ones in the padded slot layout of lb_nl_read_idx, whose pad slots are

@@ -226,6 +226,10 @@ _SIGS = {
     "lb_graph_segment_softmax_backward_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
     "lb_graph_attend_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_attend_backward_t": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    # edge messages (float32 or bfloat16 by the trailing dtype)
+    "lb_graph_conv": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_graph_pair_mul": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_graph_pair_add": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None

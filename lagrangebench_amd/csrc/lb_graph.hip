@@ -5,7 +5,8 @@
 //   lb_graph_segment_sum(role, msg (B*E_cap, C)) -> out (B*N, C)    out[i]    = sum of the real slots whose role index is i
 //
 // and, for attention and pooling layers (further down: "attention ops"), lb_graph_degree, lb_graph_segment_max / _min,
-// lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries; and lb_graph_features_backward
+// lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries; for filter x neighbour messages ("edge
+// messages") the fused lb_graph_conv and the edge-shaped lb_graph_pair_mul / lb_graph_pair_add; and lb_graph_features_backward
 // ("feature transpose"): d loss / d window from the cotangents of the features such a network was handed.
 //
 // All work in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
@@ -576,6 +577,173 @@ __global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __r
   }
 }
 
+// ------------------------------------------------------------------------------------------------ edge messages
+// conv, pair_mul and pair_add (the contracts are in include/lbhip.h): the "filter x neighbour" message of a
+// continuous-filter or equivariant network without its edge-shaped intermediates.  conv walks the rows of its role as
+// k_graph_segment_sum does and reads, per slot, the w row of the slot and the x row of the slot's OTHER node (oidx: the compact
+// list of the other role, at the compact edge lb_row::edge resolved); pair_mul / pair_add address a slot as k_graph_gather does
+// and read one node row per role.  x, a and b are (B N, K, C), w and the edge-shaped outputs (B E_cap, C): a unit divides C, so
+// a lane holds one w unit per slot and loops k.  Every product is one __fmul_rn, every sum starts from its first term and adds
+// one __fadd_rn per further term - slots ascending in conv, k ascending in pair_mul.
+//
+// One slot's loads for k-chunk k0 .. k0 + KT - 1: the w unit and KT x units (a k past K - 1 re-reads row K - 1; never stored).
+template <typename T, int W, int KT>
+__device__ __forceinline__ void graph_conv_load(const lb_row& R, int p, const int32_t* __restrict__ oidx, const T* __restrict__ x,
+                                                const T* __restrict__ w, int64_t BN, int K, int k0, int U, int u, float (&f)[W],
+                                                float (&a)[KT][W]) {
+  const int64_t e = R.edge(p);
+  int64_t node = oidx[e - R.slot0];
+  node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);   // (an index of the list is a node of the batch: never clamps)
+  lb_ld<T, W>(w + (e * U + u) * W, f);
+#pragma unroll
+  for (int q = 0; q < KT; ++q) {
+    const int k = k0 + q < K ? k0 + q : K - 1;
+    lb_ld<T, W>(x + ((node * K + k) * U + u) * W, a[q]);
+  }
+}
+// out[i][k][:] = sum over the slots of row i, ascending, of fl32(x[other node of the slot][k][:] * w[slot][:]); +0.0 for an empty
+// row.  KT accumulator rows per pass over the slots (1, or 3: a vector feature), SU slots' loads in flight; the adds sequential.
+template <typename T, int W, int KT>
+__device__ __forceinline__ void graph_conv_body(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                                const int32_t* __restrict__ perm, const int32_t* __restrict__ oidx,
+                                                const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ out,
+                                                int64_t BN, int N, int e_cap, int E, int K, int U, int lpr_shift) {
+  constexpr int SU = KT == 1 ? 4 : 2;
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
+    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    for (int u = lane; u < U; u += lpr) {
+      for (int k0 = 0; k0 < K; k0 += KT) {
+        float s[KT][W], f[SU][W], a[SU][KT][W];
+#pragma unroll
+        for (int q = 0; q < KT; ++q)
+#pragma unroll
+          for (int c = 0; c < W; ++c) s[q][c] = 0.f;
+        int p = R.p0;
+        if (p < R.p1) {   // the sum STARTS from the first product
+          graph_conv_load<T, W, KT>(R, p++, oidx, x, w, BN, K, k0, U, u, f[0], a[0]);
+#pragma unroll
+          for (int q = 0; q < KT; ++q)
+#pragma unroll
+            for (int c = 0; c < W; ++c) s[q][c] = __fmul_rn(a[0][q][c], f[0][c]);
+        }
+        for (; p + SU <= R.p1; p += SU) {
+#pragma unroll
+          for (int t = 0; t < SU; ++t) graph_conv_load<T, W, KT>(R, p + t, oidx, x, w, BN, K, k0, U, u, f[t], a[t]);
+#pragma unroll
+          for (int t = 0; t < SU; ++t)
+#pragma unroll
+            for (int q = 0; q < KT; ++q)
+#pragma unroll
+              for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[t][q][c], f[t][c]));
+        }
+        for (; p < R.p1; ++p) {
+          graph_conv_load<T, W, KT>(R, p, oidx, x, w, BN, K, k0, U, u, f[0], a[0]);
+#pragma unroll
+          for (int q = 0; q < KT; ++q)
+#pragma unroll
+            for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[0][q][c], f[0][c]));
+        }
+#pragma unroll
+        for (int q = 0; q < KT; ++q)
+          if (k0 + q < K) lb_st<T, W>(out + ((i * K + k0 + q) * U + u) * W, s[q]);
+      }
+    }
+  }
+}
+#define LB_CONV_KERNEL(name, KT)                                                                                          \
+  template <typename T, int W>                                                                                            \
+  __global__ void __launch_bounds__(256) name(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,  \
+                                              const int32_t* __restrict__ perm, const int32_t* __restrict__ oidx,        \
+                                              const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ out,     \
+                                              int64_t BN, int N, int e_cap, int E, int K, int U, int lpr_shift) {        \
+    graph_conv_body<T, W, KT>(row_ptr, seg_ptr, perm, oidx, x, w, out, BN, N, e_cap, E, K, U, lpr_shift);                \
+  }
+LB_CONV_KERNEL(k_graph_conv, 1)      // K = 1
+LB_CONV_KERNEL(k_graph_conv_k3, 3)   // K > 1, three k at a time
+#undef LB_CONV_KERNEL
+
+// out[slot][:] = fl32(a[a node][0][:] * b[b node][0][:]) + fl32(a[..][1][:] * b[..][1][:]) + ... (k ascending, the first product
+// starts the sum) in the real slots, +0.0 in the pads.  With K = 1 the plain product; with K > 1 conv's d_w.
+template <typename T, int W, bool ONE>
+__device__ __forceinline__ void graph_pair_mul_body(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ aidx,
+                                                    const int32_t* __restrict__ bidx, const T* __restrict__ a,
+                                                    const T* __restrict__ b, T* __restrict__ out, int64_t BN, int N, int B,
+                                                    int e_cap, int E, int K_, int U, int lpr_shift) {
+  const int K = ONE ? 1 : K_;   // (K = 1: no k loop, the registers of the plain product)
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
+    const int t = (int)(r / e_cap), j = (int)(r - (int64_t)t * e_cap);
+    const int base = row_ptr[(int64_t)t * N], nb = row_ptr[(int64_t)(t + 1) * N] - base;
+    const bool real = j < nb && base + j < E;
+    int64_t na = real ? aidx[base + j] : 0, nn = real ? bidx[base + j] : 0;
+    na = na < 0 ? 0 : (na >= BN ? BN - 1 : na);
+    nn = nn < 0 ? 0 : (nn >= BN ? BN - 1 : nn);
+    for (int u = lane; u < U; u += lpr) {
+      float s[W], fa[W], fb[W];
+#pragma unroll
+      for (int c = 0; c < W; ++c) s[c] = 0.f;
+      if (real) {
+        lb_ld<T, W>(a + (na * K * U + u) * W, fa);
+        lb_ld<T, W>(b + (nn * K * U + u) * W, fb);
+#pragma unroll
+        for (int c = 0; c < W; ++c) s[c] = __fmul_rn(fa[c], fb[c]);
+#pragma unroll 4
+        for (int k = 1; k < K; ++k) {
+          lb_ld<T, W>(a + ((na * K + k) * U + u) * W, fa);
+          lb_ld<T, W>(b + ((nn * K + k) * U + u) * W, fb);
+#pragma unroll
+          for (int c = 0; c < W; ++c) s[c] = __fadd_rn(s[c], __fmul_rn(fa[c], fb[c]));
+        }
+      }
+      lb_st<T, W>(out + (r * U + u) * W, s);
+    }
+  }
+}
+#define LB_PAIR_MUL_KERNEL(name, ONE)                                                                                      \
+  template <typename T, int W>                                                                                             \
+  __global__ void __launch_bounds__(256) name(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ aidx,      \
+                                              const int32_t* __restrict__ bidx, const T* __restrict__ a,                  \
+                                              const T* __restrict__ b, T* __restrict__ out, int64_t BN, int N, int B,     \
+                                              int e_cap, int E, int K, int U, int lpr_shift) {                            \
+    graph_pair_mul_body<T, W, ONE>(row_ptr, aidx, bidx, a, b, out, BN, N, B, e_cap, E, K, U, lpr_shift);                  \
+  }
+LB_PAIR_MUL_KERNEL(k_graph_pair_mul, true)      // K = 1: the plain product
+LB_PAIR_MUL_KERNEL(k_graph_pair_mul_k, false)   // K > 1: the k-sum (conv's d_w)
+#undef LB_PAIR_MUL_KERNEL
+
+// out[slot][:] = fl32(a[a node][:] + b[b node][:]) in the real slots, +0.0 in the pads.
+template <typename T, int W>
+__global__ void __launch_bounds__(256) k_graph_pair_add(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ aidx,
+                                                        const int32_t* __restrict__ bidx, const T* __restrict__ a,
+                                                        const T* __restrict__ b, T* __restrict__ out, int64_t BN, int N, int B,
+                                                        int e_cap, int E, int U, int lpr_shift) {
+  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
+  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
+    const int t = (int)(r / e_cap), j = (int)(r - (int64_t)t * e_cap);
+    const int base = row_ptr[(int64_t)t * N], nb = row_ptr[(int64_t)(t + 1) * N] - base;
+    const bool real = j < nb && base + j < E;
+    int64_t na = real ? aidx[base + j] : 0, nn = real ? bidx[base + j] : 0;
+    na = na < 0 ? 0 : (na >= BN ? BN - 1 : na);
+    nn = nn < 0 ? 0 : (nn >= BN ? BN - 1 : nn);
+    for (int u = lane; u < U; u += lpr) {
+      float s[W], fa[W], fb[W];
+#pragma unroll
+      for (int c = 0; c < W; ++c) s[c] = 0.f;
+      if (real) {
+        lb_ld<T, W>(a + (na * U + u) * W, fa);
+        lb_ld<T, W>(b + (nn * U + u) * W, fb);
+#pragma unroll
+        for (int c = 0; c < W; ++c) s[c] = __fadd_rn(fa[c], fb[c]);
+      }
+      lb_st<T, W>(out + (r * U + u) * W, s);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ feature transpose
 // d loss / d window (B N, isl, dim) fp64 from the cotangents of the features a TorchModel module receives: the transpose of the
 // feature builder as the comment above k_feat_bwd (lb_train.hip) states it, on the engine's current window and list, in the
@@ -1016,6 +1184,52 @@ extern "C" int lb_graph_attend_backward(lb_engine* e, int32_t role, const float*
                                         float* d_values_dev, int32_t H, int32_t D) {
   return graph_attend_backward(e, "lb_graph_attend_backward", role, logits_dev, values_dev, m_dev, s_dev, d_out_dev, d_logits_dev,
                                d_values_dev, H, D, LB_DTYPE_F32);
+}
+
+// ---- the edge-message entries (float32 or bfloat16 by dtype; no float32-only twins)
+extern "C" int lb_graph_conv(lb_engine* e, int32_t role, const void* x_dev, const void* w_dev, void* out_dev, int32_t K, int32_t C,
+                             int32_t dtype) {
+  // the sender view only where sender rows are walked (role 1); the other node of a slot comes from the compact list
+  LB_TRY(graph_entry(e, "lb_graph_conv", role, dtype, x_dev && w_dev && out_dev, K, C));
+  if ((int64_t)K * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_conv: K %d x C %d columns", K, C);
+  const int32_t* oidx = role ? e->receivers : e->senders;
+  const int W = graph_width(dtype, C, false, {x_dev, w_dev, out_dev});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  const unsigned blocks = graph_blocks(e->BN, sh);
+  if (K == 1)
+    GRAPH_LAUNCH(k_graph_conv, blocks, e->row_ptr, role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, oidx,
+                 (const GT*)x_dev, (const GT*)w_dev, (GT*)out_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, K, U, sh);
+  else
+    GRAPH_LAUNCH(k_graph_conv_k3, blocks, e->row_ptr, role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, oidx,
+                 (const GT*)x_dev, (const GT*)w_dev, (GT*)out_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, K, U, sh);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_pair_mul(lb_engine* e, int32_t a_role, const void* a_dev, const void* b_dev, void* out_dev, int32_t K,
+                                 int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, "lb_graph_pair_mul", a_role, dtype, a_dev && b_dev && out_dev, K, C, false));   // edge-parallel: no view
+  if ((int64_t)K * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_pair_mul: K %d x C %d columns", K, C);
+  const int W = graph_width(dtype, C, false, {a_dev, b_dev, out_dev});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  const unsigned blocks = graph_blocks((int64_t)e->g.B * e->e_cap, sh);
+  if (K == 1)
+    GRAPH_LAUNCH(k_graph_pair_mul, blocks, e->row_ptr, a_role ? e->senders : e->receivers, a_role ? e->receivers : e->senders,
+                 (const GT*)a_dev, (const GT*)b_dev, (GT*)out_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, K, U, sh);
+  else
+    GRAPH_LAUNCH(k_graph_pair_mul_k, blocks, e->row_ptr, a_role ? e->senders : e->receivers, a_role ? e->receivers : e->senders,
+                 (const GT*)a_dev, (const GT*)b_dev, (GT*)out_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, K, U, sh);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_pair_add(lb_engine* e, int32_t a_role, const void* a_dev, const void* b_dev, void* out_dev, int32_t C,
+                                 int32_t dtype) {
+  LB_TRY(graph_entry(e, "lb_graph_pair_add", a_role, dtype, a_dev && b_dev && out_dev, C, 1, false));
+  const int W = graph_width(dtype, C, false, {a_dev, b_dev, out_dev});
+  const int U = C / W, sh = graph_lpr_shift(U);
+  GRAPH_LAUNCH(k_graph_pair_add, graph_blocks((int64_t)e->g.B * e->e_cap, sh), e->row_ptr, a_role ? e->senders : e->receivers,
+               a_role ? e->receivers : e->senders, (const GT*)a_dev, (const GT*)b_dev, (GT*)out_dev, e->BN, e->g.N, e->g.B,
+               e->e_cap, (int)e->graph_E, U, sh);
+  return LB_OK;
 }
 
 extern "C" int lb_graph_features_backward(lb_engine* e, const float* d_abs_pos, const float* d_vel_hist, const float* d_vel_mag,

@@ -581,6 +581,54 @@ class RolloutEngine:
                                                   ptr(d_logits), ptr(d_values), H, D, self._GRAPH_DTYPES[dt]), symbol)
         return d_logits, d_values
 
+    def _graph_pair_args(self, symbol: str, a: torch.Tensor, b: torch.Tensor):
+        """a, b (B*N, K, C), one dtype -> (K, C, dtype)."""
+        if not isinstance(a, torch.Tensor) or a.dim() != 3 or a.shape[0] != self.B * self.N or a.shape[1] < 1 or a.shape[2] < 1:
+            raise ValueError(f"{symbol}: expected ({self.B * self.N}, K >= 1, C >= 1) tensors, got "
+                             f"{tuple(getattr(a, 'shape', ()))}")
+        dt = self._graph_dtype(symbol, a)
+        self._graph_arg(symbol, a, tuple(a.shape), dt)
+        self._graph_arg(symbol, b, tuple(a.shape), dt)
+        return int(a.shape[1]), int(a.shape[2]), dt
+
+    def graph_conv(self, role: int, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+        """x (B*N, K, C), w (B*E_cap, C), both float32 or both bfloat16 -> (B*N, K, C): per node the sum over its real slots of
+        `role`, in ascending slot order, of x[the slot's other node] * w[slot] - each product rounded to float32, one float32
+        add after the other; no edge-shaped intermediate.  float32: the bits of graph_segment_sum(graph_gather(x) * w).
+        bfloat16: the exact products summed in float32, rounded once (include/lbhip.h: lb_graph_conv)."""
+        symbol = "lb_graph_conv"
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[0] != self.B * self.N or x.shape[1] < 1 or x.shape[2] < 1:
+            raise ValueError(f"{symbol}: expected x ({self.B * self.N}, K >= 1, C >= 1), got {tuple(getattr(x, 'shape', ()))}")
+        K, C_ = int(x.shape[1]), int(x.shape[2])
+        dt = self._graph_dtype(symbol, x)
+        self._graph_arg(symbol, x, tuple(x.shape), dt)
+        self._graph_arg(symbol, w, (self.B * self.e_cap, C_), dt)
+        out = torch.empty_like(x)
+        check(self.lib.lb_graph_conv(self._h, int(role), ptr(x), ptr(w), ptr(out), K, C_, self._GRAPH_DTYPES[dt]), symbol)
+        return out
+
+    def graph_pair_mul(self, a_role: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """a, b (B*N, K, C), one dtype -> (B*E_cap, C): per real slot the sum over k ascending of a[the slot's `a_role` node, k]
+        * b[its other node, k], each product rounded to float32, the first starts the sum; +0.0 in the pad slots.  K = 1 is
+        the plain product; with K > 1 it is graph_conv's gradient to w (include/lbhip.h: lb_graph_pair_mul)."""
+        symbol = "lb_graph_pair_mul"
+        K, C_, dt = self._graph_pair_args(symbol, a, b)
+        out = torch.empty((self.B * self.e_cap, C_), dtype=dt, device=self.device)
+        check(self.lib.lb_graph_pair_mul(self._h, int(a_role), ptr(a), ptr(b), ptr(out), K, C_, self._GRAPH_DTYPES[dt]), symbol)
+        return out
+
+    def graph_pair_add(self, a_role: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """a, b (B*N, C), one dtype -> (B*E_cap, C): a[the slot's `a_role` node] + b[its other node] in the real slots, one
+        float32 add, +0.0 in the pad slots (include/lbhip.h: lb_graph_pair_add)."""
+        symbol = "lb_graph_pair_add"
+        C_ = self._graph_cols(symbol, a, self.B * self.N)
+        dt = self._graph_dtype(symbol, a)
+        self._graph_arg(symbol, a, (self.B * self.N, C_), dt)
+        self._graph_arg(symbol, b, (self.B * self.N, C_), dt)
+        out = torch.empty((self.B * self.e_cap, C_), dtype=dt, device=self.device)
+        check(self.lib.lb_graph_pair_add(self._h, int(a_role), ptr(a), ptr(b), ptr(out), C_, self._GRAPH_DTYPES[dt]), symbol)
+        return out
+
     def graph_features_backward(self, d_abs_pos=None, d_vel_hist=None, d_vel_mag=None, d_bound=None, d_rel_disp=None,
                                 d_rel_dist=None) -> torch.Tensor:
         """-> d loss / d window (B, N, isl, dim) float64 from the float32 cotangents of the features a TorchModel module

@@ -15,6 +15,11 @@ describes, in the padded layout of ``features["senders"]`` / ``["receivers"]`` (
     a = g.segment_softmax(logits, "receivers")          # (B, E_cap, C) -> (B, E_cap, C): a softmax per node and column
     out = g.attend(logits, values, "receivers")         # (B, E_cap, H), (B, E_cap, H, D) -> (B, N, H, D), one launch
 
+    ds = g.conv(x, w, "senders")             # (B, N, C) | (B, N, K, C), (B, E_cap, C) -> the shape of x, one launch:
+                                             #   segment_sum(gather(x, "receivers") * w[..., None, :], "senders")
+    e = g.pair_add(a, b)                     # (B, N, C) twice -> (B, E_cap, C): a[senders] + b[receivers]
+    m = g.pair_mul(a, b)                     # ... a[senders] * b[receivers]
+
 (with un-batched features the leading B is dropped: (N, C) -> (E_cap, C)).  Trailing dimensions beyond C are folded into C
 where the op is column-wise (all but ``attend``).
 
@@ -38,6 +43,22 @@ result or gradient is +0.0, no float atomics, two calls give the same bits:
   intermediate.  Its ``d_values`` has the composition's bits too; ``d_logits`` reduces over D in another order and agrees
   to rounding.
 
+Edge messages.  ``conv``, ``pair_mul`` and ``pair_add`` are the "filter x neighbour" message of a continuous-filter or
+equivariant network (SchNet's cfconv, PaiNN's ``segment_sum(Wij * x[receivers], senders)``) and the first edge Linear of a
+message-passing layer, without their edge-shaped intermediates, under the same contracts:
+
+* ``conv(x, w, role)``: ``out[i, k, c]`` is the sum over the real slots j whose `role` index is i, in ascending slot order,
+  of ``fl32(x[other-role index of j, k, c] * w[j, c])`` - each product rounded to float32, the first product starts the sum,
+  one float32 add per further one, +0.0 for a node without slots.  So on float32 it equals
+  ``segment_sum(gather(x, other) * w[..., None, :], role)`` bit for bit.  x is (B, N, C) - trailing dimensions equal to w's
+  fold into C - or (B, N, K, C) with w (B, E_cap, C) broadcast over K (a vector feature: K = 3); anything else is a
+  ``ValueError``.  Backward: ``d_x = conv(d_out, w, other(role))``, the composition's bits; ``d_w[j, c]`` is the sum over k
+  ascending of ``fl32(x[other index of j, k, c] * d_out[role index of j, k, c])``, +0.0 in the pad slots.  Only x and w are
+  saved, and a gradient nobody asked for is not computed.
+* ``pair_mul(a, b)`` = ``fl32(a[senders] * b[receivers])`` and ``pair_add(a, b)`` = ``fl32(a[senders] + b[receivers])``, a and b
+  (B, N, C) -> (B, E_cap, C), +0.0 in the pad slots.  Backward: ``conv(b, d, "senders")`` and ``conv(a, d, "receivers")``;
+  ``segment_sum(d, "senders")`` and ``segment_sum(d, "receivers")``.
+
 bfloat16.  Every op takes float32 or bfloat16 tensors (what ``torch.autocast(dtype=torch.bfloat16)`` hands a module) and
 returns the dtype it was given.  One contract for every op and every backward:
 
@@ -51,7 +72,10 @@ bfloat16 (atomics on 8 significant bits, in any order) cannot give; ``segment_ma
 inputs; ``segment_mean`` is ``(segment_sum(msg).float() / max(degree, 1)).to(bfloat16)``; ``segment_softmax`` saves the
 rounded y and differentiates that.  ``attend`` on bfloat16 is NOT the composition of the bfloat16 ops: the composition rounds
 the weights to bfloat16 before it multiplies, ``attend`` forms them in float32 from the widened logits and rounds the sum
-once - it is the more accurate of the two; ``m`` and ``s`` stay float32.  The engine's features stay float32, so
+once - it is the more accurate of the two; ``m`` and ``s`` stay float32.  ``conv`` on bfloat16 is NOT the composition of the
+bfloat16 ops either: the composition rounds each product to bfloat16 before it adds, ``conv`` keeps the products in float32 -
+exact there, 8 + 8 significant bits fit - and rounds the ordered sum once; its ``d_w`` likewise (products and the k-sum in
+float32, one rounding).  ``pair_mul`` and ``pair_add`` equal torch's bfloat16 arithmetic on the gathered rows.  The engine's features stay float32, so
 ``torch.cat([h_bf16, features["rel_disp"]], -1)`` promotes to float32 unless the features are cast.  float16, float64 and
 integer tensors are refused.
 
@@ -158,6 +182,87 @@ class _Attend(torch.autograd.Function):
         return d_l.reshape(g._shape(e.e_cap) + ctx.hd[:1]), d_v.reshape(g._shape(e.e_cap) + ctx.hd), None, None
 
 
+def _one_dtype(name: str, a, b, what: str) -> None:
+    if isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.dtype != b.dtype:
+        raise TypeError(f"graph.{name}: {what} must have one dtype (float32 or bfloat16), got {a.dtype} and {b.dtype}")
+
+
+class _Conv(torch.autograd.Function):
+    """conv over `role`: d_x is conv of the cotangent over the other role, d_w the K-reducing pair_mul of x and the cotangent."""
+
+    @staticmethod
+    def forward(ctx, x, w, graph, role):
+        e = graph.engine
+        _one_dtype("conv", x, w, "x and w")
+        xf, rx = graph._flat("conv", x, e.N)
+        wf, rw = graph._flat("conv", w, e.e_cap)
+        if rx == rw:                                       # trailing dimensions fold into C
+            K = 1
+        elif len(rw) == 1 and len(rx) == 2 and rx[1] == rw[0]:
+            K = rx[0]                                      # w is broadcast over the K rows of a node
+        else:
+            raise ValueError(f"graph.conv: expected x {graph._shape(e.N) + ('C',)} or {graph._shape(e.N) + ('K', 'C')} and w "
+                             f"{graph._shape(e.e_cap) + ('C',)} (or equal trailing dimensions), got {tuple(x.shape)} and "
+                             f"{tuple(w.shape)}")
+        xf = xf.reshape(e.B * e.N, K, -1)
+        out = e.graph_conv(role, xf, wf)
+        ctx.graph, ctx.role, ctx.rx, ctx.rw = graph, role, rx, rw
+        ctx.save_for_backward(xf, wf)
+        return out.reshape(graph._shape(e.N) + rx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        xf, wf = ctx.saved_tensors
+        df, _ = g._flat("conv", d, e.N, xf.dtype)
+        df = df.reshape(xf.shape)
+        d_x = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_x = e.graph_conv(1 - ctx.role, df, wf).reshape(g._shape(e.N) + ctx.rx)
+        if ctx.needs_input_grad[1]:
+            d_w = e.graph_pair_mul(1 - ctx.role, xf, df).reshape(g._shape(e.e_cap) + ctx.rw)
+        return d_x, d_w, None, None
+
+
+class _Pair(torch.autograd.Function):
+    """pair_mul / pair_add: a over senders, b over receivers."""
+
+    @staticmethod
+    def forward(ctx, a, b, graph, mul):
+        e = graph.engine
+        name = "pair_mul" if mul else "pair_add"
+        _one_dtype(name, a, b, "a and b")
+        af, ra = graph._flat(name, a, e.N)
+        bf, rb = graph._flat(name, b, e.N)
+        if ra != rb:
+            raise ValueError(f"graph.{name}: a and b must have one shape {graph._shape(e.N) + ('C',)}, got {tuple(a.shape)} and "
+                             f"{tuple(b.shape)}")
+        ctx.graph, ctx.mul, ctx.rest, ctx.dtype = graph, mul, ra, af.dtype
+        if mul:
+            ctx.save_for_backward(af, bf)
+            out = e.graph_pair_mul(_ROLES["senders"], af[:, None, :], bf[:, None, :])
+        else:
+            out = e.graph_pair_add(_ROLES["senders"], af, bf)
+        return out.reshape(graph._shape(e.e_cap) + ra)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        df, _ = g._flat("pair_mul" if ctx.mul else "pair_add", d, e.e_cap, ctx.dtype)
+        grads = [None, None]
+        for k, role in enumerate((_ROLES["senders"], _ROLES["receivers"])):
+            if not ctx.needs_input_grad[k]:
+                continue
+            if ctx.mul:   # d_a = conv(b, d, senders), d_b = conv(a, d, receivers)
+                out = e.graph_conv(role, ctx.saved_tensors[1 - k][:, None, :], df)
+            else:
+                out = e.graph_segment_sum(role, df)
+            grads[k] = out.reshape(g._shape(e.N) + ctx.rest)
+        return grads[0], grads[1], None, None
+
+
 _FLOAT_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "force", "rel_disp", "rel_dist")
 _GRAD_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "rel_disp", "rel_dist")   # ("force" is a constant of the positions)
 
@@ -230,7 +335,7 @@ def differentiable_features(features, window: torch.Tensor) -> dict:
 
 class Graph:
     """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum and the attention
-    ops (degree, segment_mean / max / min / softmax, attend).
+    ops (degree, segment_mean / max / min / softmax, attend) and the edge messages (conv, pair_mul, pair_add).
     `batched`: whether the tensors carry the leading B (default: as the features do)."""
 
     def __init__(self, features, batched: Optional[bool] = None):
@@ -350,3 +455,21 @@ class Graph:
         rounded once: not the composition of the bfloat16 ops, which rounds the weights to bfloat16 first, and the more
         accurate of the two."""
         return _Attend.apply(logits, values, self, self._role(role))
+
+    def conv(self, x: torch.Tensor, w: torch.Tensor, role: str) -> torch.Tensor:
+        """x (B, N, C) or (B, N, K, C), w (B, E_cap, C) -> the shape of x: per node the ordered sum over its real slots of
+        `role` of x[the slot's other node] * w[slot] (w broadcast over K) - bit for bit
+        segment_sum(gather(x, other role) * w[..., None, :], role) on float32, in one kernel that reads w once and writes
+        nothing edge-shaped.  Equal trailing dimensions fold into C.  On bfloat16 the exact products are summed in float32 and
+        the sum is rounded once: not the composition of the bfloat16 ops, which rounds every product first."""
+        return _Conv.apply(x, w, self, self._role(role))
+
+    def pair_mul(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """a, b (B, N, C) -> (B, E_cap, C): a[senders] * b[receivers] in the real slots (one rounded product), +0.0 in the
+        pad slots; neither gathered tensor exists."""
+        return _Pair.apply(a, b, self, True)
+
+    def pair_add(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """a, b (B, N, C) -> (B, E_cap, C): a[senders] + b[receivers] in the real slots, +0.0 in the pad slots - the edge
+        Linear of cat[x_s, x_r, e] as (x W_s)[senders] + (x W_r)[receivers] + e W_e, with the GEMMs on N rows."""
+        return _Pair.apply(a, b, self, False)
