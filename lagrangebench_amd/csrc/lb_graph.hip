@@ -31,6 +31,7 @@
 // lb_graph_*_t entries) through the same kernels - "element types" below: a 16-byte unit is then 8 elements (C % 8 == 0), the
 // arithmetic stays fp32 and each stored element is rounded once.
 #include <algorithm>
+#include <type_traits>
 
 #include "lb_device.h"
 #include "lb_features.h"
@@ -127,29 +128,130 @@ __device__ __forceinline__ void lb_sti(int32_t* p, const int32_t (&a)[W]) {
   }
 }
 
+// ---- the list, a slot, a row.  Every kernel takes the list it works on as ONE descriptor by value: the CSR of the engine's
+// receiver-sorted list and the sizes of the padded layout, with the op's units per row (U) and lanes per row (2^lpr_shift).
+// The node-parallel kernels also take the walk - the rows of their role.  Members are only ever read by name (uniform values
+// in scalar registers); a run-time index into a by-value argument would go to scratch (see lb_sel3 in k_graph_features_bwd).
+struct lb_glist {
+  const int32_t* row_ptr;
+  int64_t BN;
+  int N, B, e_cap, E;
+  int U, lpr_shift;
+};
+struct lb_gwalk {
+  const int32_t *seg_ptr, *perm;   // receivers: (row_ptr, null); senders: the sender view (snd_ptr, snd_perm)
+};
+// a node index of the list, clamped into the batch (an index of the list is a node of the batch: never clamps)
+__device__ __forceinline__ int64_t graph_clamp(const lb_glist& L, int64_t node) {
+  return node < 0 ? 0 : (node >= L.BN ? L.BN - 1 : node);
+}
+
+// Padded slot r (flat over the batch): whether it is real, the slot j within its trajectory, its compact edge k, and the nodes
+// idx / oidx (oidx may be null) hold for it - node 0 for a pad.
+struct lb_gslot {
+  bool real;
+  int j, k;
+  int64_t node, other;
+};
+__device__ __forceinline__ lb_gslot graph_slot(const lb_glist& L, int64_t r, const int32_t* __restrict__ idx,
+                                              const int32_t* __restrict__ oidx = nullptr) {
+  lb_gslot s;
+  const int b = (int)(r / L.e_cap);
+  s.j = (int)(r - (int64_t)b * L.e_cap);
+  const int base = L.row_ptr[(int64_t)b * L.N], nb = L.row_ptr[(int64_t)(b + 1) * L.N] - base;
+  s.k = base + s.j;
+  s.real = s.j < nb && s.k < L.E;
+  s.node = graph_clamp(L, s.real ? idx[s.k] : 0);
+  s.other = oidx ? graph_clamp(L, s.real ? oidx[s.k] : 0) : 0;
+  return s;
+}
+
+// Row i of (seg_ptr, perm): positions p0 .. p1 - 1; edge(p) is the padded slot (flat over the batch) of position p - compact
+// edge k = perm ? perm[p] : p, padded slot = b E_cap + k - row_ptr[b N] - clamped into the trajectory's own E_cap slots (a
+// sender view is a permutation of the trajectory's own edges: the clamp never acts on one); first is the trajectory's slot 0,
+// so edge(p) - first is the slot j within it.  Pad slots are never reached.
+struct lb_row {
+  const int32_t* perm;
+  int base, last, p0, p1;
+  int64_t slot0, first;
+  __device__ __forceinline__ int64_t edge(int p) const {
+    int k = perm ? perm[p] : p;
+    k = k < base ? base : k;
+    k = k >= last ? last - 1 : k;
+    return slot0 + k;
+  }
+};
+__device__ __forceinline__ lb_row graph_row(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
+                                            const int32_t* __restrict__ perm, int64_t i, int N, int e_cap, int E) {
+  lb_row R;
+  const int64_t b = i / N;
+  R.perm = perm;
+  R.base = row_ptr[b * N];
+  int last = row_ptr[(b + 1) * N];   // one past the trajectory's compact edges, capped by the list and by its E_cap slots
+  last = last < E ? last : E;
+  R.last = last - R.base < e_cap ? last : R.base + e_cap;
+  int p0 = seg_ptr[i], p1 = seg_ptr[i + 1];
+  R.p0 = p0 < E ? p0 : E;
+  R.p1 = p1 < E ? p1 : E;
+  // a trajectory without edges has empty rows; p1 < p0 cannot happen on a valid list (seg_ptr ascends), so that guard never acts
+  if (R.last <= R.base || R.p1 < R.p0) R.p1 = R.p0;
+  R.first = b * e_cap;
+  R.slot0 = R.first - R.base;
+  return R;
+}
+__device__ __forceinline__ lb_row graph_row(const lb_glist& L, const lb_gwalk& walk, int64_t i) {
+  return graph_row(L.row_ptr, walk.seg_ptr, walk.perm, i, L.N, L.e_cap, L.E);
+}
+
+// The loop nest of the row-shaped kernels: a group of lpr = 2^lpr_shift lanes owns row r = first, first + stride, ..., a lane
+// of it the units u = lane, lane + lpr, ... of the row.  head(r) runs once per row, body(r, its result, u) per unit.
+struct lb_glanes {
+  int lpr, lane;
+  int64_t first, stride;
+};
+__device__ __forceinline__ lb_glanes graph_lanes(const lb_glist& L) {
+  const int lpr = 1 << L.lpr_shift;
+  return {lpr, (int)threadIdx.x & (lpr - 1), (int64_t)blockIdx.x * (256 >> L.lpr_shift) + (threadIdx.x >> L.lpr_shift),
+          (int64_t)gridDim.x * (256 >> L.lpr_shift)};
+}
+template <typename Head, typename Body>
+__device__ __forceinline__ void graph_for(const lb_glist& L, int64_t rows, Head head, Body body) {
+  const lb_glanes G = graph_lanes(L);
+  for (int64_t r = G.first; r < rows; r += G.stride) {
+    const auto h = head(r);
+    for (int u = G.lane; u < L.U; u += G.lpr) body(r, h, u);
+  }
+}
+// node-parallel: body(node i, its lb_row, u); edge-parallel: body(padded slot r, its lb_gslot, u)
+template <typename Body>
+__device__ __forceinline__ void graph_for_nodes(const lb_glist& L, const lb_gwalk& walk, Body body) {
+  graph_for(L, L.BN, [&](int64_t i) { return graph_row(L, walk, i); }, body);
+}
+template <typename Body>
+__device__ __forceinline__ void graph_for_slots(const lb_glist& L, const int32_t* __restrict__ idx,
+                                                const int32_t* __restrict__ oidx, Body body) {
+  graph_for(L, (int64_t)L.B * L.e_cap, [&](int64_t r) { return graph_slot(L, r, idx, oidx); }, body);
+}
+
 // out[slot][:] = x[idx[compact edge of the slot]][:] for the real slots, +0.0 for the pads: a bit copy of U units of type T per
 // row - f32x4 (16 bytes of either element type), float, or lb_bf16; all bits zero is +0.0 in both.
 template <typename T>
-__global__ void __launch_bounds__(256) k_graph_gather(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
-                                                      const void* __restrict__ x, void* __restrict__ out, int64_t BN, int N,
-                                                      int B, int e_cap, int E, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
+__global__ void __launch_bounds__(256) k_graph_gather(lb_glist L, const int32_t* __restrict__ idx, const void* __restrict__ x,
+                                                      void* __restrict__ out) {
   const T* __restrict__ xs = reinterpret_cast<const T*>(x);
   T* __restrict__ os = reinterpret_cast<T*>(out);
-  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
-    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
-    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
-    const bool real = j < nb && base + j < E;
-    int64_t node = real ? idx[base + j] : 0;
-    node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);   // (an index of the list is a node of the batch: never clamps)
-    for (int u = lane; u < U; u += lpr) os[r * U + u] = real ? xs[node * U + u] : T{};
-  }
+  const int U = L.U;
+  graph_for_slots(L, idx, nullptr,
+                  [&](int64_t r, const lb_gslot& s, int u) { os[r * U + u] = s.real ? xs[s.node * U + u] : T{}; });
 }
 
 // out[i][:] = msg[slot of p0][:] + msg[slot of p0 + 1][:] + ... over the positions p of row i of (seg_ptr, perm): compact edge
 // k = perm ? perm[p] : p, padded slot = b E_cap + k - row_ptr[b N].  +0.0 for an empty row.  Pad slots are never read.
 // The adds are fp32 on the widened terms; the sum is rounded to E once, at the store.
+// This kernel, the hottest of the file, keeps its own text - scalar arguments, the caps and clamps of graph_row inline, the loop
+// nest of graph_for written out: through the shared descriptor and helpers it compiled to the same loop but ran 2 - 5 % slower on
+// the large case, and the cause was not found in the ISA.  graph_row states the same caps (its p1 < p0 guard never acts on a
+// valid list); a change to one goes into the other.
 template <typename T, int W>
 __global__ void __launch_bounds__(256) k_graph_segment_sum(const int32_t* __restrict__ row_ptr,
                                                            const int32_t* __restrict__ seg_ptr,
@@ -207,39 +309,9 @@ __global__ void __launch_bounds__(256) k_graph_segment_sum(const int32_t* __rest
 
 // ------------------------------------------------------------------------------------------------ attention ops
 // degree, segment max / min, segment softmax and the fused attend, forward and backward (the contracts
-// are in include/lbhip.h).  The node-parallel kernels walk a row exactly as k_graph_segment_sum does (lb_row: the same caps and
-// clamps), the edge-parallel ones address a slot as k_graph_gather does.  A unit is W = 4 floats (one 16-byte access) or W = 1.
+// are in include/lbhip.h).  The node-parallel kernels walk a row as k_graph_segment_sum does (graph_for_nodes), the edge-parallel
+// ones address a slot as k_graph_gather does (graph_slot).  A unit is W = 4 floats (one 16-byte access) or W = 1.
 // -ffp-contract=off holds for this file (build.py); the attend sum spells its roundings out with __fmul_rn / __fadd_rn anyway.
-// Row i of (seg_ptr, perm): positions p0 .. p1 - 1; edge(p) is the padded slot (flat over the batch) of position p, clamped
-// into the trajectory's own E_cap slots; first is the trajectory's slot 0, so edge(p) - first is the slot j within it.
-struct lb_row {
-  const int32_t* perm;
-  int base, last, p0, p1;
-  int64_t slot0, first;
-  __device__ __forceinline__ int64_t edge(int p) const {
-    int k = perm ? perm[p] : p;
-    k = k < base ? base : k;
-    k = k >= last ? last - 1 : k;
-    return slot0 + k;
-  }
-};
-__device__ __forceinline__ lb_row graph_row(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                            const int32_t* __restrict__ perm, int64_t i, int N, int e_cap, int E) {
-  lb_row R;
-  const int64_t b = i / N;
-  R.perm = perm;
-  R.base = row_ptr[b * N];
-  int last = row_ptr[(b + 1) * N];
-  last = last < E ? last : E;
-  R.last = last - R.base < e_cap ? last : R.base + e_cap;
-  int p0 = seg_ptr[i], p1 = seg_ptr[i + 1];
-  R.p0 = p0 < E ? p0 : E;
-  R.p1 = p1 < E ? p1 : E;
-  if (R.last <= R.base || R.p1 < R.p0) R.p1 = R.p0;
-  R.first = b * e_cap;
-  R.slot0 = R.first - R.base;
-  return R;
-}
 
 // a replaces the running s: strictly greater (MIN: smaller), or a is the first NaN (np.maximum / np.minimum keep a NaN)
 template <bool MIN>
@@ -247,193 +319,153 @@ __device__ __forceinline__ bool lb_beats(float a, float s) {
   return (MIN ? a < s : a > s) || (a != a && s == s);
 }
 
-__global__ void __launch_bounds__(256) k_graph_degree(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                      int32_t* __restrict__ out, int64_t BN, int N, int e_cap, int E) {
+__global__ void __launch_bounds__(256) k_graph_degree(lb_glist L, lb_gwalk walk, int32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= BN) return;
-  const lb_row R = graph_row(row_ptr, seg_ptr, nullptr, i, N, e_cap, E);
+  if (i >= L.BN) return;
+  const lb_row R = graph_row(L, walk, i);
   out[i] = R.p1 - R.p0;
 }
 
-// out[i][c] = the first real slot's value, replaced by each further slot in ascending slot order that beats it; win[i][c] = the
-// slot j (within the trajectory) that won, -1 and +0.0 for an empty row.
+// out[i][c] = the first real slot's value, replaced by each further slot in ascending slot order that beats it (MIN: the
+// smallest); win[i][c] = the slot j (within the trajectory) that won, -1 and +0.0 for an empty row.
 template <typename T, int W, bool MIN>
-__device__ __forceinline__ void graph_segment_max_body(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                       const int32_t* __restrict__ perm, const T* __restrict__ msg,
-                                                       T* __restrict__ out, int32_t* __restrict__ win, int64_t BN, int N,
-                                                       int e_cap, int E, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
-    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
-    for (int u = lane; u < U; u += lpr) {
-      float s[W], a[W];
-      int32_t w[W];
+__global__ void __launch_bounds__(256) k_graph_segment_max(lb_glist L, lb_gwalk walk, const T* __restrict__ msg,
+                                                           T* __restrict__ out, int32_t* __restrict__ win) {
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t i, const lb_row& R, int u) {
+    float s[W], a[W];
+    int32_t w[W];
 #pragma unroll
-      for (int k = 0; k < W; ++k) s[k] = 0.f, w[k] = -1;
-      int p = R.p0;
-      if (p < R.p1) {
-        const int64_t e = R.edge(p++);
-        lb_ld<T, W>(msg + (e * U + u) * W, s);
+    for (int k = 0; k < W; ++k) s[k] = 0.f, w[k] = -1;
+    int p = R.p0;
+    if (p < R.p1) {
+      const int64_t e = R.edge(p++);
+      lb_ld<T, W>(msg + (e * U + u) * W, s);
 #pragma unroll
-        for (int k = 0; k < W; ++k) w[k] = (int32_t)(e - R.first);
-      }
-#pragma unroll 4
-      for (; p < R.p1; ++p) {
-        const int64_t e = R.edge(p);
-        lb_ld<T, W>(msg + (e * U + u) * W, a);
-#pragma unroll
-        for (int k = 0; k < W; ++k)
-          if (lb_beats<MIN>(a[k], s[k])) s[k] = a[k], w[k] = (int32_t)(e - R.first);
-      }
-      lb_st<T, W>(out + (i * U + u) * W, s);
-      lb_sti<W>(win + (i * U + u) * W, w);
+      for (int k = 0; k < W; ++k) w[k] = (int32_t)(e - R.first);
     }
-  }
+#pragma unroll 4
+    for (; p < R.p1; ++p) {
+      const int64_t e = R.edge(p);
+      lb_ld<T, W>(msg + (e * U + u) * W, a);
+#pragma unroll
+      for (int k = 0; k < W; ++k)
+        if (lb_beats<MIN>(a[k], s[k])) s[k] = a[k], w[k] = (int32_t)(e - R.first);
+    }
+    lb_st<T, W>(out + (i * U + u) * W, s);
+    lb_sti<W>(win + (i * U + u) * W, w);
+  });
 }
-#define LB_SEGMENT_MAX_KERNEL(name, MIN)                                                                                  \
-  template <typename T, int W>                                                                                            \
-  __global__ void __launch_bounds__(256) name(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,  \
-                                              const int32_t* __restrict__ perm, const T* __restrict__ msg,               \
-                                              T* __restrict__ out, int32_t* __restrict__ win, int64_t BN, int N,         \
-                                              int e_cap, int E, int U, int lpr_shift) {                                  \
-    graph_segment_max_body<T, W, MIN>(row_ptr, seg_ptr, perm, msg, out, win, BN, N, e_cap, E, U, lpr_shift);             \
-  }
-LB_SEGMENT_MAX_KERNEL(k_graph_segment_max, false)
-LB_SEGMENT_MAX_KERNEL(k_graph_segment_min, true)
-#undef LB_SEGMENT_MAX_KERNEL
 
 // d_msg[slot][c] = d_out[node][c] where the slot won column c of its node, +0.0 in every other real slot and in the pads.
 template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_segment_max_bwd(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
+__global__ void __launch_bounds__(256) k_graph_segment_max_bwd(lb_glist L, const int32_t* __restrict__ idx,
                                                                const T* __restrict__ d_out, const int32_t* __restrict__ win,
-                                                               T* __restrict__ d_msg, int64_t BN, int N, int B, int e_cap,
-                                                               int E, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
-    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
-    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
-    const bool real = j < nb && base + j < E;
-    int64_t node = real ? idx[base + j] : 0;
-    node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
-    for (int u = lane; u < U; u += lpr) {
-      float d[W], g[W];
-      int32_t w[W];
+                                                               T* __restrict__ d_msg) {
+  const int U = L.U;
+  graph_for_slots(L, idx, nullptr, [&](int64_t r, const lb_gslot& s, int u) {
+    float d[W], g[W];
+    int32_t w[W];
 #pragma unroll
-      for (int k = 0; k < W; ++k) d[k] = 0.f;
-      if (real) {
-        lb_ld<T, W>(d_out + (node * U + u) * W, g);
-        lb_ldi<W>(win + (node * U + u) * W, w);
+    for (int k = 0; k < W; ++k) d[k] = 0.f;
+    if (s.real) {
+      lb_ld<T, W>(d_out + (s.node * U + u) * W, g);
+      lb_ldi<W>(win + (s.node * U + u) * W, w);
 #pragma unroll
-        for (int k = 0; k < W; ++k) d[k] = w[k] == j ? g[k] : 0.f;
-      }
-      lb_st<T, W>(d_msg + (r * U + u) * W, d);
+      for (int k = 0; k < W; ++k) d[k] = w[k] == s.j ? g[k] : 0.f;
     }
-  }
+    lb_st<T, W>(d_msg + (r * U + u) * W, d);
+  });
 }
 
 // y[slot][c] = expf(x[slot][c] - m) / s over the slots of node i: m the maximum as in k_graph_segment_max, s the ordered sum of
 // the exponentials.  The group that owns the node writes the node's slots; the pad slots were zeroed before the launch.
 template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_softmax(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                       const int32_t* __restrict__ perm, const T* __restrict__ x,
-                                                       T* __restrict__ y, int64_t BN, int N, int e_cap, int E, int U,
-                                                       int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
-    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
-    if (R.p0 >= R.p1) continue;
-    for (int u = lane; u < U; u += lpr) {
-      float m[W], s[W], a[W];
-      lb_ld<T, W>(x + (R.edge(R.p0) * U + u) * W, m);
+__global__ void __launch_bounds__(256) k_graph_softmax(lb_glist L, lb_gwalk walk, const T* __restrict__ x, T* __restrict__ y) {
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t, const lb_row& R, int u) {
+    if (R.p0 >= R.p1) return;
+    float m[W], s[W], a[W];
+    lb_ld<T, W>(x + (R.edge(R.p0) * U + u) * W, m);
 #pragma unroll 4
-      for (int p = R.p0 + 1; p < R.p1; ++p) {
-        lb_ld<T, W>(x + (R.edge(p) * U + u) * W, a);
+    for (int p = R.p0 + 1; p < R.p1; ++p) {
+      lb_ld<T, W>(x + (R.edge(p) * U + u) * W, a);
 #pragma unroll
-        for (int k = 0; k < W; ++k)
-          if (lb_beats<false>(a[k], m[k])) m[k] = a[k];
-      }
-      lb_ld<T, W>(x + (R.edge(R.p0) * U + u) * W, a);
-#pragma unroll
-      for (int k = 0; k < W; ++k) s[k] = expf(a[k] - m[k]);
-#pragma unroll 4
-      for (int p = R.p0 + 1; p < R.p1; ++p) {
-        lb_ld<T, W>(x + (R.edge(p) * U + u) * W, a);
-#pragma unroll
-        for (int k = 0; k < W; ++k) s[k] = __fadd_rn(s[k], expf(a[k] - m[k]));
-      }
-#pragma unroll 4
-      for (int p = R.p0; p < R.p1; ++p) {
-        const int64_t o = (R.edge(p) * U + u) * W;
-        lb_ld<T, W>(x + o, a);
-#pragma unroll
-        for (int k = 0; k < W; ++k) a[k] = expf(a[k] - m[k]) / s[k];
-        lb_st<T, W>(y + o, a);
-      }
+      for (int k = 0; k < W; ++k)
+        if (lb_beats<false>(a[k], m[k])) m[k] = a[k];
     }
-  }
+    lb_ld<T, W>(x + (R.edge(R.p0) * U + u) * W, a);
+#pragma unroll
+    for (int k = 0; k < W; ++k) s[k] = expf(a[k] - m[k]);
+#pragma unroll 4
+    for (int p = R.p0 + 1; p < R.p1; ++p) {
+      lb_ld<T, W>(x + (R.edge(p) * U + u) * W, a);
+#pragma unroll
+      for (int k = 0; k < W; ++k) s[k] = __fadd_rn(s[k], expf(a[k] - m[k]));
+    }
+#pragma unroll 4
+    for (int p = R.p0; p < R.p1; ++p) {
+      const int64_t o = (R.edge(p) * U + u) * W;
+      lb_ld<T, W>(x + o, a);
+#pragma unroll
+      for (int k = 0; k < W; ++k) a[k] = expf(a[k] - m[k]) / s[k];
+      lb_st<T, W>(y + o, a);
+    }
+  });
 }
 
 // d_x[slot][c] = y (d_y - sum_k d_y[k] y[k]) over the slots of node i, the sum ordered; the pads were zeroed before the launch.
 template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_softmax_bwd(const int32_t* __restrict__ row_ptr,
-                                                           const int32_t* __restrict__ seg_ptr,
-                                                           const int32_t* __restrict__ perm, const T* __restrict__ y,
-                                                           const T* __restrict__ d_y, T* __restrict__ d_x, int64_t BN,
-                                                           int N, int e_cap, int E, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
-    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
-    if (R.p0 >= R.p1) continue;
-    for (int u = lane; u < U; u += lpr) {
-      float dot[W], a[W], g[W];
-      {
-        const int64_t o = (R.edge(R.p0) * U + u) * W;
-        lb_ld<T, W>(y + o, a);
-        lb_ld<T, W>(d_y + o, g);
+__global__ void __launch_bounds__(256) k_graph_softmax_bwd(lb_glist L, lb_gwalk walk, const T* __restrict__ y,
+                                                           const T* __restrict__ d_y, T* __restrict__ d_x) {
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t, const lb_row& R, int u) {
+    if (R.p0 >= R.p1) return;
+    float dot[W], a[W], g[W];
+    {
+      const int64_t o = (R.edge(R.p0) * U + u) * W;
+      lb_ld<T, W>(y + o, a);
+      lb_ld<T, W>(d_y + o, g);
 #pragma unroll
-        for (int k = 0; k < W; ++k) dot[k] = __fmul_rn(g[k], a[k]);
-      }
-#pragma unroll 4
-      for (int p = R.p0 + 1; p < R.p1; ++p) {
-        const int64_t o = (R.edge(p) * U + u) * W;
-        lb_ld<T, W>(y + o, a);
-        lb_ld<T, W>(d_y + o, g);
-#pragma unroll
-        for (int k = 0; k < W; ++k) dot[k] = __fadd_rn(dot[k], __fmul_rn(g[k], a[k]));
-      }
-#pragma unroll 4
-      for (int p = R.p0; p < R.p1; ++p) {
-        const int64_t o = (R.edge(p) * U + u) * W;
-        lb_ld<T, W>(y + o, a);
-        lb_ld<T, W>(d_y + o, g);
-#pragma unroll
-        for (int k = 0; k < W; ++k) a[k] = __fmul_rn(a[k], g[k] - dot[k]);
-        lb_st<T, W>(d_x + o, a);
-      }
+      for (int k = 0; k < W; ++k) dot[k] = __fmul_rn(g[k], a[k]);
     }
-  }
+#pragma unroll 4
+    for (int p = R.p0 + 1; p < R.p1; ++p) {
+      const int64_t o = (R.edge(p) * U + u) * W;
+      lb_ld<T, W>(y + o, a);
+      lb_ld<T, W>(d_y + o, g);
+#pragma unroll
+      for (int k = 0; k < W; ++k) dot[k] = __fadd_rn(dot[k], __fmul_rn(g[k], a[k]));
+    }
+#pragma unroll 4
+    for (int p = R.p0; p < R.p1; ++p) {
+      const int64_t o = (R.edge(p) * U + u) * W;
+      lb_ld<T, W>(y + o, a);
+      lb_ld<T, W>(d_y + o, g);
+#pragma unroll
+      for (int k = 0; k < W; ++k) a[k] = __fmul_rn(a[k], g[k] - dot[k]);
+      lb_st<T, W>(d_x + o, a);
+    }
+  });
 }
 
 // out[i][h][:] = sum over the slots of node i of alpha[slot][h] v[slot][h][:], alpha = expf(l - m) / s as k_graph_softmax computes
 // it: the product rounded, the adds in ascending slot order from the first term.  A lane owns units of the H D row and runs the
-// max and the sum pass over its head's logits itself; the lane of a head's first unit stores that head's m and s.
+// max and the sum pass over its head's logits itself (kept from one unit of the row to the next while the head stays: hc, m,
+// s); the lane of a head's first unit stores that head's m and s.  That state lives across the units of a row, so this kernel
+// spells the two loops of graph_for out: carried through graph_for's callables (in a struct the head returns, or in captured
+// locals) the same source compiled to a bfloat16 sender walk 4 % slower.
 template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_attend(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                      const int32_t* __restrict__ perm, const T* __restrict__ logits,
+__global__ void __launch_bounds__(256) k_graph_attend(lb_glist L, lb_gwalk walk, const T* __restrict__ logits,
                                                       const T* __restrict__ values, T* __restrict__ out,
-                                                      float* __restrict__ m_out, float* __restrict__ s_out, int64_t BN, int N,
-                                                      int e_cap, int E, int H, int D, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
-    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+                                                      float* __restrict__ m_out, float* __restrict__ s_out, int H, int D) {
+  const int U = L.U;
+  const lb_glanes G = graph_lanes(L);
+  for (int64_t i = G.first; i < L.BN; i += G.stride) {
+    const lb_row R = graph_row(L, walk, i);
     int hc = -1;
     float m = 0.f, s = 1.f;
-    for (int u = lane; u < U; u += lpr) {
+    for (int u = G.lane; u < U; u += G.lpr) {
       const int h = (u * W) / D;
       float acc[W], v[W];
 #pragma unroll
@@ -476,56 +508,42 @@ __global__ void __launch_bounds__(256) k_graph_attend(const int32_t* __restrict_
 // d_values[slot][h][:] = alpha[slot][h] d_out[node][h][:] (one multiplication), +0.0 in the pads; alpha recomputed from the
 // saved m and s of the node.
 template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_attend_dvalues(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
+__global__ void __launch_bounds__(256) k_graph_attend_dvalues(lb_glist L, const int32_t* __restrict__ idx,
                                                               const T* __restrict__ logits, const float* __restrict__ m_in,
                                                               const float* __restrict__ s_in, const T* __restrict__ d_out,
-                                                              T* __restrict__ d_values, int64_t BN, int N, int B, int e_cap,
-                                                              int E, int H, int D, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
-    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
-    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
-    const bool real = j < nb && base + j < E;
-    int64_t node = real ? idx[base + j] : 0;
-    node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
-    for (int u = lane; u < U; u += lpr) {
-      float d[W], g[W];
+                                                              T* __restrict__ d_values, int H, int D) {
+  const int U = L.U;
+  graph_for_slots(L, idx, nullptr, [&](int64_t r, const lb_gslot& s, int u) {
+    float d[W], g[W];
 #pragma unroll
-      for (int k = 0; k < W; ++k) d[k] = 0.f;
-      if (real) {
-        const int h = (u * W) / D;
-        const float al = expf(lb_ld1<T>(logits + r * H + h) - m_in[node * H + h]) / s_in[node * H + h];
-        lb_ld<T, W>(d_out + (node * U + u) * W, g);
+    for (int k = 0; k < W; ++k) d[k] = 0.f;
+    if (s.real) {
+      const int h = (u * W) / D;
+      const float al = expf(lb_ld1<T>(logits + r * H + h) - m_in[s.node * H + h]) / s_in[s.node * H + h];
+      lb_ld<T, W>(d_out + (s.node * U + u) * W, g);
 #pragma unroll
-        for (int k = 0; k < W; ++k) d[k] = __fmul_rn(al, g[k]);
-      }
-      lb_st<T, W>(d_values + (r * U + u) * W, d);
+      for (int k = 0; k < W; ++k) d[k] = __fmul_rn(al, g[k]);
     }
-  }
+    lb_st<T, W>(d_values + (r * U + u) * W, d);
+  });
 }
 
 // t[slot][h] = sum_d d_out[node][h][d] v[slot][h][d], one lane per (slot, head), d ascending; +0.0 in the pads.  t is fp32:
 // for float tensors it IS the d_logits buffer; for bf16 ones it is the engine's buffer, and every slot of d_logits gets +0.0
 // here (k_graph_attend_dlogits then writes the real slots).
 template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_attend_t(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ idx,
-                                                        const T* __restrict__ values, const T* __restrict__ d_out,
-                                                        float* __restrict__ t, T* d_logits, int64_t BN, int N, int B,
-                                                        int e_cap, int E, int H, int D) {
-  const int64_t total = (int64_t)B * e_cap * H, stride = (int64_t)gridDim.x * 256;
+__global__ void __launch_bounds__(256) k_graph_attend_t(lb_glist L, const int32_t* __restrict__ idx, const T* __restrict__ values,
+                                                        const T* __restrict__ d_out, float* __restrict__ t, T* d_logits, int H,
+                                                        int D) {
+  const int64_t total = (int64_t)L.B * L.e_cap * H, stride = (int64_t)gridDim.x * 256;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
     const int64_t r = q / H;
     const int h = (int)(q - r * H);
-    const int b = (int)(r / e_cap), j = (int)(r - (int64_t)b * e_cap);
-    const int base = row_ptr[(int64_t)b * N], nb = row_ptr[(int64_t)(b + 1) * N] - base;
-    const bool real = j < nb && base + j < E;
+    const lb_gslot s = graph_slot(L, r, idx);
     float acc = 0.f;
-    if (real) {
-      int64_t node = idx[base + j];
-      node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);
+    if (s.real) {
       const T* __restrict__ vp = values + (r * H + h) * D;
-      const T* __restrict__ gp = d_out + (node * H + h) * D;
+      const T* __restrict__ gp = d_out + (s.node * H + h) * D;
       float v[W], g[W];
       bool first = true;
       for (int d = 0; d < D; d += W) {
@@ -548,17 +566,14 @@ __global__ void __launch_bounds__(256) k_graph_attend_t(const int32_t* __restric
 // one lane per (node, head).  In place on t for float tensors (d_logits == t); rounded once into d_logits for bf16 ones.  The
 // pad slots hold the +0.0 k_graph_attend_t wrote.
 template <typename T>
-__global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __restrict__ row_ptr,
-                                                              const int32_t* __restrict__ seg_ptr,
-                                                              const int32_t* __restrict__ perm, const T* __restrict__ logits,
+__global__ void __launch_bounds__(256) k_graph_attend_dlogits(lb_glist L, lb_gwalk walk, const T* __restrict__ logits,
                                                               const float* __restrict__ m_in, const float* __restrict__ s_in,
-                                                              const float* t, T* d_logits, int64_t BN, int N, int e_cap,
-                                                              int E, int H) {
-  const int64_t total = BN * H, stride = (int64_t)gridDim.x * 256;
+                                                              const float* t, T* d_logits, int H) {
+  const int64_t total = L.BN * H, stride = (int64_t)gridDim.x * 256;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < total; q += stride) {
     const int64_t i = q / H;
     const int h = (int)(q - i * H);
-    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
+    const lb_row R = graph_row(L, walk, i);
     if (R.p0 >= R.p1) continue;
     const float m = m_in[q], s = s_in[q];
     float dot;
@@ -589,11 +604,10 @@ __global__ void __launch_bounds__(256) k_graph_attend_dlogits(const int32_t* __r
 // One slot's loads for k-chunk k0 .. k0 + KT - 1: the w unit and KT x units (a k past K - 1 re-reads row K - 1; never stored).
 template <typename T, int W, int KT>
 __device__ __forceinline__ void graph_conv_load(const lb_row& R, int p, const int32_t* __restrict__ oidx, const T* __restrict__ x,
-                                                const T* __restrict__ w, int64_t BN, int K, int k0, int U, int u, float (&f)[W],
-                                                float (&a)[KT][W]) {
+                                                const T* __restrict__ w, const lb_glist& L, int K, int k0, int U, int u,
+                                                float (&f)[W], float (&a)[KT][W]) {
   const int64_t e = R.edge(p);
-  int64_t node = oidx[e - R.slot0];
-  node = node < 0 ? 0 : (node >= BN ? BN - 1 : node);   // (an index of the list is a node of the batch: never clamps)
+  const int64_t node = graph_clamp(L, oidx[e - R.slot0]);
   lb_ld<T, W>(w + (e * U + u) * W, f);
 #pragma unroll
   for (int q = 0; q < KT; ++q) {
@@ -602,146 +616,93 @@ __device__ __forceinline__ void graph_conv_load(const lb_row& R, int p, const in
   }
 }
 // out[i][k][:] = sum over the slots of row i, ascending, of fl32(x[other node of the slot][k][:] * w[slot][:]); +0.0 for an empty
-// row.  KT accumulator rows per pass over the slots (1, or 3: a vector feature), SU slots' loads in flight; the adds sequential.
+// row.  KT accumulator rows per pass over the slots (1 for K = 1; 3 for K > 1: a vector feature), SU slots' loads in flight; the
+// adds sequential.
 template <typename T, int W, int KT>
-__device__ __forceinline__ void graph_conv_body(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,
-                                                const int32_t* __restrict__ perm, const int32_t* __restrict__ oidx,
-                                                const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ out,
-                                                int64_t BN, int N, int e_cap, int E, int K, int U, int lpr_shift) {
+__global__ void __launch_bounds__(256) k_graph_conv(lb_glist L, lb_gwalk walk, const int32_t* __restrict__ oidx,
+                                                    const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ out, int K) {
   constexpr int SU = KT == 1 ? 4 : 2;
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t i = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); i < BN; i += stride) {
-    const lb_row R = graph_row(row_ptr, seg_ptr, perm, i, N, e_cap, E);
-    for (int u = lane; u < U; u += lpr) {
-      for (int k0 = 0; k0 < K; k0 += KT) {
-        float s[KT][W], f[SU][W], a[SU][KT][W];
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t i, const lb_row& R, int u) {
+    for (int k0 = 0; k0 < K; k0 += KT) {
+      float s[KT][W], f[SU][W], a[SU][KT][W];
+#pragma unroll
+      for (int q = 0; q < KT; ++q)
+#pragma unroll
+        for (int c = 0; c < W; ++c) s[q][c] = 0.f;
+      int p = R.p0;
+      if (p < R.p1) {   // the sum STARTS from the first product
+        graph_conv_load<T, W, KT>(R, p++, oidx, x, w, L, K, k0, U, u, f[0], a[0]);
 #pragma unroll
         for (int q = 0; q < KT; ++q)
 #pragma unroll
-          for (int c = 0; c < W; ++c) s[q][c] = 0.f;
-        int p = R.p0;
-        if (p < R.p1) {   // the sum STARTS from the first product
-          graph_conv_load<T, W, KT>(R, p++, oidx, x, w, BN, K, k0, U, u, f[0], a[0]);
-#pragma unroll
-          for (int q = 0; q < KT; ++q)
-#pragma unroll
-            for (int c = 0; c < W; ++c) s[q][c] = __fmul_rn(a[0][q][c], f[0][c]);
-        }
-        for (; p + SU <= R.p1; p += SU) {
-#pragma unroll
-          for (int t = 0; t < SU; ++t) graph_conv_load<T, W, KT>(R, p + t, oidx, x, w, BN, K, k0, U, u, f[t], a[t]);
-#pragma unroll
-          for (int t = 0; t < SU; ++t)
-#pragma unroll
-            for (int q = 0; q < KT; ++q)
-#pragma unroll
-              for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[t][q][c], f[t][c]));
-        }
-        for (; p < R.p1; ++p) {
-          graph_conv_load<T, W, KT>(R, p, oidx, x, w, BN, K, k0, U, u, f[0], a[0]);
-#pragma unroll
-          for (int q = 0; q < KT; ++q)
-#pragma unroll
-            for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[0][q][c], f[0][c]));
-        }
-#pragma unroll
-        for (int q = 0; q < KT; ++q)
-          if (k0 + q < K) lb_st<T, W>(out + ((i * K + k0 + q) * U + u) * W, s[q]);
+          for (int c = 0; c < W; ++c) s[q][c] = __fmul_rn(a[0][q][c], f[0][c]);
       }
+      for (; p + SU <= R.p1; p += SU) {
+#pragma unroll
+        for (int t = 0; t < SU; ++t) graph_conv_load<T, W, KT>(R, p + t, oidx, x, w, L, K, k0, U, u, f[t], a[t]);
+#pragma unroll
+        for (int t = 0; t < SU; ++t)
+#pragma unroll
+          for (int q = 0; q < KT; ++q)
+#pragma unroll
+            for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[t][q][c], f[t][c]));
+      }
+      for (; p < R.p1; ++p) {
+        graph_conv_load<T, W, KT>(R, p, oidx, x, w, L, K, k0, U, u, f[0], a[0]);
+#pragma unroll
+        for (int q = 0; q < KT; ++q)
+#pragma unroll
+          for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[0][q][c], f[0][c]));
+      }
+#pragma unroll
+      for (int q = 0; q < KT; ++q)
+        if (k0 + q < K) lb_st<T, W>(out + ((i * K + k0 + q) * U + u) * W, s[q]);
     }
-  }
+  });
 }
-#define LB_CONV_KERNEL(name, KT)                                                                                          \
-  template <typename T, int W>                                                                                            \
-  __global__ void __launch_bounds__(256) name(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ seg_ptr,  \
-                                              const int32_t* __restrict__ perm, const int32_t* __restrict__ oidx,        \
-                                              const T* __restrict__ x, const T* __restrict__ w, T* __restrict__ out,     \
-                                              int64_t BN, int N, int e_cap, int E, int K, int U, int lpr_shift) {        \
-    graph_conv_body<T, W, KT>(row_ptr, seg_ptr, perm, oidx, x, w, out, BN, N, e_cap, E, K, U, lpr_shift);                \
-  }
-LB_CONV_KERNEL(k_graph_conv, 1)      // K = 1
-LB_CONV_KERNEL(k_graph_conv_k3, 3)   // K > 1, three k at a time
-#undef LB_CONV_KERNEL
 
-// out[slot][:] = fl32(a[a node][0][:] * b[b node][0][:]) + fl32(a[..][1][:] * b[..][1][:]) + ... (k ascending, the first product
-// starts the sum) in the real slots, +0.0 in the pads.  With K = 1 the plain product; with K > 1 conv's d_w.
-template <typename T, int W, bool ONE>
-__device__ __forceinline__ void graph_pair_mul_body(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ aidx,
-                                                    const int32_t* __restrict__ bidx, const T* __restrict__ a,
-                                                    const T* __restrict__ b, T* __restrict__ out, int64_t BN, int N, int B,
-                                                    int e_cap, int E, int K_, int U, int lpr_shift) {
-  const int K = ONE ? 1 : K_;   // (K = 1: no k loop, the registers of the plain product)
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
-    const int t = (int)(r / e_cap), j = (int)(r - (int64_t)t * e_cap);
-    const int base = row_ptr[(int64_t)t * N], nb = row_ptr[(int64_t)(t + 1) * N] - base;
-    const bool real = j < nb && base + j < E;
-    int64_t na = real ? aidx[base + j] : 0, nn = real ? bidx[base + j] : 0;
-    na = na < 0 ? 0 : (na >= BN ? BN - 1 : na);
-    nn = nn < 0 ? 0 : (nn >= BN ? BN - 1 : nn);
-    for (int u = lane; u < U; u += lpr) {
-      float s[W], fa[W], fb[W];
+// The pair ops: a, b (B N, K, C), one unit of a's row of the slot's a node combined with b's of its b node, +0.0 in the pads.
+//   MUL: out[slot][:] = fl32(a[a node][0][:] * b[b node][0][:]) + fl32(a[..][1][:] * b[..][1][:]) + ... (k ascending, the first
+//        product starts the sum).  SUM_K false is K = 1, the plain product (no k loop, its registers); true is conv's d_w.
+//   ADD: out[slot][:] = fl32(a[a node][:] + b[b node][:]) (K = 1).
+template <typename T, int W, bool MUL, bool SUM_K>
+__device__ __forceinline__ void graph_pair_body(const lb_glist& L, const int32_t* __restrict__ aidx,
+                                                const int32_t* __restrict__ bidx, const T* __restrict__ a,
+                                                const T* __restrict__ b, T* __restrict__ out, int K_) {
+  const int K = SUM_K ? K_ : 1, U = L.U;
+  graph_for_slots(L, aidx, bidx, [&](int64_t r, const lb_gslot& t, int u) {
+    const int64_t na = t.node, nn = t.other;
+    float s[W], fa[W], fb[W];
 #pragma unroll
-      for (int c = 0; c < W; ++c) s[c] = 0.f;
-      if (real) {
-        lb_ld<T, W>(a + (na * K * U + u) * W, fa);
-        lb_ld<T, W>(b + (nn * K * U + u) * W, fb);
+    for (int c = 0; c < W; ++c) s[c] = 0.f;
+    if (t.real) {
+      lb_ld<T, W>(a + (na * K * U + u) * W, fa);
+      lb_ld<T, W>(b + (nn * K * U + u) * W, fb);
 #pragma unroll
-        for (int c = 0; c < W; ++c) s[c] = __fmul_rn(fa[c], fb[c]);
+      for (int c = 0; c < W; ++c) s[c] = MUL ? __fmul_rn(fa[c], fb[c]) : __fadd_rn(fa[c], fb[c]);
 #pragma unroll 4
-        for (int k = 1; k < K; ++k) {
-          lb_ld<T, W>(a + ((na * K + k) * U + u) * W, fa);
-          lb_ld<T, W>(b + ((nn * K + k) * U + u) * W, fb);
+      for (int k = 1; k < K; ++k) {
+        lb_ld<T, W>(a + ((na * K + k) * U + u) * W, fa);
+        lb_ld<T, W>(b + ((nn * K + k) * U + u) * W, fb);
 #pragma unroll
-          for (int c = 0; c < W; ++c) s[c] = __fadd_rn(s[c], __fmul_rn(fa[c], fb[c]));
-        }
+        for (int c = 0; c < W; ++c) s[c] = __fadd_rn(s[c], __fmul_rn(fa[c], fb[c]));
       }
-      lb_st<T, W>(out + (r * U + u) * W, s);
     }
-  }
+    lb_st<T, W>(out + (r * U + u) * W, s);
+  });
 }
-#define LB_PAIR_MUL_KERNEL(name, ONE)                                                                                      \
-  template <typename T, int W>                                                                                             \
-  __global__ void __launch_bounds__(256) name(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ aidx,      \
-                                              const int32_t* __restrict__ bidx, const T* __restrict__ a,                  \
-                                              const T* __restrict__ b, T* __restrict__ out, int64_t BN, int N, int B,     \
-                                              int e_cap, int E, int K, int U, int lpr_shift) {                            \
-    graph_pair_mul_body<T, W, ONE>(row_ptr, aidx, bidx, a, b, out, BN, N, B, e_cap, E, K, U, lpr_shift);                  \
-  }
-LB_PAIR_MUL_KERNEL(k_graph_pair_mul, true)      // K = 1: the plain product
-LB_PAIR_MUL_KERNEL(k_graph_pair_mul_k, false)   // K > 1: the k-sum (conv's d_w)
-#undef LB_PAIR_MUL_KERNEL
-
-// out[slot][:] = fl32(a[a node][:] + b[b node][:]) in the real slots, +0.0 in the pads.
-template <typename T, int W>
-__global__ void __launch_bounds__(256) k_graph_pair_add(const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ aidx,
+template <typename T, int W, bool SUM_K>
+__global__ void __launch_bounds__(256) k_graph_pair_mul(lb_glist L, const int32_t* __restrict__ aidx,
                                                         const int32_t* __restrict__ bidx, const T* __restrict__ a,
-                                                        const T* __restrict__ b, T* __restrict__ out, int64_t BN, int N, int B,
-                                                        int e_cap, int E, int U, int lpr_shift) {
-  const int lpr = 1 << lpr_shift, lane = threadIdx.x & (lpr - 1);
-  const int64_t rows = (int64_t)B * e_cap, stride = (int64_t)gridDim.x * (256 >> lpr_shift);
-  for (int64_t r = (int64_t)blockIdx.x * (256 >> lpr_shift) + (threadIdx.x >> lpr_shift); r < rows; r += stride) {
-    const int t = (int)(r / e_cap), j = (int)(r - (int64_t)t * e_cap);
-    const int base = row_ptr[(int64_t)t * N], nb = row_ptr[(int64_t)(t + 1) * N] - base;
-    const bool real = j < nb && base + j < E;
-    int64_t na = real ? aidx[base + j] : 0, nn = real ? bidx[base + j] : 0;
-    na = na < 0 ? 0 : (na >= BN ? BN - 1 : na);
-    nn = nn < 0 ? 0 : (nn >= BN ? BN - 1 : nn);
-    for (int u = lane; u < U; u += lpr) {
-      float s[W], fa[W], fb[W];
-#pragma unroll
-      for (int c = 0; c < W; ++c) s[c] = 0.f;
-      if (real) {
-        lb_ld<T, W>(a + (na * U + u) * W, fa);
-        lb_ld<T, W>(b + (nn * U + u) * W, fb);
-#pragma unroll
-        for (int c = 0; c < W; ++c) s[c] = __fadd_rn(fa[c], fb[c]);
-      }
-      lb_st<T, W>(out + (r * U + u) * W, s);
-    }
-  }
+                                                        const T* __restrict__ b, T* __restrict__ out, int K) {
+  graph_pair_body<T, W, true, SUM_K>(L, aidx, bidx, a, b, out, K);
+}
+template <typename T, int W>
+__global__ void __launch_bounds__(256) k_graph_pair_add(lb_glist L, const int32_t* __restrict__ aidx,
+                                                        const int32_t* __restrict__ bidx, const T* __restrict__ a,
+                                                        const T* __restrict__ b, T* __restrict__ out) {
+  graph_pair_body<T, W, false, false>(L, aidx, bidx, a, b, out, 1);
 }
 
 // ------------------------------------------------------------------------------------------------ feature transpose
@@ -951,49 +912,71 @@ static int graph_entry(lb_engine* e, const char* entry, int32_t role, int32_t dt
   if (role && view) LB_TRY(graph_sender_view(e));
   return LB_OK;
 }
-// kernel<GT, W> for the call's dtype and W (both in scope); the arguments name the element type as GT.  GRAPH_LAUNCH_HD also
-// has the 8-byte bf16 units of attend.
-#define GRAPH_LAUNCH_ONE(kernel, T_, W_, blocks, ...)                                         \
-  {                                                                                           \
-    typedef T_ GT;                                                                            \
-    hipLaunchKernelGGL((kernel<GT, W_>), dim3(blocks), dim3(256), 0, e->stream, __VA_ARGS__); \
+
+// One launch's plan: the list descriptor with the op's units (U = cols / W) and lanes per row, the walk of `role` and its two
+// compact index lists, the unit width W (graph_width over `span` and `ptrs`) and the grid.  Rows: a lane group per node or per
+// padded slot.  (The flat kernels - degree, attend_t, attend_dlogits: one lane per output element - take graph_list /
+// graph_walk as they are.)
+enum lb_grows { LB_NODES, LB_SLOTS };
+struct lb_gplan {
+  lb_glist L;
+  lb_gwalk walk;
+  const int32_t *idx, *oidx;   // the node of `role` per compact edge, and the other one
+  int W;
+  unsigned blocks;
+};
+static lb_glist graph_list(const lb_engine* e, int U, int lpr_shift) {
+  return lb_glist{e->row_ptr, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, lpr_shift};
+}
+static lb_gwalk graph_walk(const lb_engine* e, int32_t role) {
+  return lb_gwalk{role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr};
+}
+static lb_gplan graph_plan(const lb_engine* e, int32_t role, int32_t dtype, lb_grows rows, int cols, int span, bool half_units,
+                           std::initializer_list<const void*> ptrs) {
+  const int64_t n = rows == LB_NODES ? e->BN : (int64_t)e->g.B * e->e_cap;
+  lb_gplan P{};
+  P.W = graph_width(dtype, span, half_units, ptrs);
+  const int U = cols / P.W, sh = graph_lpr_shift(U);
+  P.L = graph_list(e, U, sh);
+  P.walk = graph_walk(e, role);
+  P.idx = role ? e->senders : e->receivers;
+  P.oidx = role ? e->receivers : e->senders;
+  P.blocks = graph_blocks(n, sh);
+  return P;
+}
+// f(T{}, lb_w<W>{}) with the element type and the unit width of the call as types: (float, 4 | 1), (lb_bf16, 8 | 1) and, for the
+// ops that have them (HALF: attend), the 8-byte bf16 units (lb_bf16, 4).  f launches; its launch error is the result.
+template <int W>
+using lb_w = std::integral_constant<int, W>;
+template <bool HALF = false, typename F>
+static int graph_dispatch(int32_t dtype, int W, F f) {
+  if (dtype == LB_DTYPE_F32 && W == 4) {
+    f(float{}, lb_w<4>{});
+  } else if (dtype == LB_DTYPE_F32) {
+    f(float{}, lb_w<1>{});
+  } else if (W == 8) {
+    f(lb_bf16{}, lb_w<8>{});
+  } else if (HALF && W == 4) {
+    if constexpr (HALF) f(lb_bf16{}, lb_w<4>{});
+  } else {
+    f(lb_bf16{}, lb_w<1>{});
   }
-#define GRAPH_LAUNCH_ANY(kernel, HALF, blocks, ...)                                     \
-  do {                                                                                  \
-    if (dtype == LB_DTYPE_F32 && W == 4)                                                \
-      GRAPH_LAUNCH_ONE(kernel, float, 4, blocks, __VA_ARGS__)                           \
-    else if (dtype == LB_DTYPE_F32)                                                     \
-      GRAPH_LAUNCH_ONE(kernel, float, 1, blocks, __VA_ARGS__)                           \
-    else if (W == 8)                                                                    \
-      GRAPH_LAUNCH_ONE(kernel, lb_bf16, 8, blocks, __VA_ARGS__)                         \
-    HALF(kernel, blocks, __VA_ARGS__)                                                   \
-    else GRAPH_LAUNCH_ONE(kernel, lb_bf16, 1, blocks, __VA_ARGS__)                      \
-    LB_HIP(hipGetLastError());                                                          \
-  } while (0)
-#define GRAPH_NO_HALF(kernel, blocks, ...)
-#define GRAPH_HALF(kernel, blocks, ...) else if (W == 4) GRAPH_LAUNCH_ONE(kernel, lb_bf16, 4, blocks, __VA_ARGS__)
-#define GRAPH_LAUNCH(kernel, blocks, ...) GRAPH_LAUNCH_ANY(kernel, GRAPH_NO_HALF, blocks, __VA_ARGS__)
-#define GRAPH_LAUNCH_HD(kernel, blocks, ...) GRAPH_LAUNCH_ANY(kernel, GRAPH_HALF, blocks, __VA_ARGS__)
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+template <typename Kernel, typename... Args>
+static void graph_launch(lb_engine* e, unsigned blocks, Kernel kernel, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, e->stream, args...);
+}
 
 static int graph_gather(lb_engine* e, const char* entry, int32_t role, const void* x, void* out, int32_t C, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, x && out, C, 1, false));
-  const int32_t* idx = role ? e->senders : e->receivers;
   // a bit copy: 16-byte units (4 floats, 8 bf16) when the row is made of them and the pointers are aligned, elements otherwise
-  const int W = graph_width(dtype, C, false, {x, out});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  const unsigned blocks = graph_blocks((int64_t)e->g.B * e->e_cap, sh);
-#define GRAPH_GATHER(T_)                                                                                                 \
-  hipLaunchKernelGGL(k_graph_gather<T_>, dim3(blocks), dim3(256), 0, e->stream, e->row_ptr, idx, x, out, e->BN, e->g.N, \
-                     e->g.B, e->e_cap, (int)e->graph_E, U, sh)
-  if (W > 1)
-    GRAPH_GATHER(f32x4);
-  else if (dtype == LB_DTYPE_F32)
-    GRAPH_GATHER(float);
-  else
-    GRAPH_GATHER(lb_bf16);
-#undef GRAPH_GATHER
-  LB_HIP(hipGetLastError());
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, role, dtype, LB_SLOTS, C, C, false, {x, out});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using V = std::conditional_t<(decltype(w)::value > 1), f32x4, decltype(t)>;
+    graph_launch(e, P.blocks, k_graph_gather<V>, P.L, P.idx, x, out);
+  });
 }
 extern "C" int lb_graph_gather_t(lb_engine* e, int32_t role, const void* x_dev, void* out_dev, int32_t C, int32_t dtype) {
   return graph_gather(e, "lb_graph_gather_t", role, x_dev, out_dev, C, dtype);
@@ -1004,11 +987,12 @@ extern "C" int lb_graph_gather(lb_engine* e, int32_t role, const float* x_dev, f
 
 static int graph_segment_sum(lb_engine* e, const char* entry, int32_t role, const void* msg, void* out, int32_t C, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, msg && out, C, 1));
-  const int W = graph_width(dtype, C, false, {msg, out});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  GRAPH_LAUNCH(k_graph_segment_sum, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-               role ? e->snd_perm : nullptr, (const GT*)msg, (GT*)out, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {msg, out});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_segment_sum<T, decltype(w)::value>, e->row_ptr, P.walk.seg_ptr, P.walk.perm, (const T*)msg,
+                 (T*)out, e->BN, e->g.N, e->e_cap, (int)e->graph_E, P.L.U, P.L.lpr_shift);
+  });
 }
 extern "C" int lb_graph_segment_sum_t(lb_engine* e, int32_t role, const void* msg_dev, void* out_dev, int32_t C, int32_t dtype) {
   return graph_segment_sum(e, "lb_graph_segment_sum_t", role, msg_dev, out_dev, C, dtype);
@@ -1022,8 +1006,7 @@ extern "C" int32_t lb_graph_sender_sorts(lb_engine* e) { return e ? e->snd_sorts
 // ---- the attention ops' entries
 extern "C" int lb_graph_degree(lb_engine* e, int32_t role, int32_t* out_dev) {
   LB_TRY(graph_entry(e, "lb_graph_degree", role, LB_DTYPE_F32, out_dev != nullptr, 1, 1));
-  hipLaunchKernelGGL(k_graph_degree, GRID1(e->BN), 0, e->stream, e->row_ptr, role ? e->snd_ptr : e->row_ptr, out_dev, e->BN,
-                     e->g.N, e->e_cap, (int)e->graph_E);
+  hipLaunchKernelGGL(k_graph_degree, GRID1(e->BN), 0, e->stream, graph_list(e, 0, 0), graph_walk(e, role), out_dev);
   LB_HIP(hipGetLastError());
   return LB_OK;
 }
@@ -1031,18 +1014,13 @@ extern "C" int lb_graph_degree(lb_engine* e, int32_t role, int32_t* out_dev) {
 static int graph_segment_max(lb_engine* e, const char* entry, bool minimum, int32_t role, const void* msg, void* out, int32_t* win,
                              int32_t C, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, msg && out && win, C, 1));
-  const int32_t* seg = role ? e->snd_ptr : e->row_ptr;
-  const int32_t* perm = role ? e->snd_perm : nullptr;
-  const int W = graph_width(dtype, C, false, {msg, out, win});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  const unsigned blocks = graph_blocks(e->BN, sh);
-  if (minimum)
-    GRAPH_LAUNCH(k_graph_segment_min, blocks, e->row_ptr, seg, perm, (const GT*)msg, (GT*)out, win, e->BN, e->g.N, e->e_cap,
-                 (int)e->graph_E, U, sh);
-  else
-    GRAPH_LAUNCH(k_graph_segment_max, blocks, e->row_ptr, seg, perm, (const GT*)msg, (GT*)out, win, e->BN, e->g.N, e->e_cap,
-                 (int)e->graph_E, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {msg, out, win});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    graph_launch(e, P.blocks, minimum ? k_graph_segment_max<T, W, true> : k_graph_segment_max<T, W, false>, P.L, P.walk,
+                 (const T*)msg, (T*)out, win);
+  });
 }
 extern "C" int lb_graph_segment_max_t(lb_engine* e, int32_t role, const void* msg_dev, void* out_dev, int32_t* win_dev, int32_t C,
                                       int32_t dtype) {
@@ -1062,12 +1040,11 @@ extern "C" int lb_graph_segment_min(lb_engine* e, int32_t role, const float* msg
 static int graph_segment_max_backward(lb_engine* e, const char* entry, int32_t role, const void* d_out, const int32_t* win,
                                       void* d_msg, int32_t C, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, d_out && win && d_msg, C, 1));
-  const int32_t* idx = role ? e->senders : e->receivers;
-  const int W = graph_width(dtype, C, false, {d_out, win, d_msg});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  GRAPH_LAUNCH(k_graph_segment_max_bwd, graph_blocks((int64_t)e->g.B * e->e_cap, sh), e->row_ptr, idx, (const GT*)d_out, win,
-               (GT*)d_msg, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, role, dtype, LB_SLOTS, C, C, false, {d_out, win, d_msg});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_segment_max_bwd<T, decltype(w)::value>, P.L, P.idx, (const T*)d_out, win, (T*)d_msg);
+  });
 }
 extern "C" int lb_graph_segment_max_backward_t(lb_engine* e, int32_t role, const void* d_out_dev, const int32_t* win_dev,
                                                void* d_msg_dev, int32_t C, int32_t dtype) {
@@ -1081,12 +1058,12 @@ extern "C" int lb_graph_segment_max_backward(lb_engine* e, int32_t role, const f
 static int graph_segment_softmax(lb_engine* e, const char* entry, int32_t role, const void* logits, void* out, int32_t C,
                                  int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, logits && out, C, 1));
-  const int W = graph_width(dtype, C, false, {logits, out});
-  const int U = C / W, sh = graph_lpr_shift(U);
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {logits, out});
   LB_HIP(hipMemsetAsync(out, 0, graph_esize(dtype) * (size_t)e->g.B * e->e_cap * C, e->stream));   // the pad slots: +0.0
-  GRAPH_LAUNCH(k_graph_softmax, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-               role ? e->snd_perm : nullptr, (const GT*)logits, (GT*)out, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_softmax<T, decltype(w)::value>, P.L, P.walk, (const T*)logits, (T*)out);
+  });
 }
 extern "C" int lb_graph_segment_softmax_t(lb_engine* e, int32_t role, const void* logits_dev, void* out_dev, int32_t C,
                                           int32_t dtype) {
@@ -1099,13 +1076,12 @@ extern "C" int lb_graph_segment_softmax(lb_engine* e, int32_t role, const float*
 static int graph_segment_softmax_backward(lb_engine* e, const char* entry, int32_t role, const void* y, const void* d_y, void* d_x,
                                           int32_t C, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, y && d_y && d_x, C, 1));
-  const int W = graph_width(dtype, C, false, {y, d_y, d_x});
-  const int U = C / W, sh = graph_lpr_shift(U);
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {y, d_y, d_x});
   LB_HIP(hipMemsetAsync(d_x, 0, graph_esize(dtype) * (size_t)e->g.B * e->e_cap * C, e->stream));
-  GRAPH_LAUNCH(k_graph_softmax_bwd, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-               role ? e->snd_perm : nullptr, (const GT*)y, (const GT*)d_y, (GT*)d_x, e->BN, e->g.N, e->e_cap, (int)e->graph_E, U,
-               sh);
-  return LB_OK;
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_softmax_bwd<T, decltype(w)::value>, P.L, P.walk, (const T*)y, (const T*)d_y, (T*)d_x);
+  });
 }
 extern "C" int lb_graph_segment_softmax_backward_t(lb_engine* e, int32_t role, const void* y_dev, const void* d_y_dev,
                                                    void* d_x_dev, int32_t C, int32_t dtype) {
@@ -1120,12 +1096,12 @@ static int graph_attend(lb_engine* e, const char* entry, int32_t role, const voi
                         float* m, float* s, int32_t H, int32_t D, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, logits && values && out && m && s, H, D));
   if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "%s: H %d x D %d columns", entry, H, D);
-  const int W = graph_width(dtype, D, true, {values, out});
-  const int U = H * D / W, sh = graph_lpr_shift(U);
-  GRAPH_LAUNCH_HD(k_graph_attend, graph_blocks(e->BN, sh), e->row_ptr, role ? e->snd_ptr : e->row_ptr,
-                  role ? e->snd_perm : nullptr, (const GT*)logits, (const GT*)values, (GT*)out, m, s, e->BN, e->g.N, e->e_cap,
-                  (int)e->graph_E, H, D, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, H * D, D, true, {values, out});
+  return graph_dispatch<true>(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_attend<T, decltype(w)::value>, P.L, P.walk, (const T*)logits, (const T*)values, (T*)out, m,
+                 s, H, D);
+  });
 }
 extern "C" int lb_graph_attend_t(lb_engine* e, int32_t role, const void* logits_dev, const void* values_dev, void* out_dev,
                                  float* m_dev, float* s_dev, int32_t H, int32_t D, int32_t dtype) {
@@ -1141,7 +1117,6 @@ static int graph_attend_backward(lb_engine* e, const char* entry, int32_t role, 
                                  int32_t D, int32_t dtype) {
   LB_TRY(graph_entry(e, entry, role, dtype, logits && values && m && s && d_out && d_logits && d_values, H, D));
   if ((int64_t)H * D > INT32_MAX) return lb_fail(LB_ERR_ARG, "%s: H %d x D %d columns", entry, H, D);
-  const int32_t* idx = role ? e->senders : e->receivers;
   const int64_t slots = (int64_t)e->g.B * e->e_cap;
   // t (slots, H) fp32: the d_logits buffer itself for float tensors, the engine's buffer for bf16 ones (t is never rounded)
   float* t = (float*)d_logits;
@@ -1150,28 +1125,24 @@ static int graph_attend_backward(lb_engine* e, const char* entry, int32_t role, 
       LB_TRY(lb_regrow(e->stream, &e->graph_t_cap, slots * H + slots * H / 8, [&](int64_t n) { return e->mem.get(&e->graph_t, (size_t)n); }));
     t = e->graph_t;
   }
-  {
-    const int W = graph_width(dtype, D, true, {d_out, d_values});
-    const int U = H * D / W, sh = graph_lpr_shift(U);
-    GRAPH_LAUNCH_HD(k_graph_attend_dvalues, graph_blocks(slots, sh), e->row_ptr, idx, (const GT*)logits, m, s, (const GT*)d_out,
-                    (GT*)d_values, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, H, D, U, sh);
-  }
-  {
-    const int W = graph_width(dtype, D, true, {values, d_out});
-    GRAPH_LAUNCH_HD(k_graph_attend_t, graph_blocks1(slots * H), e->row_ptr, idx, (const GT*)values, (const GT*)d_out, t,
-                    (GT*)d_logits, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, H, D);
-  }
-#define GRAPH_DLOGITS(T_)                                                                                                    \
-  hipLaunchKernelGGL(k_graph_attend_dlogits<T_>, dim3(graph_blocks1(e->BN * H)), dim3(256), 0, e->stream, e->row_ptr,      \
-                     role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, (const T_*)logits, m, s, t, (T_*)d_logits, \
-                     e->BN, e->g.N, e->e_cap, (int)e->graph_E, H)
-  if (dtype == LB_DTYPE_F32)
-    GRAPH_DLOGITS(float);
-  else
-    GRAPH_DLOGITS(lb_bf16);
-#undef GRAPH_DLOGITS
-  LB_HIP(hipGetLastError());
-  return LB_OK;
+  const lb_gplan Pv = graph_plan(e, role, dtype, LB_SLOTS, H * D, D, true, {d_out, d_values});
+  LB_TRY(graph_dispatch<true>(dtype, Pv.W, [&](auto t_, auto w) {
+    using T = decltype(t_);
+    graph_launch(e, Pv.blocks, k_graph_attend_dvalues<T, decltype(w)::value>, Pv.L, Pv.idx, (const T*)logits, m, s, (const T*)d_out,
+                 (T*)d_values, H, D);
+  }));
+  // the two flat kernels - one lane per (slot, head), then per (node, head): no units, no lanes per row
+  const lb_glist L = graph_list(e, 0, 0);
+  LB_TRY(graph_dispatch<true>(dtype, graph_width(dtype, D, true, {values, d_out}), [&](auto t_, auto w) {
+    using T = decltype(t_);
+    graph_launch(e, graph_blocks1(slots * H), k_graph_attend_t<T, decltype(w)::value>, L, Pv.idx, (const T*)values,
+                 (const T*)d_out, t, (T*)d_logits, H, D);
+  }));
+  return graph_dispatch(dtype, 1, [&](auto t_, auto) {
+    using T = decltype(t_);
+    graph_launch(e, graph_blocks1(e->BN * H), k_graph_attend_dlogits<T>, L, graph_walk(e, role), (const T*)logits, m, s,
+                 (const float*)t, (T*)d_logits, H);
+  });
 }
 extern "C" int lb_graph_attend_backward_t(lb_engine* e, int32_t role, const void* logits_dev, const void* values_dev,
                                           const float* m_dev, const float* s_dev, const void* d_out_dev, void* d_logits_dev,
@@ -1192,44 +1163,37 @@ extern "C" int lb_graph_conv(lb_engine* e, int32_t role, const void* x_dev, cons
   // the sender view only where sender rows are walked (role 1); the other node of a slot comes from the compact list
   LB_TRY(graph_entry(e, "lb_graph_conv", role, dtype, x_dev && w_dev && out_dev, K, C));
   if ((int64_t)K * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_conv: K %d x C %d columns", K, C);
-  const int32_t* oidx = role ? e->receivers : e->senders;
-  const int W = graph_width(dtype, C, false, {x_dev, w_dev, out_dev});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  const unsigned blocks = graph_blocks(e->BN, sh);
-  if (K == 1)
-    GRAPH_LAUNCH(k_graph_conv, blocks, e->row_ptr, role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, oidx,
-                 (const GT*)x_dev, (const GT*)w_dev, (GT*)out_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, K, U, sh);
-  else
-    GRAPH_LAUNCH(k_graph_conv_k3, blocks, e->row_ptr, role ? e->snd_ptr : e->row_ptr, role ? e->snd_perm : nullptr, oidx,
-                 (const GT*)x_dev, (const GT*)w_dev, (GT*)out_dev, e->BN, e->g.N, e->e_cap, (int)e->graph_E, K, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {x_dev, w_dev, out_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;   // K > 1: three k at a time
+    graph_launch(e, P.blocks, K == 1 ? k_graph_conv<T, W, 1> : k_graph_conv<T, W, 3>, P.L, P.walk, P.oidx, (const T*)x_dev,
+                 (const T*)w_dev, (T*)out_dev, K);
+  });
 }
 
 extern "C" int lb_graph_pair_mul(lb_engine* e, int32_t a_role, const void* a_dev, const void* b_dev, void* out_dev, int32_t K,
                                  int32_t C, int32_t dtype) {
   LB_TRY(graph_entry(e, "lb_graph_pair_mul", a_role, dtype, a_dev && b_dev && out_dev, K, C, false));   // edge-parallel: no view
   if ((int64_t)K * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_pair_mul: K %d x C %d columns", K, C);
-  const int W = graph_width(dtype, C, false, {a_dev, b_dev, out_dev});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  const unsigned blocks = graph_blocks((int64_t)e->g.B * e->e_cap, sh);
-  if (K == 1)
-    GRAPH_LAUNCH(k_graph_pair_mul, blocks, e->row_ptr, a_role ? e->senders : e->receivers, a_role ? e->receivers : e->senders,
-                 (const GT*)a_dev, (const GT*)b_dev, (GT*)out_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, K, U, sh);
-  else
-    GRAPH_LAUNCH(k_graph_pair_mul_k, blocks, e->row_ptr, a_role ? e->senders : e->receivers, a_role ? e->receivers : e->senders,
-                 (const GT*)a_dev, (const GT*)b_dev, (GT*)out_dev, e->BN, e->g.N, e->g.B, e->e_cap, (int)e->graph_E, K, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, a_role, dtype, LB_SLOTS, C, C, false, {a_dev, b_dev, out_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    graph_launch(e, P.blocks, K == 1 ? k_graph_pair_mul<T, W, false> : k_graph_pair_mul<T, W, true>, P.L, P.idx, P.oidx,
+                 (const T*)a_dev, (const T*)b_dev, (T*)out_dev, K);
+  });
 }
 
 extern "C" int lb_graph_pair_add(lb_engine* e, int32_t a_role, const void* a_dev, const void* b_dev, void* out_dev, int32_t C,
                                  int32_t dtype) {
   LB_TRY(graph_entry(e, "lb_graph_pair_add", a_role, dtype, a_dev && b_dev && out_dev, C, 1, false));
-  const int W = graph_width(dtype, C, false, {a_dev, b_dev, out_dev});
-  const int U = C / W, sh = graph_lpr_shift(U);
-  GRAPH_LAUNCH(k_graph_pair_add, graph_blocks((int64_t)e->g.B * e->e_cap, sh), e->row_ptr, a_role ? e->senders : e->receivers,
-               a_role ? e->receivers : e->senders, (const GT*)a_dev, (const GT*)b_dev, (GT*)out_dev, e->BN, e->g.N, e->g.B,
-               e->e_cap, (int)e->graph_E, U, sh);
-  return LB_OK;
+  const lb_gplan P = graph_plan(e, a_role, dtype, LB_SLOTS, C, C, false, {a_dev, b_dev, out_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_pair_add<T, decltype(w)::value>, P.L, P.idx, P.oidx, (const T*)a_dev, (const T*)b_dev,
+                 (T*)out_dev);
+  });
 }
 
 extern "C" int lb_graph_features_backward(lb_engine* e, const float* d_abs_pos, const float* d_vel_hist, const float* d_vel_mag,

@@ -32,6 +32,51 @@ def _n_strided(n: int, stride: int) -> int:
     return (n + stride - 1) // stride if stride >= 1 and n >= 1 else 0
 
 
+def _graph_ops():
+    """The lb_graph_* entries (include/lbhip.h) as a table for RolloutEngine._graph_call - symbol: (library entry, inputs,
+    outputs, sizes) in the entry's argument order.  An input is (shape, dtype): a shape entry is 1, "nodes" (B N), "slots" (B
+    E_cap), a size the caller fixes, or the name of a free size >= 1 that the first input which has it binds; dtype None marks
+    a data tensor - float32 or bfloat16, one dtype for the whole call, whose code the entry then takes last.  `sizes` names
+    the free sizes the entry takes; a trailing True says that an input may be None (a null pointer).  An output is (shape,
+    dtype, like): like is the index, among the inputs followed by the earlier outputs, of a tensor of its shape and dtype, or
+    -1."""
+    nc, sc, sh, shd, nh, nhd, nkc = ("nodes", "C"), ("slots", "C"), ("slots", "H"), ("slots", "H", "D"), ("nodes", "H"), \
+        ("nodes", "H", "D"), ("nodes", "K", "C")
+    f32, i32 = torch.float32, torch.int32
+    ops = {
+        "lb_graph_gather": ("lb_graph_gather_t", ((nc, None),), ((sc, None),), ("C",)),
+        "lb_graph_segment_sum": ("lb_graph_segment_sum_t", ((sc, None),), ((nc, None),), ("C",)),
+        "lb_graph_degree": ("lb_graph_degree", (), ((("nodes",), i32),), ()),
+        "lb_graph_segment_max": ("lb_graph_segment_max_t", ((sc, None),), ((nc, None), (nc, i32)), ("C",)),
+        "lb_graph_segment_min": ("lb_graph_segment_min_t", ((sc, None),), ((nc, None), (nc, i32)), ("C",)),
+        "lb_graph_segment_max_backward": ("lb_graph_segment_max_backward_t", ((nc, None), (nc, i32)), ((sc, None),), ("C",)),
+        "lb_graph_segment_softmax": ("lb_graph_segment_softmax_t", ((sc, None),), ((sc, None),), ("C",)),
+        "lb_graph_segment_softmax_backward": ("lb_graph_segment_softmax_backward_t", ((sc, None), (sc, None)), ((sc, None),),
+                                              ("C",)),
+        "lb_graph_attend": ("lb_graph_attend_t", ((sh, None), (shd, None)), ((nhd, None), (nh, f32), (nh, f32)), ("H", "D")),
+        "lb_graph_attend_backward": ("lb_graph_attend_backward_t", ((sh, None), (shd, None), (nh, f32), (nh, f32), (nhd, None)),
+                                     ((sh, None), (shd, None)), ("H", "D")),
+        "lb_graph_conv": ("lb_graph_conv", ((nkc, None), (sc, None)), ((nkc, None),), ("K", "C")),
+        "lb_graph_pair_mul": ("lb_graph_pair_mul", ((nkc, None), (nkc, None)), ((sc, None),), ("K", "C")),
+        "lb_graph_pair_add": ("lb_graph_pair_add", ((nc, None), (nc, None)), ((sc, None),), ("C",)),
+        "lb_graph_features_backward": ("lb_graph_features_backward",
+                                       ((("nodes", "isl", "dim"), f32), (("nodes", "vel"), f32), (("nodes", "mag"), f32),
+                                        (("nodes", "bound"), f32), (("slots", "dim"), f32), (("slots", 1), f32)),
+                                       ((("B", "N", "isl", "dim"), torch.float64),), (), True),
+    }
+    table = {}
+    for symbol, (entry, ins, outs, sizes, *optional) in ops.items():
+        known, liked = list(ins), []
+        for spec in outs:
+            liked.append(spec + (known.index(spec) if spec in known else -1,))
+            known.append(spec)
+        table[symbol] = (entry, ins, tuple(liked), sizes, bool(optional))
+    return table
+
+
+_GRAPH_OPS = _graph_ops()
+
+
 class ForceSpec:
     """How external_force_fn(position) (features.py:105-107) is evaluated on the device.
 
@@ -451,106 +496,101 @@ class RolloutEngine:
     # contract: round_to_bf16(float32 op(upcast inputs)) bit for bit.
     _GRAPH_DTYPES = {torch.float32: 0, torch.bfloat16: 1}   # LB_DTYPE_F32, LB_DTYPE_BF16
 
-    def _graph_dtype(self, symbol: str, t) -> torch.dtype:
-        dtype = getattr(t, "dtype", None)
-        if dtype not in self._GRAPH_DTYPES:
-            raise ValueError(f"{symbol}: expected a float32 or bfloat16 tensor on {self.device}, got "
-                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', None)}")
-        return dtype
+    def _graph_call(self, symbol: str, role, tensors=(), **fixed):
+        """The one way into the lb_graph_* entries (_GRAPH_OPS): check every input against its shape, dtype, device and
+        contiguity, allocate the outputs, call, return the outputs.  Where the table allows it, None passes a null pointer;
+        `fixed` gives the sizes of a shape that the caller sets (graph_features_backward)."""
+        entry, ins, outs, sizes, optional = _GRAPH_OPS[symbol]
+        dims = {"nodes": self.B * self.N, "slots": self.B * self.e_cap, 1: 1}
+        if fixed:
+            dims.update(fixed)
+        data, device, codes = None, self.device, self._GRAPH_DTYPES
+        args = [self._h] if role is None else [self._h, int(role)]
+        seen = []
+        for t, (shape, dtype) in zip(tensors, ins):
+            seen.append(t)
+            if t is None and optional:
+                args.append(None)
+                continue
+            ok = isinstance(t, torch.Tensor)
+            if ok:
+                got = t.shape
+                ok = len(got) == len(shape)
+                for d, n in zip(shape, got):
+                    if dims.setdefault(d, n) != n or n < 1:   # (binds a free size at its first sight)
+                        ok = False
+                have = t.dtype
+                if dtype is None:
+                    if data is None and have in codes:
+                        data, first = have, t
+                    dtype = data
+                ok = ok and have == dtype and t.device == device and t.is_contiguous()
+            if not ok:
+                text = ", ".join(str(dims[d]) if dims.get(d, 0) > 0 else f"{d} >= 1" for d in shape)
+                raise ValueError(f"{symbol}: expected a contiguous ({text}) {dtype or data or 'float32 or bfloat16'} tensor on "
+                                 f"{device}, got {tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} on "
+                                 f"{getattr(t, 'device', None)}")
+            args.append(t.data_ptr())
+        made = []
+        for shape, dtype, like in outs:   # (the cheapest allocation that fits: a twin's, the data tensors', a plain one)
+            if like >= 0:
+                o = torch.empty_like(seen[like])
+            elif dtype is None:
+                o = first.new_empty([dims[d] for d in shape])
+            else:
+                o = torch.empty([dims[d] for d in shape], dtype=dtype, device=device)
+            seen.append(o)
+            made.append(o)
+            args.append(o.data_ptr())
+        for s in sizes:
+            args.append(dims[s])
+        if data is not None:
+            args.append(codes[data])
+        check(getattr(self.lib, entry)(*args), symbol)
+        return made[0] if len(made) == 1 else tuple(made)
 
     def _graph_op(self, symbol: str, role: int, src: torch.Tensor, rows_in: int, rows_out: int) -> torch.Tensor:
-        if getattr(src, "dtype", None) not in self._GRAPH_DTYPES or src.device != self.device or not src.is_contiguous() \
-                or src.dim() != 2 or src.shape[0] != rows_in or src.shape[1] < 1:
-            raise ValueError(f"{symbol}: expected a contiguous ({rows_in}, C >= 1) float32 or bfloat16 tensor on {self.device}, "
-                             f"got {tuple(src.shape)} {src.dtype} on {src.device}")
-        out = torch.empty((rows_out, src.shape[1]), dtype=src.dtype, device=self.device)
-        check(getattr(self.lib, symbol + "_t")(self._h, int(role), ptr(src), ptr(out), int(src.shape[1]),
-                                               self._GRAPH_DTYPES[src.dtype]), symbol)
-        return out
+        """A one-tensor op on rows the caller counts: (rows_in, C) -> (rows_out, C).  Kept for one purpose: the test of the
+        library's refusal on an engine without a list (e_cap == 0, so no output could be allocated otherwise) calls it.  No
+        graph_* method does; with input and output both in slots (softmax) rows_out would stand for both."""
+        _, ins, outs, _, _ = _GRAPH_OPS[symbol]
+        return self._graph_call(symbol, role, (src,), **{ins[0][0][0]: rows_in, outs[0][0][0]: rows_out})
 
     def graph_gather(self, role: int, x: torch.Tensor) -> torch.Tensor:
         """x (B*N, C) float32 or bfloat16 -> (B*E_cap, C): the node row of every real edge slot of the current list in the
         padded layout of nl_idx(), +0.0 in the pad slots; a bit copy.  role: 0 receivers, 1 senders (include/lbhip.h:
         lb_graph_gather_t)."""
-        return self._graph_op("lb_graph_gather", role, x, self.B * self.N, self.B * self.e_cap)
+        return self._graph_call("lb_graph_gather", role, (x,))
 
     def graph_segment_sum(self, role: int, msg: torch.Tensor) -> torch.Tensor:
         """msg (B*E_cap, C) float32 or bfloat16 -> (B*N, C): per node the sum of its real edge slots in ascending slot order, one
         fp32 add after the other; no atomics.  bfloat16: the terms are widened, the fp32 sum is rounded once (include/lbhip.h:
         lb_graph_segment_sum_t)."""
-        return self._graph_op("lb_graph_segment_sum", role, msg, self.B * self.e_cap, self.B * self.N)
-
-    def _graph_arg(self, symbol: str, t: torch.Tensor, shape, dtype=torch.float32) -> torch.Tensor:
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() \
-                or tuple(t.shape) != tuple(shape) or t.numel() == 0:
-            raise ValueError(f"{symbol}: expected a contiguous {tuple(shape)} {dtype} tensor on {self.device}, got "
-                             f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', None)}")
-        return t
-
-    def _graph_cols(self, symbol: str, t: torch.Tensor, rows: int) -> int:
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < 1:
-            raise ValueError(f"{symbol}: expected a ({rows}, C >= 1) tensor, got {tuple(getattr(t, 'shape', ()))}")
-        return int(t.shape[1])
+        return self._graph_call("lb_graph_segment_sum", role, (msg,))
 
     def graph_degree(self, role: int) -> torch.Tensor:
         """-> (B*N,) int32: the real edge slots of the current list whose role index is the node (lb_graph_degree)."""
-        out = torch.empty((self.B * self.N,), dtype=torch.int32, device=self.device)
-        check(self.lib.lb_graph_degree(self._h, int(role), ptr(out)), "lb_graph_degree")
-        return out
+        return self._graph_call("lb_graph_degree", role)
 
     def graph_segment_max(self, role: int, msg: torch.Tensor, minimum: bool = False):
         """msg (B*E_cap, C) float32 or bfloat16 -> (out (B*N, C), win (B*N, C) int32): per node and column the first real slot's
         value, replaced in ascending slot order by a strictly greater (minimum: smaller) one, and the slot that won (-1 and +0.0
         for a node without edges) (include/lbhip.h: lb_graph_segment_max_t / _min_t)."""
-        symbol = "lb_graph_segment_min" if minimum else "lb_graph_segment_max"
-        C_ = self._graph_cols(symbol, msg, self.B * self.e_cap)
-        dt = self._graph_dtype(symbol, msg)
-        self._graph_arg(symbol, msg, (self.B * self.e_cap, C_), dt)
-        out = torch.empty((self.B * self.N, C_), dtype=dt, device=self.device)
-        win = torch.empty((self.B * self.N, C_), dtype=torch.int32, device=self.device)
-        check(getattr(self.lib, symbol + "_t")(self._h, int(role), ptr(msg), ptr(out), ptr(win), C_, self._GRAPH_DTYPES[dt]), symbol)
-        return out, win
+        return self._graph_call("lb_graph_segment_min" if minimum else "lb_graph_segment_max", role, (msg,))
 
     def graph_segment_max_backward(self, role: int, d_out: torch.Tensor, win: torch.Tensor) -> torch.Tensor:
         """d_out (B*N, C), win (B*N, C) int32 -> d_msg (B*E_cap, C) in d_out's dtype: d_out in the winning slots, +0.0 elsewhere."""
-        symbol = "lb_graph_segment_max_backward"
-        C_ = self._graph_cols(symbol, d_out, self.B * self.N)
-        dt = self._graph_dtype(symbol, d_out)
-        self._graph_arg(symbol, d_out, (self.B * self.N, C_), dt)
-        self._graph_arg(symbol, win, (self.B * self.N, C_), torch.int32)
-        d_msg = torch.empty((self.B * self.e_cap, C_), dtype=dt, device=self.device)
-        check(self.lib.lb_graph_segment_max_backward_t(self._h, int(role), ptr(d_out), ptr(win), ptr(d_msg), C_,
-                                                       self._GRAPH_DTYPES[dt]), symbol)
-        return d_msg
+        return self._graph_call("lb_graph_segment_max_backward", role, (d_out, win))
 
     def graph_segment_softmax(self, role: int, logits: torch.Tensor) -> torch.Tensor:
         """logits (B*E_cap, C) float32 or bfloat16 -> (B*E_cap, C): per node and column the softmax over the node's real slots,
         shifted by their maximum, the denominator summed in ascending slot order; +0.0 in the pad slots
         (lb_graph_segment_softmax_t)."""
-        return self._graph_op("lb_graph_segment_softmax", role, logits, self.B * self.e_cap, self.B * self.e_cap)
+        return self._graph_call("lb_graph_segment_softmax", role, (logits,))
 
     def graph_segment_softmax_backward(self, role: int, y: torch.Tensor, d_y: torch.Tensor) -> torch.Tensor:
         """y, d_y (B*E_cap, C), one dtype -> d_logits (B*E_cap, C) = y (d_y - the node's ordered sum of d_y y)."""
-        symbol = "lb_graph_segment_softmax_backward"
-        C_ = self._graph_cols(symbol, y, self.B * self.e_cap)
-        dt = self._graph_dtype(symbol, y)
-        self._graph_arg(symbol, y, (self.B * self.e_cap, C_), dt)
-        self._graph_arg(symbol, d_y, (self.B * self.e_cap, C_), dt)
-        d_x = torch.empty_like(y)
-        check(self.lib.lb_graph_segment_softmax_backward_t(self._h, int(role), ptr(y), ptr(d_y), ptr(d_x), C_,
-                                                           self._GRAPH_DTYPES[dt]), symbol)
-        return d_x
-
-    def _graph_attend_args(self, symbol: str, logits: torch.Tensor, values: torch.Tensor):
-        slots = self.B * self.e_cap
-        H = self._graph_cols(symbol, logits, slots)
-        if not isinstance(values, torch.Tensor) or values.dim() != 3 or values.shape[2] < 1:
-            raise ValueError(f"{symbol}: expected values ({slots}, {H}, D >= 1), got {tuple(getattr(values, 'shape', ()))}")
-        D = int(values.shape[2])
-        dt = self._graph_dtype(symbol, logits)
-        self._graph_arg(symbol, logits, (slots, H), dt)
-        self._graph_arg(symbol, values, (slots, H, D), dt)
-        return H, D, dt
+        return self._graph_call("lb_graph_segment_softmax_backward", role, (y, d_y))
 
     def graph_attend(self, role: int, logits: torch.Tensor, values: torch.Tensor):
         """logits (B*E_cap, H), values (B*E_cap, H, D), both float32 or both bfloat16 -> (out (B*N, H, D) in that dtype,
@@ -559,75 +599,31 @@ class RolloutEngine:
         launch.  bfloat16: that float32 result on the widened inputs, rounded once - the weights are not rounded to bfloat16
         on the way, as the composition's are.  m and s are the maximum and the denominator it used (include/lbhip.h:
         lb_graph_attend_t)."""
-        H, D, dt = self._graph_attend_args("lb_graph_attend", logits, values)
-        out = torch.empty((self.B * self.N, H, D), dtype=dt, device=self.device)
-        m = torch.empty((self.B * self.N, H), dtype=torch.float32, device=self.device)
-        s = torch.empty_like(m)
-        check(self.lib.lb_graph_attend_t(self._h, int(role), ptr(logits), ptr(values), ptr(out), ptr(m), ptr(s), H, D,
-                                         self._GRAPH_DTYPES[dt]), "lb_graph_attend")
-        return out, m, s
+        return self._graph_call("lb_graph_attend", role, (logits, values))
 
     def graph_attend_backward(self, role: int, logits: torch.Tensor, values: torch.Tensor, m: torch.Tensor, s: torch.Tensor,
                               d_out: torch.Tensor):
         """-> (d_logits (B*E_cap, H), d_values (B*E_cap, H, D)) of graph_attend, in the dtype of logits, values and d_out
         (include/lbhip.h: lb_graph_attend_backward_t)."""
-        symbol = "lb_graph_attend_backward"
-        H, D, dt = self._graph_attend_args(symbol, logits, values)
-        self._graph_arg(symbol, m, (self.B * self.N, H))
-        self._graph_arg(symbol, s, (self.B * self.N, H))
-        self._graph_arg(symbol, d_out, (self.B * self.N, H, D), dt)
-        d_logits, d_values = torch.empty_like(logits), torch.empty_like(values)
-        check(self.lib.lb_graph_attend_backward_t(self._h, int(role), ptr(logits), ptr(values), ptr(m), ptr(s), ptr(d_out),
-                                                  ptr(d_logits), ptr(d_values), H, D, self._GRAPH_DTYPES[dt]), symbol)
-        return d_logits, d_values
-
-    def _graph_pair_args(self, symbol: str, a: torch.Tensor, b: torch.Tensor):
-        """a, b (B*N, K, C), one dtype -> (K, C, dtype)."""
-        if not isinstance(a, torch.Tensor) or a.dim() != 3 or a.shape[0] != self.B * self.N or a.shape[1] < 1 or a.shape[2] < 1:
-            raise ValueError(f"{symbol}: expected ({self.B * self.N}, K >= 1, C >= 1) tensors, got "
-                             f"{tuple(getattr(a, 'shape', ()))}")
-        dt = self._graph_dtype(symbol, a)
-        self._graph_arg(symbol, a, tuple(a.shape), dt)
-        self._graph_arg(symbol, b, tuple(a.shape), dt)
-        return int(a.shape[1]), int(a.shape[2]), dt
+        return self._graph_call("lb_graph_attend_backward", role, (logits, values, m, s, d_out))
 
     def graph_conv(self, role: int, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
         """x (B*N, K, C), w (B*E_cap, C), both float32 or both bfloat16 -> (B*N, K, C): per node the sum over its real slots of
         `role`, in ascending slot order, of x[the slot's other node] * w[slot] - each product rounded to float32, one float32
         add after the other; no edge-shaped intermediate.  float32: the bits of graph_segment_sum(graph_gather(x) * w).
         bfloat16: the exact products summed in float32, rounded once (include/lbhip.h: lb_graph_conv)."""
-        symbol = "lb_graph_conv"
-        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[0] != self.B * self.N or x.shape[1] < 1 or x.shape[2] < 1:
-            raise ValueError(f"{symbol}: expected x ({self.B * self.N}, K >= 1, C >= 1), got {tuple(getattr(x, 'shape', ()))}")
-        K, C_ = int(x.shape[1]), int(x.shape[2])
-        dt = self._graph_dtype(symbol, x)
-        self._graph_arg(symbol, x, tuple(x.shape), dt)
-        self._graph_arg(symbol, w, (self.B * self.e_cap, C_), dt)
-        out = torch.empty_like(x)
-        check(self.lib.lb_graph_conv(self._h, int(role), ptr(x), ptr(w), ptr(out), K, C_, self._GRAPH_DTYPES[dt]), symbol)
-        return out
+        return self._graph_call("lb_graph_conv", role, (x, w))
 
     def graph_pair_mul(self, a_role: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         """a, b (B*N, K, C), one dtype -> (B*E_cap, C): per real slot the sum over k ascending of a[the slot's `a_role` node, k]
         * b[its other node, k], each product rounded to float32, the first starts the sum; +0.0 in the pad slots.  K = 1 is
         the plain product; with K > 1 it is graph_conv's gradient to w (include/lbhip.h: lb_graph_pair_mul)."""
-        symbol = "lb_graph_pair_mul"
-        K, C_, dt = self._graph_pair_args(symbol, a, b)
-        out = torch.empty((self.B * self.e_cap, C_), dtype=dt, device=self.device)
-        check(self.lib.lb_graph_pair_mul(self._h, int(a_role), ptr(a), ptr(b), ptr(out), K, C_, self._GRAPH_DTYPES[dt]), symbol)
-        return out
+        return self._graph_call("lb_graph_pair_mul", a_role, (a, b))
 
     def graph_pair_add(self, a_role: int, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         """a, b (B*N, C), one dtype -> (B*E_cap, C): a[the slot's `a_role` node] + b[its other node] in the real slots, one
         float32 add, +0.0 in the pad slots (include/lbhip.h: lb_graph_pair_add)."""
-        symbol = "lb_graph_pair_add"
-        C_ = self._graph_cols(symbol, a, self.B * self.N)
-        dt = self._graph_dtype(symbol, a)
-        self._graph_arg(symbol, a, (self.B * self.N, C_), dt)
-        self._graph_arg(symbol, b, (self.B * self.N, C_), dt)
-        out = torch.empty((self.B * self.e_cap, C_), dtype=dt, device=self.device)
-        check(self.lib.lb_graph_pair_add(self._h, int(a_role), ptr(a), ptr(b), ptr(out), C_, self._GRAPH_DTYPES[dt]), symbol)
-        return out
+        return self._graph_call("lb_graph_pair_add", a_role, (a, b))
 
     def graph_features_backward(self, d_abs_pos=None, d_vel_hist=None, d_vel_mag=None, d_bound=None, d_rel_disp=None,
                                 d_rel_dist=None) -> torch.Tensor:
@@ -636,17 +632,13 @@ class RolloutEngine:
         d_vel_mag (B*N, isl-1), d_bound (B*N, 2*dim), d_rel_disp (B*E_cap, dim), d_rel_dist (B*E_cap, 1); the pad slots of the
         last two are never read.  fp64 sums in a fixed order, no atomics (include/lbhip.h: lb_graph_features_backward)."""
         symbol = "lb_graph_features_backward"
-        BN, slots, K = self.B * self.N, self.B * self.e_cap, self.isl - 1
         if d_vel_mag is not None and not self.has_vel_mag:
             raise ValueError(f"{symbol}: d_vel_mag given, but the engine has no vel_mag feature")
         if d_bound is not None and not self.has_bound:
             raise ValueError(f"{symbol}: d_bound given, but the engine has no bound feature")
-        shapes = ((d_abs_pos, (BN, self.isl, self.dim)), (d_vel_hist, (BN, K * self.dim)), (d_vel_mag, (BN, K)),
-                  (d_bound, (BN, 2 * self.dim)), (d_rel_disp, (slots, self.dim)), (d_rel_dist, (slots, 1)))
-        args = [None if t is None else self._graph_arg(symbol, t, shape) for t, shape in shapes]
-        out = torch.empty((self.B, self.N, self.isl, self.dim), dtype=torch.float64, device=self.device)
-        check(self.lib.lb_graph_features_backward(self._h, *[ptr(t) for t in args], ptr(out)), symbol)
-        return out
+        return self._graph_call(symbol, None, (d_abs_pos, d_vel_hist, d_vel_mag, d_bound, d_rel_disp, d_rel_dist), B=self.B,
+                                N=self.N, isl=self.isl, dim=self.dim, vel=(self.isl - 1) * self.dim, mag=self.isl - 1,
+                                bound=2 * self.dim)
 
     def graph_sender_sorts(self) -> int:
         """Sender-ordered views the graph ops built by the radix sort (a list with an edge in one direction only)."""

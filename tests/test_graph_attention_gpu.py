@@ -3,7 +3,8 @@ and the fused attend, over receivers and senders, forward and backward.
 
 Cases and columns are those of tests/test_graph_ops_gpu.py (its docstring says which path each reaches); the attend shapes
 (H, D): (1, 1); (1, 5) scalars; (3, 4) 16-byte units, H no power of two; (8, 16) C = 128; (2, 65) a head boundary inside a
-lane's stride, no multiple of 4.  Every pad slot of every edge input holds NaN.
+lane's stride, no multiple of 4; (5, 52) 65 units of 16 bytes, one more than a row's 64 lanes.  Every pad slot of every edge
+input holds NaN.
 
 What is held to the bit (view(uint32)): degree, segment_mean, the extrema with their gradient (numpy float32 loops that state
 the order contract), attend against the composition of this library's own segment_softmax and segment_sum, its d_values, and
@@ -29,7 +30,7 @@ from tests.test_graph_ops_gpu import CASES, COLUMNS, ROLES, _bits, _build, _np, 
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (1, 5), (3, 4), (8, 16), (2, 65)]
+SHAPES = [(1, 1), (1, 5), (3, 4), (8, 16), (2, 65), (5, 52)]
 ULP = 2.0 ** -24
 
 

@@ -4,9 +4,11 @@ models.TorchModel(autocast=torch.bfloat16).  The contract, for every op and ever
     the bfloat16 op  ==  round_to_bf16( the float32 op( upcast(inputs) ) )        bit for bit (view(uint16); a NaN matches a NaN)
 
 Cases and roles are those of tests/test_graph_ops_gpu.py.  Columns: 1; 5; 12 (a multiple of 4 but not of 8: float32 would take
-16-byte units, bfloat16 must not); 64 (8 lanes of 16 bytes); 136 (past 128, a multiple of 8: a lane owns two units).  Attend
-shapes (H, D): (1, 1), (1, 5) elements; (3, 4) 8-byte units; (2, 8), (8, 16) 16-byte units; (2, 65) a head boundary inside a
-lane's stride.  Inputs are float32 random values times 10^k, k in -2 .. 2, rounded to bfloat16; every pad slot holds NaN.
+16-byte units, bfloat16 must not); 64 (8 lanes of 16 bytes); 136 (past 128, a multiple of 8: a lane owns two units); 520 (65
+units of 16 bytes: one more than a row's 64 lanes).  Attend shapes (H, D): (1, 1), (1, 5) elements; (3, 4) 8-byte units; (2,
+8), (8, 16) 16-byte units; (2, 65) a head boundary inside a lane's stride; (5, 52) and (5, 104): 65 units of 8 and of 16
+bytes, one more than a row's 64 lanes.  Inputs are float32 random values times 10^k, k in -2 .. 2, rounded to bfloat16; every
+pad slot holds NaN.
 
   1  gather / segment_sum, forward and backward, against the numpy twin (tests/_graph_bf16.py), with planted rows: the three
      rows that tell a bfloat16 accumulator and another order from the contract, two exact ties and an overflow to inf
@@ -15,7 +17,7 @@ lane's stride.  Inputs are float32 random values times 10^k, k in -2 .. 2, round
   3  segment_softmax and attend against the float64 restatements on the same inputs: today's bound (1e-5 of the scale
      tests/test_graph_attention_gpu.py uses) plus one bfloat16 rounding, 2^-8 |reference| per element; softmax rows sum to 1
      within (deg + 8) 2^-24 + deg 2^-9 (deg roundings of at most 2^-9 each)
-  4  a tensor whose storage starts one element (2 bytes) off alignment gives the aligned call's bits
+  4  a tensor whose storage starts one element (2 bytes; for float32 4 bytes) off alignment gives the aligned call's bits
   5  TorchModel(autocast=torch.bfloat16): per output and gradient leaf the deviation from the float64 CPU restatement is at
      most 3x that of the CPU restatement under torch.autocast("cpu", bfloat16) on CpuGraphBf16; Trainer, checkpoint, infer,
      autograd.TorchModule
@@ -36,8 +38,8 @@ from tests.test_graph_ops_gpu import CASES, ROLES, _build, _np, np_gather  # noq
 
 pytestmark = pytest.mark.gpu
 
-COLUMNS = [1, 5, 12, 64, 136]
-SHAPES = [(1, 1), (1, 5), (3, 4), (2, 8), (8, 16), (2, 65)]
+COLUMNS = [1, 5, 12, 64, 136, 520]
+SHAPES = [(1, 1), (1, 5), (3, 4), (2, 8), (8, 16), (2, 65), (5, 52), (5, 104)]
 NAN = 0x7FC0
 BF = torch.bfloat16
 TIE_DOWN, TIE_UP, OVERFLOW = [1.0, 2.0 ** -8], [1.0 + 2.0 ** -7, 2.0 ** -8], [GB.widen([0x7F7F])[0], 2.0 ** 119]
@@ -286,19 +288,38 @@ def test_a_tensor_two_bytes_off_alignment_gives_the_same_bits():
     rng = np.random.default_rng(5)
 
     def shifted(t):
-        buf = torch.empty(t.numel() + 1, dtype=BF, device=eng.device)
+        """t one element off alignment: 2 bytes for bfloat16, 4 for float32."""
+        buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=eng.device)
         out = buf[1:].view(t.shape)
         out.copy_(t)
-        assert out.is_contiguous() and out.data_ptr() % 16 == 2 and t.data_ptr() % 16 == 0
+        assert out.is_contiguous() and out.data_ptr() % 16 == t.element_size() and t.data_ptr() % 16 == 0
         return out
 
+    def bits32(t):
+        return t.contiguous().view(torch.int32)
+
     x, msg = _dev(_rand_bits(rng, (B, N, C)), eng), _dev(_pad_nan(_rand_bits(rng, (B, E, C)), ne), eng)
+    x2 = _dev(_rand_bits(rng, (B, N, C)), eng)
     clean = _dev(_pad_nan(_rand_bits(rng, (B, E, C)), ne), eng)
     for role in ROLES:
         for op, t in ((g.gather, x), (g.segment_sum, msg), (g.segment_max, msg), (g.segment_softmax, clean)):
             assert GB.same_bits(_b(op(shifted(t), role)), _b(op(t, role))), (role, op.__name__)
         l, v = clean[..., :8].contiguous(), msg.reshape(B, E, 8, 8)
         assert GB.same_bits(_b(g.attend(l, shifted(v), role)), _b(g.attend(l, v, role)))
+        want = _b(g.conv(x, clean, role))                                    # (the pad slots of w are never read)
+        assert GB.same_bits(_b(g.conv(shifted(x), clean, role)), want) and GB.same_bits(_b(g.conv(x, shifted(clean), role)), want)
+    for op in (g.pair_mul, g.pair_add):
+        want = _b(op(x, x2))
+        assert GB.same_bits(_b(op(shifted(x), x2)), want) and GB.same_bits(_b(op(x, shifted(x2))), want), op.__name__
+    # float32, 4 bytes off (data_ptr() % 16 == 4): no 16-byte units either
+    x32, msg32, w32 = x.float(), msg.float(), clean.float()
+    assert shifted(x32).data_ptr() % 16 == 4
+    for role in ROLES:
+        assert torch.equal(bits32(g.gather(shifted(x32), role)), bits32(g.gather(x32, role))), role
+        assert torch.equal(bits32(g.segment_sum(shifted(msg32), role)), bits32(g.segment_sum(msg32, role))), role
+        want = bits32(g.conv(x32, w32, role))
+        assert torch.equal(bits32(g.conv(shifted(x32), w32, role)), want), role
+        assert torch.equal(bits32(g.conv(x32, shifted(w32), role)), want), role
 
 
 # ------------------------------------------------------------------------------------------------ 5: TorchModel(autocast)

@@ -8,7 +8,8 @@ Cases - the smallest that reach every path:
   lj              the LJ fixture with input_seq_length 3: N = 3 - rows shorter than a wave, nearly every slot a pad
   asym            tests._asym.asym_case("tgv2d", B=2): edges without a transpose, the sender view comes from the radix sort
 Columns: 1 (narrowest row), 5 (the row ends inside a 16-byte access: the scalar kernels), 64 (16 lanes of 16 bytes), 130 (past
-128 and no multiple of 4: a lane owns several columns).
+128 and no multiple of 4: a lane owns several columns), 260 (65 units of 16 bytes: one more than the 64 lanes of a row, so the
+second pass over the row has one live lane).
 """
 import functools
 import os
@@ -25,7 +26,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.abspath(__file__))
 LJ = os.path.join(ROOT, "golden", "3D_LJ_3_1214every1")
 CASES = ["rpf2d_b1", "rpf2d_b2", "ldc3d", "lj", "asym"]
-COLUMNS = [1, 5, 64, 130]
+COLUMNS = [1, 5, 64, 130, 260]
 ROLES = ("receivers", "senders")
 
 

@@ -24,7 +24,8 @@ from tests.test_graph_ops_gpu import CASES, COLUMNS, ROLES, _build, _setup, np_g
 pytestmark = pytest.mark.gpu
 
 KS = [1, 3]
-BF16_COLUMNS = [5, 64, 130]     # 8-element units need C % 8 == 0: 64 takes them, the others the scalar path
+# 8-element units need C % 8 == 0: 64 and 520 (65 units, past a row's 64 lanes) take them, the others the scalar path
+BF16_COLUMNS = [5, 64, 130, 520]
 
 
 def _need_gpu():
