@@ -826,6 +826,40 @@ int lb_graph_pair_mul(lb_engine* eng, int32_t a_role, const void* a_dev /*(B*N,K
                       void* out_dev /*(B*E_cap,C)*/, int32_t K, int32_t C, int32_t dtype);
 int lb_graph_pair_add(lb_engine* eng, int32_t a_role, const void* a_dev /*(B*N,C)*/, const void* b_dev /*(B*N,C)*/,
                       void* out_dev /*(B*E_cap,C)*/, int32_t C, int32_t dtype);
+/* ---- equivariant vector messages: scalar <-> vector channels through a per-edge vector -----
+ * The rules of the edge messages hold (layout, roles, pads never read, +0.0 in the pad slots of edge-shaped outputs, no float
+ * atomics, two calls the same bits, dtype for every data tensor).  u (B*E_cap, K) is any per-edge vector - rel_disp, or spherical
+ * harmonics up to l = 2 -, 1 <= K <= 9, read with scalar loads; x (B*N, C), v (B*N, K, C), w (B*E_cap, C).  o(j) is the
+ * other(role) node of slot j, n(j) its `role` node.  Every product is one fp32 multiplication, every add one fp32 add, no FMA
+ * contraction.  LB_ERR_ARG on a null pointer, a role other than 0 / 1, a dtype other than the two, K < 1, K > 9 or C < 1.
+ * conv_vec: out[i, k, c] = the sum over the real slots j with n(j) = i, ascending, of fl32(fl32(x[o(j), c] * w[j, c]) * u[j, k]);
+ *   the first term starts the sum, +0.0 for a node without a slot.  With fp32 tensors bit for bit
+ *   segment_sum((gather(x, other(role)) * w)[:, None, :] * u[:, :, None], role).
+ * conv_dot: t[j, c] = fl32(v[o(j), 0, c] * u[j, 0]) + fl32(v[o(j), 1, c] * u[j, 1]) + ... (k ascending, the first product starts
+ *   the sum); out[i, c] = the sum over the real slots j with n(j) = i, ascending, of fl32(w[j, c] * t[j, c]).  With fp32 tensors
+ *   bit for bit segment_sum(w * t, role) with t added k by k from gather(v, other(role))[:, k] * u[:, k:k+1].
+ * Adjoints: d_x of conv_vec over role = conv_dot(d_out, w, u, other(role)); d_v of conv_dot over role = conv_vec(d_out, w, u,
+ *   other(role)) - the same kernels, the same bits.
+ * conv_vec_edge_grad: the gradients to w and u of both ops from a scalar-side node tensor S (B*N, C), read at the slot's s_role
+ *   node, and a vector-side one V (B*N, K, C), read at its other node - conv_vec over role: S = x, s_role = other(role), V =
+ *   d_out; conv_dot over role: S = d_out, s_role = role, V = v:
+ *     d_w[j, c] = fl32(S[c] * t[j, c]), t formed from V and u as in conv_dot;
+ *     d_u[j, k] = sum over c of fl32(fl32(S[c] * w[j, c]) * V[k, c]) in a FIXED order: the columns in consecutive blocks of
+ *       LB_GRAPH_DU_BLOCK (the last may be short), inside a block c ascending and the first product starts the sum, then the
+ *       block sums added in ascending block order from the first one.  The order does not depend on C's divisibility, the
+ *       pointers' alignment or the dtype; a numpy loop reproduces it.
+ *   Either of d_w_dev (B*E_cap, C) and d_u_dev (B*E_cap, K) may be null: that gradient is not computed (both null: LB_ERR_ARG).
+ * LB_DTYPE_BF16: round_to_bf16(the fp32 op(upcast inputs)), one rounding per stored element, d_u included; no partial result is
+ *   held in bf16, so neither op is the composition of the bf16 ops. */
+#define LB_GRAPH_DU_BLOCK 16
+int lb_graph_conv_vec(lb_engine* eng, int32_t role, const void* x_dev /*(B*N,C)*/, const void* w_dev /*(B*E_cap,C)*/,
+                      const void* u_dev /*(B*E_cap,K)*/, void* out_dev /*(B*N,K,C)*/, int32_t K, int32_t C, int32_t dtype);
+int lb_graph_conv_dot(lb_engine* eng, int32_t role, const void* v_dev /*(B*N,K,C)*/, const void* w_dev /*(B*E_cap,C)*/,
+                      const void* u_dev /*(B*E_cap,K)*/, void* out_dev /*(B*N,C)*/, int32_t K, int32_t C, int32_t dtype);
+int lb_graph_conv_vec_edge_grad(lb_engine* eng, int32_t s_role, const void* s_dev /*(B*N,C)*/, const void* v_dev /*(B*N,K,C)*/,
+                                const void* w_dev /*(B*E_cap,C)*/, const void* u_dev /*(B*E_cap,K)*/,
+                                void* d_w_dev /*(B*E_cap,C) or NULL*/, void* d_u_dev /*(B*E_cap,K) or NULL*/, int32_t K, int32_t C,
+                                int32_t dtype);
 /* d loss / d window from the cotangents of the features a TorchModel module receives (graph.differentiable_features), on the
  * engine's CURRENT window and list: the transpose of the feature builder.  Every input may be NULL (= zero).  fp32 inputs in the
  * layouts of TorchModel's feature dict; the edge-shaped ones in the padded slot layout of lb_nl_read_idx, whose pad slots are

@@ -230,6 +230,10 @@ _SIGS = {
     "lb_graph_conv": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_pair_mul": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_pair_add": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
+    # equivariant vector messages: (x | v, w, u, out); the edge gradients (S, V, w, u, d_w or null, d_u or null)
+    "lb_graph_conv_vec": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_graph_conv_dot": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_graph_conv_vec_edge_grad": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -6,7 +6,8 @@
 //
 // and, for attention and pooling layers (further down: "attention ops"), lb_graph_degree, lb_graph_segment_max / _min,
 // lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries; for filter x neighbour messages ("edge
-// messages") the fused lb_graph_conv and the edge-shaped lb_graph_pair_mul / lb_graph_pair_add; and lb_graph_features_backward
+// messages") the fused lb_graph_conv and the edge-shaped lb_graph_pair_mul / lb_graph_pair_add, and the equivariant couplings
+// through a per-edge vector, lb_graph_conv_vec / lb_graph_conv_dot with lb_graph_conv_vec_edge_grad; and lb_graph_features_backward
 // ("feature transpose"): d loss / d window from the cotangents of the features such a network was handed.
 //
 // All work in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
@@ -705,6 +706,253 @@ __global__ void __launch_bounds__(256) k_graph_pair_add(lb_glist L, const int32_
   graph_pair_body<T, W, false, false>(L, aidx, bidx, a, b, out, 1);
 }
 
+// conv_vec and conv_dot: the scalar <-> vector couplings of an equivariant layer through a per-edge vector u (B E_cap, K), K <= 9
+// (rel_disp, or spherical harmonics up to l = 2), without the (B E_cap, K, C) product.  Both walk the rows of their role as conv
+// does; u rows are K elements wide (12 bytes at K = 3), so u is read with scalar loads - one address per lane group, a broadcast.
+//
+// One slot's loads of conv_vec for k-chunk k0 .. k0 + KT - 1: the w unit, the x unit of the other node and KT scalars of u (a k
+// past K - 1 re-reads column K - 1; never stored).
+template <typename T, int W, int KT>
+__device__ __forceinline__ void graph_conv_vec_load(const lb_row& R, int p, const int32_t* __restrict__ oidx,
+                                                    const T* __restrict__ x, const T* __restrict__ w, const T* __restrict__ uv,
+                                                    const lb_glist& L, int K, int k0, int U, int u, float (&f)[W], float (&a)[W],
+                                                    float (&g)[KT]) {
+  const int64_t e = R.edge(p);
+  const int64_t node = graph_clamp(L, oidx[e - R.slot0]);
+  lb_ld<T, W>(w + (e * U + u) * W, f);
+  lb_ld<T, W>(x + (node * U + u) * W, a);
+#pragma unroll
+  for (int q = 0; q < KT; ++q) g[q] = lb_ld1<T>(uv + e * K + (k0 + q < K ? k0 + q : K - 1));
+}
+// out[i][k][:] = sum over the slots of row i, ascending, of fl32(fl32(x[other node of the slot][:] * w[slot][:]) * u[slot][k]);
+// +0.0 for an empty row.  KT accumulator rows per pass over the slots (1 for K = 1, 3 for K > 1, as k_graph_conv: nine rows of a
+// bf16 unit would be 72 accumulators beside the loads in flight; K = 3, the common case, is one pass), SU slots' loads in flight;
+// the adds sequential.
+template <typename T, int W, int KT>
+__global__ void __launch_bounds__(256) k_graph_conv_vec(lb_glist L, lb_gwalk walk, const int32_t* __restrict__ oidx,
+                                                        const T* __restrict__ x, const T* __restrict__ w,
+                                                        const T* __restrict__ uv, T* __restrict__ out, int K) {
+  constexpr int SU = KT == 1 ? 4 : 2;
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t i, const lb_row& R, int u) {
+    for (int k0 = 0; k0 < K; k0 += KT) {
+      float s[KT][W], f[SU][W], a[SU][W], g[SU][KT];
+#pragma unroll
+      for (int q = 0; q < KT; ++q)
+#pragma unroll
+        for (int c = 0; c < W; ++c) s[q][c] = 0.f;
+      int p = R.p0;
+      if (p < R.p1) {   // the sum STARTS from the first product
+        graph_conv_vec_load<T, W, KT>(R, p++, oidx, x, w, uv, L, K, k0, U, u, f[0], a[0], g[0]);
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+          const float xw = __fmul_rn(a[0][c], f[0][c]);
+#pragma unroll
+          for (int q = 0; q < KT; ++q) s[q][c] = __fmul_rn(xw, g[0][q]);
+        }
+      }
+      for (; p + SU <= R.p1; p += SU) {
+#pragma unroll
+        for (int t = 0; t < SU; ++t) graph_conv_vec_load<T, W, KT>(R, p + t, oidx, x, w, uv, L, K, k0, U, u, f[t], a[t], g[t]);
+#pragma unroll
+        for (int t = 0; t < SU; ++t)
+#pragma unroll
+          for (int c = 0; c < W; ++c) {
+            const float xw = __fmul_rn(a[t][c], f[t][c]);
+#pragma unroll
+            for (int q = 0; q < KT; ++q) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(xw, g[t][q]));
+          }
+      }
+      for (; p < R.p1; ++p) {
+        graph_conv_vec_load<T, W, KT>(R, p, oidx, x, w, uv, L, K, k0, U, u, f[0], a[0], g[0]);
+#pragma unroll
+        for (int c = 0; c < W; ++c) {
+          const float xw = __fmul_rn(a[0][c], f[0][c]);
+#pragma unroll
+          for (int q = 0; q < KT; ++q) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(xw, g[0][q]));
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < KT; ++q)
+        if (k0 + q < K) lb_st<T, W>(out + ((i * K + k0 + q) * U + u) * W, s[q]);
+    }
+  });
+}
+
+// t[:] = fl32(v[node][0][:] * u[slot][0]) + fl32(v[node][1][:] * u[slot][1]) + ... (k ascending, the first product starts the
+// sum): one unit of the per-edge contraction of a vector feature with u (the edge gradients form the same t from the V units
+// they hold anyway).
+template <typename T, int W>
+__device__ __forceinline__ void graph_vec_dot(const T* __restrict__ v, const T* __restrict__ uv, int64_t node, int64_t e, int K,
+                                              int U, int u, float (&t)[W]) {
+  float a[W];
+  lb_ld<T, W>(v + (node * K * U + u) * W, a);
+  float g = lb_ld1<T>(uv + e * K);
+#pragma unroll
+  for (int c = 0; c < W; ++c) t[c] = __fmul_rn(a[c], g);
+#pragma unroll 4
+  for (int k = 1; k < K; ++k) {
+    lb_ld<T, W>(v + ((node * K + k) * U + u) * W, a);
+    g = lb_ld1<T>(uv + e * K + k);
+#pragma unroll
+    for (int c = 0; c < W; ++c) t[c] = __fadd_rn(t[c], __fmul_rn(a[c], g));
+  }
+}
+// out[i][:] = sum over the slots of row i, ascending, of fl32(w[slot][:] * t[slot][:]), t of the slot's other node as above; +0.0
+// for an empty row.  One accumulator row; two slots' loads (a w unit, K v units, K scalars of u each) in flight, the adds sequential.
+template <typename T, int W>
+__global__ void __launch_bounds__(256) k_graph_conv_dot(lb_glist L, lb_gwalk walk, const int32_t* __restrict__ oidx,
+                                                        const T* __restrict__ v, const T* __restrict__ w,
+                                                        const T* __restrict__ uv, T* __restrict__ out, int K) {
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t i, const lb_row& R, int u) {
+    float s[W], f[2][W], t[2][W];
+#pragma unroll
+    for (int c = 0; c < W; ++c) s[c] = 0.f;
+    auto term = [&](int p, float (&fw)[W], float (&tt)[W]) {
+      const int64_t e = R.edge(p);
+      lb_ld<T, W>(w + (e * U + u) * W, fw);
+      graph_vec_dot<T, W>(v, uv, graph_clamp(L, oidx[e - R.slot0]), e, K, U, u, tt);
+    };
+    int p = R.p0;
+    if (p < R.p1) {   // the sum STARTS from the first product
+      term(p++, f[0], t[0]);
+#pragma unroll
+      for (int c = 0; c < W; ++c) s[c] = __fmul_rn(f[0][c], t[0][c]);
+    }
+    for (; p + 2 <= R.p1; p += 2) {
+      term(p, f[0], t[0]);
+      term(p + 1, f[1], t[1]);
+#pragma unroll
+      for (int c = 0; c < W; ++c) {
+        s[c] = __fadd_rn(s[c], __fmul_rn(f[0][c], t[0][c]));
+        s[c] = __fadd_rn(s[c], __fmul_rn(f[1][c], t[1][c]));
+      }
+    }
+    if (p < R.p1) {
+      term(p, f[0], t[0]);
+#pragma unroll
+      for (int c = 0; c < W; ++c) s[c] = __fadd_rn(s[c], __fmul_rn(f[0][c], t[0][c]));
+    }
+    lb_st<T, W>(out + (i * U + u) * W, s);
+  });
+}
+
+// The edge gradients of both ops, from a scalar-side node tensor S (B N, C), read at the slot's node of `idx`, and a vector-side
+// one V (B N, K, C), read at its node of `oidx`:
+//   d_w[slot][c] = fl32(S[c] * t[c]), t the contraction of V with u above;
+//   d_u[slot][k] = sum over c of fl32(fl32(S[c] * w[slot][c]) * V[k][c]) in the FIXED order of LB_GRAPH_DU_BLOCK (include/lbhip.h):
+//                  consecutive blocks of 16 columns, c ascending inside a block from its first product, the block sums added in
+//                  ascending block order from the first one - whatever the unit width, the lanes per slot or the element type.
+// +0.0 in the pad slots of both.  A group of 2^lpr_shift lanes owns a slot and a lane the units lane, lane + lpr, ... as in the
+// pair kernels, so every load and the d_w store is one contiguous run per slot.  A block of 16 columns is BL = 16 / W
+// neighbouring lanes (W divides C and 16: a unit lies in one block; the last block may be short).  Its sum is a chain along
+// those lanes: the block's first lane adds its W products from the first one, each further lane takes its neighbour's partial
+// sum (one shuffle per k) and adds its own W products to it, c ascending - BL - 1 steps, every block of the wave at once.  The
+// block sums, held by each block's last lane, are then added in ascending block order (one shuffle per block and k); every
+// lane of the group holds the running sum, which carries over the rounds of a row wider than the group; lane 0 stores it.
+// (Lanes that own whole blocks need no chain, but read 16 bytes at a stride of 64, four times the cache lines per load: that
+// form ran clearly slower.)  Both outputs share the loads of S, V, w
+// and u; a null output is not computed.  KM: the k rows held in registers - 3 for K <= 3, LB_GRAPH_MAX_K otherwise.  The
+// slot's state lives across its units, so this kernel spells graph_for's two loops out, as k_graph_attend does.
+#define LB_GRAPH_MAX_K 9
+template <typename T, int W, int KM>
+__global__ void __launch_bounds__(256) k_graph_vec_edge_grad(lb_glist L, const int32_t* __restrict__ idx,
+                                                             const int32_t* __restrict__ oidx, const T* __restrict__ S,
+                                                             const T* __restrict__ V, const T* __restrict__ w,
+                                                             const T* __restrict__ uv, T* __restrict__ d_w, T* __restrict__ d_u,
+                                                             int K) {
+  static_assert(LB_GRAPH_DU_BLOCK % W == 0, "a unit lies in one block");
+  constexpr int BL = LB_GRAPH_DU_BLOCK / W;   // lanes of one block
+  const int U = L.U;
+  const lb_glanes G = graph_lanes(L);
+  const int lane0 = ((int)threadIdx.x & 63) - G.lane, pos = G.lane & (BL - 1);   // the group's first lane; this lane in its block
+  const int64_t rows = (int64_t)L.B * L.e_cap;
+  for (int64_t r = G.first; r < rows; r += G.stride) {
+    const lb_gslot sl = graph_slot(L, r, idx, oidx);   // (uniform over the group)
+    float tot[KM], g[KM];
+#pragma unroll
+    for (int k = 0; k < KM; ++k) tot[k] = 0.f, g[k] = 0.f;
+    if (sl.real) {
+#pragma unroll
+      for (int k = 0; k < KM; ++k)
+        if (k < K) g[k] = lb_ld1<T>(uv + r * K + k);
+    }
+    for (int u0 = 0; u0 < U; u0 += G.lpr) {   // one round: unit u0 + lane of every lane (uniform trip count)
+      const int u = u0 + G.lane, live = U - u0 < G.lpr ? U - u0 : G.lpr;   // live: the round's units
+      float du[KM][W], part[KM];
+#pragma unroll
+      for (int k = 0; k < KM; ++k) {
+        part[k] = 0.f;
+#pragma unroll
+        for (int c = 0; c < W; ++c) du[k][c] = 0.f;
+      }
+      if (u < U) {
+        float dw[W];
+#pragma unroll
+        for (int c = 0; c < W; ++c) dw[c] = 0.f;
+        if (sl.real) {
+          float s[W], f[W], t[W];
+          lb_ld<T, W>(S + (sl.node * U + u) * W, s);
+          lb_ld<T, W>(w + (r * U + u) * W, f);
+#pragma unroll
+          for (int k = 0; k < KM; ++k)
+            if (k < K) lb_ld<T, W>(V + ((sl.other * K + k) * U + u) * W, du[k]);
+#pragma unroll
+          for (int c = 0; c < W; ++c) f[c] = __fmul_rn(s[c], f[c]), t[c] = 0.f;   // fl32(S w)
+#pragma unroll
+          for (int k = 0; k < KM; ++k)
+            if (k < K) {
+#pragma unroll
+              for (int c = 0; c < W; ++c) {
+                const float tv = __fmul_rn(du[k][c], g[k]);
+                t[c] = k == 0 ? tv : __fadd_rn(t[c], tv);
+                du[k][c] = __fmul_rn(f[c], du[k][c]);
+              }
+            }
+#pragma unroll
+          for (int c = 0; c < W; ++c) dw[c] = __fmul_rn(s[c], t[c]);
+        }
+        if (d_w) lb_st<T, W>(d_w + (r * U + u) * W, dw);
+      }
+      if (d_u && sl.real) {
+        // the chain along the lanes of a block: step j is the block's lane j (all blocks of the wave at once)
+#pragma unroll
+        for (int j = 0; j < BL; ++j) {
+          if (j < live) {   // (uniform; a round shorter than a block ends its chain early)
+#pragma unroll
+            for (int k = 0; k < KM; ++k)
+              if (k < K) {
+                float v = j == 0 ? 0.f : __shfl_up(part[k], 1);
+                if (pos == j) {
+                  v = j == 0 ? du[k][0] : __fadd_rn(v, du[k][0]);
+#pragma unroll
+                  for (int c = 1; c < W; ++c) v = __fadd_rn(v, du[k][c]);
+                  part[k] = v;
+                }
+              }
+          }
+        }
+        // the block sums in ascending block order, from each block's last live lane
+        for (int b = 0; b * BL < live; ++b) {
+          const int end = ((b + 1) * BL < live ? (b + 1) * BL : live) - 1;
+#pragma unroll
+          for (int k = 0; k < KM; ++k)
+            if (k < K) {
+              const float v = __shfl(part[k], lane0 + end);
+              tot[k] = (u0 == 0 && b == 0) ? v : __fadd_rn(tot[k], v);
+            }
+        }
+      }
+    }
+    if (d_u && G.lane == 0) {
+#pragma unroll
+      for (int k = 0; k < KM; ++k)
+        if (k < K) lb_st1<T>(d_u + r * K + k, tot[k]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ feature transpose
 // d loss / d window (B N, isl, dim) fp64 from the cotangents of the features a TorchModel module receives: the transpose of the
 // feature builder as the comment above k_feat_bwd (lb_train.hip) states it, on the engine's current window and list, in the
@@ -1169,6 +1417,54 @@ extern "C" int lb_graph_conv(lb_engine* e, int32_t role, const void* x_dev, cons
     constexpr int W = decltype(w)::value;   // K > 1: three k at a time
     graph_launch(e, P.blocks, K == 1 ? k_graph_conv<T, W, 1> : k_graph_conv<T, W, 3>, P.L, P.walk, P.oidx, (const T*)x_dev,
                  (const T*)w_dev, (T*)out_dev, K);
+  });
+}
+
+// K and C of the vector ops: 1 <= K <= LB_GRAPH_MAX_K (u rows are read as scalars into registers), C >= 1
+static int graph_vec_sizes(const char* entry, int32_t K, int32_t C) {
+  if (K < 1 || K > LB_GRAPH_MAX_K || C < 1)
+    return lb_fail(LB_ERR_ARG, "%s: K %d (1 .. %d), C %d (>= 1)", entry, K, LB_GRAPH_MAX_K, C);
+  if ((int64_t)K * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "%s: K %d x C %d columns", entry, K, C);
+  return LB_OK;
+}
+
+extern "C" int lb_graph_conv_vec(lb_engine* e, int32_t role, const void* x_dev, const void* w_dev, const void* u_dev,
+                                 void* out_dev, int32_t K, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, "lb_graph_conv_vec", role, dtype, x_dev && w_dev && u_dev && out_dev, 1, 1));
+  LB_TRY(graph_vec_sizes("lb_graph_conv_vec", K, C));
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {x_dev, w_dev, out_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;   // K > 1: three k at a time
+    graph_launch(e, P.blocks, K == 1 ? k_graph_conv_vec<T, W, 1> : k_graph_conv_vec<T, W, 3>, P.L, P.walk, P.oidx, (const T*)x_dev,
+                 (const T*)w_dev, (const T*)u_dev, (T*)out_dev, K);
+  });
+}
+
+extern "C" int lb_graph_conv_dot(lb_engine* e, int32_t role, const void* v_dev, const void* w_dev, const void* u_dev,
+                                 void* out_dev, int32_t K, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, "lb_graph_conv_dot", role, dtype, v_dev && w_dev && u_dev && out_dev, 1, 1));
+  LB_TRY(graph_vec_sizes("lb_graph_conv_dot", K, C));
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {v_dev, w_dev, out_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    graph_launch(e, P.blocks, k_graph_conv_dot<T, decltype(w)::value>, P.L, P.walk, P.oidx, (const T*)v_dev, (const T*)w_dev,
+                 (const T*)u_dev, (T*)out_dev, K);
+  });
+}
+
+extern "C" int lb_graph_conv_vec_edge_grad(lb_engine* e, int32_t s_role, const void* s_dev, const void* v_dev, const void* w_dev,
+                                           const void* u_dev, void* d_w_dev, void* d_u_dev, int32_t K, int32_t C, int32_t dtype) {
+  // edge-parallel: no view.  Either output may be null (not wanted), not both.
+  LB_TRY(graph_entry(e, "lb_graph_conv_vec_edge_grad", s_role, dtype, s_dev && v_dev && w_dev && u_dev && (d_w_dev || d_u_dev), 1,
+                     1, false));
+  LB_TRY(graph_vec_sizes("lb_graph_conv_vec_edge_grad", K, C));
+  const lb_gplan P = graph_plan(e, s_role, dtype, LB_SLOTS, C, C, false, {s_dev, v_dev, w_dev, d_w_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;   // K <= 3 (a vector in space): three k rows in registers
+    graph_launch(e, P.blocks, K <= 3 ? k_graph_vec_edge_grad<T, W, 3> : k_graph_vec_edge_grad<T, W, LB_GRAPH_MAX_K>, P.L, P.idx,
+                 P.oidx, (const T*)s_dev, (const T*)v_dev, (const T*)w_dev, (const T*)u_dev, (T*)d_w_dev, (T*)d_u_dev, K);
   });
 }
 

@@ -40,8 +40,8 @@ def _graph_ops():
     the free sizes the entry takes; a trailing True says that an input may be None (a null pointer).  An output is (shape,
     dtype, like): like is the index, among the inputs followed by the earlier outputs, of a tensor of its shape and dtype, or
     -1."""
-    nc, sc, sh, shd, nh, nhd, nkc = ("nodes", "C"), ("slots", "C"), ("slots", "H"), ("slots", "H", "D"), ("nodes", "H"), \
-        ("nodes", "H", "D"), ("nodes", "K", "C")
+    nc, sc, sh, shd, nh, nhd, nkc, sk = ("nodes", "C"), ("slots", "C"), ("slots", "H"), ("slots", "H", "D"), ("nodes", "H"), \
+        ("nodes", "H", "D"), ("nodes", "K", "C"), ("slots", "K")
     f32, i32 = torch.float32, torch.int32
     ops = {
         "lb_graph_gather": ("lb_graph_gather_t", ((nc, None),), ((sc, None),), ("C",)),
@@ -59,6 +59,10 @@ def _graph_ops():
         "lb_graph_conv": ("lb_graph_conv", ((nkc, None), (sc, None)), ((nkc, None),), ("K", "C")),
         "lb_graph_pair_mul": ("lb_graph_pair_mul", ((nkc, None), (nkc, None)), ((sc, None),), ("K", "C")),
         "lb_graph_pair_add": ("lb_graph_pair_add", ((nc, None), (nc, None)), ((sc, None),), ("C",)),
+        "lb_graph_conv_vec": ("lb_graph_conv_vec", ((nc, None), (sc, None), (sk, None)), ((nkc, None),), ("K", "C")),
+        "lb_graph_conv_dot": ("lb_graph_conv_dot", ((nkc, None), (sc, None), (sk, None)), ((nc, None),), ("K", "C")),
+        "lb_graph_conv_vec_edge_grad": ("lb_graph_conv_vec_edge_grad", ((nc, None), (nkc, None), (sc, None), (sk, None)),
+                                        ((sc, None), (sk, None)), ("K", "C")),
         "lb_graph_features_backward": ("lb_graph_features_backward",
                                        ((("nodes", "isl", "dim"), f32), (("nodes", "vel"), f32), (("nodes", "mag"), f32),
                                         (("nodes", "bound"), f32), (("slots", "dim"), f32), (("slots", 1), f32)),
@@ -496,10 +500,11 @@ class RolloutEngine:
     # contract: round_to_bf16(float32 op(upcast inputs)) bit for bit.
     _GRAPH_DTYPES = {torch.float32: 0, torch.bfloat16: 1}   # LB_DTYPE_F32, LB_DTYPE_BF16
 
-    def _graph_call(self, symbol: str, role, tensors=(), **fixed):
+    def _graph_call(self, symbol: str, role, tensors=(), want=None, **fixed):
         """The one way into the lb_graph_* entries (_GRAPH_OPS): check every input against its shape, dtype, device and
         contiguity, allocate the outputs, call, return the outputs.  Where the table allows it, None passes a null pointer;
-        `fixed` gives the sizes of a shape that the caller sets (graph_features_backward)."""
+        `fixed` gives the sizes of a shape that the caller sets (graph_features_backward).  `want`: one flag per output - an
+        output not wanted is not allocated, the entry gets a null pointer and None is returned in its place."""
         entry, ins, outs, sizes, optional = _GRAPH_OPS[symbol]
         dims = {"nodes": self.B * self.N, "slots": self.B * self.e_cap, 1: 1}
         if fixed:
@@ -532,7 +537,13 @@ class RolloutEngine:
                                  f"{getattr(t, 'device', None)}")
             args.append(t.data_ptr())
         made = []
-        for shape, dtype, like in outs:   # (the cheapest allocation that fits: a twin's, the data tensors', a plain one)
+        # (the cheapest allocation that fits: a twin's, the data tensors', a plain one)
+        for n, (shape, dtype, like) in enumerate(outs):
+            if want is not None and not want[n]:
+                seen.append(None)
+                made.append(None)
+                args.append(None)
+                continue
             if like >= 0:
                 o = torch.empty_like(seen[like])
             elif dtype is None:
@@ -624,6 +635,33 @@ class RolloutEngine:
         """a, b (B*N, C), one dtype -> (B*E_cap, C): a[the slot's `a_role` node] + b[its other node] in the real slots, one
         float32 add, +0.0 in the pad slots (include/lbhip.h: lb_graph_pair_add)."""
         return self._graph_call("lb_graph_pair_add", a_role, (a, b))
+
+    def graph_conv_vec(self, role: int, x: torch.Tensor, w: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+        """x (B*N, C), w (B*E_cap, C), u (B*E_cap, K), 1 <= K <= 9, one dtype (float32 or bfloat16) -> (B*N, K, C): per node
+        the sum over its real slots of `role`, in ascending slot order, of (x[the slot's other node] * w[slot]) * u[slot, k] -
+        two rounded float32 products, one float32 add after the other, the first term starts the sum; nothing edge-shaped of K C
+        columns exists.  float32: the bits of graph_segment_sum((graph_gather(x) * w)[:, None, :] * u[:, :, None]).  bfloat16:
+        that float32 result on the widened inputs, rounded once (include/lbhip.h: lb_graph_conv_vec)."""
+        return self._graph_call("lb_graph_conv_vec", role, (x, w, u))
+
+    def graph_conv_dot(self, role: int, v: torch.Tensor, w: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+        """v (B*N, K, C), w (B*E_cap, C), u (B*E_cap, K), one dtype -> (B*N, C): per node the sum over its real slots of `role`,
+        ascending, of w[slot] * t[slot], t = v[the slot's other node, 0] * u[slot, 0] + v[.., 1] * u[slot, 1] + ... (k
+        ascending, every product rounded to float32, the first starts the sum).  The adjoint of graph_conv_vec over the other
+        role (include/lbhip.h: lb_graph_conv_dot)."""
+        return self._graph_call("lb_graph_conv_dot", role, (v, w, u))
+
+    def graph_conv_vec_edge_grad(self, s_role: int, s: torch.Tensor, v: torch.Tensor, w: torch.Tensor, u: torch.Tensor,
+                                 want_w: bool = True, want_u: bool = True):
+        """s (B*N, C) read at the slot's `s_role` node, v (B*N, K, C) at its other node, w (B*E_cap, C), u (B*E_cap, K) -> (d_w
+        (B*E_cap, C), d_u (B*E_cap, K)), the gradients of graph_conv_vec (s = x, v = the cotangent) and graph_conv_dot (s = the
+        cotangent, v = v) to w and u, +0.0 in the pad slots: d_w = s * t with t as in graph_conv_dot; d_u[slot, k] = the sum over c
+        of (s[c] * w[slot, c]) * v[k, c] in blocks of 16 columns - c ascending inside a block, the block sums added in ascending
+        order.  One launch shares the loads; an output not wanted is neither computed nor allocated (None in its place)
+        (include/lbhip.h: lb_graph_conv_vec_edge_grad)."""
+        if not (want_w or want_u):
+            return None, None
+        return self._graph_call("lb_graph_conv_vec_edge_grad", s_role, (s, v, w, u), want=(want_w, want_u))
 
     def graph_features_backward(self, d_abs_pos=None, d_vel_hist=None, d_vel_mag=None, d_bound=None, d_rel_disp=None,
                                 d_rel_dist=None) -> torch.Tensor:

@@ -19,6 +19,9 @@ describes, in the padded layout of ``features["senders"]`` / ``["receivers"]`` (
                                              #   segment_sum(gather(x, "receivers") * w[..., None, :], "senders")
     e = g.pair_add(a, b)                     # (B, N, C) twice -> (B, E_cap, C): a[senders] + b[receivers]
     m = g.pair_mul(a, b)                     # ... a[senders] * b[receivers]
+    dv = g.conv_vec(s, w, u, "senders")      # (B, N, C), (B, E_cap, C), (B, E_cap, K) -> (B, N, K, C): scalar -> vector channels,
+                                             #   segment_sum((gather(s, "receivers") * w)[..., None, :] * u[..., :, None], "senders")
+    ds = g.conv_dot(v, w, u, "senders")      # (B, N, K, C), ... -> (B, N, C): vector -> scalar, sum of w * <v[receivers], u>
 
 (with un-batched features the leading B is dropped: (N, C) -> (E_cap, C)).  Trailing dimensions beyond C are folded into C
 where the op is column-wise (all but ``attend``).
@@ -58,6 +61,27 @@ message-passing layer, without their edge-shaped intermediates, under the same c
 * ``pair_mul(a, b)`` = ``fl32(a[senders] * b[receivers])`` and ``pair_add(a, b)`` = ``fl32(a[senders] + b[receivers])``, a and b
   (B, N, C) -> (B, E_cap, C), +0.0 in the pad slots.  Backward: ``conv(b, d, "senders")`` and ``conv(a, d, "receivers")``;
   ``segment_sum(d, "senders")`` and ``segment_sum(d, "receivers")``.
+
+Vector messages.  ``conv_vec`` and ``conv_dot`` couple scalar channels to vector channels through a per-edge vector ``u``
+(B, E_cap, K), 1 <= K <= 9 - ``features["rel_disp"]``, or spherical harmonics up to l = 2: PaiNN's ``w_vs s_j (x) r_ij`` and
+``w_sv <v_j, r_ij>``, EGNN's position update at C = 1 - without the (B, E_cap, K, C) product, under the same contracts (n(j) is
+the `role` node of slot j, o(j) its other node; every product is rounded to float32, every sum starts from its first term):
+
+* ``conv_vec(x, w, u, role)[i, k, c]``: the sum over the real slots j with n(j) = i, ascending, of
+  ``fl32(fl32(x[o(j), c] * w[j, c]) * u[j, k])``; on float32 the composition written above, bit for bit.
+* ``conv_dot(v, w, u, role)[i, c]``: the sum over those slots of ``fl32(w[j, c] * t[j, c])`` with ``t[j, c] = fl32(v[o(j), 0, c] *
+  u[j, 0]) + fl32(v[o(j), 1, c] * u[j, 1]) + ...``, k ascending.
+* They are each other's adjoints: ``d_x`` of ``conv_vec`` over `role` is ``conv_dot(d, w, u, other role)`` and ``d_v`` of
+  ``conv_dot`` is ``conv_vec(d, w, u, other role)`` - the same kernels, the same bits.
+* The gradients to w and u of either op come from one edge-parallel launch over a scalar-side node tensor S and a vector-side
+  one V (``conv_vec``: S = x at o(j), V = d at n(j); ``conv_dot``: S = d at n(j), V = v at o(j)): ``d_w[j, c] = fl32(S[c] *
+  t[j, c])`` with t formed from V and u as above, and ``d_u[j, k]`` = the sum over c of ``fl32(fl32(S[c] * w[j, c]) * V[k, c])``
+  in a fixed order - the columns in consecutive blocks of 16 (the last may be short), c ascending inside a block, the block sums
+  added in ascending block order - which a numpy loop reproduces.  Pad slots of both are +0.0; a gradient nobody asked for is
+  neither computed nor allocated; only x / v, w and u are saved.  The gradient to u flows on to the window through
+  ``differentiable_features``.
+* On bfloat16 every output, ``d_u`` included, is the float32 result on the widened inputs rounded once - not the composition
+  of the bfloat16 ops.
 
 bfloat16.  Every op takes float32 or bfloat16 tensors (what ``torch.autocast(dtype=torch.bfloat16)`` hands a module) and
 returns the dtype it was given.  One contract for every op and every backward:
@@ -263,6 +287,86 @@ class _Pair(torch.autograd.Function):
         return grads[0], grads[1], None, None
 
 
+_MAX_K = 9   # LB_GRAPH_MAX_K (csrc/lb_graph.hip): u rows are read as scalars into registers
+
+
+def _vec_args(graph, name: str, node, w, u, vector: bool):
+    """The checks of conv_vec (node = x (B, N, C)) and conv_dot (node = v (B, N, K, C)) -> the flat node tensor ((B N, C) or
+    (B N, K, C)), w (B E_cap, C), u (B E_cap, K)."""
+    e = graph.engine
+    _one_dtype(name, node, w, "x, w and u" if not vector else "v, w and u")
+    _one_dtype(name, w, u, "x, w and u" if not vector else "v, w and u")
+    nf, rn = graph._flat(name, node, e.N)
+    wf, rw = graph._flat(name, w, e.e_cap)
+    uf, ru = graph._flat(name, u, e.e_cap)
+    if len(rw) != 1 or len(ru) != 1 or rn != ((ru + rw) if vector else rw) or not 1 <= ru[0] <= _MAX_K:
+        raise ValueError(f"graph.{name}: expected {'v' if vector else 'x'} {graph._shape(e.N) + (('K', 'C') if vector else ('C',))}, "
+                         f"w {graph._shape(e.e_cap) + ('C',)} and u {graph._shape(e.e_cap) + ('K',)} with 1 <= K <= {_MAX_K}, got "
+                         f"{tuple(node.shape)}, {tuple(w.shape)} and {tuple(u.shape)}")
+    return (nf.reshape(e.B * e.N, ru[0], rw[0]) if vector else nf), wf, uf
+
+
+class _ConvVec(torch.autograd.Function):
+    """conv_vec over `role`: d_x is conv_dot of the cotangent over the other role; d_w and d_u come from one edge launch with
+    S = x at the slot's other node and V = the cotangent at its `role` node."""
+
+    @staticmethod
+    def forward(ctx, x, w, u, graph, role):
+        e = graph.engine
+        xf, wf, uf = _vec_args(graph, "conv_vec", x, w, u, False)
+        out = e.graph_conv_vec(role, xf, wf, uf)
+        ctx.graph, ctx.role = graph, role
+        ctx.save_for_backward(xf, wf, uf)
+        return out.reshape(graph._shape(e.N) + (uf.shape[1], wf.shape[1]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        xf, wf, uf = ctx.saved_tensors
+        df, _ = g._flat("conv_vec", d, e.N, xf.dtype)
+        df = df.reshape(e.B * e.N, uf.shape[1], wf.shape[1])
+        need = ctx.needs_input_grad
+        d_x = d_w = d_u = None
+        if need[0]:
+            d_x = e.graph_conv_dot(1 - ctx.role, df, wf, uf).reshape(g._shape(e.N) + (wf.shape[1],))
+        if need[1] or need[2]:
+            d_w, d_u = e.graph_conv_vec_edge_grad(1 - ctx.role, xf, df, wf, uf, need[1], need[2])
+            d_w = None if d_w is None else d_w.reshape(g._shape(e.e_cap) + (wf.shape[1],))
+            d_u = None if d_u is None else d_u.reshape(g._shape(e.e_cap) + (uf.shape[1],))
+        return d_x, d_w, d_u, None, None
+
+
+class _ConvDot(torch.autograd.Function):
+    """conv_dot over `role`: d_v is conv_vec of the cotangent over the other role; d_w and d_u come from one edge launch with
+    S = the cotangent at the slot's `role` node and V = v at its other node."""
+
+    @staticmethod
+    def forward(ctx, v, w, u, graph, role):
+        e = graph.engine
+        vf, wf, uf = _vec_args(graph, "conv_dot", v, w, u, True)
+        out = e.graph_conv_dot(role, vf, wf, uf)
+        ctx.graph, ctx.role = graph, role
+        ctx.save_for_backward(vf, wf, uf)
+        return out.reshape(graph._shape(e.N) + (wf.shape[1],))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        vf, wf, uf = ctx.saved_tensors
+        df, _ = g._flat("conv_dot", d, e.N, vf.dtype)
+        need = ctx.needs_input_grad
+        d_v = d_w = d_u = None
+        if need[0]:
+            d_v = e.graph_conv_vec(1 - ctx.role, df, wf, uf).reshape(g._shape(e.N) + (uf.shape[1], wf.shape[1]))
+        if need[1] or need[2]:
+            d_w, d_u = e.graph_conv_vec_edge_grad(ctx.role, df, vf, wf, uf, need[1], need[2])
+            d_w = None if d_w is None else d_w.reshape(g._shape(e.e_cap) + (wf.shape[1],))
+            d_u = None if d_u is None else d_u.reshape(g._shape(e.e_cap) + (uf.shape[1],))
+        return d_v, d_w, d_u, None, None
+
+
 _FLOAT_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "force", "rel_disp", "rel_dist")
 _GRAD_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "rel_disp", "rel_dist")   # ("force" is a constant of the positions)
 
@@ -335,7 +439,8 @@ def differentiable_features(features, window: torch.Tensor) -> dict:
 
 class Graph:
     """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum and the attention
-    ops (degree, segment_mean / max / min / softmax, attend) and the edge messages (conv, pair_mul, pair_add).
+    ops (degree, segment_mean / max / min / softmax, attend) and the edge messages (conv, pair_mul, pair_add, conv_vec,
+    conv_dot).
     `batched`: whether the tensors carry the leading B (default: as the features do)."""
 
     def __init__(self, features, batched: Optional[bool] = None):
@@ -463,6 +568,21 @@ class Graph:
         nothing edge-shaped.  Equal trailing dimensions fold into C.  On bfloat16 the exact products are summed in float32 and
         the sum is rounded once: not the composition of the bfloat16 ops, which rounds every product first."""
         return _Conv.apply(x, w, self, self._role(role))
+
+    def conv_vec(self, x: torch.Tensor, w: torch.Tensor, u: torch.Tensor, role: str) -> torch.Tensor:
+        """x (B, N, C), w (B, E_cap, C), u (B, E_cap, K) with 1 <= K <= 9 -> (B, N, K, C), scalar to vector channels: per node
+        the ordered sum over its real slots of `role` of (x[the slot's other node] * w[slot]) * u[slot, k] - PaiNN's
+        ``w_vs s_j (x) r_ij``, EGNN's position update at C = 1 - bit for bit
+        segment_sum((gather(x, other role) * w)[..., None, :] * u[..., :, None], role) on float32, in one kernel that writes
+        nothing edge-shaped.  On bfloat16 the float32 result on the widened inputs, rounded once."""
+        return _ConvVec.apply(x, w, u, self, self._role(role))
+
+    def conv_dot(self, v: torch.Tensor, w: torch.Tensor, u: torch.Tensor, role: str) -> torch.Tensor:
+        """v (B, N, K, C), w (B, E_cap, C), u (B, E_cap, K) with 1 <= K <= 9 -> (B, N, C), vector to scalar channels: per node
+        the ordered sum over its real slots of `role` of w[slot] * <v[the slot's other node], u[slot]>, the inner product added
+        k by k from its first product - bit for bit segment_sum(w * t, role) on float32 with t spelled out from
+        gather(v, other role)[..., k, :] * u[..., k:k+1].  The adjoint of conv_vec over the other role."""
+        return _ConvDot.apply(v, w, u, self, self._role(role))
 
     def pair_mul(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         """a, b (B, N, C) -> (B, E_cap, C): a[senders] * b[receivers] in the real slots (one rounded product), +0.0 in the
