@@ -701,6 +701,20 @@ int lb_edge_accounting(lb_engine* eng, int64_t* sum_edges, int64_t* n_builds, in
  * roofline line is about with this.  No reference counterpart (measurement aid). */
 int lb_kernel_names(lb_engine* eng, char* out, int32_t cap);
 
+/* What the most recent neighbor-list build (lb_nl_allocate, lb_nl_update, a rollout step outside a replayed graph) launched,
+ * as "key=value;" pairs (NUL-terminated, truncated to cap), read from host bookkeeping only:
+ *   build     k_nl_small | k_nl_mid (the whole build in one launch) | multi
+ *   cells     none | strided | cells_small | cells_traj | cells_mid | sort (the counting sort)
+ *   search    none | k_nl | k_nlw | k_nlc: the sweep that writes edges;  f32, dim: the template instance of the search or
+ *             single-launch kernel;  cell_list, dense: 0 | 1
+ *   cand      staged candidates of k_nl (128 .. 1024 one wave, 2048 four waves; 0 for the other kernels)
+ *   count, count_cand   the same for the counting sweep of an allocation (it may run another kernel than the fill)
+ *   mode      none | rows (one sweep into per-node rows) | count+fill (two sweeps)
+ *   finish    none | compact_scan | rows_small | scan+finish, "+compact" appended when k_nl_compact follows
+ *   reentry   none, or the kernel an allocation counted with before it hit the stencil limit and ran again dense
+ * An allocation reports its whole call.  No reference counterpart (test aid). */
+int lb_nl_route(lb_engine* eng, char* out, int32_t cap);
+
 /* Stand-alone jraph.segment_sum(messages, receivers, N) on the CURRENT list (gns.py:117-119):
  * msg (E_total,D) fp32 in engine edge order -> out (B*N,D) fp32.  Used by tests and by the
  * aggregation-roofline leg of bench.py. */

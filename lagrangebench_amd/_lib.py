@@ -153,6 +153,7 @@ _SIGS = {
     "lb_edge_accounting": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                      C.POINTER(C.c_int64), C.c_int32]),
     "lb_kernel_names": (C.c_int, [_P, C.c_char_p, C.c_int32]),
+    "lb_nl_route": (C.c_int, [_P, C.c_char_p, C.c_int32]),
     "lb_gns_train_create": (C.c_int, [_P, C.POINTER(GnsDesc), C.POINTER(C.c_float), C.c_int64, C.POINTER(_P)]),
     "lb_gns_train_destroy": (None, [_P]),
     "lb_gns_train_loss_grad": (C.c_int, [_P, _P, C.c_float, C.POINTER(C.c_double), _P]),

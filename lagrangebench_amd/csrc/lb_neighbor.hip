@@ -1075,6 +1075,36 @@ __device__ __forceinline__ int lb_did_overflow(const lb_geom& g, int eb, int e_c
   return (eb > e_cap) || (g.use_cell_list && max_occ > cell_capacity) || row_overflow;
 }
 
+// The bins of a build, for the largest cell occupancy of ONE trajectory: fixed-stride slots keep every cell's particle count
+// in cnt (cap > 0, counts may exceed cap), the CSR bins its first slot in start.
+struct lb_cell_bins {
+  const int32_t* cnt;
+  const int32_t* start;
+  int32_t cap;
+};
+
+// did_buffer_overflow is per trajectory (the reference vmaps the list over the batch), ctrl->max_cell_occ is the batch's.
+// True when some trajectory's cells overflowed (the same for every thread); then occ_out[b] receives trajectory b's largest
+// occupancy, re-counted from the bins.  Called by every thread of ONE workgroup; on the usual path it costs one read.
+// (k_cells_traj already leaves each trajectory's occupancy in cell_count[b]; the re-count serves every binning route alike.)
+__device__ __forceinline__ bool lb_traj_cell_occ(const lb_geom& g, const lb_ctrl* __restrict__ ctrl, const lb_cell_bins& c,
+                                                 int32_t cell_capacity, int32_t* __restrict__ occ_out) {
+  if (!g.use_cell_list || ctrl->max_cell_occ <= cell_capacity) return false;
+  for (int b = threadIdx.x; b < g.B; b += blockDim.x) occ_out[b] = 0;
+  __syncthreads();
+  for (int b = 0; b < g.B; ++b) {
+    int m = 0;
+    for (int h = threadIdx.x; h < g.ncells; h += blockDim.x) {
+      const int gc = b * g.ncells + h;
+      m = max(m, c.cap ? c.cnt[gc] : c.start[gc + 1] - c.start[gc]);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(&occ_out[b], m);
+  }
+  __syncthreads();
+  return true;
+}
+
 // The control block after a build: edge counts and, on the update path (frozen), a did_buffer_overflow or an edge list longer
 // than the allocation poisons the step (overflow_step + the pinned host word, visible once the kernel retires)
 __device__ __forceinline__ void lb_ctrl_finish(lb_ctrl* __restrict__ ctrl, int total, int64_t e_alloc, bool frozen, bool ov,
@@ -1113,7 +1143,8 @@ __global__ void __launch_bounds__(256)
                       const float* __restrict__ tfeat, const double* __restrict__ tfeat64,
                       int32_t* __restrict__ senders, int32_t* __restrict__ receivers, float* __restrict__ efeat,
                       double* __restrict__ efeat64, int64_t e_alloc, int32_t* __restrict__ overflow,
-                      int32_t* __restrict__ nedges_b, int32_t cell_capacity, int32_t e_cap, int32_t* host_flag) {
+                      int32_t* __restrict__ nedges_b, int32_t cell_capacity, int32_t e_cap, int32_t* host_flag,
+                      lb_cell_bins bins) {
   __shared__ int s_red[4], s_deg[16], s_b[64];
   if (ctrl->overflow_step >= 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1154,12 +1185,13 @@ __global__ void __launch_bounds__(256)
     if (tid == 0) s_b[b] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
   }
   __syncthreads();
+  const bool cells_over = lb_traj_cell_occ(g, ctrl, bins, cell_capacity, overflow);  // (overflow[b]: trajectory b's occupancy)
   if (tid == 0) {
     int any = 0;
     for (int b = 0; b < g.B; ++b) {
       const int eb = s_b[b];
       nedges_b[b] = eb;
-      const int ov = lb_did_overflow(g, eb, e_cap, ctrl->max_cell_occ, cell_capacity, ctrl->row_overflow);
+      const int ov = lb_did_overflow(g, eb, e_cap, cells_over ? overflow[b] : 0, cell_capacity, ctrl->row_overflow);
       overflow[b] = ov;
       any |= ov;
     }
@@ -1176,13 +1208,14 @@ __device__ __forceinline__ void lb_row_finish_body(const lb_geom& g, const int32
                                                    lb_ctrl* __restrict__ ctrl, int32_t* __restrict__ overflow,
                                                    int32_t* __restrict__ nedges_b, int32_t cell_capacity,
                                                    int32_t e_cap, int64_t e_alloc, int frozen, int32_t* host_flag,
-                                                   int* s_any) {
+                                                   int* s_any, const lb_cell_bins& bins) {
   if (threadIdx.x == 0) *s_any = 0;
   __syncthreads();
+  const bool cells_over = frozen && lb_traj_cell_occ(g, ctrl, bins, cell_capacity, overflow);  // (overflow[b]: b's occupancy)
   for (int b = threadIdx.x; b < g.B; b += blockDim.x) {
     const int eb = row_ptr[(b + 1) * g.N] - row_ptr[b * g.N];
     nedges_b[b] = eb;
-    const int ov = frozen ? lb_did_overflow(g, eb, e_cap, ctrl->max_cell_occ, cell_capacity, ctrl->row_overflow) : 0;
+    const int ov = frozen ? lb_did_overflow(g, eb, e_cap, cells_over ? overflow[b] : 0, cell_capacity, ctrl->row_overflow) : 0;
     overflow[b] = ov;
     if (ov) atomicExch(s_any, 1);
   }
@@ -1194,18 +1227,19 @@ __global__ void __launch_bounds__(256)
     k_row_finish(lb_geom g, const int32_t* __restrict__ row_ptr, int n, lb_ctrl* __restrict__ ctrl,
                  int32_t* __restrict__ overflow, int32_t* __restrict__ nedges_b,
                  int32_t cell_capacity, int32_t e_cap, int64_t e_alloc, int frozen,
-                 int32_t* host_flag) {
+                 int32_t* host_flag, lb_cell_bins bins) {
   if (ctrl->overflow_step >= 0) return;
   __shared__ int s_any;
   lb_row_finish_body(g, row_ptr, n, ctrl, overflow, nedges_b, cell_capacity, e_cap, e_alloc, frozen, host_flag,
-                     &s_any);
+                     &s_any, bins);
 }
 
 // Small problems: degree scan (both passes) + k_row_finish in one single-workgroup launch.
 __global__ void __launch_bounds__(LB_SMALL_T)
     k_rows_small(lb_geom g, const int32_t* __restrict__ deg, int32_t* __restrict__ row_ptr, int n,
                  lb_ctrl* __restrict__ ctrl, int32_t* __restrict__ overflow, int32_t* __restrict__ nedges_b,
-                 int32_t cell_capacity, int32_t e_cap, int64_t e_alloc, int frozen, int32_t* host_flag) {
+                 int32_t cell_capacity, int32_t e_cap, int64_t e_alloc, int frozen, int32_t* host_flag,
+                 lb_cell_bins bins) {
   __shared__ int s_scan[LB_SMALL_T];
   __shared__ int s_any;
   if (ctrl->overflow_step >= 0) return;
@@ -1242,7 +1276,7 @@ __global__ void __launch_bounds__(LB_SMALL_T)
   if (tid == LB_SMALL_T - 1) row_ptr[n] = s_scan[tid];
   __syncthreads();  // row_ptr written by this workgroup is visible to it
   lb_row_finish_body(g, row_ptr, n, ctrl, overflow, nedges_b, cell_capacity, e_cap, e_alloc, frozen, host_flag,
-                     &s_any);
+                     &s_any, bins);
 }
 
 // ---------------------------------------------------------------- one trajectory, <= 4096 particles: ONE launch
@@ -1748,6 +1782,8 @@ static void lb_launch_lds(int limit, dim3 grid, dim3 block, size_t lds, hipStrea
 template <int MODE>
 static void lb_launch_nl(lb_engine* e, int small, const lb_nl_args& a) {
   const int kind = lb_nl_kernel_kind(e);
+  (MODE == NL_COUNT ? e->nl_route.count : e->nl_route.search) = (int8_t)kind;
+  (MODE == NL_COUNT ? e->nl_route.count_cand : e->nl_route.cand) = (int16_t)(kind ? 0 : small ? small : LB_MAX_STENCIL_CAND);
   // NL_ROWS in a rollout step: workgroups behind the search's write the node-feature rows
   const bool ride = MODE == NL_ROWS && e->feat_job.xnode && !a.out.efeat64;
   if (ride) e->feat_done = true;
@@ -1834,6 +1870,8 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   const int ncell_tot = g.B * g.ncells;
   hipStream_t s = e->stream;
   const int frozen = e->e_cap > 0;
+  lb_engine::nl_route_rec& route = e->nl_route;
+  route = {};
 
   // LB_SMALL_FUSED=0: always the multi-launch bookkeeping (lb_fused_launches, lb_internal.h)
   const bool small_ok = lb_fused_launches();
@@ -1854,6 +1892,7 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   const bool nlm = one_traj && BN > LB_SMALL_N && BN <= NLM_N && g.use_cell_list && nlm_lds <= LB_NLS_MAX_LDS &&
                    (int64_t)e->cell_capacity * g.nstencil <= NLM_ROWBUF - LB_MAX_ROW * (NLM_RPW - 1);
   if (nls || nlm) {
+    route.single = nls ? 1 : 2;
     lb_tic(e, LB_T_NEIGH);
     const lb_nls_args a = lb_nls_setup(e, want_efeat64, npad);
     const auto launch = g.f32 ? (g.dim == 3 ? lb_launch_one_traj<true, 3> : lb_launch_one_traj<true, 2>)
@@ -1882,6 +1921,7 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   const bool strided = small_ok && frozen && g.use_cell_list && e->cell_capacity > 0 && lb_nl_kernel_kind(e) != 1 &&
                        strided_slots < ((int64_t)1 << 30);
 #endif
+  route.cells = strided ? 1 : small_cells ? 2 : traj_cells ? 3 : mid_cells ? 4 : 5;
   if (strided) {
     if (strided_slots > e->cell_slots)   // (first build after an allocation: never inside a graph capture)
       LB_TRY(lb_regrow(s, &e->cell_slots, strided_slots + strided_slots / 4, [&](int64_t n) {
@@ -1945,6 +1985,8 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   a.row_ptr = e->row_ptr;
   a.e_alloc = e->e_alloc;
   a.maxd = e->maxd;
+  const lb_cell_bins bins{e->cell_count, e->cell_start, a.cell_cap};
+  route.rows = rows;
   if (rows) {
     a.out = {e->tmp_send, nullptr, e->tmp_feat, want_efeat64 ? e->tmp_feat64 : nullptr};
     lb_launch_nl<NL_ROWS>(e, small, a);
@@ -1953,18 +1995,20 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   }
   // update path of a small batch: scan + finish + compaction in one launch (LB_SMALL_FUSED=0: the separate launches)
   if (rows && small_ok && BN <= LB_CSCAN_N && g.B <= 64) {
+    route.finish = 1;
     hipLaunchKernelGGL(k_nl_compact_scan, dim3((int)((BN + 15) / 16)), dim3(256), 0, s, g, BN, e->ctrl, e->deg, e->row_ptr,
                        e->maxd, e->tmp_send, e->tmp_feat, want_efeat64 ? e->tmp_feat64 : (const double*)nullptr,
                        e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : (double*)nullptr, e->e_alloc,
-                       e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->host_flag_dev);
+                       e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->host_flag_dev, bins);
     lb_toc(e);
     LB_HIP(hipGetLastError());
     return LB_OK;
   }
+  route.finish = small_rows ? 2 : 3;
   if (small_rows) {
     hipLaunchKernelGGL(k_rows_small, dim3(1), dim3(LB_SMALL_T), 0, s, g, e->deg, e->row_ptr, (int)BN, e->ctrl,
                        e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->e_alloc, frozen,
-                       e->host_flag_dev);
+                       e->host_flag_dev, bins);
   } else {
     const int nsb_r = (int)((BN + SCAN_CHUNK - 1) / SCAN_CHUNK);
     hipLaunchKernelGGL(k_scan_partials, dim3(nsb_r), dim3(SCAN_THREADS), 0, s, e->deg, (int)BN,
@@ -1973,9 +2017,10 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
                        e->scan_part, e->ctrl);
     hipLaunchKernelGGL(k_row_finish, dim3(1), dim3(256), 0, s, g, e->row_ptr, (int)BN, e->ctrl,
                        e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->e_alloc, frozen,
-                       e->host_flag_dev);
+                       e->host_flag_dev, bins);
   }
   if (rows) {
+    route.compact = 1;
     hipLaunchKernelGGL(k_nl_compact, dim3((int)((BN + 15) / 16)), dim3(256), 0, s, BN, e->ctrl, e->deg,
                        e->row_ptr, e->maxd, e->tmp_send, e->tmp_feat,
                        want_efeat64 ? e->tmp_feat64 : (const double*)nullptr, e->senders, e->receivers,
@@ -1996,7 +2041,10 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
       e->nl_dense = true;
       e->ctrl_host->density_error = 0;
       LB_HIP(hipMemcpyAsync(&e->ctrl->density_error, &e->ctrl_host->density_error, sizeof(int32_t), hipMemcpyHostToDevice, s));
-      return lbk_nl_build(e, want_efeat64);  // count again with the kernel that has no candidate limit
+      const int8_t first = (int8_t)(route.count + 1);
+      const int rc = lbk_nl_build(e, want_efeat64);  // count again with the kernel that has no candidate limit
+      route.reentry = first;
+      return rc;
     }
     if (e->ctrl_host->max_deg > LB_MAX_ROW) e->nl_dense = true;
     if (e->nl_dense) {
@@ -2023,6 +2071,22 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   lb_launch_nl<NL_FILL>(e, small, a);
   lb_toc(e);
   LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+
+extern "C" int lb_nl_route(lb_engine* e, char* out, int32_t cap) {
+  if (!e || !out || cap < 1) return lb_fail(LB_ERR_ARG, "null argument");
+  const lb_engine::nl_route_rec& r = e->nl_route;
+  static const char* const single[] = {"multi", "k_nl_small", "k_nl_mid"};
+  static const char* const cells[] = {"none", "strided", "cells_small", "cells_traj", "cells_mid", "sort"};
+  static const char* const search[] = {"none", "k_nl", "k_nlw", "k_nlc"};
+  static const char* const finish[] = {"none", "compact_scan", "rows_small", "scan+finish"};
+  snprintf(out, (size_t)cap,
+           "build=%s;cells=%s;search=%s;cand=%d;count=%s;count_cand=%d;mode=%s;finish=%s%s;reentry=%s;f32=%d;dim=%d;cell_list=%d;"
+           "dense=%d",
+           single[r.single], cells[r.cells], search[r.search + 1], (int)r.cand, search[r.count + 1], (int)r.count_cand,
+           r.rows ? "rows" : r.count >= 0 ? "count+fill" : "none", finish[r.finish], r.compact ? "+compact" : "",
+           search[r.reentry], (int)e->g.f32, e->g.dim, (int)e->g.use_cell_list, (int)e->nl_dense);
   return LB_OK;
 }
 

@@ -302,6 +302,14 @@ class RolloutEngine:
         check(self.lib.lb_nl_read_idx(self._h, ptr(idx), ptr(ne)), "lb_nl_read_idx")
         return idx, ne
 
+    def nl_route(self) -> dict:
+        """What the most recent neighbor-list build launched (include/lbhip.h: lb_nl_route), e.g. {"build": "multi", "cells":
+        "strided", "search": "k_nl", "cand": 256, "mode": "rows", "finish": "compact_scan", ...}; numbers come back as int."""
+        buf = C.create_string_buffer(512)
+        check(self.lib.lb_nl_route(self._h, buf, 512), "lb_nl_route")
+        kv = dict(p.split("=", 1) for p in buf.value.decode().split(";") if "=" in p)
+        return {k: int(v) if v.lstrip("-").isdigit() else v for k, v in kv.items()}
+
     def stats(self) -> Dict[str, int]:
         n, ec, cc = C.c_int64(), C.c_int32(), C.c_int32()
         check(self.lib.lb_stats(self._h, C.byref(n), C.byref(ec), C.byref(cc)), "lb_stats")

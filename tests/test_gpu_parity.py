@@ -156,6 +156,7 @@ def test_dense_neighborhoods_fall_back_instead_of_failing(name, scale, rc_factor
     pos, pt = ds[0]
     N = len(pt)
     feats, nbrs = hcase.allocate_eval((pos[:, :isl], pt))
+    _route_is(hcase.engine(1), dict(search="k_nlw", dense=1))   # (the fill sweep already runs the dense kernel)
     of, on = ocase.allocate_eval((pos[:, :isl].astype(np.float64), pt))
     want = O.canonical_edges(on.idx, N)
     ne = want.shape[1]
@@ -189,7 +190,8 @@ CASES = [("small2d", 1.0), ("small3d", 1.0), ("tgv2d", 0.6), ("rpf2d", 0.5), ("t
                                         ("tgv3d", 1.0), ("ldc3d", 1.0)])
 def test_single_trajectory_update_path_bitexact(name, scale):
     """One trajectory per engine (the BASELINE configs as stated): the UPDATE path builds the list in one launch
-    (k_nl_small up to 4096 particles, k_nl_mid up to 8192 where its masks fit LDS; k_nl_compact_scan otherwise).  Edge
+    (k_nl_small up to 4096 particles, k_nl_mid up to 8192 where its masks fit LDS: every case here reaches one of the
+    two, asserted through Engine.nl_route; the allocation before it counts and fills in separate sweeps).  Edge
     list, edge features, edge count and did_buffer_overflow of an update on a LATER frame equal the oracle's
     preprocess_eval bit for bit; the same update with the capacity shrunk below the edge count flags overflow."""
     _need_gpu()
@@ -200,10 +202,12 @@ def test_single_trajectory_update_path_bitexact(name, scale):
     pos, pt = ds[0]
     N = pos.shape[0]
     _, nbrs = hcase.allocate_eval((pos[None][:, :, :isl], pt[None]))
+    assert hcase.engine(1).nl_route()["mode"] == "count+fill"
     _, on = ocase.allocate_eval((pos[:, :isl].astype(np.float64), pt))
     for shift in (1, 3):
         win = pos[:, shift:shift + isl]
         feats, nbrs = hcase.preprocess_eval((win[None], pt[None]), nbrs)
+        assert hcase.engine(1).nl_route()["build"] == ("k_nl_small" if N <= 4096 else "k_nl_mid"), hcase.engine(1).nl_route()
         of, on = ocase.preprocess_eval((win.astype(np.float64), pt), on)
         assert not bool(nbrs.did_buffer_overflow.any()) and not bool(on.did_buffer_overflow)
         idx = _np(nbrs.idx)[0]
@@ -224,9 +228,15 @@ def test_single_trajectory_update_path_bitexact(name, scale):
     assert int(eng.nl_flags()[0]) == 1
 
 
-def _batched_update_check(ds, B, pos, pt, shifts=(1, 2), f32=False):
+def _route_is(eng, want):
+    got = eng.nl_route()
+    assert {k: got[k] for k in want} == want, got
+
+
+def _batched_update_check(ds, B, pos, pt, shifts=(1, 2), f32=False, route=None):
     """Edge lists, counts and edge features of the batched UPDATE path against the oracle's preprocess_eval, bit for bit.
-    f32: both sides in float32 geometry (case.py:169; the engine keeps float32 VALUES in its fp64 containers)."""
+    f32: both sides in float32 geometry (case.py:169; the engine keeps float32 VALUES in its fp64 containers).
+    route: what Engine.nl_route must report after every update."""
     ocase, hcase = (oracle_case(ds, dtype=np.float32), hip_case(ds, dtype="float32")) if f32 else (oracle_case(ds), hip_case(ds))
     odt = np.float32 if f32 else np.float64
     cast = (lambda x: x.astype(np.float32)) if f32 else (lambda x: x)
@@ -239,6 +249,8 @@ def _batched_update_check(ds, B, pos, pt, shifts=(1, 2), f32=False):
         assert int(_np(nbrs.n_edges)[b]) == want.shape[1] and (_np(nbrs.idx)[b][:, :want.shape[1]] == want).all(), ("allocate", b)
     for shift in shifts:
         feats, nbrs = hcase.preprocess_eval((pos[:, :, shift:shift + isl], pt), nbrs)
+        if route is not None:
+            _route_is(hcase.engine(B), route)
         assert not bool(nbrs.did_buffer_overflow.any())
         idx_all, ne_all = _np(nbrs.idx), _np(nbrs.n_edges)
         rd, rdist = _np(feats["rel_disp"]), _np(feats["rel_dist"])
@@ -255,6 +267,10 @@ def _batched_update_check(ds, B, pos, pt, shifts=(1, 2), f32=False):
     return hcase
 
 
+# the update route of a batch whose search walks cells with one wave each: fixed-stride bins, per-node rows, fused scan + compaction
+K_NLC_ROUTE = dict(build="multi", cells="strided", search="k_nlc", mode="rows", finish="compact_scan", dense=0)
+
+
 @pytest.mark.parametrize("name,scale,B", [("tgv3d", 0.6, 3), ("tgv2d", 0.8, 3), ("dam2d", 0.5, 2)])
 def test_batched_update_path_float32_geometry_bitexact(name, scale, B):
     """dtype=float32 batches: every float32 engine searches with one wave per cell (k_nlc<.., F32>, 2D and 3D) - allocation
@@ -265,7 +281,7 @@ def test_batched_update_path_float32_geometry_bitexact(name, scale, B):
     ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
     pos = np.stack([ds[b][0] for b in range(B)])
     pt = np.stack([ds[b][1] for b in range(B)])
-    _batched_update_check(ds, B, pos, pt, f32=True)
+    _batched_update_check(ds, B, pos, pt, f32=True, route=dict(K_NLC_ROUTE, f32=1))
 
 
 @pytest.mark.parametrize("name,scale,B", [("tgv3d", 0.6, 3), ("ldc3d", 0.5, 3)])
@@ -278,7 +294,7 @@ def test_batched_update_path_3d_wave_per_cell_bitexact(name, scale, B):
     ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
     pos = np.stack([ds[b][0] for b in range(B)])
     pt = np.stack([ds[b][1] for b in range(B)])
-    _batched_update_check(ds, B, pos, pt)
+    _batched_update_check(ds, B, pos, pt, route=dict(K_NLC_ROUTE, f32=0, dim=3))
 
 
 @pytest.mark.parametrize("kind", ["clumped", "on_the_cutoff"])
@@ -292,7 +308,7 @@ def test_wave_per_cell_search_hard_cases_bitexact(kind):
     from lagrangebench_amd.data import make_case
     B = 2
     ds = make_case("tgv3d", n_trajs=B, extra_seq_length=3, scale=0.6)
-    pos = np.stack([ds[b][0] for b in range(B)]).copy()
+    pos = np.stack([ds[b][0] for b in range(B)]).astype(np.float64)   # (fp64: the offsets below vanish in a float32 array)
     pt = np.stack([ds[b][1] for b in range(B)])
     box = np.asarray(ds.box, np.float64)
     rc = float(ds.metadata["default_connectivity_radius"])
@@ -312,7 +328,7 @@ def test_wave_per_cell_search_hard_cases_bitexact(kind):
                 u /= np.linalg.norm(u)
                 off = rc * (1.0 + ds_[q % len(ds_)]) * u
                 pos[b][i + 1] = np.mod(pos[b][i] + off, box)   # same offset in every frame
-    hcase = _batched_update_check(ds, B, pos, pt)
+    hcase = _batched_update_check(ds, B, pos, pt, route=dict(K_NLC_ROUTE, f32=0, dim=3))
     if kind == "clumped":
         st = hcase.engine(B).stats()
         assert st["n_edges_total"] / (B * N) > 20, st
@@ -320,9 +336,11 @@ def test_wave_per_cell_search_hard_cases_bitexact(kind):
 
 @pytest.mark.parametrize("name,scale,B", [("tgv2d", 1.0, 3), ("dam2d", 1.0, 2), ("rpf2d", 1.0, 4)])
 def test_batched_update_path_bitexact(name, scale, B):
-    """Batches of mid-size trajectories (more than 4096 particles in total, at most 6144 each): the UPDATE path bins every
-    trajectory with its own workgroup in one launch (k_cells_traj, round 4).  Edge lists, edge counts and edge features of
-    an update on a later frame equal the oracle's preprocess_eval bit for bit, trajectory by trajectory."""
+    """Batches of mid-size trajectories (more than 4096 particles in total, at most 6144 each): the UPDATE path bins into
+    fixed-stride cell slots (k_cell_zero + k_cell_bin), searches with the one-wave 128-candidate k_nl and finishes in
+    k_nl_compact_scan - asserted through Engine.nl_route.  (The one-launch per-trajectory binning k_cells_traj is taken only
+    by a dense batch: tests/test_nl_routes_gpu.py, clump_batch.)  Edge lists, edge counts and edge features of an update on a
+    later frame equal the oracle's preprocess_eval bit for bit, trajectory by trajectory."""
     _need_gpu()
     from lagrangebench_amd.data import make_case
     ds = make_case(name, n_trajs=B, extra_seq_length=3, scale=scale)
@@ -336,6 +354,8 @@ def test_batched_update_path_bitexact(name, scale, B):
     ons = [ocase.allocate_eval((pos[b][:, :isl].astype(np.float64), pt[b]))[1] for b in range(B)]
     for shift in (1, 2):
         feats, nbrs = hcase.preprocess_eval((pos[:, :, shift:shift + isl], pt), nbrs)
+        _route_is(hcase.engine(B), dict(build="multi", cells="strided", search="k_nl", cand=128, mode="rows",
+                                        finish="compact_scan", dense=0))
         assert not bool(nbrs.did_buffer_overflow.any())
         idx_all, ne_all = _np(nbrs.idx), _np(nbrs.n_edges)
         rd, rdist = _np(feats["rel_disp"]), _np(feats["rel_dist"])
