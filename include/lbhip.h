@@ -874,6 +874,46 @@ int lb_graph_conv_vec_edge_grad(lb_engine* eng, int32_t s_role, const void* s_de
                                 const void* w_dev /*(B*E_cap,C)*/, const void* u_dev /*(B*E_cap,K)*/,
                                 void* d_w_dev /*(B*E_cap,C) or NULL*/, void* d_u_dev /*(B*E_cap,K) or NULL*/, int32_t K, int32_t C,
                                 int32_t dtype);
+/* ---- the multi-aggregator: sum, mean, max, min, std and var of one message in one launch -----
+ * The rules of the graph ops hold (layout, roles, pads never read, +0.0 in the pad slots of edge-shaped outputs, no float atomics,
+ * two calls the same bits, dtype for every data tensor).  msg (B*E_cap, C) -> out (B*N, A, C): plane a holds the op whose code
+ * LB_AGG_* stands in nibble a of `ops`, from the low end; a 0 nibble ends the list, A is the number of codes before it.  Per
+ * node i and column c, with the real slots j1 < ... < jd of `role` in ascending slot order and d the degree:
+ *   sum:  x_j1 + x_j2 + ... - the first term starts the sum, one fp32 add per further slot: the bits of lb_graph_segment_sum;
+ *   mean: m = fl32(sum / max(d, 1)), one correctly rounded division;
+ *   max, min: the first slot, replaced only by a strictly greater / smaller one (ties keep the earlier slot, a NaN wins and
+ *         stays): the bits and the winning slots of lb_graph_segment_max / _min;
+ *   var:  fl32(q / max(d, 1)), centred and two-pass: t_j = fl32(x_j - m), q = the ordered fp32 sum of fl32(t_j t_j), the first
+ *         term starting it - never E[x^2] - m^2;
+ *   std:  sqrt_rn(fl32(var + eps)), eps inside the root.
+ * A node without slots gets +0.0 in every plane, std included.  Every step is one correctly rounded IEEE operation (no FMA
+ * contraction), so a numpy float32 loop reproduces the planes bit for bit.
+ * Side outputs for the backward, required only when an op that needs them is in `ops` (else they may be NULL and are not
+ * touched): win (B*N, 2, C) int32 - the winning slot within the trajectory of the max, then of the min, -1 for a node without
+ * slots - with max or min; stats (B*N, 2, C) fp32 - m, then std (+0.0 when std is not in `ops`) - with std or var.
+ * Backward: d_msg (B*E_cap, C), +0.0 in the pad slots; for a real slot j of node n the PRESENT terms in this fixed order,
+ * whatever the order of `ops`, the first present one starting the sum: g_sum; fl32(g_mean / d); g_max if j is the max winner
+ * of (n, c); g_min likewise; fl32(fl32(g_std t_j) / fl32(d std)); fl32(fl32(fl32(2 g_var) t_j) / d) - t_j recomputed from msg
+ * and the saved m.  A real slot with no present term gets +0.0.  msg_dev and stats_dev are required with std or var, win_dev
+ * with max or min.
+ * LB_DTYPE_BF16: out and d_msg are round_to_bf16(the fp32 result on the widened inputs), one rounding per stored element; stats
+ * stay fp32, so the mean inside var and in the backward is the fp32 mean, not its rounded copy.
+ * LB_ERR_ARG on a null handle, a null required pointer, a role other than 0 / 1, a dtype other than the two, C < 1, an `ops`
+ * word that is empty, repeats a code, holds a code above LB_AGG_VAR or a code after the end, or eps <= 0 with std (forward);
+ * LB_ERR_STATE without a list or with an overflowed one. */
+#define LB_AGG_SUM 1
+#define LB_AGG_MEAN 2
+#define LB_AGG_MAX 3
+#define LB_AGG_MIN 4
+#define LB_AGG_STD 5
+#define LB_AGG_VAR 6
+int lb_graph_aggregate(lb_engine* eng, int32_t role, const void* msg_dev /*(B*E_cap,C)*/, void* out_dev /*(B*N,A,C)*/,
+                       int32_t* win_dev /*(B*N,2,C) or NULL*/, float* stats_dev /*(B*N,2,C) or NULL*/, int32_t C, int32_t ops,
+                       float eps, int32_t dtype);
+int lb_graph_aggregate_backward(lb_engine* eng, int32_t role, const void* d_out_dev /*(B*N,A,C)*/,
+                                const void* msg_dev /*(B*E_cap,C) or NULL*/, const int32_t* win_dev /*(B*N,2,C) or NULL*/,
+                                const float* stats_dev /*(B*N,2,C) or NULL*/, void* d_msg_dev /*(B*E_cap,C)*/, int32_t C,
+                                int32_t ops, int32_t dtype);
 /* d loss / d window from the cotangents of the features a TorchModel module receives (graph.differentiable_features), on the
  * engine's CURRENT window and list: the transpose of the feature builder.  Every input may be NULL (= zero).  fp32 inputs in the
  * layouts of TorchModel's feature dict; the edge-shaped ones in the padded slot layout of lb_nl_read_idx, whose pad slots are

@@ -7,7 +7,8 @@
 // and, for attention and pooling layers (further down: "attention ops"), lb_graph_degree, lb_graph_segment_max / _min,
 // lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries; for filter x neighbour messages ("edge
 // messages") the fused lb_graph_conv and the edge-shaped lb_graph_pair_mul / lb_graph_pair_add, and the equivariant couplings
-// through a per-edge vector, lb_graph_conv_vec / lb_graph_conv_dot with lb_graph_conv_vec_edge_grad; and lb_graph_features_backward
+// through a per-edge vector, lb_graph_conv_vec / lb_graph_conv_dot with lb_graph_conv_vec_edge_grad; the multi-aggregator
+// lb_graph_aggregate (sum, mean, max, min, std, var of one message from one walk) with its backward; and lb_graph_features_backward
 // ("feature transpose"): d loss / d window from the cotangents of the features such a network was handed.
 //
 // All work in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
@@ -953,6 +954,222 @@ __global__ void __launch_bounds__(256) k_graph_vec_edge_grad(lb_glist L, const i
   }
 }
 
+// ------------------------------------------------------------------------------------------------ multi-aggregator
+// aggregate: sum, mean, max, min, std and var of one message from one walk of the row (the contract is in
+// include/lbhip.h above lb_graph_aggregate).  out is (B N, A, C): plane a of node i is row i A + a of C columns.  Where each op
+// stores its plane comes as a named member of lb_gagg (-1: not asked for) - uniform values in scalar registers, never an array
+// indexed at run time (see lb_glist).  EXT: max / min and their winners are wanted; MOM: the centred second moment is (std / var),
+// which costs the second walk of the row - cache-hot, the lane re-reads the lines it just read.
+struct lb_gagg {
+  int A;
+  int sum, mean, max, min, std, var;   // plane of the op among the A of out, -1 when it was not asked for
+  float eps;
+};
+// The correctly rounded root of the contract.  Not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the HIP headers define it as
+// the native approximation (1 ulp).  sqrtf compiles to the correctly rounded expansion - hipcc's default
+// -fhip-fp32-correctly-rounded-divide-sqrt, which also makes __fdiv_rn (there: x / y) the correctly rounded quotient.
+__device__ __forceinline__ float lb_sqrt_rn(float x) { return sqrtf(x); }
+// W fp32 (the saved mean and std): 16-byte accesses when W > 1
+template <int W>
+__device__ __forceinline__ void lb_ldf(const float* p, float (&a)[W]) {
+  if constexpr (W == 1) {
+    a[0] = *p;
+  } else {
+#pragma unroll
+    for (int q = 0; q < W; q += 4) {
+      const f32x4 t = *reinterpret_cast<const f32x4*>(p + q);
+      a[q] = t[0], a[q + 1] = t[1], a[q + 2] = t[2], a[q + 3] = t[3];
+    }
+  }
+}
+template <int W>
+__device__ __forceinline__ void lb_stf(float* p, const float (&a)[W]) {
+  if constexpr (W == 1) {
+    *p = a[0];
+  } else {
+#pragma unroll
+    for (int q = 0; q < W; q += 4) *reinterpret_cast<f32x4*>(p + q) = f32x4{a[q], a[q + 1], a[q + 2], a[q + 3]};
+  }
+}
+
+// Per node i and column c over the real slots j1 < ... < jd of the row: s = the ordered sum (k_graph_segment_sum's bits), the
+// maximum and the minimum with their winning slots (k_graph_segment_max's), m = s / max(d, 1), and with MOM the second walk:
+// q = the ordered sum of fl32(t t), t = fl32(x - m); var = q / max(d, 1), std = sqrt(var + eps).  An empty row stores +0.0 in
+// every plane (std included), -1 in win and +0.0 in stats.  win (B N, 2, C): max plane, min plane; stats (B N, 2, C) fp32: m, std.
+template <typename T, int W, bool EXT, bool MOM>
+__global__ void __launch_bounds__(256) k_graph_aggregate(lb_glist L, lb_gwalk walk, lb_gagg G, const T* __restrict__ msg,
+                                                         T* __restrict__ out, int32_t* __restrict__ win,
+                                                         float* __restrict__ stats) {
+  const int U = L.U;
+  graph_for_nodes(L, walk, [&](int64_t i, const lb_row& R, int u) {
+    float s[W], hi[W], lo[W], a[W];
+    int32_t whi[W], wlo[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) s[k] = 0.f, hi[k] = 0.f, lo[k] = 0.f, whi[k] = -1, wlo[k] = -1;
+    int p = R.p0;
+    if (p < R.p1) {   // every reduction STARTS from the first slot
+      const int64_t e = R.edge(p++);
+      lb_ld<T, W>(msg + (e * U + u) * W, s);
+#pragma unroll
+      for (int k = 0; k < W; ++k) hi[k] = s[k], lo[k] = s[k], whi[k] = wlo[k] = (int32_t)(e - R.first);
+    }
+#pragma unroll 4
+    for (; p < R.p1; ++p) {
+      const int64_t e = R.edge(p);
+      lb_ld<T, W>(msg + (e * U + u) * W, a);
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        s[k] = __fadd_rn(s[k], a[k]);
+        if constexpr (EXT) {
+          if (lb_beats<false>(a[k], hi[k])) hi[k] = a[k], whi[k] = (int32_t)(e - R.first);
+          if (lb_beats<true>(a[k], lo[k])) lo[k] = a[k], wlo[k] = (int32_t)(e - R.first);
+        }
+      }
+    }
+    const int d = R.p1 - R.p0;
+    const float dd = (float)(d > 1 ? d : 1);
+    const int64_t o = i * G.A * U + u;   // unit u of plane 0 of node i; plane a is a U units further
+    float m[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) m[k] = __fdiv_rn(s[k], dd);
+    if (G.sum >= 0) lb_st<T, W>(out + (o + (int64_t)G.sum * U) * W, s);
+    if (G.mean >= 0) lb_st<T, W>(out + (o + (int64_t)G.mean * U) * W, m);
+    if constexpr (EXT) {
+      if (G.max >= 0) lb_st<T, W>(out + (o + (int64_t)G.max * U) * W, hi);
+      if (G.min >= 0) lb_st<T, W>(out + (o + (int64_t)G.min * U) * W, lo);
+      lb_sti<W>(win + ((i * 2 + 0) * U + u) * W, whi);
+      lb_sti<W>(win + ((i * 2 + 1) * U + u) * W, wlo);
+    }
+    if constexpr (MOM) {
+      float q[W], sd[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) q[k] = 0.f, sd[k] = 0.f;
+      p = R.p0;
+      if (p < R.p1) {
+        lb_ld<T, W>(msg + (R.edge(p++) * U + u) * W, a);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          const float t = __fsub_rn(a[k], m[k]);
+          q[k] = __fmul_rn(t, t);
+        }
+      }
+#pragma unroll 4
+      for (; p < R.p1; ++p) {
+        lb_ld<T, W>(msg + (R.edge(p) * U + u) * W, a);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          const float t = __fsub_rn(a[k], m[k]);
+          q[k] = __fadd_rn(q[k], __fmul_rn(t, t));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < W; ++k) q[k] = __fdiv_rn(q[k], dd);   // (q is var from here)
+      if (G.std >= 0 && d > 0) {   // a node without slots keeps +0.0, not sqrt(eps)
+#pragma unroll
+        for (int k = 0; k < W; ++k) sd[k] = lb_sqrt_rn(__fadd_rn(q[k], G.eps));
+      }
+      if (G.var >= 0) lb_st<T, W>(out + (o + (int64_t)G.var * U) * W, q);
+      if (G.std >= 0) lb_st<T, W>(out + (o + (int64_t)G.std * U) * W, sd);
+      lb_stf<W>(stats + ((i * 2 + 0) * U + u) * W, m);
+      lb_stf<W>(stats + ((i * 2 + 1) * U + u) * W, sd);
+    }
+  });
+}
+
+// d_msg[slot j of node n][c] = the present terms added in this fixed order, the first present one starting the sum (d the
+// degree of n, t = fl32(x_j - m) from msg and the saved mean): g_sum; fl32(g_mean / d); g_max if j won the maximum of (n, c);
+// g_min likewise; fl32(fl32(g_std t) / fl32(d std)); fl32(fl32(fl32(2 g_var) t) / d).  A real slot without a present term (an
+// extremum it did not win, nothing else asked for) and every pad slot get +0.0.  The head of a slot adds the degree of its node,
+// read from the role's seg_ptr as graph_row caps it.
+struct lb_gslot_deg {
+  lb_gslot s;
+  int d;
+};
+template <typename T, int W, bool EXT, bool MOM>
+__global__ void __launch_bounds__(256) k_graph_aggregate_bwd(lb_glist L, lb_gwalk walk, lb_gagg G,
+                                                             const int32_t* __restrict__ idx, const T* __restrict__ d_out,
+                                                             const T* __restrict__ msg, const int32_t* __restrict__ win,
+                                                             const float* __restrict__ stats, T* __restrict__ d_msg) {
+  const int U = L.U;
+  graph_for(
+      L, (int64_t)L.B * L.e_cap,
+      [&](int64_t r) {
+        lb_gslot_deg h;
+        h.s = graph_slot(L, r, idx);
+        h.d = 1;
+        if (h.s.real) {
+          const lb_row R = graph_row(L, walk, h.s.node);
+          h.d = R.p1 - R.p0;
+        }
+        return h;
+      },
+      [&](int64_t r, const lb_gslot_deg& h, int u) {
+        float acc[W], g[W];
+        bool any[W];
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc[k] = 0.f, any[k] = false;
+        if (h.s.real) {
+          const float dd = (float)(h.d > 1 ? h.d : 1);
+          const int64_t o = h.s.node * G.A * U + u;
+          if (G.sum >= 0) {
+            lb_ld<T, W>(d_out + (o + (int64_t)G.sum * U) * W, g);
+#pragma unroll
+            for (int k = 0; k < W; ++k) acc[k] = g[k], any[k] = true;
+          }
+          if (G.mean >= 0) {
+            lb_ld<T, W>(d_out + (o + (int64_t)G.mean * U) * W, g);
+#pragma unroll
+            for (int k = 0; k < W; ++k) {
+              const float t = __fdiv_rn(g[k], dd);
+              acc[k] = any[k] ? __fadd_rn(acc[k], t) : t, any[k] = true;
+            }
+          }
+          if constexpr (EXT) {
+            int32_t w[W];
+            if (G.max >= 0) {
+              lb_ld<T, W>(d_out + (o + (int64_t)G.max * U) * W, g);
+              lb_ldi<W>(win + ((h.s.node * 2 + 0) * U + u) * W, w);
+#pragma unroll
+              for (int k = 0; k < W; ++k)
+                if (w[k] == h.s.j) acc[k] = any[k] ? __fadd_rn(acc[k], g[k]) : g[k], any[k] = true;
+            }
+            if (G.min >= 0) {
+              lb_ld<T, W>(d_out + (o + (int64_t)G.min * U) * W, g);
+              lb_ldi<W>(win + ((h.s.node * 2 + 1) * U + u) * W, w);
+#pragma unroll
+              for (int k = 0; k < W; ++k)
+                if (w[k] == h.s.j) acc[k] = any[k] ? __fadd_rn(acc[k], g[k]) : g[k], any[k] = true;
+            }
+          }
+          if constexpr (MOM) {
+            float x[W], m[W], sd[W];
+            lb_ld<T, W>(msg + (r * U + u) * W, x);
+            lb_ldf<W>(stats + ((h.s.node * 2 + 0) * U + u) * W, m);
+#pragma unroll
+            for (int k = 0; k < W; ++k) x[k] = __fsub_rn(x[k], m[k]);   // (x is t from here)
+            if (G.std >= 0) {
+              lb_ld<T, W>(d_out + (o + (int64_t)G.std * U) * W, g);
+              lb_ldf<W>(stats + ((h.s.node * 2 + 1) * U + u) * W, sd);
+#pragma unroll
+              for (int k = 0; k < W; ++k) {
+                const float t = __fdiv_rn(__fmul_rn(g[k], x[k]), __fmul_rn(dd, sd[k]));
+                acc[k] = any[k] ? __fadd_rn(acc[k], t) : t, any[k] = true;
+              }
+            }
+            if (G.var >= 0) {
+              lb_ld<T, W>(d_out + (o + (int64_t)G.var * U) * W, g);
+#pragma unroll
+              for (int k = 0; k < W; ++k) {
+                const float t = __fdiv_rn(__fmul_rn(__fmul_rn(2.f, g[k]), x[k]), dd);
+                acc[k] = any[k] ? __fadd_rn(acc[k], t) : t, any[k] = true;
+              }
+            }
+          }
+        }
+        lb_st<T, W>(d_msg + (r * U + u) * W, acc);
+      });
+}
+
 // ------------------------------------------------------------------------------------------------ feature transpose
 // d loss / d window (B N, isl, dim) fp64 from the cotangents of the features a TorchModel module receives: the transpose of the
 // feature builder as the comment above k_feat_bwd (lb_train.hip) states it, on the engine's current window and list, in the
@@ -1489,6 +1706,81 @@ extern "C" int lb_graph_pair_add(lb_engine* e, int32_t a_role, const void* a_dev
     using T = decltype(t);
     graph_launch(e, P.blocks, k_graph_pair_add<T, decltype(w)::value>, P.L, P.idx, P.oidx, (const T*)a_dev, (const T*)b_dev,
                  (T*)out_dev);
+  });
+}
+
+// ---- the multi-aggregator's entries.  `ops`: one nibble per plane of out from the low end, an op code LB_AGG_SUM .. LB_AGG_VAR,
+// 0 ends the list; every code at most once, at least one, nothing after the end.
+static int graph_aggregate_ops(const char* entry, int32_t ops, float eps, bool need_eps, lb_gagg* G) {
+  int* const pos[6] = {&G->sum, &G->mean, &G->max, &G->min, &G->std, &G->var};
+  *G = lb_gagg{0, -1, -1, -1, -1, -1, -1, eps};
+  bool ended = false, ok = ops > 0;
+  for (int a = 0; a < 8 && ok; ++a) {
+    const int code = (ops >> (4 * a)) & 15;
+    if (code == 0) {
+      ended = true;
+    } else if (ended || code > LB_AGG_VAR || *pos[code - 1] >= 0) {
+      ok = false;
+    } else {
+      *pos[code - 1] = a;
+      G->A = a + 1;
+    }
+  }
+  if (!ok || G->A < 1) return lb_fail(LB_ERR_ARG, "%s: ops 0x%x (a nibble per plane: distinct codes 1 .. 6, 0 ends)", entry, ops);
+  if (need_eps && G->std >= 0 && !(eps > 0.f)) return lb_fail(LB_ERR_ARG, "%s: eps %g with std (> 0)", entry, (double)eps);
+  return LB_OK;
+}
+// <EXT, MOM> of the call as types, like graph_dispatch's (T, W)
+template <typename F>
+static void graph_aggregate_flags(bool ext, bool mom, F f) {
+  using yes = std::true_type;
+  using no = std::false_type;
+  if (ext && mom) f(yes{}, yes{});
+  else if (ext) f(yes{}, no{});
+  else if (mom) f(no{}, yes{});
+  else f(no{}, no{});
+}
+
+extern "C" int lb_graph_aggregate(lb_engine* e, int32_t role, const void* msg_dev, void* out_dev, int32_t* win_dev,
+                                  float* stats_dev, int32_t C, int32_t ops, float eps, int32_t dtype) {
+  if (!e) return lb_fail(LB_ERR_ARG, "null argument");
+  lb_gagg G;
+  LB_TRY(graph_aggregate_ops("lb_graph_aggregate", ops, eps, true, &G));
+  const bool ext = G.max >= 0 || G.min >= 0, mom = G.std >= 0 || G.var >= 0;
+  LB_TRY(graph_entry(e, "lb_graph_aggregate", role, dtype, msg_dev && out_dev && (win_dev || !ext) && (stats_dev || !mom), C, 1));
+  if ((int64_t)G.A * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_aggregate: %d planes x C %d columns", G.A, C);
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, C, false, {msg_dev, out_dev, ext ? win_dev : nullptr,
+                                                                        mom ? stats_dev : nullptr});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    graph_aggregate_flags(ext, mom, [&](auto x, auto m) {
+      graph_launch(e, P.blocks, k_graph_aggregate<T, W, decltype(x)::value, decltype(m)::value>, P.L, P.walk, G, (const T*)msg_dev,
+                   (T*)out_dev, win_dev, stats_dev);
+    });
+  });
+}
+
+extern "C" int lb_graph_aggregate_backward(lb_engine* e, int32_t role, const void* d_out_dev, const void* msg_dev,
+                                           const int32_t* win_dev, const float* stats_dev, void* d_msg_dev, int32_t C, int32_t ops,
+                                           int32_t dtype) {
+  if (!e) return lb_fail(LB_ERR_ARG, "null argument");
+  lb_gagg G;
+  LB_TRY(graph_aggregate_ops("lb_graph_aggregate_backward", ops, 0.f, false, &G));
+  const bool ext = G.max >= 0 || G.min >= 0, mom = G.std >= 0 || G.var >= 0;
+  // edge-parallel, but the degree of a slot's node comes from the rows of the role: the sender view for role 1
+  LB_TRY(graph_entry(e, "lb_graph_aggregate_backward", role, dtype,
+                     d_out_dev && d_msg_dev && (win_dev || !ext) && ((msg_dev && stats_dev) || !mom), C, 1));
+  if ((int64_t)G.A * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "lb_graph_aggregate_backward: %d planes x C %d columns", G.A, C);
+  const lb_gplan P = graph_plan(e, role, dtype, LB_SLOTS, C, C, false, {d_out_dev, d_msg_dev, ext ? win_dev : nullptr,
+                                                                        mom ? msg_dev : nullptr, mom ? stats_dev : nullptr});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    graph_aggregate_flags(ext, mom, [&](auto x, auto m) {
+      graph_launch(e, P.blocks, k_graph_aggregate_bwd<T, W, decltype(x)::value, decltype(m)::value>, P.L, P.walk, G, P.idx,
+                   (const T*)d_out_dev, (const T*)msg_dev, win_dev, stats_dev, (T*)d_msg_dev);
+    });
   });
 }
 

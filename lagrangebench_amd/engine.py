@@ -37,12 +37,14 @@ def _graph_ops():
     outputs, sizes) in the entry's argument order.  An input is (shape, dtype): a shape entry is 1, "nodes" (B N), "slots" (B
     E_cap), a size the caller fixes, or the name of a free size >= 1 that the first input which has it binds; dtype None marks
     a data tensor - float32 or bfloat16, one dtype for the whole call, whose code the entry then takes last.  `sizes` names
-    the free sizes the entry takes; a trailing True says that an input may be None (a null pointer).  An output is (shape,
+    the free sizes the entry takes, in its order; a name the caller fixes may also stand for a scalar argument that is no size
+    (aggregate's ops word and eps).  A trailing True says that an input may be None (a null pointer).  An output is (shape,
     dtype, like): like is the index, among the inputs followed by the earlier outputs, of a tensor of its shape and dtype, or
     -1."""
     nc, sc, sh, shd, nh, nhd, nkc, sk = ("nodes", "C"), ("slots", "C"), ("slots", "H"), ("slots", "H", "D"), ("nodes", "H"), \
         ("nodes", "H", "D"), ("nodes", "K", "C"), ("slots", "K")
     f32, i32 = torch.float32, torch.int32
+    nac, npc = ("nodes", "A", "C"), ("nodes", "planes", "C")   # aggregate: A planes of out; the 2 planes of win and of stats
     ops = {
         "lb_graph_gather": ("lb_graph_gather_t", ((nc, None),), ((sc, None),), ("C",)),
         "lb_graph_segment_sum": ("lb_graph_segment_sum_t", ((sc, None),), ((nc, None),), ("C",)),
@@ -63,6 +65,9 @@ def _graph_ops():
         "lb_graph_conv_dot": ("lb_graph_conv_dot", ((nkc, None), (sc, None), (sk, None)), ((nc, None),), ("K", "C")),
         "lb_graph_conv_vec_edge_grad": ("lb_graph_conv_vec_edge_grad", ((nc, None), (nkc, None), (sc, None), (sk, None)),
                                         ((sc, None), (sk, None)), ("K", "C")),
+        "lb_graph_aggregate": ("lb_graph_aggregate", ((sc, None),), ((nac, None), (npc, i32), (npc, f32)), ("C", "ops", "eps")),
+        "lb_graph_aggregate_backward": ("lb_graph_aggregate_backward", ((nac, None), (sc, None), (npc, i32), (npc, f32)),
+                                        ((sc, None),), ("C", "ops"), True),
         "lb_graph_features_backward": ("lb_graph_features_backward",
                                        ((("nodes", "isl", "dim"), f32), (("nodes", "vel"), f32), (("nodes", "mag"), f32),
                                         (("nodes", "bound"), f32), (("slots", "dim"), f32), (("slots", 1), f32)),
@@ -552,7 +557,7 @@ class RolloutEngine:
                 made.append(None)
                 args.append(None)
                 continue
-            if like >= 0:
+            if like >= 0 and seen[like] is not None:
                 o = torch.empty_like(seen[like])
             elif dtype is None:
                 o = first.new_empty([dims[d] for d in shape])
@@ -670,6 +675,22 @@ class RolloutEngine:
         if not (want_w or want_u):
             return None, None
         return self._graph_call("lb_graph_conv_vec_edge_grad", s_role, (s, v, w, u), want=(want_w, want_u))
+
+    def graph_aggregate(self, role: int, msg: torch.Tensor, ops: int, eps: float, planes: int):
+        """msg (B*E_cap, C) float32 or bfloat16 -> (out (B*N, planes, C) in the dtype of msg, win (B*N, 2, C) int32 or None, stats
+        (B*N, 2, C) float32 or None): the reductions the nibbles of `ops` name (1 sum, 2 mean, 3 max, 4 min, 5 std, 6 var; one per
+        plane of out from the low end) over the real slots of each node, from one walk of its row and a second one for std /
+        var.  win - the winning slots of max, then min - exists with max or min; stats - the float32 mean, then std - with std or
+        var (include/lbhip.h: lb_graph_aggregate)."""
+        codes = [(ops >> (4 * a)) & 15 for a in range(8)]
+        return self._graph_call("lb_graph_aggregate", role, (msg,), want=(True, 3 in codes or 4 in codes, 5 in codes or 6 in codes),
+                                A=int(planes), planes=2, ops=int(ops), eps=float(eps))
+
+    def graph_aggregate_backward(self, role: int, d_out: torch.Tensor, msg, win, stats, ops: int) -> torch.Tensor:
+        """-> d_msg (B*E_cap, C) of graph_aggregate in the dtype of d_out (B*N, A, C), +0.0 in the pad slots, from one
+        edge-parallel launch; msg and stats may be None without std / var, win without max / min (include/lbhip.h:
+        lb_graph_aggregate_backward)."""
+        return self._graph_call("lb_graph_aggregate_backward", role, (d_out, msg, win, stats), planes=2, ops=int(ops))
 
     def graph_features_backward(self, d_abs_pos=None, d_vel_hist=None, d_vel_mag=None, d_bound=None, d_rel_disp=None,
                                 d_rel_dist=None) -> torch.Tensor:

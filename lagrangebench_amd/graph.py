@@ -14,6 +14,8 @@ describes, in the padded layout of ``features["senders"]`` / ``["receivers"]`` (
     g.segment_max(msg, "senders")            # (B, E_cap, C) -> (B, N, C); segment_min likewise
     a = g.segment_softmax(logits, "receivers")          # (B, E_cap, C) -> (B, E_cap, C): a softmax per node and column
     out = g.attend(logits, values, "receivers")         # (B, E_cap, H), (B, E_cap, H, D) -> (B, N, H, D), one launch
+    agg = g.aggregate(msg, "receivers", ("sum", "mean", "max", "min", "std"))   # (B, E_cap, C) -> (B, N, 5, C), one launch
+    g.segment_std(msg, "receivers"), g.segment_var(msg, "receivers")            # (B, E_cap, C) -> (B, N, C)
 
     ds = g.conv(x, w, "senders")             # (B, N, C) | (B, N, K, C), (B, E_cap, C) -> the shape of x, one launch:
                                              #   segment_sum(gather(x, "receivers") * w[..., None, :], "senders")
@@ -45,6 +47,32 @@ result or gradient is +0.0, no float atomics, two calls give the same bits:
   bit - the same weights, each product rounded to float32, added in ascending slot order - without the (E_cap, H, D)
   intermediate.  Its ``d_values`` has the composition's bits too; ``d_logits`` reduces over D in another order and agrees
   to rounding.
+
+Multi-aggregator.  ``aggregate(msg, role, ops, eps)`` gives the reductions a PNA layer concatenates - any distinct names out of
+``sum, mean, max, min, std, var`` - as the planes of one (B, N, A, C) result, in the order of ``ops``, from one node-parallel
+launch: one walk of the row for the sum, both extrema and their winners, a second, cache-hot walk for the centred squares only
+when ``std`` or ``var`` is asked for.  ``segment_std`` and ``segment_var`` are its one-plane forms.  An empty or unknown
+``ops``, a name twice, or ``eps <= 0`` with ``std`` is a ``ValueError``.  Per node and column, over the real slots
+j1 < ... < jd of `role` in ascending slot order (d the degree), under the contracts above:
+
+* ``sum``: the bits of ``segment_sum``; ``mean``: ``m = fl32(sum / max(d, 1))``, the bits of ``segment_mean``; ``max`` /
+  ``min``: the bits and the winning slots of ``segment_max`` / ``segment_min`` (first slot, replaced only by a strictly
+  greater / smaller one, ties keep the earlier slot, a NaN wins and stays).
+* ``var = fl32(q / max(d, 1))``, centred and two-pass: ``t_j = fl32(x_j - m)`` and q is the ordered float32 sum of
+  ``fl32(t_j * t_j)``, the first term starting it - never ``E[x^2] - m^2``, which loses every digit once the mean is large
+  against the spread.  ``std = sqrt_rn(fl32(var + eps))``, eps inside the root as PNA has it.
+* A node without slots gets +0.0 in every plane, ``std`` included (not ``sqrt(eps)``).  Every step is one correctly rounded
+  IEEE operation, so a numpy float32 loop reproduces every plane bit for bit.
+* Backward: one edge-parallel launch writes ``d_msg`` once, +0.0 in the pad slots.  For a real slot j of node n the present
+  terms are added in this fixed order, whatever the order of ``ops``, the first present one starting the sum: ``g_sum``;
+  ``fl32(g_mean / d)``; ``g_max`` if j is the max winner of (n, c); ``g_min`` likewise; ``fl32(fl32(g_std * t_j) / fl32(d *
+  std))``; ``fl32(fl32(fl32(2 * g_var) * t_j) / d)`` - ``t_j`` recomputed from msg and the saved mean.  A slot without a present
+  term gets +0.0, so the single-op gradients of sum, mean, max and min have the bits of the separate ops'.  The forward hands
+  the backward the winning slots (int32) and the float32 mean and std, allocated only when asked for; msg is saved only with
+  ``std`` or ``var``.
+* bfloat16: the forward and ``d_msg`` are the float32 result on the widened inputs, rounded once per stored element; the mean
+  inside ``var`` and in the backward is the float32 mean, not its rounded copy (so the ``mean`` plane is rounded once, where
+  ``segment_mean`` on bfloat16 rounds the sum first).
 
 Edge messages.  ``conv``, ``pair_mul`` and ``pair_add`` are the "filter x neighbour" message of a continuous-filter or
 equivariant network (SchNet's cfconv, PaiNN's ``segment_sum(Wij * x[receivers], senders)``) and the first edge Linear of a
@@ -367,6 +395,49 @@ class _ConvDot(torch.autograd.Function):
         return d_v, d_w, d_u, None, None
 
 
+_AGG_CODES = {"sum": 1, "mean": 2, "max": 3, "min": 4, "std": 5, "var": 6}   # LB_AGG_* (include/lbhip.h)
+
+
+def _agg_word(name: str, ops, eps) -> tuple:
+    """The checks of aggregate's `ops` and `eps` -> (the names as a tuple, the ops word: one nibble per plane from the low end)."""
+    names = (ops,) if isinstance(ops, str) else tuple(ops)
+    if not names:
+        raise ValueError(f"graph.{name}: ops is empty; expected some of {tuple(_AGG_CODES)}")
+    word = 0
+    for a, op in enumerate(names):
+        if op not in _AGG_CODES:
+            raise ValueError(f"graph.{name}: unknown op {op!r}; expected some of {tuple(_AGG_CODES)}")
+        if op in names[:a]:
+            raise ValueError(f"graph.{name}: op {op!r} is named twice in {names}")
+        word |= _AGG_CODES[op] << (4 * a)
+    if "std" in names and not float(eps) > 0.0:
+        raise ValueError(f"graph.{name}: eps must be > 0 with 'std', got {eps!r}")
+    return names, word
+
+
+class _Aggregate(torch.autograd.Function):
+    """aggregate over `role`: one node-parallel launch forward, one edge-parallel launch backward.  The winning slots and the
+    float32 mean and std come back from the forward; msg is saved only when std or var needs the centred values again."""
+
+    @staticmethod
+    def forward(ctx, msg, graph, role, names, word, eps):
+        e = graph.engine
+        flat, rest = graph._flat("aggregate", msg, e.e_cap)
+        out, win, stats = e.graph_aggregate(role, flat, word, eps, len(names))
+        ctx.graph, ctx.role, ctx.word, ctx.planes, ctx.rest, ctx.dtype = graph, role, word, len(names), rest, flat.dtype
+        ctx.save_for_backward(flat if stats is not None else None, win, stats)
+        return out.reshape(graph._shape(e.N) + (len(names),) + rest)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        msg, win, stats = ctx.saved_tensors
+        flat, _ = g._flat("aggregate", d, e.N, ctx.dtype)
+        d_msg = e.graph_aggregate_backward(ctx.role, flat.reshape(e.B * e.N, ctx.planes, -1), msg, win, stats, ctx.word)
+        return d_msg.reshape(g._shape(e.e_cap) + ctx.rest), None, None, None, None, None
+
+
 _FLOAT_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "force", "rel_disp", "rel_dist")
 _GRAD_KEYS = ("abs_pos", "vel_hist", "vel_mag", "bound", "rel_disp", "rel_dist")   # ("force" is a constant of the positions)
 
@@ -439,7 +510,7 @@ def differentiable_features(features, window: torch.Tensor) -> dict:
 
 class Graph:
     """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum and the attention
-    ops (degree, segment_mean / max / min / softmax, attend) and the edge messages (conv, pair_mul, pair_add, conv_vec,
+    ops (degree, segment_mean / max / min / softmax, attend), the multi-aggregator (aggregate, segment_std / var) and the edge messages (conv, pair_mul, pair_add, conv_vec,
     conv_dot).
     `batched`: whether the tensors carry the leading B (default: as the features do)."""
 
@@ -547,6 +618,31 @@ class Graph:
     def segment_min(self, msg: torch.Tensor, role: str) -> torch.Tensor:
         """segment_max with "strictly smaller"; a node without edges gets +0.0 (jraph: +inf)."""
         return _SegmentMax.apply(msg, self, self._role(role), True)
+
+    def aggregate(self, msg: torch.Tensor, role: str, ops=("sum", "mean", "max", "min", "std"), eps: float = 1e-5) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, N, A, C), A = len(ops): the named reductions of msg over each node's real slots of `role`,
+        in the order of `ops` - distinct names out of sum, mean, max, min, std, var - from ONE launch that walks the row once
+        (twice with std / var, for the centred squares) and ONE launch backward.  sum, mean, max and min have the bits of
+        segment_sum, segment_mean, segment_max and segment_min; var is the centred two-pass population variance, std is
+        sqrt(var + eps); a node without slots gets +0.0 in every plane.  The module docstring states every rounding."""
+        names, word = _agg_word("aggregate", ops, eps)
+        return _Aggregate.apply(msg, self, self._role(role), names, word, float(eps))
+
+    def segment_std(self, msg: torch.Tensor, role: str, eps: float = 1e-5) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, N, C): aggregate(msg, role, ("std",), eps) without the plane axis - sqrt(var + eps) of the
+        node's real slots, +0.0 for a node without slots."""
+        names, word = _agg_word("segment_std", ("std",), eps)
+        return _Aggregate.apply(msg, self, self._role(role), names, word, float(eps)).select(self._plane, 0)
+
+    def segment_var(self, msg: torch.Tensor, role: str) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, N, C): aggregate(msg, role, ("var",)) without the plane axis - the centred two-pass
+        population variance of the node's real slots."""
+        names, word = _agg_word("segment_var", ("var",), 1.0)
+        return _Aggregate.apply(msg, self, self._role(role), names, word, 1.0).select(self._plane, 0)
+
+    @property
+    def _plane(self) -> int:
+        return 2 if self.batched else 1   # the axis of aggregate's planes
 
     def segment_softmax(self, logits: torch.Tensor, role: str) -> torch.Tensor:
         """logits (B, E_cap, C) -> (B, E_cap, C): one softmax per node and column over the node's real slots, shifted by
