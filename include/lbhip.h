@@ -874,6 +874,45 @@ int lb_graph_conv_vec_edge_grad(lb_engine* eng, int32_t s_role, const void* s_de
                                 const void* w_dev /*(B*E_cap,C)*/, const void* u_dev /*(B*E_cap,K)*/,
                                 void* d_w_dev /*(B*E_cap,C) or NULL*/, void* d_u_dev /*(B*E_cap,K) or NULL*/, int32_t K, int32_t C,
                                 int32_t dtype);
+/* ---- filter_conv: conv with its one-Linear filter formed in registers -----
+ * The rules of the edge messages hold (layout, roles, pads never read - the pad slots of f may hold NaN -, +0.0 in the pad slots of
+ * edge-shaped outputs, no float atomics, two calls the same bits, dtype for every data tensor, weight included).  x (B*N, K, C),
+ * f (B*E_cap, R) any per-edge basis, weight (R, C) shared by the batch, 1 <= R <= LB_GRAPH_MAX_R.  o(j) is the other(role) node
+ * of slot j, n(j) its `role` node.  Every product is one fp32 multiplication, every add one fp32 add, no FMA contraction.
+ * The filter, never stored: wf[j, c] = fl32(f[j, 0] * weight[0, c]) + fl32(f[j, 1] * weight[1, c]) + ..., r ascending, the first
+ *   product starts the sum.
+ * filter_conv: out[i, k, c] = the sum over the real slots j with n(j) = i, ascending, of fl32(x[o(j), k, c] * wf[j, c]); the first
+ *   term starts the sum, +0.0 for a node without a slot: with fp32 tensors bit for bit lb_graph_conv on wf.  Its adjoint:
+ *   d_x = filter_conv(d_out, f, weight, other(role)).
+ * filter_conv_grad (role: the forward's), from g[j, c] = fl32(x[o(j), 0, c] * d[n(j), 0, c]) + fl32(x[o(j), 1, c] * d[n(j), 1, c])
+ *   + ... (k ascending, the first product starts the sum: conv's d_w), never stored:
+ *     d_f[j, r] = the sum over c of fl32(weight[r, c] * g[j, c]) in the order of LB_GRAPH_DU_BLOCK (blocks of consecutive columns,
+ *       c ascending inside a block from its first product, the block sums added in ascending order from the first one); +0.0 in
+ *       the pad slots;
+ *     d_weight[r, c] = the sum over every real slot of every trajectory of fl32(f[j, r] * g[j, c]) in a two-level order: the flat
+ *       padded slots b * E_cap + j in consecutive chunks of LB_GRAPH_FILTER_CHUNK; per chunk a partial sum that starts at +0.0
+ *       and takes the terms of the chunk's real slots in ascending order (a chunk of pads keeps +0.0); the total starts at +0.0
+ *       and takes the partials in ascending chunk order.  A numpy loop reproduces it.
+ *   Either of d_f_dev (B*E_cap, R) and d_weight_dev (R, C) may be null: that gradient is not computed (both null: LB_ERR_ARG).
+ *   With d_weight_dev the caller gives partials_dev, fp32 scratch of at least lb_graph_filter_partials(eng, R, C) =
+ *   ceil(B*E_cap / LB_GRAPH_FILTER_CHUNK) * R * C elements (partials_len: what it holds); nothing else is allocated, and nothing of
+ *   E_cap x C elements exists.  One launch for d_f, two for d_weight (the partials, the ordered finish).
+ * LB_DTYPE_BF16: every output, d_f and d_weight included, is round_to_bf16(the fp32 result on the widened inputs), one rounding
+ *   per stored element; wf and g stay fp32.
+ * LB_ERR_ARG on a null required pointer, a role other than 0 / 1, a dtype other than the two, K < 1, R < 1, R > LB_GRAPH_MAX_R,
+ *   C < 1 or partials too short; LB_ERR_STATE without a list or with an overflowed one. */
+#define LB_GRAPH_MAX_R 32
+#define LB_GRAPH_FILTER_CHUNK 256
+int lb_graph_filter_conv(lb_engine* eng, int32_t role, const void* x_dev /*(B*N,K,C)*/, const void* f_dev /*(B*E_cap,R)*/,
+                         const void* weight_dev /*(R,C)*/, void* out_dev /*(B*N,K,C)*/, int32_t K, int32_t R, int32_t C,
+                         int32_t dtype);
+int lb_graph_filter_conv_grad(lb_engine* eng, int32_t role, const void* x_dev /*(B*N,K,C)*/, const void* d_dev /*(B*N,K,C)*/,
+                              const void* f_dev /*(B*E_cap,R)*/, const void* weight_dev /*(R,C)*/,
+                              void* d_f_dev /*(B*E_cap,R) or NULL*/, void* d_weight_dev /*(R,C) or NULL*/,
+                              float* partials_dev /*NULL without d_weight*/, int64_t partials_len, int32_t K, int32_t R, int32_t C,
+                              int32_t dtype);
+/* elements of the fp32 partials of lb_graph_filter_conv_grad on the engine's current E_cap; 0 without a list or on bad sizes */
+int64_t lb_graph_filter_partials(lb_engine* eng, int32_t R, int32_t C);
 /* ---- the multi-aggregator: sum, mean, max, min, std and var of one message in one launch -----
  * The rules of the graph ops hold (layout, roles, pads never read, +0.0 in the pad slots of edge-shaped outputs, no float atomics,
  * two calls the same bits, dtype for every data tensor).  msg (B*E_cap, C) -> out (B*N, A, C): plane a holds the op whose code

@@ -235,6 +235,12 @@ _SIGS = {
     "lb_graph_conv_vec": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_conv_dot": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_conv_vec_edge_grad": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    # filter_conv: (x, f, weight, out, K, R, C); its edge gradients (x, d, f, weight, d_f or null, d_weight or null, partials,
+    # partials_len, K, R, C)
+    "lb_graph_filter_conv": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "lb_graph_filter_conv_grad": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32]),
+    "lb_graph_filter_partials": (C.c_int64, [_P, C.c_int32, C.c_int32]),
     # the multi-aggregator: (msg, out, win or null, stats or null, C, ops, eps); backward (d_out, msg, win, stats, d_msg, C, ops)
     "lb_graph_aggregate": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32]),
     "lb_graph_aggregate_backward": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),

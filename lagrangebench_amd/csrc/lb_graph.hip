@@ -7,7 +7,8 @@
 // and, for attention and pooling layers (further down: "attention ops"), lb_graph_degree, lb_graph_segment_max / _min,
 // lb_graph_segment_softmax and the fused lb_graph_attend with their backward entries; for filter x neighbour messages ("edge
 // messages") the fused lb_graph_conv and the edge-shaped lb_graph_pair_mul / lb_graph_pair_add, and the equivariant couplings
-// through a per-edge vector, lb_graph_conv_vec / lb_graph_conv_dot with lb_graph_conv_vec_edge_grad; the multi-aggregator
+// through a per-edge vector, lb_graph_conv_vec / lb_graph_conv_dot with lb_graph_conv_vec_edge_grad; the continuous-filter
+// convolution with its Linear inside, lb_graph_filter_conv with lb_graph_filter_conv_grad; the multi-aggregator
 // lb_graph_aggregate (sum, mean, max, min, std, var of one message from one walk) with its backward; and lb_graph_features_backward
 // ("feature transpose"): d loss / d window from the cotangents of the features such a network was handed.
 //
@@ -954,6 +955,313 @@ __global__ void __launch_bounds__(256) k_graph_vec_edge_grad(lb_glist L, const i
   }
 }
 
+// ------------------------------------------------------------------------------------------------ filter_conv
+// conv with its filter formed in registers: wf[slot][c] = fl32(f[slot][0] * weight[0][c]) + fl32(f[slot][1] * weight[1][c]) + ...
+// (r ascending, the first product starts the sum) from a per-edge basis f (B E_cap, R), R <= LB_GRAPH_MAX_R, and a weight (R, C)
+// shared by the batch (the contract is in include/lbhip.h).  wf never reaches memory.
+//
+// Where the weight lives.  A lane owns unit u of a row and needs the R x W weight columns of that unit - at most 32 x 4 floats,
+// which it keeps in registers (bfloat16 rows are read in 8-byte units here, W = 4, so that they fit).  A lane's unit does not change
+// from one row to the next while a row is no wider than its lane group (C <= 256), so the weight is loaded once per lane and
+// kernel; a wider row reloads it per unit from L1 / L2, once per row, not per slot.  That state lives across rows, so the kernel
+// spells graph_for's two loops out, as k_graph_attend does.  RM: the r rows held (20 - PaiNN's n_rbf - or 32); rows past R are zero, their
+// terms are formed and dropped by a select - no branch in the slot loop, and every f load of a slot is issued before its use.
+// f rows are R elements wide (80 bytes at R = 20): one address per lane group, a broadcast, as u is read in conv_vec - four
+// elements per load when R % 4 == 0 and f is 16-byte aligned (FV), scalar loads otherwise; an r past R - 1 re-reads the row's end.
+template <typename T, int W, int RM>
+__device__ __forceinline__ void graph_filter_unit(const float (&fr)[RM], const float (&wt)[RM][W], int R, float (&wf)[W]) {
+#pragma unroll
+  for (int c = 0; c < W; ++c) wf[c] = __fmul_rn(fr[0], wt[0][c]);
+#pragma unroll
+  for (int r = 1; r < RM; ++r)
+#pragma unroll
+    for (int c = 0; c < W; ++c) {
+      const float t = __fadd_rn(wf[c], __fmul_rn(fr[r], wt[r][c]));
+      wf[c] = r < R ? t : wf[c];
+    }
+}
+// One slot's loads for k-chunk k0 .. k0 + KT - 1: the R scalars of f and KT x units of the slot's other node.
+template <typename T, int W, int KT, int RM, bool FV>
+__device__ __forceinline__ void graph_filter_load(const lb_row& Rw, int p, const int32_t* __restrict__ oidx,
+                                                  const T* __restrict__ x, const T* __restrict__ f, const lb_glist& L, int K, int k0,
+                                                  int R, int U, int u, float (&fr)[RM], float (&a)[KT][W]) {
+  const int64_t e = Rw.edge(p);
+  const int64_t node = graph_clamp(L, oidx[e - Rw.slot0]);
+  if constexpr (FV) {   // R % 4 == 0 and f aligned: four elements per load; a group past R re-reads the last one
+    static_assert(RM % 4 == 0, "groups of four");
+#pragma unroll
+    for (int r = 0; r < RM; r += 4) {
+      float t[4];
+      lb_ld<T, 4>(f + e * R + (r < R ? r : R - 4), t);
+      fr[r] = t[0], fr[r + 1] = t[1], fr[r + 2] = t[2], fr[r + 3] = t[3];
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < RM; ++r) fr[r] = lb_ld1<T>(f + e * R + (r < R ? r : R - 1));
+  }
+#pragma unroll
+  for (int q = 0; q < KT; ++q) {
+    const int k = k0 + q < K ? k0 + q : K - 1;
+    lb_ld<T, W>(x + ((node * K + k) * U + u) * W, a[q]);
+  }
+}
+// out[i][k][:] = sum over the slots of row i, ascending, of fl32(x[other node of the slot][k][:] * wf[slot][:]); +0.0 for an empty
+// row: k_graph_conv's sum on the filter above.  KT accumulator rows per pass over the slots (1 for K = 1, 3 for K > 1), two slots'
+// loads in flight; the adds sequential.
+template <typename T, int W, int KT, int RM, bool FV>
+__global__ void __launch_bounds__(256) k_graph_filter_conv(lb_glist L, lb_gwalk walk, const int32_t* __restrict__ oidx,
+                                                           const T* __restrict__ x, const T* __restrict__ f,
+                                                           const T* __restrict__ weight, T* __restrict__ out, int K, int R) {
+  const int U = L.U;
+  const lb_glanes G = graph_lanes(L);
+  float wt[RM][W];
+  int held = -1;   // the unit whose weight columns wt holds
+  for (int64_t i = G.first; i < L.BN; i += G.stride) {
+    const lb_row Rw = graph_row(L, walk, i);
+    for (int u = G.lane; u < U; u += G.lpr) {
+      if (u != held) {
+        held = u;
+#pragma unroll
+        for (int r = 0; r < RM; ++r) {
+#pragma unroll
+          for (int c = 0; c < W; ++c) wt[r][c] = 0.f;
+          if (r < R) lb_ld<T, W>(weight + ((int64_t)r * U + u) * W, wt[r]);
+        }
+      }
+      for (int k0 = 0; k0 < K; k0 += KT) {
+        float s[KT][W], fr[2][RM], a[2][KT][W], wf[2][W];
+#pragma unroll
+        for (int q = 0; q < KT; ++q)
+#pragma unroll
+          for (int c = 0; c < W; ++c) s[q][c] = 0.f;
+        int p = Rw.p0;
+        if (p < Rw.p1) {   // the sum STARTS from the first product
+          graph_filter_load<T, W, KT, RM, FV>(Rw, p++, oidx, x, f, L, K, k0, R, U, u, fr[0], a[0]);
+          graph_filter_unit<T, W, RM>(fr[0], wt, R, wf[0]);
+#pragma unroll
+          for (int q = 0; q < KT; ++q)
+#pragma unroll
+            for (int c = 0; c < W; ++c) s[q][c] = __fmul_rn(a[0][q][c], wf[0][c]);
+        }
+        for (; p + 2 <= Rw.p1; p += 2) {
+#pragma unroll
+          for (int t = 0; t < 2; ++t) graph_filter_load<T, W, KT, RM, FV>(Rw, p + t, oidx, x, f, L, K, k0, R, U, u, fr[t], a[t]);
+#pragma unroll
+          for (int t = 0; t < 2; ++t) {
+            graph_filter_unit<T, W, RM>(fr[t], wt, R, wf[t]);
+#pragma unroll
+            for (int q = 0; q < KT; ++q)
+#pragma unroll
+              for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[t][q][c], wf[t][c]));
+          }
+        }
+        if (p < Rw.p1) {
+          graph_filter_load<T, W, KT, RM, FV>(Rw, p, oidx, x, f, L, K, k0, R, U, u, fr[0], a[0]);
+          graph_filter_unit<T, W, RM>(fr[0], wt, R, wf[0]);
+#pragma unroll
+          for (int q = 0; q < KT; ++q)
+#pragma unroll
+            for (int c = 0; c < W; ++c) s[q][c] = __fadd_rn(s[q][c], __fmul_rn(a[0][q][c], wf[0][c]));
+        }
+#pragma unroll
+        for (int q = 0; q < KT; ++q)
+          if (k0 + q < K) lb_st<T, W>(out + ((i * K + k0 + q) * U + u) * W, s[q]);
+      }
+    }
+  }
+}
+
+// The edge gradients of filter_conv, from g[slot][c] = fl32(x[o][0][c] * d[n][0][c]) + fl32(x[o][1][c] * d[n][1][c]) + ... (k
+// ascending, the first product starts the sum; o the slot's other node, n its `role` node: conv's d_w), which is never stored:
+//   d_f[slot][r]   = the sum over c of fl32(weight[r][c] * g[slot][c]) in the order of LB_GRAPH_DU_BLOCK: consecutive blocks of 16
+//                    columns, c ascending inside a block from its first product, the block sums added in ascending block order from
+//                    the first one; +0.0 in the pad slots;
+//   d_weight[r][c] = the sum over every real slot of the batch of fl32(f[slot][r] * g[slot][c]) in the two-level order of
+//                    LB_GRAPH_FILTER_CHUNK: per chunk of consecutive flat padded slots a partial sum from +0.0 over its real slots,
+//                    ascending (k_graph_filter_dw); the total from +0.0 over the partials, ascending (k_graph_filter_finish).
+// Both are small dense products against an edge-shaped operand that exists only tile by tile: a workgroup forms g for a tile of
+// LB_GF_TILE slots and LB_GF_COLS columns in LDS - a lane per unit of a slot's row, so x and d rows are read as whole lines as in
+// k_graph_pair_mul - and every lane then owns outputs whose sums it runs alone, in order, from LDS: no shuffle, no atomics.
+#define LB_GF_TILE 32    // slots of a tile
+#define LB_GF_COLS 128   // columns of a tile: a multiple of LB_GRAPH_DU_BLOCK, and 256 lanes make whole slots of its units
+static_assert(LB_GF_COLS % LB_GRAPH_DU_BLOCK == 0 && LB_GRAPH_FILTER_CHUNK % LB_GF_TILE == 0 && LB_GRAPH_MAX_R <= 32, "tile sizes");
+struct lb_gf_slots {
+  int real[LB_GF_TILE];
+  int64_t node[LB_GF_TILE], other[LB_GF_TILE];
+};
+// the tile's slots from flat padded slot r0 (a slot past the batch is a pad), by the first LB_GF_TILE lanes
+__device__ __forceinline__ void graph_filter_slots(const lb_glist& L, int64_t r0, int64_t total, const int32_t* __restrict__ idx,
+                                                   const int32_t* __restrict__ oidx, lb_gf_slots& S) {
+  if (threadIdx.x < LB_GF_TILE) {
+    const int64_t r = r0 + threadIdx.x;
+    lb_gslot s{};
+    if (r < total) s = graph_slot(L, r, idx, oidx);
+    S.real[threadIdx.x] = s.real, S.node[threadIdx.x] = s.node, S.other[threadIdx.x] = s.other;
+  }
+}
+// g of the tile's real slots for columns c0 .. c0 + LB_GF_COLS - 1 (those below C) -> gs; a pad slot's row is left as it was
+template <typename T, int W>
+__device__ __forceinline__ void graph_filter_g(const T* __restrict__ x, const T* __restrict__ d, int K, int C, int c0,
+                                               const lb_gf_slots& S, float (*gs)[LB_GF_COLS + 1]) {
+  constexpr int UC = LB_GF_COLS / W;   // units of a tile row
+  const int u = (int)threadIdx.x % UC, col = c0 + u * W;
+  if (col >= C) return;
+  for (int s = (int)threadIdx.x / UC; s < LB_GF_TILE; s += 256 / UC) {
+    if (!S.real[s]) continue;
+    const T* __restrict__ xp = x + S.other[s] * K * C + col;
+    const T* __restrict__ dp = d + S.node[s] * K * C + col;
+    float g[W], a[W], b[W];
+    lb_ld<T, W>(xp, a);
+    lb_ld<T, W>(dp, b);
+#pragma unroll
+    for (int c = 0; c < W; ++c) g[c] = __fmul_rn(a[c], b[c]);
+#pragma unroll 4
+    for (int k = 1; k < K; ++k) {
+      lb_ld<T, W>(xp + (int64_t)k * C, a);
+      lb_ld<T, W>(dp + (int64_t)k * C, b);
+#pragma unroll
+      for (int c = 0; c < W; ++c) g[c] = __fadd_rn(g[c], __fmul_rn(a[c], b[c]));
+    }
+#pragma unroll
+    for (int c = 0; c < W; ++c) gs[s][u * W + c] = g[c];
+  }
+}
+
+// d_f: lane (s, rg) of the workgroup owns slot s of the tile and the rows r = rg, rg + 8, ... (RN of them) and runs their blocked
+// sums over the columns - all passes of LB_GF_COLS columns of a tile before the next tile, the running totals in registers.  The
+// weight columns of a pass are staged in LDS (rows past R zero; once per workgroup when C is one pass); g is read at an odd
+// row stride (no bank conflict across s), the weight as a broadcast.
+template <typename T, int W, int RN>
+__global__ void __launch_bounds__(256) k_graph_filter_df(lb_glist L, const int32_t* __restrict__ idx,
+                                                         const int32_t* __restrict__ oidx, const T* __restrict__ x,
+                                                         const T* __restrict__ d, const T* __restrict__ weight, T* __restrict__ d_f,
+                                                         int K, int R, int C) {
+  __shared__ float gs[LB_GF_TILE][LB_GF_COLS + 1];
+  __shared__ __attribute__((aligned(16))) float ws[8 * RN][LB_GF_COLS];
+  __shared__ lb_gf_slots S;
+  const int64_t total = (int64_t)L.B * L.e_cap, tiles = (total + LB_GF_TILE - 1) / LB_GF_TILE;
+  const int s = threadIdx.x & (LB_GF_TILE - 1), rg = threadIdx.x / LB_GF_TILE;
+  const int passes = (C + LB_GF_COLS - 1) / LB_GF_COLS;
+  bool staged = false;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t r0 = tile * LB_GF_TILE;
+    __syncthreads();   // (the last tile's readers are done)
+    graph_filter_slots(L, r0, total, idx, oidx, S);
+    float tot[RN];
+#pragma unroll
+    for (int n = 0; n < RN; ++n) tot[n] = 0.f;
+    for (int pass = 0; pass < passes; ++pass) {
+      const int c0 = pass * LB_GF_COLS, cn = C - c0 < LB_GF_COLS ? C - c0 : LB_GF_COLS;
+      if (pass) __syncthreads();   // (the last pass's readers are done)
+      if (passes > 1 || !staged) {
+        staged = true;
+        for (int q = threadIdx.x; q < 8 * RN * LB_GF_COLS; q += 256) {
+          const int r = q / LB_GF_COLS, c = q % LB_GF_COLS;
+          ws[r][c] = (r < R && c < cn) ? lb_ld1<T>(weight + (int64_t)r * C + c0 + c) : 0.f;
+        }
+      }
+      __syncthreads();
+      graph_filter_g<T, W>(x, d, K, C, c0, S, gs);
+      __syncthreads();
+      if (S.real[s]) {
+        for (int cb = 0; cb < cn; cb += LB_GRAPH_DU_BLOCK) {
+          const int bn = cn - cb;   // the block's columns (LB_GRAPH_DU_BLOCK or more: a full block)
+          float gv[LB_GRAPH_DU_BLOCK];
+#pragma unroll
+          for (int c = 0; c < LB_GRAPH_DU_BLOCK; ++c) gv[c] = gs[s][cb + c];   // (past bn: whatever LDS holds, dropped below)
+#pragma unroll
+          for (int n = 0; n < RN; ++n) {
+            const float* __restrict__ wr = ws[rg + 8 * n] + cb;
+            float part = __fmul_rn(wr[0], gv[0]);
+#pragma unroll
+            for (int c = 1; c < LB_GRAPH_DU_BLOCK; ++c) {
+              const float t = __fadd_rn(part, __fmul_rn(wr[c], gv[c]));
+              part = c < bn ? t : part;
+            }
+            tot[n] = (pass == 0 && cb == 0) ? part : __fadd_rn(tot[n], part);
+          }
+        }
+      }
+    }
+    if (r0 + s < total) {
+#pragma unroll
+      for (int n = 0; n < RN; ++n)
+        if (rg + 8 * n < R) lb_st1<T>(d_f + (r0 + s) * R + rg + 8 * n, tot[n]);
+    }
+  }
+}
+
+// The partial sums of d_weight: workgroup (q, pass) owns chunk q of `chunk` flat padded slots and columns c0 .. c0 + LB_GF_COLS - 1;
+// lane (cl, rg) of it the outputs r = rg, rg + 8, ... x c = c0 + cl, c0 + cl + 32, ...: RN x 4 accumulators from +0.0, fed tile by
+// tile with the real slots in ascending order - f and g of the tile from LDS.  partials is (chunks, R, C) fp32, every element
+// written (+0.0 by a chunk of pads).
+template <typename T, int W, int RN>
+__global__ void __launch_bounds__(256) k_graph_filter_dw(lb_glist L, const int32_t* __restrict__ idx,
+                                                         const int32_t* __restrict__ oidx, const T* __restrict__ x,
+                                                         const T* __restrict__ d, const T* __restrict__ f,
+                                                         float* __restrict__ partials, int K, int R, int C, int chunk) {
+  __shared__ float gs[LB_GF_TILE][LB_GF_COLS + 1];
+  __shared__ float fs[LB_GF_TILE][8 * RN + 1];
+  __shared__ lb_gf_slots S;
+  const int64_t total = (int64_t)L.B * L.e_cap, q = blockIdx.x;
+  const int c0 = blockIdx.y * LB_GF_COLS;
+  const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
+  const int64_t end = (q + 1) * chunk < total ? (q + 1) * chunk : total;
+  float acc[RN][4];
+#pragma unroll
+  for (int n = 0; n < RN; ++n)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) acc[n][m] = 0.f;
+  for (int64_t r0 = q * chunk; r0 < end; r0 += LB_GF_TILE) {
+    __syncthreads();   // (the last tile's readers are done)
+    graph_filter_slots(L, r0, total, idx, oidx, S);
+    __syncthreads();
+    graph_filter_g<T, W>(x, d, K, C, c0, S, gs);
+    for (int t = threadIdx.x; t < LB_GF_TILE * 8 * RN; t += 256) {
+      const int s = t / (8 * RN), r = t % (8 * RN);
+      if (S.real[s] && r < R) fs[s][r] = lb_ld1<T>(f + (r0 + s) * R + r);   // (a pad slot's f is never read)
+    }
+    __syncthreads();
+    for (int s = 0; s < LB_GF_TILE; ++s) {
+      if (!S.real[s]) continue;   // (uniform)
+      float gv[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) gv[m] = gs[s][cl + 32 * m];
+#pragma unroll
+      for (int n = 0; n < RN; ++n) {
+        const float fr = fs[s][rg + 8 * n];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) acc[n][m] = __fadd_rn(acc[n][m], __fmul_rn(fr, gv[m]));
+      }
+    }
+  }
+#pragma unroll
+  for (int n = 0; n < RN; ++n)
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int r = rg + 8 * n, c = c0 + cl + 32 * m;
+      if (r < R && c < C) partials[(q * R + r) * C + c] = acc[n][m];
+    }
+}
+// d_weight[r][c] = +0.0 + partials[0][r][c] + partials[1][r][c] + ...: one lane per element, the chunks ascending.
+template <typename T>
+__global__ void __launch_bounds__(256) k_graph_filter_finish(const float* __restrict__ partials, int64_t chunks, int64_t RC,
+                                                             T* __restrict__ d_weight) {
+  const int64_t stride = (int64_t)gridDim.x * 256;   // (the grid is capped: graph_blocks1)
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < RC; q += stride) {
+    float tot = 0.f, v[16];
+    int64_t k = 0;
+    for (; k + 16 <= chunks; k += 16) {   // sixteen loads in flight; the adds stay sequential
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = partials[(k + j) * RC + q];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) tot = __fadd_rn(tot, v[j]);
+    }
+    for (; k < chunks; ++k) tot = __fadd_rn(tot, partials[k * RC + q]);
+    lb_st1<T>(d_weight + q, tot);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ multi-aggregator
 // aggregate: sum, mean, max, min, std and var of one message from one walk of the row (the contract is in
 // include/lbhip.h above lb_graph_aggregate).  out is (B N, A, C): plane a of node i is row i A + a of C columns.  Where each op
@@ -1682,6 +1990,85 @@ extern "C" int lb_graph_conv_vec_edge_grad(lb_engine* e, int32_t s_role, const v
     constexpr int W = decltype(w)::value;   // K <= 3 (a vector in space): three k rows in registers
     graph_launch(e, P.blocks, K <= 3 ? k_graph_vec_edge_grad<T, W, 3> : k_graph_vec_edge_grad<T, W, LB_GRAPH_MAX_K>, P.L, P.idx,
                  P.oidx, (const T*)s_dev, (const T*)v_dev, (const T*)w_dev, (const T*)u_dev, (T*)d_w_dev, (T*)d_u_dev, K);
+  });
+}
+
+// ---- filter_conv's entries.  K, R and C: K >= 1, 1 <= R <= LB_GRAPH_MAX_R (the weight columns of a unit live in registers), C >= 1
+static int graph_filter_sizes(const char* entry, int32_t K, int32_t R, int32_t C) {
+  if (K < 1 || R < 1 || R > LB_GRAPH_MAX_R || C < 1)
+    return lb_fail(LB_ERR_ARG, "%s: K %d (>= 1), R %d (1 .. %d), C %d (>= 1)", entry, K, R, LB_GRAPH_MAX_R, C);
+  if ((int64_t)K * C > INT32_MAX || (int64_t)R * C > INT32_MAX) return lb_fail(LB_ERR_ARG, "%s: K %d, R %d x C %d columns", entry, K, R, C);
+  return LB_OK;
+}
+// the span graph_width is asked for: units of at most 4 elements - bfloat16 rows in 8-byte units - so that the R x W weight columns
+// of a unit fit a lane's registers
+static int graph_filter_span(int32_t dtype, int C) { return dtype == LB_DTYPE_BF16 && C % 4 == 0 ? 4 : C; }
+// f(lb_w<N>{}) with a compile-time bound N >= n out of the list
+template <int... Ns, typename F>
+static void graph_at_most(int n, F f) {
+  bool done = false;
+  ((!done && n <= Ns ? (f(lb_w<Ns>{}), done = true) : false), ...);
+}
+
+extern "C" int lb_graph_filter_conv(lb_engine* e, int32_t role, const void* x_dev, const void* f_dev, const void* weight_dev,
+                                    void* out_dev, int32_t K, int32_t R, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, "lb_graph_filter_conv", role, dtype, x_dev && f_dev && weight_dev && out_dev, 1, 1));
+  LB_TRY(graph_filter_sizes("lb_graph_filter_conv", K, R, C));
+  const lb_gplan P = graph_plan(e, role, dtype, LB_NODES, C, graph_filter_span(dtype, C), true, {x_dev, weight_dev, out_dev});
+  return graph_dispatch<true>(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    if constexpr (W <= 4)
+      graph_at_most<20, 32>(R, [&](auto rm) {
+        constexpr int RM = decltype(rm)::value;   // K > 1: three k at a time; f in groups of four where its rows allow it
+        auto kernel = K == 1 ? k_graph_filter_conv<T, W, 1, RM, false> : k_graph_filter_conv<T, W, 3, RM, false>;
+        if (R % 4 == 0 && graph_aligned({f_dev})) kernel = K == 1 ? k_graph_filter_conv<T, W, 1, RM, true> : k_graph_filter_conv<T, W, 3, RM, true>;
+        graph_launch(e, P.blocks, kernel, P.L, P.walk, P.oidx, (const T*)x_dev, (const T*)f_dev, (const T*)weight_dev, (T*)out_dev,
+                     K, R);
+      });
+  });
+}
+
+extern "C" int64_t lb_graph_filter_partials(lb_engine* e, int32_t R, int32_t C) {
+  if (!e || e->e_cap <= 0 || R < 1 || C < 1) return 0;
+  const int64_t slots = (int64_t)e->g.B * e->e_cap;
+  return (slots + LB_GRAPH_FILTER_CHUNK - 1) / LB_GRAPH_FILTER_CHUNK * R * C;
+}
+
+extern "C" int lb_graph_filter_conv_grad(lb_engine* e, int32_t role, const void* x_dev, const void* d_dev, const void* f_dev,
+                                         const void* weight_dev, void* d_f_dev, void* d_weight_dev, float* partials_dev,
+                                         int64_t partials_len, int32_t K, int32_t R, int32_t C, int32_t dtype) {
+  // edge-parallel: no view.  Either output may be null (not wanted), not both; the partials go with d_weight.
+  const char* entry = "lb_graph_filter_conv_grad";
+  LB_TRY(graph_entry(e, entry, role, dtype,
+                     x_dev && d_dev && f_dev && weight_dev && (d_f_dev || d_weight_dev) && (partials_dev || !d_weight_dev), 1, 1,
+                     false));
+  LB_TRY(graph_filter_sizes(entry, K, R, C));
+  const int64_t slots = (int64_t)e->g.B * e->e_cap, chunks = (slots + LB_GRAPH_FILTER_CHUNK - 1) / LB_GRAPH_FILTER_CHUNK;
+  const int passes = (C + LB_GF_COLS - 1) / LB_GF_COLS;
+  if (d_weight_dev && (partials_len < chunks * R * C || passes > 65535 || chunks > INT32_MAX))
+    return lb_fail(LB_ERR_ARG, "%s: partials of %lld floats, %lld chunks x R %d x C %d needed", entry, (long long)partials_len,
+                   (long long)chunks, R, C);
+  const lb_gplan P = graph_plan(e, role, dtype, LB_SLOTS, C, graph_filter_span(dtype, C), true, {x_dev, d_dev});
+  const lb_glist L = graph_list(e, 0, 0);   // (the tile kernels lay their lanes out themselves)
+  const int64_t tiles = (slots + LB_GF_TILE - 1) / LB_GF_TILE;
+  return graph_dispatch<true>(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    if constexpr (W <= 4)
+      graph_at_most<1, 2, 3, 4>((R + 7) / 8, [&](auto rn) {
+        constexpr int RN = decltype(rn)::value;
+        if (d_f_dev)
+          graph_launch(e, (unsigned)std::min<int64_t>(tiles, 2048), k_graph_filter_df<T, W, RN>, L, P.idx, P.oidx, (const T*)x_dev,
+                       (const T*)d_dev, (const T*)weight_dev, (T*)d_f_dev, K, R, C);
+        if (d_weight_dev) {
+          hipLaunchKernelGGL((k_graph_filter_dw<T, W, RN>), dim3((unsigned)chunks, (unsigned)passes), dim3(256), 0, e->stream, L,
+                             P.idx, P.oidx, (const T*)x_dev, (const T*)d_dev, (const T*)f_dev, partials_dev, K, R, C,
+                             (int)LB_GRAPH_FILTER_CHUNK);
+          graph_launch(e, graph_blocks1((int64_t)R * C), k_graph_filter_finish<T>, (const float*)partials_dev, chunks,
+                       (int64_t)R * C, (T*)d_weight_dev);
+        }
+      });
   });
 }
 

@@ -65,6 +65,12 @@ def _graph_ops():
         "lb_graph_conv_dot": ("lb_graph_conv_dot", ((nkc, None), (sc, None), (sk, None)), ((nc, None),), ("K", "C")),
         "lb_graph_conv_vec_edge_grad": ("lb_graph_conv_vec_edge_grad", ((nc, None), (nkc, None), (sc, None), (sk, None)),
                                         ((sc, None), (sk, None)), ("K", "C")),
+        "lb_graph_filter_conv": ("lb_graph_filter_conv", ((nkc, None), (("slots", "R"), None), (("R", "C"), None)), ((nkc, None),),
+                                 ("K", "R", "C")),
+        "lb_graph_filter_conv_grad": ("lb_graph_filter_conv_grad",
+                                      ((nkc, None), (nkc, None), (("slots", "R"), None), (("R", "C"), None)),
+                                      ((("slots", "R"), None), (("R", "C"), None), (("partials",), f32)),
+                                      ("partials", "K", "R", "C")),
         "lb_graph_aggregate": ("lb_graph_aggregate", ((sc, None),), ((nac, None), (npc, i32), (npc, f32)), ("C", "ops", "eps")),
         "lb_graph_aggregate_backward": ("lb_graph_aggregate_backward", ((nac, None), (sc, None), (npc, i32), (npc, f32)),
                                         ((sc, None),), ("C", "ops"), True),
@@ -675,6 +681,30 @@ class RolloutEngine:
         if not (want_w or want_u):
             return None, None
         return self._graph_call("lb_graph_conv_vec_edge_grad", s_role, (s, v, w, u), want=(want_w, want_u))
+
+    def graph_filter_conv(self, role: int, x: torch.Tensor, f: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+        """x (B*N, K, C), f (B*E_cap, R), weight (R, C), 1 <= R <= 32, one dtype (float32 or bfloat16) -> (B*N, K, C): graph_conv
+        with the filter wf[slot, c] = f[slot, 0] * weight[0, c] + f[slot, 1] * weight[1, c] + ... (r ascending, every product
+        rounded to float32, the first starts the sum) formed in registers - wf never reaches memory.  float32: the bits of
+        graph_conv(role, x, wf).  bfloat16: that float32 result on the widened inputs, rounded once (include/lbhip.h:
+        lb_graph_filter_conv)."""
+        return self._graph_call("lb_graph_filter_conv", role, (x, f, weight))
+
+    def graph_filter_conv_grad(self, role: int, x: torch.Tensor, d: torch.Tensor, f: torch.Tensor, weight: torch.Tensor,
+                               want_f: bool = True, want_weight: bool = True):
+        """The gradients of graph_filter_conv over `role` to f and weight from x and the cotangent d (both (B*N, K, C)) -> (d_f
+        (B*E_cap, R), d_weight (R, C)).  With g[slot, c] = the sum over k ascending of x[the slot's other node, k, c] * d[its
+        `role` node, k, c] (never stored): d_f[slot, r] = the sum over c of weight[r, c] * g[slot, c] in blocks of 16 columns - c
+        ascending inside a block, the block sums added in ascending order -, +0.0 in the pad slots; d_weight[r, c] = the sum over
+        every real slot of f[slot, r] * g[slot, c]: per chunk of LB_GRAPH_FILTER_CHUNK flat padded slots a partial from +0.0 in
+        ascending slot order, then the partials from +0.0 in ascending chunk order - no atomics.  An output not wanted is neither
+        computed nor allocated (None in its place); the float32 partials (chunks, R, C) are the only scratch (include/lbhip.h:
+        lb_graph_filter_conv_grad)."""
+        if not (want_f or want_weight):
+            return None, None
+        n = int(self.lib.lb_graph_filter_partials(self._h, int(f.shape[-1]), int(weight.shape[-1]))) if want_weight else 1
+        return self._graph_call("lb_graph_filter_conv_grad", role, (x, d, f, weight), want=(want_f, want_weight, want_weight),
+                                partials=max(n, 1))[:2]
 
     def graph_aggregate(self, role: int, msg: torch.Tensor, ops: int, eps: float, planes: int):
         """msg (B*E_cap, C) float32 or bfloat16 -> (out (B*N, planes, C) in the dtype of msg, win (B*N, 2, C) int32 or None, stats

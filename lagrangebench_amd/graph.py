@@ -24,6 +24,7 @@ describes, in the padded layout of ``features["senders"]`` / ``["receivers"]`` (
     dv = g.conv_vec(s, w, u, "senders")      # (B, N, C), (B, E_cap, C), (B, E_cap, K) -> (B, N, K, C): scalar -> vector channels,
                                              #   segment_sum((gather(s, "receivers") * w)[..., None, :] * u[..., :, None], "senders")
     ds = g.conv_dot(v, w, u, "senders")      # (B, N, K, C), ... -> (B, N, C): vector -> scalar, sum of w * <v[receivers], u>
+    ds = g.filter_conv(x, f, weight, "senders")   # f (B, E_cap, R), weight (R, C): conv(x, f @ weight, "senders") without f @ weight
 
 (with un-batched features the leading B is dropped: (N, C) -> (E_cap, C)).  Trailing dimensions beyond C are folded into C
 where the op is column-wise (all but ``attend``).
@@ -110,6 +111,30 @@ the `role` node of slot j, o(j) its other node; every product is rounded to floa
   ``differentiable_features``.
 * On bfloat16 every output, ``d_u`` included, is the float32 result on the widened inputs rounded once - not the composition
   of the bfloat16 ops.
+
+Continuous filter.  ``filter_conv(x, f, weight, role)`` is ``conv`` with the dense layer that makes its filter inside: f
+(B, E_cap, R), 1 <= R <= 32, is any per-edge basis the module computed (Gaussians of ``rel_dist`` times a cutoff; its pad slots
+may hold NaN), weight (R, C) is shared by the batch - the first graph op that takes a parameter.  Under the same contracts:
+
+* The filter ``wf[j, c] = fl32(f[j, 0] * weight[0, c]) + fl32(f[j, 1] * weight[1, c]) + ...``, r ascending, the first product
+  starts the sum - formed in registers, never stored; NOT torch's ``f @ weight``, whose order is unstated.  ``out[i, k, c]`` is
+  ``conv``'s sum of ``fl32(x[o(j), k, c] * wf[j, c])`` over the real slots of node i in ascending slot order, +0.0 for a node
+  without slots: on float32 bit for bit ``conv(x, wf, role)``.  The forward allocates its output only.
+* No bias argument: a bias is a column of f - ones, or the cutoff envelope, since ``(Linear(rbf) + b) * fcut = [rbf * fcut,
+  fcut] @ [W; b]``.
+* Backward, from x, f and weight alone; a gradient nobody asked for is neither computed nor allocated.  With ``g[j, c] =
+  fl32(x[o(j), 0, c] * d[n(j), 0, c]) + ...``, k ascending (``conv``'s ``d_w``, never stored): ``d_x = filter_conv(d, f, weight,
+  other role)``, the composition's bits; ``d_f[j, r]`` = the sum over c of ``fl32(weight[r, c] * g[j, c])`` in the blocked column
+  order of ``d_u`` above, +0.0 in the pad slots - it flows on to the window through ``differentiable_features``;
+  ``d_weight[r, c]`` = the sum over every real slot of every trajectory of ``fl32(f[j, r] * g[j, c])`` in a two-level order: the
+  flat padded slots ``b * E_cap + j`` in consecutive chunks of ``LB_GRAPH_FILTER_CHUNK`` (include/lbhip.h), per chunk a partial
+  that starts at +0.0 and takes its real slots' terms in ascending order, the total from +0.0 over the partials in ascending
+  chunk order.  No atomics, two calls the same bits, a numpy loop reproduces it.  One launch for ``d_x``, one for ``d_f``, two for
+  ``d_weight``; the float32 partials (chunks, R, C) are the only scratch.
+* bfloat16: every output, ``d_f`` and ``d_weight`` included, is the float32 result on the widened inputs rounded once; wf and g
+  stay float32, so it is not the composition of the bfloat16 ops but the more accurate of the two.  A float32 weight beside
+  bfloat16 x and f - a Parameter under ``TorchModel(autocast=torch.bfloat16)`` - is cast with a differentiable
+  ``.to(bfloat16)``, as torch casts a Linear's weight; its gradient arrives in float32.  Every other dtype mix is a ``TypeError``.
 
 bfloat16.  Every op takes float32 or bfloat16 tensors (what ``torch.autocast(dtype=torch.bfloat16)`` hands a module) and
 returns the dtype it was given.  One contract for every op and every backward:
@@ -395,6 +420,52 @@ class _ConvDot(torch.autograd.Function):
         return d_v, d_w, d_u, None, None
 
 
+_MAX_R = 32   # LB_GRAPH_MAX_R (include/lbhip.h): the weight columns of a unit live in registers
+
+
+class _FilterConv(torch.autograd.Function):
+    """filter_conv over `role`: d_x is filter_conv of the cotangent over the other role; d_f and d_weight come from the edge
+    launches of graph_filter_conv_grad.  Only x, f and weight are saved."""
+
+    @staticmethod
+    def forward(ctx, x, f, weight, graph, role):
+        e = graph.engine
+        _one_dtype("filter_conv", x, f, "x, f and weight")
+        _one_dtype("filter_conv", x, weight, "x, f and weight")
+        xf, rx = graph._flat("filter_conv", x, e.N)
+        ff, rf = graph._flat("filter_conv", f, e.e_cap)
+        ok = (isinstance(weight, torch.Tensor) and weight.dim() == 2 and len(rf) == 1 and len(rx) in (1, 2)
+              and tuple(weight.shape) == (rf[0], rx[-1]) and 1 <= rf[0] <= _MAX_R)
+        if not ok:
+            raise ValueError(f"graph.filter_conv: expected x {graph._shape(e.N) + ('C',)} or {graph._shape(e.N) + ('K', 'C')}, f "
+                             f"{graph._shape(e.e_cap) + ('R',)} and weight ('R', 'C') with 1 <= R <= {_MAX_R}, got {tuple(x.shape)}, "
+                             f"{tuple(f.shape)} and {tuple(getattr(weight, 'shape', ()))}")
+        if weight.device != e.device:
+            raise TypeError(f"graph.filter_conv: weight is on {weight.device}, the engine on {e.device}")
+        wt = weight.detach().contiguous()
+        xf = xf.reshape(e.B * e.N, -1, rx[-1])
+        out = e.graph_filter_conv(role, xf, ff, wt)
+        ctx.graph, ctx.role, ctx.rx = graph, role, rx
+        ctx.save_for_backward(xf, ff, wt)
+        return out.reshape(graph._shape(e.N) + rx)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        xf, ff, wt = ctx.saved_tensors
+        df, _ = g._flat("filter_conv", d, e.N, xf.dtype)
+        df = df.reshape(xf.shape)
+        need = ctx.needs_input_grad
+        d_x = d_f = d_weight = None
+        if need[0]:
+            d_x = e.graph_filter_conv(1 - ctx.role, df, ff, wt).reshape(g._shape(e.N) + ctx.rx)
+        if need[1] or need[2]:
+            d_f, d_weight = e.graph_filter_conv_grad(ctx.role, xf, df, ff, wt, need[1], need[2])
+            d_f = None if d_f is None else d_f.reshape(g._shape(e.e_cap) + (ff.shape[1],))
+        return d_x, d_f, d_weight, None, None
+
+
 _AGG_CODES = {"sum": 1, "mean": 2, "max": 3, "min": 4, "std": 5, "var": 6}   # LB_AGG_* (include/lbhip.h)
 
 
@@ -511,7 +582,7 @@ def differentiable_features(features, window: torch.Tensor) -> dict:
 class Graph:
     """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum and the attention
     ops (degree, segment_mean / max / min / softmax, attend), the multi-aggregator (aggregate, segment_std / var) and the edge messages (conv, pair_mul, pair_add, conv_vec,
-    conv_dot).
+    conv_dot, filter_conv).
     `batched`: whether the tensors carry the leading B (default: as the features do)."""
 
     def __init__(self, features, batched: Optional[bool] = None):
@@ -664,6 +735,21 @@ class Graph:
         nothing edge-shaped.  Equal trailing dimensions fold into C.  On bfloat16 the exact products are summed in float32 and
         the sum is rounded once: not the composition of the bfloat16 ops, which rounds every product first."""
         return _Conv.apply(x, w, self, self._role(role))
+
+    def filter_conv(self, x: torch.Tensor, f: torch.Tensor, weight: torch.Tensor, role: str) -> torch.Tensor:
+        """x (B, N, C) or (B, N, K, C), f (B, E_cap, R) with 1 <= R <= 32, weight (R, C) -> the shape of x: conv(x, wf, role) with
+        the continuous filter wf = f @ weight formed in registers - wf[j, c] = f[j, 0] * weight[0, c] + f[j, 1] * weight[1, c] +
+        ..., r ascending, every product rounded to float32, the first starts the sum (not torch's matmul, whose order is
+        unstated) - so that nothing edge-shaped of C columns exists, forward or backward.  f is any per-edge basis (Gaussians of
+        rel_dist times a cutoff); its pad slots may hold NaN.  There is no bias argument: a bias is a column of f - ones, or the
+        cutoff envelope, since (Linear(rbf) + b) * fcut = [rbf * fcut, fcut] @ [W; b].  On float32 bit for bit conv on that wf;
+        on bfloat16 the float32 result on the widened inputs, rounded once, d_f and d_weight included.  A float32 weight beside
+        bfloat16 x and f (a Parameter under autocast) is cast to bfloat16 first; its gradient arrives in float32.  The module
+        docstring states the order of every gradient sum."""
+        if (isinstance(weight, torch.Tensor) and isinstance(x, torch.Tensor) and isinstance(f, torch.Tensor)
+                and weight.dtype == torch.float32 and x.dtype == f.dtype == torch.bfloat16):
+            weight = weight.to(x.dtype)                    # differentiable: what autocast does to a Linear's weight
+        return _FilterConv.apply(x, f, weight, self, self._role(role))
 
     def conv_vec(self, x: torch.Tensor, w: torch.Tensor, u: torch.Tensor, role: str) -> torch.Tensor:
         """x (B, N, C), w (B, E_cap, C), u (B, E_cap, K) with 1 <= K <= 9 -> (B, N, K, C), scalar to vector channels: per node
