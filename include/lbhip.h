@@ -953,6 +953,32 @@ int lb_graph_aggregate_backward(lb_engine* eng, int32_t role, const void* d_out_
                                 const void* msg_dev /*(B*E_cap,C) or NULL*/, const int32_t* win_dev /*(B*N,2,C) or NULL*/,
                                 const float* stats_dev /*(B*N,2,C) or NULL*/, void* d_msg_dev /*(B*E_cap,C)*/, int32_t C,
                                 int32_t ops, int32_t dtype);
+/* ---- edge pairs: an edge beside its transpose -----
+ * The rules of the graph ops hold (the padded layout, pads never read, +0.0 in the pad slots of edge-shaped outputs, no atomics,
+ * two calls the same bits, int64 addresses).
+ * reverse: out (B*E_cap) int32.  For the real slot j of (receiver r, sender s) the slot, within its trajectory, of the edge
+ *   (receiver s, sender r) of the same trajectory; a self-edge maps to itself; -1 where the list holds no such edge (the periodic
+ *   displacement is antisymmetric only up to one rounding, so a pair at the cutoff can be an edge in one direction only) and -1
+ *   in every pad slot.  So out[out[j]] == j wherever out[j] >= 0.  The engine builds the map at its first use after a list
+ *   build - one edge-parallel launch that bisects the sender's CSR row (a row holds a sender at most once), nothing read back,
+ *   independent of the sender view - keeps it in its arena and copies it out here.
+ * edge_pair_t: msg, out (B*E_cap, C), out != msg; p(j) = reverse[j]:
+ *   LB_GRAPH_PAIR_SWAP     out[j, c] = msg[p(j), c], a bit copy;
+ *   LB_GRAPH_PAIR_SYM      out[j, c] = fl32(msg[j, c] + msg[p(j), c]);
+ *   LB_GRAPH_PAIR_ANTISYM  out[j, c] = fl32(msg[j, c] - msg[p(j), c]);
+ *   a slot without a partner (p(j) = -1) gets +0.0 in every mode - an edge without its transpose takes no part, so the result is
+ *   an exactly symmetric / antisymmetric edge field on every list -, and so does every pad slot.  A self-edge: fl32(m + m), and
+ *   +0.0 for a finite m under ANTISYM.  Each mode is its own adjoint (ANTISYM: d_msg = ANTISYM(d_out), the two signs cancel), so
+ *   the backward is the same call on the cotangent.  LB_DTYPE_BF16: round_to_bf16(the fp32 op(upcast inputs)), rounded once;
+ *   SWAP copies the 16 bits.  16-byte accesses when C % 4 == 0 (bf16: C % 8 == 0) and both pointers are 16-byte aligned.
+ * LB_ERR_ARG on a null pointer, a mode or dtype other than those named, C < 1, out == msg; LB_ERR_STATE without a list or with an
+ *   overflowed one. */
+#define LB_GRAPH_PAIR_SWAP 0
+#define LB_GRAPH_PAIR_SYM 1
+#define LB_GRAPH_PAIR_ANTISYM 2
+int lb_graph_reverse(lb_engine* eng, int32_t* out_dev /*(B*E_cap)*/);
+int lb_graph_edge_pair_t(lb_engine* eng, int32_t mode, const void* msg_dev /*(B*E_cap,C)*/, void* out_dev /*(B*E_cap,C)*/,
+                         int32_t C, int32_t dtype);
 /* d loss / d window from the cotangents of the features a TorchModel module receives (graph.differentiable_features), on the
  * engine's CURRENT window and list: the transpose of the feature builder.  Every input may be NULL (= zero).  fp32 inputs in the
  * layouts of TorchModel's feature dict; the edge-shaped ones in the padded slot layout of lb_nl_read_idx, whose pad slots are

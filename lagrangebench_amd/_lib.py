@@ -231,6 +231,9 @@ _SIGS = {
     "lb_graph_conv": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_pair_mul": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_pair_add": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32]),
+    # edge pairs: the reverse map (out (B E_cap) int32); swap / symmetrize / antisymmetrize (mode, msg, out, C, dtype)
+    "lb_graph_reverse": (C.c_int, [_P, _P]),
+    "lb_graph_edge_pair_t": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32]),
     # equivariant vector messages: (x | v, w, u, out); the edge gradients (S, V, w, u, d_w or null, d_u or null)
     "lb_graph_conv_vec": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
     "lb_graph_conv_dot": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32]),

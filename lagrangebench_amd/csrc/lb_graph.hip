@@ -9,7 +9,8 @@
 // messages") the fused lb_graph_conv and the edge-shaped lb_graph_pair_mul / lb_graph_pair_add, and the equivariant couplings
 // through a per-edge vector, lb_graph_conv_vec / lb_graph_conv_dot with lb_graph_conv_vec_edge_grad; the continuous-filter
 // convolution with its Linear inside, lb_graph_filter_conv with lb_graph_filter_conv_grad; the multi-aggregator
-// lb_graph_aggregate (sum, mean, max, min, std, var of one message from one walk) with its backward; and lb_graph_features_backward
+// lb_graph_aggregate (sum, mean, max, min, std, var of one message from one walk) with its backward; the reverse-edge map
+// lb_graph_reverse with swap / symmetrize / antisymmetrize on it, lb_graph_edge_pair_t ("edge pairs"); and lb_graph_features_backward
 // ("feature transpose"): d loss / d window from the cotangents of the features such a network was handed.
 //
 // All work in the PADDED layout of lb_nl_read_idx: slot (b, j), j < n_edges[b], is compact edge row_ptr[b N] + j of the engine's
@@ -706,6 +707,84 @@ __global__ void __launch_bounds__(256) k_graph_pair_add(lb_glist L, const int32_
                                                         const int32_t* __restrict__ bidx, const T* __restrict__ a,
                                                         const T* __restrict__ b, T* __restrict__ out) {
   graph_pair_body<T, W, false, false>(L, aidx, bidx, a, b, out, 1);
+}
+
+// ---- edge pairs: an edge (s -> r) beside its transpose (r -> s).
+// The reverse map, rev (B E_cap) int32: for the real slot of (receiver r, sender s) the slot j' within its trajectory of the edge
+// (receiver s, sender r), -1 where the list does not hold that edge (tests/_asym.py) and in every pad slot; a self-edge maps to
+// itself.  One lane per padded slot bisects the CSR row of its sender for its receiver - the arithmetic of k_sender_transpose
+// (lb_sender_view.h); a row holds a sender at most once (lb_neighbor.hip: a receiver meets every particle of its stencil once), so
+// the first position whose sender is >= r is the only candidate - and turns the compact edge it finds into a padded slot as
+// lb_row::edge does: k - row_ptr[b N], here refused (-1) rather than clamped when it falls outside the trajectory's own real
+// slots, which a valid list never does.  By construction rev[rev[j]] == j wherever rev[j] >= 0.  No flag, no atomics.
+__global__ void __launch_bounds__(256) k_graph_reverse(lb_glist L, const int32_t* __restrict__ senders,
+                                                       const int32_t* __restrict__ receivers, int32_t* __restrict__ rev) {
+  const int64_t rows = (int64_t)L.B * L.e_cap;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < rows; q += (int64_t)gridDim.x * 256) {
+    const lb_gslot t = graph_slot(L, q, receivers, senders);   // node: the receiver r, other: the sender s (both clamped)
+    int32_t found = -1;
+    if (t.real) {
+      const int r = (int)t.node, s = (int)t.other;
+      int lo = L.row_ptr[s], hi = L.row_ptr[s + 1];   // first position of row s whose sender is >= r
+      hi = hi < L.E ? hi : L.E;
+      lo = lo < 0 ? 0 : lo;
+      const int end = hi;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (senders[mid] < r) lo = mid + 1; else hi = mid;
+      }
+      if (lo < end && senders[lo] == r) {
+        const int base = t.k - t.j, jr = lo - base;   // the trajectory's first compact edge; the transpose's slot within it
+        int nb = L.row_ptr[(int64_t)(q / L.e_cap + 1) * L.N] - base;
+        nb = nb < L.e_cap ? nb : L.e_cap;
+        if (jr >= 0 && jr < nb) found = jr;
+      }
+    }
+    rev[q] = found;
+  }
+}
+
+// swap / symmetrize / antisymmetrize, one kernel with a mode: out[slot][:] = msg[partner][:] (a bit copy), fl32(msg[slot][:] +
+// msg[partner][:]) or fl32(msg[slot][:] - msg[partner][:]) for a real slot whose rev entry names a partner; +0.0 for a slot
+// without one and for every pad.  Edge-parallel in the shape of the pair ops: a lane group per padded slot, one scattered row
+// read (the partner's) beside the streamed one.  rev is -1 in the pads, so a pad slot of msg is never read; the partner of a real
+// slot is a real slot of the same trajectory (v < E_cap is checked: no address leaves the tensor).
+struct lb_gpartner {
+  bool paired;
+  int64_t q;   // the partner's padded slot, flat over the batch
+};
+template <typename T, int W, int MODE>
+__global__ void __launch_bounds__(256) k_graph_edge_pair(lb_glist L, const int32_t* __restrict__ idx,
+                                                         const int32_t* __restrict__ rev, const T* __restrict__ msg,
+                                                         T* __restrict__ out) {
+  const int U = L.U;
+  graph_for(
+      L, (int64_t)L.B * L.e_cap,
+      [&](int64_t r) {
+        const lb_gslot t = graph_slot(L, r, idx);
+        const int v = t.real ? rev[r] : -1;
+        const bool paired = v >= 0 && v < L.e_cap;
+        return lb_gpartner{paired, r - t.j + (paired ? v : 0)};
+      },
+      [&](int64_t r, const lb_gpartner& p, int u) {
+        if constexpr (MODE == LB_GRAPH_PAIR_SWAP) {   // the bits as they are: 16 bytes of either element type, or one element
+          using V = std::conditional_t<(W > 1), f32x4, T>;
+          const V* __restrict__ ms = reinterpret_cast<const V*>(msg);
+          V* __restrict__ os = reinterpret_cast<V*>(out);
+          os[r * U + u] = p.paired ? ms[p.q * U + u] : V{};
+        } else {
+          float s[W], fa[W], fb[W];
+#pragma unroll
+          for (int c = 0; c < W; ++c) s[c] = 0.f;
+          if (p.paired) {
+            lb_ld<T, W>(msg + (r * U + u) * W, fa);
+            lb_ld<T, W>(msg + (p.q * U + u) * W, fb);
+#pragma unroll
+            for (int c = 0; c < W; ++c) s[c] = MODE == LB_GRAPH_PAIR_SYM ? __fadd_rn(fa[c], fb[c]) : __fsub_rn(fa[c], fb[c]);
+          }
+          lb_st<T, W>(out + (r * U + u) * W, s);
+        }
+      });
 }
 
 // conv_vec and conv_dot: the scalar <-> vector couplings of an equivariant layer through a per-edge vector u (B E_cap, K), K <= 9
@@ -2093,6 +2172,47 @@ extern "C" int lb_graph_pair_add(lb_engine* e, int32_t a_role, const void* a_dev
     using T = decltype(t);
     graph_launch(e, P.blocks, k_graph_pair_add<T, decltype(w)::value>, P.L, P.idx, P.oidx, (const T*)a_dev, (const T*)b_dev,
                  (T*)out_dev);
+  });
+}
+
+// ---- edge pairs.  The reverse map of the current list -> e->rev (B E_cap): built at its first use after a list build, keyed on
+// nl_gen and E_cap as the sender view is (whose buffers and flag it does not touch); one launch, nothing read back.
+static int graph_reverse_map(lb_engine* e) {
+  if (e->rev_seen && e->rev_gen == e->nl_gen && e->rev_ecap == e->e_cap) return LB_OK;
+  const int64_t rows = (int64_t)e->g.B * e->e_cap;
+  e->rev_seen = false;
+  if (rows > e->rev_cap)
+    LB_TRY(lb_regrow(e->stream, &e->rev_cap, rows, [&](int64_t n) { return e->mem.get(&e->rev, (size_t)n); }));
+  hipLaunchKernelGGL(k_graph_reverse, dim3(graph_blocks1(rows)), dim3(256), 0, e->stream, graph_list(e, 0, 0), e->senders,
+                     e->receivers, e->rev);
+  LB_HIP(hipGetLastError());
+  e->rev_gen = e->nl_gen;
+  e->rev_ecap = e->e_cap;
+  e->rev_seen = true;
+  return LB_OK;
+}
+
+extern "C" int lb_graph_reverse(lb_engine* e, int32_t* out_dev) {
+  LB_TRY(graph_entry(e, "lb_graph_reverse", 0, LB_DTYPE_F32, out_dev != nullptr, 1, 1, false));
+  LB_TRY(graph_reverse_map(e));
+  LB_HIP(hipMemcpyAsync(out_dev, e->rev, sizeof(int32_t) * (size_t)e->g.B * (size_t)e->e_cap, hipMemcpyDeviceToDevice, e->stream));
+  return LB_OK;
+}
+
+extern "C" int lb_graph_edge_pair_t(lb_engine* e, int32_t mode, const void* msg_dev, void* out_dev, int32_t C, int32_t dtype) {
+  LB_TRY(graph_entry(e, "lb_graph_edge_pair_t", 0, dtype, msg_dev && out_dev, C, 1, false));   // edge-parallel: no sender view
+  if (mode < LB_GRAPH_PAIR_SWAP || mode > LB_GRAPH_PAIR_ANTISYM)
+    return lb_fail(LB_ERR_ARG, "lb_graph_edge_pair_t: mode %d (0 swap, 1 symmetrize, 2 antisymmetrize)", mode);
+  if (msg_dev == out_dev) return lb_fail(LB_ERR_ARG, "lb_graph_edge_pair_t: out must not be msg (a slot reads its partner's row)");
+  LB_TRY(graph_reverse_map(e));
+  const lb_gplan P = graph_plan(e, 0, dtype, LB_SLOTS, C, C, false, {msg_dev, out_dev});
+  return graph_dispatch(dtype, P.W, [&](auto t, auto w) {
+    using T = decltype(t);
+    constexpr int W = decltype(w)::value;
+    auto kernel = mode == LB_GRAPH_PAIR_SWAP ? k_graph_edge_pair<T, W, LB_GRAPH_PAIR_SWAP>
+                  : mode == LB_GRAPH_PAIR_SYM ? k_graph_edge_pair<T, W, LB_GRAPH_PAIR_SYM>
+                                              : k_graph_edge_pair<T, W, LB_GRAPH_PAIR_ANTISYM>;
+    graph_launch(e, P.blocks, kernel, P.L, P.idx, (const int32_t*)e->rev, (const T*)msg_dev, (T*)out_dev);
   });
 }
 

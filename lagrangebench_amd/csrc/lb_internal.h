@@ -202,6 +202,11 @@ struct lb_engine {
   int64_t snd_cap = 0;
   bool snd_radix = false;
   int32_t snd_sorts = 0;                             // sender views built by the radix sort
+  bool rev_seen = false;                             // the reverse-edge map below is that of build rev_gen under rev_ecap
+  uint64_t rev_gen = 0;
+  int32_t rev_ecap = 0;
+  int32_t* rev = nullptr;                            // [rev_cap] per padded slot the slot of its transposed edge, -1 without one
+  int64_t rev_cap = 0;
   float* graph_t = nullptr;                          // [graph_t_cap] fp32 t (B E_cap, H) of a bf16 lb_graph_attend_backward_t
   int64_t graph_t_cap = 0;
 

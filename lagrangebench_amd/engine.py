@@ -61,6 +61,8 @@ def _graph_ops():
         "lb_graph_conv": ("lb_graph_conv", ((nkc, None), (sc, None)), ((nkc, None),), ("K", "C")),
         "lb_graph_pair_mul": ("lb_graph_pair_mul", ((nkc, None), (nkc, None)), ((sc, None),), ("K", "C")),
         "lb_graph_pair_add": ("lb_graph_pair_add", ((nc, None), (nc, None)), ((sc, None),), ("C",)),
+        "lb_graph_reverse": ("lb_graph_reverse", (), ((("slots",), i32),), ()),
+        "lb_graph_edge_pair": ("lb_graph_edge_pair_t", ((sc, None),), ((sc, None),), ("C",)),   # (`role` carries the mode)
         "lb_graph_conv_vec": ("lb_graph_conv_vec", ((nc, None), (sc, None), (sk, None)), ((nkc, None),), ("K", "C")),
         "lb_graph_conv_dot": ("lb_graph_conv_dot", ((nkc, None), (sc, None), (sk, None)), ((nc, None),), ("K", "C")),
         "lb_graph_conv_vec_edge_grad": ("lb_graph_conv_vec_edge_grad", ((nc, None), (nkc, None), (sc, None), (sk, None)),
@@ -654,6 +656,19 @@ class RolloutEngine:
         """a, b (B*N, C), one dtype -> (B*E_cap, C): a[the slot's `a_role` node] + b[its other node] in the real slots, one
         float32 add, +0.0 in the pad slots (include/lbhip.h: lb_graph_pair_add)."""
         return self._graph_call("lb_graph_pair_add", a_role, (a, b))
+
+    def graph_reverse(self) -> torch.Tensor:
+        """-> (B*E_cap,) int32: per padded slot of the current list the slot, within its trajectory, of the transposed edge
+        (receiver and sender exchanged); a self-edge maps to itself; -1 where the list holds no such edge and in every pad slot.
+        The engine builds the map once per list build, in one launch, and keeps it; this is a copy (include/lbhip.h:
+        lb_graph_reverse)."""
+        return self._graph_call("lb_graph_reverse", None)
+
+    def graph_edge_pair(self, mode: int, msg: torch.Tensor) -> torch.Tensor:
+        """msg (B*E_cap, C) float32 or bfloat16 -> (B*E_cap, C), with p the reverse map: mode 0 msg[p] (a bit copy), 1
+        msg + msg[p], 2 msg - msg[p] - one float32 operation, bfloat16 rounded once; +0.0 in a slot without a partner and in
+        the pad slots, which are never read (include/lbhip.h: lb_graph_edge_pair_t)."""
+        return self._graph_call("lb_graph_edge_pair", mode, (msg,))
 
     def graph_conv_vec(self, role: int, x: torch.Tensor, w: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
         """x (B*N, C), w (B*E_cap, C), u (B*E_cap, K), 1 <= K <= 9, one dtype (float32 or bfloat16) -> (B*N, K, C): per node

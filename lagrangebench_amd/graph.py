@@ -26,6 +26,10 @@ describes, in the padded layout of ``features["senders"]`` / ``["receivers"]`` (
     ds = g.conv_dot(v, w, u, "senders")      # (B, N, K, C), ... -> (B, N, C): vector -> scalar, sum of w * <v[receivers], u>
     ds = g.filter_conv(x, f, weight, "senders")   # f (B, E_cap, R), weight (R, C): conv(x, f @ weight, "senders") without f @ weight
 
+    g.reverse                                # (B, E_cap) int32: the slot of the transposed edge (r -> s) of slot (s -> r), -1 without one
+    t = g.swap(msg)                          # (B, E_cap, C) -> (B, E_cap, C): msg[reverse]
+    m = g.antisymmetrize(msg)                # ... msg - msg[reverse]: m_ij = -m_ji exactly; symmetrize: msg + msg[reverse]
+
 (with un-batched features the leading B is dropped: (N, C) -> (E_cap, C)).  Trailing dimensions beyond C are folded into C
 where the op is column-wise (all but ``attend``).
 
@@ -135,6 +139,31 @@ may hold NaN), weight (R, C) is shared by the batch - the first graph op that ta
   stay float32, so it is not the composition of the bfloat16 ops but the more accurate of the two.  A float32 weight beside
   bfloat16 x and f - a Parameter under ``TorchModel(autocast=torch.bfloat16)`` - is cast with a differentiable
   ``.to(bfloat16)``, as torch casts a Linear's weight; its gradient arrives in float32.  Every other dtype mix is a ``TypeError``.
+
+Edge pairs.  Every op above sees an edge (s -> r) alone; ``reverse``, ``swap``, ``symmetrize`` and ``antisymmetrize`` relate it to
+its transpose (r -> s) - pairwise forces with ``F_ij = -F_ji`` (linear momentum conserved by construction), symmetric edge
+features, edge states that read the opposite edge's - under the same contracts (pad slots never read, +0.0 in every pad slot of a
+result or gradient, no atomics, two calls the same bits):
+
+* ``reverse`` is (B, E_cap) int32: for the real slot j of (receiver r, sender s) the slot, within its trajectory, of the edge
+  (receiver s, sender r); a self-edge maps to itself; -1 where the list holds no such edge, and -1 in every pad slot.  The
+  displacement is antisymmetric only up to one rounding, so a pair at the cutoff can be an edge in one direction only: the
+  map says which, and ``reverse[reverse[j]] == j`` wherever ``reverse[j] >= 0``.  The engine builds it in one launch at its first
+  use after a list build - each slot bisects the sorted CSR row of its sender for its receiver - and keeps it; the property is
+  a copy, cached per features version.  Nothing is read back, and the sender view is not involved.
+* ``swap(msg)[j] = msg[reverse[j]]``, a bit copy; ``symmetrize(msg)[j] = fl32(msg[j] + msg[reverse[j]])``;
+  ``antisymmetrize(msg)[j] = fl32(msg[j] - msg[reverse[j]])`` - one float32 operation, no rounding for ``swap``.  msg is
+  (B, E_cap, C); trailing dimensions fold into C.
+* The unpaired rule: a slot without a partner (``reverse[j] == -1``) gets +0.0 from all three - an edge without its transpose takes
+  no part - so the result is an exactly symmetric (``out[reverse] == out`` in bits) or antisymmetric (``out[reverse] == -out``) edge
+  field on every list, one-directional ones included.  Who wants another rule has ``reverse`` and ``swap``.
+* The self-edge rule: a self-edge is its own partner: ``swap`` copies it, ``symmetrize`` gives ``fl32(m + m)``, ``antisymmetrize``
+  gives +0.0 for a finite m (NaN for an infinite or NaN one).
+* Backward: each op is its own adjoint - the two signs of ``antisymmetrize`` cancel - so the gradient of msg is the same op applied
+  to the cotangent: the same kernel, the same bits.  Nothing is saved but the graph.
+* bfloat16: ``round_to_bf16(float32 op(upcast))``, rounded once; ``swap`` copies the 16 bits.
+* There is no fused "symmetrize, then segment_sum": as a set of terms it is ``segment_sum(msg, "receivers") + segment_sum(msg,
+  "senders")``, which the library already does node-shaped.
 
 bfloat16.  Every op takes float32 or bfloat16 tensors (what ``torch.autocast(dtype=torch.bfloat16)`` hands a module) and
 returns the dtype it was given.  One contract for every op and every backward:
@@ -338,6 +367,29 @@ class _Pair(torch.autograd.Function):
                 out = e.graph_segment_sum(role, df)
             grads[k] = out.reshape(g._shape(e.N) + ctx.rest)
         return grads[0], grads[1], None, None
+
+
+_SWAP, _SYM, _ANTISYM = 0, 1, 2   # LB_GRAPH_PAIR_* (include/lbhip.h)
+_PAIR_NAMES = ("swap", "symmetrize", "antisymmetrize")
+
+
+class _EdgePair(torch.autograd.Function):
+    """swap / symmetrize / antisymmetrize: each is its own adjoint, so the backward is the forward on the cotangent.  Nothing is
+    saved but the graph."""
+
+    @staticmethod
+    def forward(ctx, msg, graph, mode):
+        e = graph.engine
+        flat, rest = graph._flat(_PAIR_NAMES[mode], msg, e.e_cap)
+        ctx.graph, ctx.mode, ctx.dtype = graph, mode, flat.dtype
+        return e.graph_edge_pair(mode, flat).reshape(graph._shape(e.e_cap) + rest)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d):
+        g, e = ctx.graph, ctx.graph.engine
+        flat, rest = g._flat(_PAIR_NAMES[ctx.mode], d, e.e_cap, ctx.dtype)
+        return e.graph_edge_pair(ctx.mode, flat).reshape(g._shape(e.e_cap) + rest), None, None
 
 
 _MAX_K = 9   # LB_GRAPH_MAX_K (csrc/lb_graph.hip): u rows are read as scalars into registers
@@ -582,7 +634,7 @@ def differentiable_features(features, window: torch.Tensor) -> dict:
 class Graph:
     """The engine's current list behind `features` (a FeatureDict), as differentiable gather / segment_sum and the attention
     ops (degree, segment_mean / max / min / softmax, attend), the multi-aggregator (aggregate, segment_std / var) and the edge messages (conv, pair_mul, pair_add, conv_vec,
-    conv_dot, filter_conv).
+    conv_dot, filter_conv), and the edge pairs (reverse, swap, symmetrize, antisymmetrize).
     `batched`: whether the tensors carry the leading B (default: as the features do)."""
 
     def __init__(self, features, batched: Optional[bool] = None):
@@ -595,6 +647,7 @@ class Graph:
         if not self.batched and engine.B != 1:
             raise ValueError(f"graph.Graph: un-batched tensors on an engine of batch {engine.B}")
         self._idx = None
+        self._rev = None
 
     # ------------------------------------------------------------------ the list
     def _check_fresh(self, what: str) -> None:
@@ -622,6 +675,17 @@ class Graph:
     @property
     def senders(self) -> torch.Tensor:
         return self._lead(self._export()[0][:, 1])
+
+    @property
+    def reverse(self) -> torch.Tensor:
+        """(B, E_cap) int32: for the real slot of (receiver r, sender s) the slot, within its trajectory, of the edge (receiver s,
+        sender r); a self-edge maps to itself; -1 where the list holds no such edge (an edge in one direction only) and in every
+        pad slot.  reverse[reverse[j]] == j wherever reverse[j] >= 0.  Built by the engine in one launch per list build; read
+        once per Graph.  No autograd."""
+        self._check_fresh("reverse")
+        if self._rev is None:
+            self._rev = self.engine.graph_reverse().reshape(self._shape(self.engine.e_cap))
+        return self._rev
 
     # ------------------------------------------------------------------ the ops
     @staticmethod
@@ -775,3 +839,24 @@ class Graph:
         """a, b (B, N, C) -> (B, E_cap, C): a[senders] + b[receivers] in the real slots, +0.0 in the pad slots - the edge
         Linear of cat[x_s, x_r, e] as (x W_s)[senders] + (x W_r)[receivers] + e W_e, with the GEMMs on N rows."""
         return _Pair.apply(a, b, self, False)
+
+    def swap(self, msg: torch.Tensor) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, E_cap, C): msg[reverse[j]] in slot j, a bit copy - what the opposite edge holds.  +0.0 in a
+        slot without a partner and in the pad slots.  Its own adjoint: the backward is swap of the cotangent."""
+        return _EdgePair.apply(msg, self, _SWAP)
+
+    def symmetrize(self, msg: torch.Tensor) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, E_cap, C): fl32(msg[j] + msg[reverse[j]]), so that out[reverse] == out bit for bit.  A slot
+        whose edge has no transpose in the list gets +0.0 - it takes no part, which keeps the field exactly symmetric on a list
+        with one-directional edges; another rule can be written with `reverse` and `swap`.  A self-edge gives fl32(m + m).  Pad
+        slots are +0.0 and never read.  bfloat16: the float32 sum of the widened values, rounded once.  Its own adjoint.  There is
+        no fused symmetrize-then-segment_sum: as a set of terms it is segment_sum(msg, "receivers") + segment_sum(msg, "senders")."""
+        return _EdgePair.apply(msg, self, _SYM)
+
+    def antisymmetrize(self, msg: torch.Tensor) -> torch.Tensor:
+        """msg (B, E_cap, C) -> (B, E_cap, C): fl32(msg[j] - msg[reverse[j]]), so that out[reverse] == -out exactly - a pairwise
+        force with F_ij = -F_ji, whose segment_sum over receivers conserves linear momentum up to the rounding of the row sums.
+        A slot whose edge has no transpose in the list gets +0.0 (it takes no part; see symmetrize), and so does a self-edge
+        with a finite value.  Pad slots are +0.0 and never read.  Its own adjoint: the backward is antisymmetrize of the
+        cotangent."""
+        return _EdgePair.apply(msg, self, _ANTISYM)
