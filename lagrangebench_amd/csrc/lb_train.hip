@@ -70,41 +70,57 @@ static bool lb_train_f16x2_default() {
   return !(m && (m[0] == 'f' && m[1] == '3'));
 }
 
+struct lb_gns_train;
+// What the shared frame knows about the model a handle trains: one constant record per model, defined in the model's section
+// (gns_model below, segnn_model / egnn_model / linear_model / painn_model in the lb_train_*.h), t->model points to it.
+// "Is this my handle" is t->model == &the record.
+struct lb_train_model {
+  const char* name;         // for messages: "GNS", "SEGNN", ...
+  const char* loss_entry;   // the entry name its fused loss + gradient step reports to train_step_begin
+  bool f16x2;               // may run the f16x2 products (lb_train_exact_math(t, 0) gives them back)
+  bool window_grad;         // its backward can also form d loss / d window
+  bool acc_loss;            // trains on the masked _mse of a (B*N, dim) target (train_loss); false: a loss of its own
+  void (*free)(lb_gns_train* t);                         // the model's state behind the handle (its buffers are the arena's)
+  int (*ensure)(lb_gns_train* t, int64_t BN, int64_t E);  // scratch for BN nodes / E edges, through train_ensure
+  // between the frame's begin + ensure and the pred copy-out: the network with what its backward needs kept.  *pred comes in
+  // as t->pred; a model whose prediction lies elsewhere points it there
+  int (*forward)(lb_gns_train* t, const float** pred);
+  // between the forward and the frame's end, from d loss / d pred where the model's loss leaves it (t->dy unless dpred_load
+  // says otherwise); dpos_out_dev != null (window_grad models only): also d loss / d window
+  int (*backward)(lb_gns_train* t, double* dpos_out_dev);
+  // lb_train_backward: the caller's d loss / d pred (t->dsave, BN x dim) into the buffer `backward` starts from; null: a plain
+  // copy into t->dy
+  int (*dpred_load)(lb_gns_train* t);
+};
+
+struct lb_gnt;  // GNS-specific state of a training handle (the GNS section below)
 struct lb_sgt;  // SEGNN-specific state of a training handle (lb_train_segnn.h)
 struct lb_egt;  // EGNN-specific state of a training handle (lb_train_egnn.h)
-struct lb_linear;  // lb_linear.hip
+struct lb_lnt;  // Linear-specific state of a training handle (lb_train_linear.h)
 struct lb_pnt;  // PaiNN-specific state of a training handle (lb_train_painn.h)
 
+// The handle: what the frame or at least two models use.  Everything one model alone needs is behind its state pointer.
+// (t->tmax, the sender view and the f16x2 site state are written by the shared product / sort helpers on behalf of GNS and
+// SEGNN; pred / dy / dsave are allocated by each model's ensure because their order in the arena is the model's.)
 struct lb_gns_train {
-  lb_arena mem;           // owns every device / pinned buffer of the handle, those of t->sg / t->eg included
-  lb_sgt* sg = nullptr;   // non-null: this handle trains a SEGNN (created by lb_segnn_train_create)
-  lb_egt* eg = nullptr;   // non-null: this handle trains an EGNN (created by lb_egnn_train_create)
-  lb_linear* ln = nullptr;  // non-null: this handle trains a Linear (lb_linear_train_create): the inference view of t->w
-  lb_linear_desc ln_desc{};
-  lb_pnt* pa = nullptr;   // non-null: this handle trains a PaiNN (created by lb_painn_train_create)
-  bool blob = false;      // lb_blob_train_create: optimiser state only (w / g / m / v of n_floats), no model behind it
-  lb_gns_desc desc;
+  lb_arena mem;           // owns every device / pinned buffer of the handle, those of the model's state included
+  const lb_train_model* model = nullptr;  // null: lb_blob_train_create - optimiser state only (w / g / m / v of n_floats)
+  lb_gnt* gn = nullptr;   // the state of the one model the handle trains (set by its create, touched by its section only)
+  lb_sgt* sg = nullptr;
+  lb_egt* eg = nullptr;
+  lb_lnt* ln = nullptr;
+  lb_pnt* pa = nullptr;
   lb_engine* eng;
   int64_t n_floats = 0;   // floats of the DEVICE blobs (latent padded to 128)
   int64_t n_compact = 0;  // floats of the caller's blob (GNS.flatten with the model's latent size)
   int64_t n_frozen = 0;   // the last n_frozen floats of the blobs are not parameters: AdamW leaves them alone (PaiNN's
                           // radial basis with gaussian_rbf(trainable=False))
-  int lat = TD;           // the model's latent size (<= 128)
   std::vector<int64_t> cmap;  // caller index -> device index (empty: identity, latent 128)
   float *w = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;  // weights, gradients, AdamW moments
-  int64_t off_embed = 0;
-  lb_train_mlp enc_node, enc_edge, dec;
-  std::vector<lb_train_mlp> pe, pn;
-  int nin = 0, kpad = 0;
   int64_t step = 0;
   // scratch of every model is sized for cap_n nodes / cap_e edges (train_ensure)
   int64_t cap_n = 0, cap_e = 0;
-  float *xnode = nullptr, *a_en = nullptr, *z_en = nullptr, *a_ee = nullptr, *z_ee = nullptr;
-  std::vector<float*> nlat, elat;            // [L+1] node / edge latents entering layer k
-  std::vector<float*> ae, ze, xn, an, zn;  // per layer: post-ReLU hidden, pre-LayerNorm output; node block: concat input
-  float *a_d = nullptr, *pred = nullptr;
-  float *dn = nullptr, *de = nullptr, *dy = nullptr, *dz = nullptr, *da = nullptr, *dx = nullptr, *dagg = nullptr;
-  float* agg = nullptr;
+  float *pred = nullptr, *dy = nullptr;   // the prediction and d loss / d pred (B*N x dim)
   // partial sums of every gradient reduction of a step (k_dw_part / k_dw_narrow / k_ln_bwd2 / k_colsum_part): one slot per
   // producer, summed in one k_part_reduce launch at the end of the backward pass
   float* dwpart = nullptr;
@@ -112,7 +128,6 @@ struct lb_gns_train {
   std::vector<lb_red_ent> red_tab;
   lb_red_ent *red_host = nullptr, *red_dev = nullptr;  // pinned staging copy / device table
   int red_blocks = 0;
-  float* proj = nullptr;     // edge block: [n W_s ; n W_r] (2 x cap_n x 128), reused for their gradients
   float* node_w = nullptr;   // per node loss weight (0 for kinematic particles)
   double* loss_dev = nullptr;
   double* loss_part = nullptr;  // one partial per wave of k_mse_grad
@@ -142,11 +157,6 @@ struct lb_gns_train {
   // exponents of the sites that fired and repeats the step in f16x2.  A site whose chunks do not fit one window (it fires
   // again right after a re-centring) switches to per-chunk scaling inside the kernel (dw_xdyn[c]: one more pass over its
   // X slice).
-  // MLP depth (round 6: any num_mlp_layers >= 2, models/utils.py:100-115): a block keeps nlin - 1 hidden activations, the
-  // first at its `a` pointer, the next ones hs_n / hs_e floats further on (node- / edge-sized blocks)
-  int nlin = 2;
-  int64_t hs_n = 0, hs_e = 0;
-  float* da2 = nullptr;         // second d(hidden) buffer: the middle Linears' backward ping-pongs between da and da2
   int32_t* dw_flag = nullptr;   // [1 + LB_DW_CALLS], behind loss_dev (bit 4 of [0]: k_sender_transpose met an edge without its transpose)
   int32_t dw_fallbacks = 0;     // steps repeated because of the guard
   int32_t sort_fallbacks = 0;   // steps repeated with the radix sort (guard bit 4: an edge without its transpose)
@@ -160,14 +170,12 @@ struct lb_gns_train {
   lb_pack_ent_h* pack_dev_h = nullptr;
   float* wsc = nullptr;
   // The step split at d loss / d pred (lb_train_forward / lb_train_backward): the edge and node counts of the step between
-  // its two parts, whether a forward's activations are still those of the engine's window, the caller's d loss / d pred
-  // (pads zeroed; what a repeated attempt starts from again) and, for d loss / d window, the gradient of the edge features
+  // its two parts, whether a forward's activations are still those of the engine's window, and the caller's d loss / d pred
+  // (pads zeroed; what a repeated attempt starts from again)
   bool fwd_live = false;
   bool fwd_f16x2 = false;       // the arithmetic lb_train_forward ran in (a repeated attempt of the backward re-runs it so)
   int64_t fwd_E = 0, fwd_BN = 0;
-  bool want_dx = false;         // this step's backward also forms d xnode (t->dx) and d efeat (t->dxe)
   float* dsave = nullptr;       // [cap_n][4]
-  float* dxe = nullptr;         // [cap_e][8], the stride of lb_engine::efeat (GNS)
 };
 #define LB_PACK_MAX 1024
 
@@ -1235,6 +1243,11 @@ static void red_push(lb_gns_train* t, int64_t part, int G, int64_t stride, int n
   t->red_tab.push_back(d);
   t->red_blocks += (n0 + n1 + RED_OUT - 1) / RED_OUT;
 }
+static void red_reset(lb_gns_train* t) {   // an empty table, every slot free
+  t->red_tab.clear();
+  t->red_off = 0;
+  t->red_blocks = 0;
+}
 static int red_flush(lb_gns_train* t) {
   const size_t n = t->red_tab.size();
   if (n) {
@@ -1244,30 +1257,17 @@ static int red_flush(lb_gns_train* t) {
     hipLaunchKernelGGL(k_part_reduce, dim3((unsigned)t->red_blocks), dim3(1024), 0, s, t->dwpart, t->red_dev, (int)n, t->g,
                        t->dw_flag);
   }
-  t->red_tab.clear();
-  t->red_off = 0;
-  t->red_blocks = 0;
+  red_reset(t);
   return LB_OK;
 }
-// floats of partial-sum slots a step needs for BN <= cn nodes and E <= ce edges (mirrors the backward pass below)
-static int64_t red_capacity(const lb_gns_train* t, int64_t cn, int64_t ce) {
-  auto slot = [](int64_t rows, int K) { return (dw_groups_max(std::max<int64_t>(rows, 1)) * (K + 1) * 128 + 63) / 64 * 64; };
-  auto lnp = [](int64_t rows) { return ((rows + LNB_ROWS - 1) / LNB_ROWS * 256 + 63) / 64 * 64 + 64; };
-  const int L = t->desc.num_mp_steps;
-  int64_t tot = 0;
-  tot += (int64_t)L * (2 * slot(ce, 128) + 3 * slot(cn, 128) + slot(cn, 256) + lnp(ce) + lnp(cn));  // processor blocks
-  tot += slot(cn, 128) + slot(cn, std::max(128, t->kpad)) + lnp(cn);                             // node encoder
-  tot += 2 * slot(ce, 128) + lnp(ce);                                                            // edge encoder
-  tot += 2 * slot(cn, 128) + (cn + 127) / 128 * 128 + 64;                                        // decoder (narrow dW, column sums)
-  const int64_t mid = t->nlin - 2;                                                               // middle Linears of every block
-  tot += mid * ((int64_t)L * (slot(ce, 128) + slot(cn, 128)) + 2 * slot(cn, 128) + slot(ce, 128));
-  return tot + 4096;
-}
+// Every producer below is followed by the floats of partial-sum slot it takes for at most rows_cap rows: what a model's
+// ensure adds up, launch by launch of its backward pass, for t->red_cap (red_slot hands out multiples of 64 floats).
+static int64_t red_round(int64_t floats) { return (floats + 63) / 64 * 64; }
 // dW[K x 128] += X^T dY, db[128] += column sums of dY (k_dw_part + a descriptor for k_part_reduce); false = refused
 // (nb: how many of dY's 128 column sums are added to db - the SEGNN blocks keep only their Ms scalar-output columns)
 // dY_b / dW_b (dw_acc_pair): a second product X^T dY_b -> dW_b (no bias) in the same launch - f16x2 kernel only
 static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx, const float* dY, float* dW, float* db,
-                   int nb, const float* tmax, const float* dY_b, float* dW_b) {
+                   int nb = 128, const float* tmax = nullptr, const float* dY_b = nullptr, float* dW_b = nullptr) {
   // (every refusal leaves its reason in lb_last_error - ADVICE r05: callers return a bare LB_ERR_STATE)
   if (K > 384 || rows <= 0) {
     (void)lb_fail(LB_ERR_STATE, "dw_acc: K = %d (<= 384) / rows = %lld (> 0) out of range", K, (long long)rows);
@@ -1311,6 +1311,9 @@ static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx
   if (part_b) red_push(t, off_b, G, (int64_t)(K + 1) * 128, K * 128, 0, K * 128, dW_b, nullptr);
   return true;
 }
+static int64_t dw_acc_floats(int64_t rows_cap, int K) {   // (one product; a paired launch takes two)
+  return red_round(dw_groups_max(std::max<int64_t>(rows_cap, 1)) * (K + 1) * 128);
+}
 // dW_a += X^T dY_a and dW_b += X^T dY_b: one launch on the f16x2 kernel, two otherwise
 static bool dw_acc_pair(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx, const float* dY_a, float* dW_a,
                         const float* dY_b, float* dW_b) {
@@ -1333,6 +1336,7 @@ static int dw_narrow(lb_gns_train* t, int64_t rows, int M, int K, const float* X
   red_push(t, off, G, (int64_t)K * M, K * M, 0, 0, dW, nullptr);
   return LB_OK;
 }
+static int64_t dw_narrow_floats(int64_t rows_cap, int K, int M) { return red_round(dw_groups_max(rows_cap) * K * M); }
 // out[cols] += column sums of x (k_colsum_part: fixed blocks of 128 rows, summed in block order by k_part_reduce)
 static int colsum_add(lb_gns_train* t, const float* x, int64_t rows, int cols, int ld, float* out) {
   if (rows == 0) return LB_OK;
@@ -1344,6 +1348,7 @@ static int colsum_add(lb_gns_train* t, const float* x, int64_t rows, int cols, i
   red_push(t, off, nb, 128, cols, 0, 0, out, nullptr);
   return LB_OK;
 }
+static int64_t colsum_floats(int64_t rows_cap) { return (rows_cap + 127) / 128 * 128 + 64; }   // (+ 64 spare)
 
 // gembed[type][emb] += the rows of dx[:, col0 : col0 + emb] of that type (k_embed_grad: adds nothing under a raised guard)
 static void embed_grad_acc(lb_gns_train* t, const float* dx, int ld, int col0, int emb, const int32_t* ptype, int ntypes,
@@ -1352,68 +1357,6 @@ static void embed_grad_acc(lb_gns_train* t, const float* dx, int ld, int col0, i
                      t->dw_flag);
 }
 
-static int mlp_fwd_tail(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, float* a, float* z, const float* resid, float* y,
-                        float* y2);
-// forward of one MLP block: X (rows x in, ldx) -> a = relu(X W0 + b0) -> z = a W1 + b1 -> [LayerNorm (+ resid)] -> y
-// the middle Linears of a block: a_{m+1} = relu(a_m Wm + bm), hidden m at a + m * stride
-static int mlp_mid_fwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, float* a, int64_t stride) {
-  for (size_t m = 0; m < p.wm.size(); ++m)
-    LB_TRY(gemm_nn(t, rows, TD, TD, a + m * stride, TD, t->w + p.wm[m], a + (m + 1) * stride, TD, 0.f, t->w + p.bm[m], 1));
-  return LB_OK;
-}
-// ... and their backward.  In: t->da = d(last hidden), ReLU-masked; out: t->da = d(first hidden), masked (the two buffers swap)
-static bool dw_acc(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx, const float* dY, float* dW, float* db,
-                   int nb = 128, const float* tmax = nullptr, const float* dY_b = nullptr, float* dW_b = nullptr);
-static bool dw_acc_pair(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx, const float* dY_a, float* dW_a,
-                        const float* dY_b, float* dW_b);
-static int mlp_mid_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* a, int64_t stride) {
-  for (size_t m = p.wm.size(); m-- > 0;) {
-    const float* ain = a + m * stride;  // input of middle Linear m
-    LB_TRY(gemm_nt(t, rows, TD, TD, t->da, t->w + p.wm[m], t->da2, TD, 0.f, 0, ain, TD, t->tmax));  // ReLU mask of ain
-    if (!dw_acc(t, rows, TD, ain, TD, t->da, t->g + p.wm[m], t->g + p.bm[m], 128, t->tmax_ok ? t->tmax : nullptr))
-      return lb_fail(LB_ERR_STATE, "dw_acc refused a middle Linear");
-    std::swap(t->da, t->da2);
-  }
-  t->tmax_ok = false;
-  return LB_OK;
-}
-static int mlp_fwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* X, int ldx, float* a, float* z,
-                   const float* resid, float* y, int64_t stride) {
-  hipStream_t s = t->eng->stream;
-  (void)s;
-  LB_TRY(gemm_nn(t, rows, TD, p.in, X, ldx, t->w + p.w0, a, TD, 0.f, t->w + p.b0, 1));  // bias + ReLU in the epilogue
-  LB_TRY(mlp_mid_fwd(t, p, rows, a, stride));
-  float* al = a + p.wm.size() * stride;
-  return resid ? mlp_fwd_tail(t, p, rows, al, z, resid, nullptr, y) : mlp_fwd_tail(t, p, rows, al, z, nullptr, y, nullptr);
-}
-// forward of the edge block (gns.py:86-101) without the concatenated input (see k_edge_dP's comment)
-// y = e' = LN(MLP([n_s | n_r | e])) (the message), el_next = e + e' (the next edge latent)
-static int edge_fwd(lb_gns_train* t, const lb_train_mlp& p, int64_t E, int64_t BN, const float* n, const float* el, float* a,
-                    float* z, float* y, float* el_next) {
-  hipStream_t s = t->eng->stream;
-  lb_engine* e = t->eng;
-  float *Ps = t->proj, *Pr = t->proj + (size_t)BN * TD;
-  LB_TRY(gemm_nn_pair(t, BN, TD, n, TD, t->w + p.w0, Ps, t->w + p.w0 + (size_t)TD * TD, Pr, TD));
-  {  // a = relu(e W_e + Ps[snd] + Pr[rcv] + b0): the gathers and the bias ride in the product's epilogue
-    lb_lin_args g{};
-    g.X = el; g.ldx = TD; g.NR = TD; g.Y = a; g.ldy = TD; g.NO = TD; g.rows = E;
-    g.bias = t->w + p.b0; g.gat1 = Ps; g.gidx1 = e->senders; g.gat2 = Pr; g.gidx2 = e->receivers;
-    LB_TRY(lin32(t, g, t->w + p.w0 + (size_t)2 * TD * TD, TD, 0));
-  }
-  LB_TRY(mlp_mid_fwd(t, p, E, a, t->hs_e));
-  return mlp_fwd_tail(t, p, E, a + p.wm.size() * t->hs_e, z, el, y, el_next);
-}
-// y = LN(...) (may be null), y2 = resid + y (may be null); without LayerNorm (decoder): y = a W1 + b1
-static int mlp_fwd_tail(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, float* a, float* z, const float* resid,
-                        float* y, float* y2) {
-  hipStream_t s = t->eng->stream;
-  (void)s;
-  if (!p.ln) return gemm_nn(t, rows, p.out, TD, a, TD, t->w + p.w1, y, p.out, 0.f, t->w + p.b1, 0);
-  // second Linear with the LayerNorm in its epilogue: z = a W1 (kept without the bias for the backward), y = LN(z + b1),
-  // y2 = resid + y (round 4: k_ln_fwd and, in the edge block, k_add2 were launches of their own over the same arrays)
-  lb_ln_epi ln{t->w + p.lns, t->w + p.lno, resid, y, y2, t->lat};
-  return gemm_nn(t, rows, TD, TD, a, TD, t->w + p.w1, z, TD, 0.f, t->w + p.b1, 0, &ln);
-}
 // LayerNorm backward of `rows` rows of width d (k_ln_bwd2): dz = d loss / d z from dy (+ gth[gidx], the gathered aggregate
 // gradient), the scale / offset gradients accumulated into g_lns / g_lno through the ordered reduce
 static int ln_bwd_acc(lb_gns_train* t, int64_t rows, const float* z, const float* b1, const float* sc, const float* dy, float* dz,
@@ -1430,59 +1373,7 @@ static int ln_bwd_acc(lb_gns_train* t, int64_t rows, const float* z, const float
   red_push(t, off, nb, 256, 128, 128, 128, g_lns, g_lno);
   return LB_OK;
 }
-// backward of one MLP block.  dy: gradient w.r.t. the block's output BEFORE the residual add (rows x out);
-// produces parameter gradients (accumulated) and, if dX != null, dX (rows x in, ld = ldx).  Scratch: t->dz, t->da.
-// first part (shared with the edge block): LayerNorm and second Linear backward, ReLU mask -> t->da = d loss / d (X W0 + b0)
-static int mlp_bwd_head(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* a, const float* z, const float* dy,
-                        const float* gth = nullptr, const int32_t* gidx = nullptr) {
-  if (rows == 0) return LB_OK;
-  const float* dzz = dy;
-  if (p.ln) {
-    LB_TRY(ln_bwd_acc(t, rows, z, t->w + p.b1, t->w + p.lns, dy, t->dz, t->lat, gth, gidx, t->g + p.lns, t->g + p.lno));
-    dzz = t->dz;
-  }
-  // dX first: k_lin32h leaves the row-tile maxima of dzz behind, which the weight-gradient kernel scales by
-  LB_TRY(gemm_nt(t, rows, p.out, TD, dzz, t->w + p.w1, t->da, TD, 0.f, 0, a, TD, t->tmax));  // ReLU mask in the epilogue
-  if (p.out != TD || !dw_acc(t, rows, TD, a, TD, dzz, t->g + p.w1, t->g + p.b1, 128, t->tmax_ok ? t->tmax : nullptr)) {
-    LB_TRY(dw_narrow(t, rows, p.out, TD, a, TD, dzz, p.out, t->g + p.w1));
-    LB_TRY(colsum_add(t, dzz, rows, p.out, p.out, t->g + p.b1));
-  }
-  return LB_OK;
-}
-static int mlp_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* X, int ldx, const float* a,
-                   const float* z, const float* dy, float* dX, int64_t stride) {
-  if (rows == 0) return LB_OK;
-  LB_TRY(mlp_bwd_head(t, p, rows, a + p.wm.size() * stride, z, dy));
-  LB_TRY(mlp_mid_bwd(t, p, rows, a, stride));
-  t->tmax_ok = false;
-  if (dX) LB_TRY(gemm_nt(t, rows, TD, p.in, t->da, t->w + p.w0, dX, ldx, 0.f, 0, nullptr, 0, t->tmax));
-  if (!dw_acc(t, rows, p.in, X, ldx, t->da, t->g + p.w0, t->g + p.b0, 128, t->tmax_ok ? t->tmax : nullptr))
-    return lb_fail(LB_ERR_UNSUPPORTED, "training: first Linear with %d inputs (row stride %d) is not covered", p.in, ldx);
-  return LB_OK;
-}
-
-// backward of the edge block: parameter gradients, de += d loss / d e_k, dn += the node-side terms (see k_edge_dP)
-static int edge_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t E, int64_t BN, const float* n, const float* el,
-                    const float* a, const float* z, const float* dagg, float* de, float* dn) {
-  if (E == 0) return LB_OK;
-  hipStream_t s = t->eng->stream;
-  lb_engine* e = t->eng;
-  // e' feeds agg (gather of dagg over the receivers) and e_{k+1} = e_k + e' (de): d e' = de + dagg[rcv], formed in the load
-  LB_TRY(mlp_bwd_head(t, p, E, a + p.wm.size() * t->hs_e, z, de, dagg, e->receivers));  // -> t->da (E x 128)
-  LB_TRY(mlp_mid_bwd(t, p, E, a, t->hs_e));
-  const float *Ws = t->w + p.w0, *Wr = Ws + (size_t)TD * TD, *We = Wr + (size_t)TD * TD;
-  float *gWs = t->g + p.w0, *gWr = gWs + (size_t)TD * TD, *gWe = gWr + (size_t)TD * TD;
-  // edge rows: dW_e += e^T da, db0 += column sums of da, de += da W_e^T
-  LB_TRY(gemm_nt(t, E, TD, TD, t->da, We, de, TD, 1.f, 0, nullptr, 0, t->tmax));
-  if (!dw_acc(t, E, TD, el, TD, t->da, gWe, t->g + p.b0, 128, t->tmax_ok ? t->tmax : nullptr))
-    return lb_fail(LB_ERR_STATE, "dw_acc refused the edge block");
-  // node rows: dP = transpose of the two gathers, then dW_s += n^T dPs, dW_r += n^T dPr, dn += dPs W_s^T + dPr W_r^T
-  float *dPs = t->proj, *dPr = t->proj + (size_t)BN * TD;
-  hipLaunchKernelGGL(k_edge_dP, GRID1(BN * 32), 0, s, t->da, t->snd_ptr, t->snd_perm, e->row_ptr, dPs, dPr, BN, E);
-  if (!dw_acc_pair(t, BN, TD, n, TD, dPs, gWs, dPr, gWr)) return lb_fail(LB_ERR_STATE, "dw_acc refused the edge block");
-  (void)Wr;
-  return gemm_nt_stack2(t, BN, dPs, (int64_t)BN * TD, Ws, dn);
-}
+static int64_t ln_bwd_floats(int64_t rows_cap) { return red_round((rows_cap + LNB_ROWS - 1) / LNB_ROWS * 256) + 64; }   // (+ 64 spare)
 
 // Scratch for BN nodes and E edges - the frame every model shares: the capacity test, the growth rule (edges with head
 // room: the list changes from step to step) and the training core's own buffers.  model(cn, ce, cm) allocates the model's
@@ -1503,45 +1394,6 @@ static int train_ensure(lb_gns_train* t, int64_t BN, int64_t E, F model) {
     LB_TRY(t->mem.get(&t->dsave, (size_t)cn * 4));
     LB_TRY(t->mem.get(&t->loss_part, (size_t)(cn / 64 + 8)));
     t->cap_e = ce;
-    return LB_OK;
-  });
-}
-static int gns_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
-  return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t cm) -> int {
-    const int L = t->desc.num_mp_steps;
-    const size_t nh = (size_t)(t->nlin - 1);   // hidden activations kept per block
-    t->hs_n = cn * TD;
-    t->hs_e = ce * TD;
-    LB_TRY(t->mem.get(&t->xnode, (size_t)cn * t->kpad));
-    LB_TRY(t->mem.get(&t->a_en, nh * cn * TD));
-    LB_TRY(t->mem.get(&t->z_en, (size_t)cn * TD));
-    LB_TRY(t->mem.get(&t->a_ee, nh * ce * TD));
-    LB_TRY(t->mem.get(&t->z_ee, (size_t)ce * TD));
-    for (int k = 0; k <= L; ++k) {
-      LB_TRY(t->mem.get(&t->nlat[k], (size_t)cn * TD));
-      LB_TRY(t->mem.get(&t->elat[k], (size_t)ce * TD));
-    }
-    for (int k = 0; k < L; ++k) {
-      LB_TRY(t->mem.get(&t->ae[k], nh * ce * TD));
-      LB_TRY(t->mem.get(&t->ze[k], (size_t)ce * TD));
-      LB_TRY(t->mem.get(&t->xn[k], (size_t)cn * 2 * TD));
-      LB_TRY(t->mem.get(&t->an[k], nh * cn * TD));
-      LB_TRY(t->mem.get(&t->zn[k], (size_t)cn * TD));
-    }
-    LB_TRY(t->mem.get(&t->a_d, nh * cn * TD));
-    LB_TRY(t->mem.get(&t->pred, (size_t)cn * 4));
-    LB_TRY(t->mem.get(&t->dn, (size_t)cn * TD));
-    LB_TRY(t->mem.get(&t->de, (size_t)ce * TD));
-    LB_TRY(t->mem.get(&t->dy, (size_t)cm * TD));
-    LB_TRY(t->mem.get(&t->dz, (size_t)cm * TD));
-    LB_TRY(t->mem.get(&t->da, (size_t)cm * TD));
-    if (t->nlin > 2) LB_TRY(t->mem.get(&t->da2, (size_t)cm * TD));
-    LB_TRY(t->mem.get(&t->dx, (size_t)cn * std::max(3 * TD, t->kpad)));
-    LB_TRY(t->mem.get(&t->dagg, (size_t)cn * TD));
-    LB_TRY(t->mem.get(&t->agg, (size_t)cn * TD));
-    LB_TRY(t->mem.get(&t->proj, (size_t)cn * 2 * TD));
-    LB_TRY(t->mem.get(&t->dxe, (size_t)ce * 8));
-    t->red_cap = red_capacity(t, cn, ce);
     return LB_OK;
   });
 }
@@ -1601,100 +1453,6 @@ static int train_sender_sort(lb_gns_train* t, int64_t E, int64_t BN) {
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
-// The layout of a GNS training handle's blobs for description d (no HIP call): the offsets of every MLP in the device
-// blob, its float count (t->n_floats), the caller blob's (t->n_compact) and the index map between them (t->cmap)
-static void gns_train_layout(lb_gns_train* t, const lb_gns_desc* d) {
-  const int L = d->num_mp_steps;
-  const bool has_emb = d->num_particle_types > 1;
-  const int emb = has_emb ? d->embedding_size : 0;
-  t->desc = *d;
-  t->nlin = d->blocks_per_step;
-  const int nmid = t->nlin - 2;
-  t->nin = d->node_in + emb;
-  t->kpad = (t->nin + 31) / 32 * 32;
-  int64_t o = 0;
-  t->off_embed = 0;
-  if (has_emb) o += (int64_t)d->num_particle_types * emb;
-  auto mlp = [&](int in, int outw, bool ln) {
-    lb_train_mlp p{};
-    p.in = in;
-    p.out = outw;
-    p.ln = ln;
-    p.w0 = o; o += (int64_t)in * TD;
-    p.b0 = o; o += TD;
-    for (int m = 0; m < nmid; ++m) {   // GNS.flatten order: linear_0, linear_1, ..., LayerNorm
-      p.wm.push_back(o); o += (int64_t)TD * TD;
-      p.bm.push_back(o); o += TD;
-    }
-    p.w1 = o; o += (int64_t)TD * outw;
-    p.b1 = o; o += outw;
-    if (ln) {
-      p.lns = o; o += outw;
-      p.lno = o; o += outw;
-    }
-    return p;
-  };
-  t->enc_node = mlp(t->nin, TD, true);
-  t->enc_edge = mlp(d->edge_in, TD, true);
-  for (int k = 0; k < L; ++k) {
-    t->pe.push_back(mlp(3 * TD, TD, true));
-    t->pn.push_back(mlp(2 * TD, TD, true));
-  }
-  t->dec = mlp(TD, d->out_dim, false);
-  // Latents narrower than 128 (round 4; GNS-5-64 of docs/pages/baselines.rst): the device blobs keep the 128-wide layout with
-  // zeros in the padded rows / columns - they stay zero under the step (a padded hidden unit is relu(0) = 0, so its weight
-  // gradients vanish; padded LayerNorm columns are masked in k_ln_bwd2; AdamW of (w, g, m, v) = 0 is 0) - and the caller's
-  // blob (GNS.flatten with the model's latent size) is scattered into / gathered from it through an index map.
-  const int lat = d->latent_size;
-  t->lat = lat;
-  int64_t oc = has_emb ? (int64_t)d->num_particle_types * emb : 0;
-  if (lat != TD) t->cmap.reserve((size_t)o);
-  for (int64_t i = 0; i < oc && lat != TD; ++i) t->cmap.push_back(i);  // embedding table: as is
-  auto map_mlp = [&](const lb_train_mlp& p, int in_c, int nblk, int out_c) {
-    // in_c caller rows of w0: nblk blocks of `lat` latent rows (row j of block q -> device row 128 q + j), or plain rows (nblk 0)
-    if (lat != TD) {
-      for (int r = 0; r < in_c; ++r) {
-        const int rp = nblk ? (r / lat) * TD + (r % lat) : r;
-        for (int c = 0; c < lat; ++c) t->cmap.push_back(p.w0 + (int64_t)rp * TD + c);
-      }
-      for (int c = 0; c < lat; ++c) t->cmap.push_back(p.b0 + c);
-      for (size_t m = 0; m < p.wm.size(); ++m) {
-        for (int r = 0; r < lat; ++r)
-          for (int c = 0; c < lat; ++c) t->cmap.push_back(p.wm[m] + (int64_t)r * TD + c);
-        for (int c = 0; c < lat; ++c) t->cmap.push_back(p.bm[m] + c);
-      }
-      for (int r = 0; r < lat; ++r)
-        for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.w1 + (int64_t)r * p.out + c);
-      for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.b1 + c);
-      if (p.ln) {
-        for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.lns + c);
-        for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.lno + c);
-      }
-    }
-    oc += (int64_t)in_c * lat + lat + (int64_t)p.wm.size() * ((int64_t)lat * lat + lat) + (int64_t)lat * out_c + out_c +
-          (p.ln ? 2 * out_c : 0);
-  };
-  map_mlp(t->enc_node, t->nin, 0, lat);
-  map_mlp(t->enc_edge, d->edge_in, 0, lat);
-  for (int k = 0; k < L; ++k) {
-    map_mlp(t->pe[k], 3 * lat, 3, lat);
-    map_mlp(t->pn[k], 2 * lat, 2, lat);
-  }
-  map_mlp(t->dec, lat, 1, d->out_dim);
-  t->n_floats = o;
-  t->n_compact = oc;
-}
-int lb_gns_train_padded_map(const lb_gns_desc* d, std::vector<int64_t>* cmap, int64_t* n_dev, int64_t* n_compact) {
-  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
-    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
-  lb_gns_train t;
-  gns_train_layout(&t, d);
-  cmap->swap(t.cmap);
-  *n_dev = t.n_floats;
-  *n_compact = t.n_compact;
-  return LB_OK;
-}
-
 // The rest of a handle's construction, once its create has filled the layout (n_floats, n_compact, cmap): the four blobs,
 // the small buffers of every step, and the caller's weights (`what`, for the message) scattered through cmap into the device
 // layout; gradients and moments start at zero.  The caller destroys the handle on failure.
@@ -1718,29 +1476,11 @@ static int train_handle_init(lb_gns_train* t, const char* what, const float* w, 
   for (float* p : {t->g, t->m, t->v}) LB_HIP(hipMemset(p, 0, sizeof(float) * o));
   return LB_OK;
 }
-
-extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats,
-                                   lb_gns_train** out) {
-  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
-    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
-  if (d->out_dim != e->g.dim || d->node_in != e->g.node_in || d->edge_in != e->g.dim + 1)
-    return lb_fail(LB_ERR_ARG, "model widths do not match the case");
-  lb_gns_train* t = new lb_gns_train();
-  t->eng = e;
-  gns_train_layout(t, d);
-  const int L = d->num_mp_steps;
-  t->nlat.assign(L + 1, nullptr);
-  t->elat.assign(L + 1, nullptr);
-  t->ae.assign(L, nullptr); t->ze.assign(L, nullptr);
-  t->xn.assign(L, nullptr); t->an.assign(L, nullptr); t->zn.assign(L, nullptr);
-  const int rc = train_handle_init(t, "weight blob", w, n_floats);
-  if (rc) {
-    lb_gns_train_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return LB_OK;
+// the tail of every create: rc is what the construction came to - the handle goes to the caller, or is destroyed
+static int train_create_finish(lb_gns_train* t, int rc, lb_gns_train** out) {
+  if (rc) lb_gns_train_destroy(t);
+  else *out = t;
+  return rc;
 }
 
 // A training handle with no model in it (lagrangebench_amd/models/torch_model.py: the network and its loss are torch's):
@@ -1753,33 +1493,18 @@ extern "C" int lb_blob_train_create(lb_engine* e, const float* w, int64_t n_floa
   if (n_floats < 1) return lb_fail(LB_ERR_ARG, "lb_blob_train_create: %lld floats", (long long)n_floats);
   lb_gns_train* t = new lb_gns_train();
   t->eng = e;
-  t->blob = true;
   t->f16x2 = false;
-  t->desc = lb_gns_desc{};
   t->n_floats = t->n_compact = n_floats;
-  const int rc = train_handle_init(t, "weight blob", w, n_floats);
-  if (rc) {
-    lb_gns_train_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return LB_OK;
+  return train_create_finish(t, train_handle_init(t, "weight blob", w, n_floats), out);
 }
 static int blob_refuse(const char* entry) {
   return lb_fail(LB_ERR_UNSUPPORTED, "%s: a blob training handle (lb_blob_train_create) holds optimiser state only - the model, "
                  "its forward and its loss are the caller's", entry);
 }
 
-static void sgt_free(lb_gns_train* t);
-static void egt_free(lb_gns_train* t);
-static void lnt_free(lb_gns_train* t);
-static void pnt_free(lb_gns_train* t);
 extern "C" void lb_gns_train_destroy(lb_gns_train* t) {
   if (!t) return;
-  sgt_free(t);
-  egt_free(t);
-  lnt_free(t);
-  pnt_free(t);
+  if (t->model) t->model->free(t);
   delete t;  // (t->mem frees the buffers)
 }
 
@@ -1846,9 +1571,7 @@ static int train_step_begin(lb_gns_train* t, const char* entry, int64_t* E, int6
   *E = e->ctrl_host->n_edges_total;
   *BN = e->BN;
   pack_all(t);
-  t->red_tab.clear();
-  t->red_off = 0;
-  t->red_blocks = 0;
+  red_reset(t);
   return LB_OK;
 }
 // End: every weight / bias / LayerNorm gradient, partials -> gradient blob in one launch; the loss and the guard flag behind
@@ -1859,72 +1582,375 @@ static int train_step_end(lb_gns_train* t) {
   LB_HIP(hipMemcpyAsync(status_loss(t), t->loss_dev, sizeof(double) + sizeof(int32_t), hipMemcpyDeviceToHost, t->eng->stream));
   return LB_OK;
 }
-
-// value_and_grad of _mse, summed over the batch (trainer.py:63-89), on the engine's CURRENT window / neighbor list.
-// target_dev: (B*N, dim) fp32 normalised accelerations.  Gradients ACCUMULATE into the gradient blob (zero it with
-// lb_gns_train_zero_grad); *loss_out = mean over the batch of the per-trajectory losses (host-synchronous).
-// The step in two parts, split at d loss / d pred (a plain (B*N, dim) fp32 buffer, t->dy).  Forward part: the frame's begin,
-// scratch, features, the network with saved activations -> t->pred (and pred_out_dev).
-static int gns_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
-  lb_engine* e = t->eng;
-  hipStream_t s = e->stream;
+// The step in two parts over the model's record, split at d loss / d pred.  Forward part: the frame's begin, the model's
+// scratch, its network with saved activations, the prediction (and a copy in pred_out_dev)
+static int train_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
   int64_t E = 0, BN = 0;
   LB_TRY(train_step_begin(t, entry, &E, &BN));
   t->fwd_E = E;
   t->fwd_BN = BN;
-  const int L = t->desc.num_mp_steps, dim = t->desc.out_dim;
-  LB_TRY(gns_ensure(t, BN, E));
-  const bool has_emb = t->desc.num_particle_types > 1;
-  const int emb = has_emb ? t->desc.embedding_size : 0;
+  LB_TRY(t->model->ensure(t, BN, E));
+  const float* pred = t->pred;
+  LB_TRY(t->model->forward(t, &pred));
+  if (pred_out_dev)
+    LB_HIP(hipMemcpyAsync(pred_out_dev, pred, sizeof(float) * BN * t->eng->g.dim, hipMemcpyDeviceToDevice, t->eng->stream));
+  return LB_OK;
+}
+// Backward part: the model's hand-written backward, the frame's end
+static int train_backward_part(lb_gns_train* t, double* dpos_out_dev) {
+  LB_TRY(t->model->backward(t, dpos_out_dev));
+  return train_step_end(t);
+}
+// value_and_grad of _mse, summed over the batch (trainer.py:63-89), on the engine's CURRENT window / neighbor list, for every
+// model with acc_loss.  target_dev: (B*N, dim) fp32 normalised accelerations.  Gradients ACCUMULATE into the gradient blob
+// (zero it with lb_gns_train_zero_grad); *loss_out = mean over the batch of the per-trajectory losses (host-synchronous).
+// (Only the f16x2 models and their sender view can raise the guard: for the others the loop is one attempt.)
+static int train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out, float* pred_out_dev) {
+  t->fwd_live = false;
+  return train_loss_grad_guarded(t, loss_out, [&] {
+    LB_TRY(train_forward_part(t, t->model->loss_entry, pred_out_dev));
+    LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));   // loss and d loss / d pred
+    return train_backward_part(t, nullptr);
+  });
+}
+
+// ------------------------------------------------------------------------------------------------ GNS
+struct lb_gnt {
+  lb_gns_desc desc;
+  int lat = TD;           // the model's latent size (<= 128)
+  int64_t off_embed = 0;
+  lb_train_mlp enc_node, enc_edge, dec;
+  std::vector<lb_train_mlp> pe, pn;
+  int nin = 0, kpad = 0;
+  // MLP depth (round 6: any num_mlp_layers >= 2, models/utils.py:100-115): a block keeps nlin - 1 hidden activations, the
+  // first at its `a` pointer, the next ones hs_n / hs_e floats further on (node- / edge-sized blocks)
+  int nlin = 2;
+  int64_t hs_n = 0, hs_e = 0;
+  float *xnode = nullptr, *a_en = nullptr, *z_en = nullptr, *a_ee = nullptr, *z_ee = nullptr;
+  std::vector<float*> nlat, elat;            // [L+1] node / edge latents entering layer k
+  std::vector<float*> ae, ze, xn, an, zn;  // per layer: post-ReLU hidden, pre-LayerNorm output; node block: concat input
+  float* a_d = nullptr;
+  float *dn = nullptr, *de = nullptr, *dz = nullptr, *da = nullptr, *dx = nullptr, *dagg = nullptr, *agg = nullptr;
+  float* da2 = nullptr;      // second d(hidden) buffer: the middle Linears' backward ping-pongs between da and da2
+  float* proj = nullptr;     // edge block: [n W_s ; n W_r] (2 x cap_n x 128), reused for their gradients
+  float* dxe = nullptr;      // d loss / d efeat for d loss / d window: [cap_e][8], the stride of lb_engine::efeat
+};
+
+// forward of one MLP block: X (rows x in, ldx) -> a = relu(X W0 + b0) -> z = a W1 + b1 -> [LayerNorm (+ resid)] -> y
+// its tail: y = LN(...) (may be null), y2 = resid + y (may be null); without LayerNorm (decoder): y = a W1 + b1
+static int mlp_fwd_tail(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, float* a, float* z, const float* resid,
+                        float* y, float* y2) {
+  if (!p.ln) return gemm_nn(t, rows, p.out, TD, a, TD, t->w + p.w1, y, p.out, 0.f, t->w + p.b1, 0);
+  // second Linear with the LayerNorm in its epilogue: z = a W1 (kept without the bias for the backward), y = LN(z + b1),
+  // y2 = resid + y (round 4: k_ln_fwd and, in the edge block, k_add2 were launches of their own over the same arrays)
+  lb_ln_epi ln{t->w + p.lns, t->w + p.lno, resid, y, y2, t->gn->lat};
+  return gemm_nn(t, rows, TD, TD, a, TD, t->w + p.w1, z, TD, 0.f, t->w + p.b1, 0, &ln);
+}
+// the middle Linears of a block: a_{m+1} = relu(a_m Wm + bm), hidden m at a + m * stride
+static int mlp_mid_fwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, float* a, int64_t stride) {
+  for (size_t m = 0; m < p.wm.size(); ++m)
+    LB_TRY(gemm_nn(t, rows, TD, TD, a + m * stride, TD, t->w + p.wm[m], a + (m + 1) * stride, TD, 0.f, t->w + p.bm[m], 1));
+  return LB_OK;
+}
+// ... and their backward.  In: g->da = d(last hidden), ReLU-masked; out: g->da = d(first hidden), masked (the two buffers swap)
+static int mlp_mid_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* a, int64_t stride) {
+  lb_gnt* g = t->gn;
+  for (size_t m = p.wm.size(); m-- > 0;) {
+    const float* ain = a + m * stride;  // input of middle Linear m
+    LB_TRY(gemm_nt(t, rows, TD, TD, g->da, t->w + p.wm[m], g->da2, TD, 0.f, 0, ain, TD, t->tmax));  // ReLU mask of ain
+    if (!dw_acc(t, rows, TD, ain, TD, g->da, t->g + p.wm[m], t->g + p.bm[m], 128, t->tmax_ok ? t->tmax : nullptr))
+      return lb_fail(LB_ERR_STATE, "dw_acc refused a middle Linear");
+    std::swap(g->da, g->da2);
+  }
+  t->tmax_ok = false;
+  return LB_OK;
+}
+static int mlp_fwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* X, int ldx, float* a, float* z,
+                   const float* resid, float* y, int64_t stride) {
+  LB_TRY(gemm_nn(t, rows, TD, p.in, X, ldx, t->w + p.w0, a, TD, 0.f, t->w + p.b0, 1));  // bias + ReLU in the epilogue
+  LB_TRY(mlp_mid_fwd(t, p, rows, a, stride));
+  float* al = a + p.wm.size() * stride;
+  return resid ? mlp_fwd_tail(t, p, rows, al, z, resid, nullptr, y) : mlp_fwd_tail(t, p, rows, al, z, nullptr, y, nullptr);
+}
+// forward of the edge block (gns.py:86-101) without the concatenated input (see k_edge_dP's comment)
+// y = e' = LN(MLP([n_s | n_r | e])) (the message), el_next = e + e' (the next edge latent)
+static int edge_fwd(lb_gns_train* t, const lb_train_mlp& p, int64_t E, int64_t BN, const float* n, const float* el, float* a,
+                    float* z, float* y, float* el_next) {
+  lb_engine* e = t->eng;
+  lb_gnt* g = t->gn;
+  float *Ps = g->proj, *Pr = g->proj + (size_t)BN * TD;
+  LB_TRY(gemm_nn_pair(t, BN, TD, n, TD, t->w + p.w0, Ps, t->w + p.w0 + (size_t)TD * TD, Pr, TD));
+  {  // a = relu(e W_e + Ps[snd] + Pr[rcv] + b0): the gathers and the bias ride in the product's epilogue
+    lb_lin_args ga{};
+    ga.X = el; ga.ldx = TD; ga.NR = TD; ga.Y = a; ga.ldy = TD; ga.NO = TD; ga.rows = E;
+    ga.bias = t->w + p.b0; ga.gat1 = Ps; ga.gidx1 = e->senders; ga.gat2 = Pr; ga.gidx2 = e->receivers;
+    LB_TRY(lin32(t, ga, t->w + p.w0 + (size_t)2 * TD * TD, TD, 0));
+  }
+  LB_TRY(mlp_mid_fwd(t, p, E, a, g->hs_e));
+  return mlp_fwd_tail(t, p, E, a + p.wm.size() * g->hs_e, z, el, y, el_next);
+}
+// backward of one MLP block.  dy: gradient w.r.t. the block's output BEFORE the residual add (rows x out);
+// produces parameter gradients (accumulated) and, if dX != null, dX (rows x in, ld = ldx).  Scratch: g->dz, g->da.
+// first part (shared with the edge block): LayerNorm and second Linear backward, ReLU mask -> g->da = d loss / d (X W0 + b0)
+static int mlp_bwd_head(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* a, const float* z, const float* dy,
+                        const float* gth = nullptr, const int32_t* gidx = nullptr) {
+  if (rows == 0) return LB_OK;
+  lb_gnt* g = t->gn;
+  const float* dzz = dy;
+  if (p.ln) {
+    LB_TRY(ln_bwd_acc(t, rows, z, t->w + p.b1, t->w + p.lns, dy, g->dz, g->lat, gth, gidx, t->g + p.lns, t->g + p.lno));
+    dzz = g->dz;
+  }
+  // dX first: k_lin32h leaves the row-tile maxima of dzz behind, which the weight-gradient kernel scales by
+  LB_TRY(gemm_nt(t, rows, p.out, TD, dzz, t->w + p.w1, g->da, TD, 0.f, 0, a, TD, t->tmax));  // ReLU mask in the epilogue
+  if (p.out != TD || !dw_acc(t, rows, TD, a, TD, dzz, t->g + p.w1, t->g + p.b1, 128, t->tmax_ok ? t->tmax : nullptr)) {
+    LB_TRY(dw_narrow(t, rows, p.out, TD, a, TD, dzz, p.out, t->g + p.w1));
+    LB_TRY(colsum_add(t, dzz, rows, p.out, p.out, t->g + p.b1));
+  }
+  return LB_OK;
+}
+static int mlp_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t rows, const float* X, int ldx, const float* a,
+                   const float* z, const float* dy, float* dX, int64_t stride) {
+  if (rows == 0) return LB_OK;
+  lb_gnt* g = t->gn;
+  LB_TRY(mlp_bwd_head(t, p, rows, a + p.wm.size() * stride, z, dy));
+  LB_TRY(mlp_mid_bwd(t, p, rows, a, stride));
+  t->tmax_ok = false;
+  if (dX) LB_TRY(gemm_nt(t, rows, TD, p.in, g->da, t->w + p.w0, dX, ldx, 0.f, 0, nullptr, 0, t->tmax));
+  if (!dw_acc(t, rows, p.in, X, ldx, g->da, t->g + p.w0, t->g + p.b0, 128, t->tmax_ok ? t->tmax : nullptr))
+    return lb_fail(LB_ERR_UNSUPPORTED, "training: first Linear with %d inputs (row stride %d) is not covered", p.in, ldx);
+  return LB_OK;
+}
+
+// backward of the edge block: parameter gradients, de += d loss / d e_k, dn += the node-side terms (see k_edge_dP)
+static int edge_bwd(lb_gns_train* t, const lb_train_mlp& p, int64_t E, int64_t BN, const float* n, const float* el,
+                    const float* a, const float* z, const float* dagg, float* de, float* dn) {
+  if (E == 0) return LB_OK;
+  hipStream_t s = t->eng->stream;
+  lb_engine* e = t->eng;
+  lb_gnt* g = t->gn;
+  // e' feeds agg (gather of dagg over the receivers) and e_{k+1} = e_k + e' (de): d e' = de + dagg[rcv], formed in the load
+  LB_TRY(mlp_bwd_head(t, p, E, a + p.wm.size() * g->hs_e, z, de, dagg, e->receivers));  // -> g->da (E x 128)
+  LB_TRY(mlp_mid_bwd(t, p, E, a, g->hs_e));
+  const float *Ws = t->w + p.w0, *We = Ws + (size_t)2 * TD * TD;
+  float *gWs = t->g + p.w0, *gWr = gWs + (size_t)TD * TD, *gWe = gWr + (size_t)TD * TD;
+  // edge rows: dW_e += e^T da, db0 += column sums of da, de += da W_e^T
+  LB_TRY(gemm_nt(t, E, TD, TD, g->da, We, de, TD, 1.f, 0, nullptr, 0, t->tmax));
+  if (!dw_acc(t, E, TD, el, TD, g->da, gWe, t->g + p.b0, 128, t->tmax_ok ? t->tmax : nullptr))
+    return lb_fail(LB_ERR_STATE, "dw_acc refused the edge block");
+  // node rows: dP = transpose of the two gathers, then dW_s += n^T dPs, dW_r += n^T dPr, dn += dPs W_s^T + dPr W_r^T
+  float *dPs = g->proj, *dPr = g->proj + (size_t)BN * TD;
+  hipLaunchKernelGGL(k_edge_dP, GRID1(BN * 32), 0, s, g->da, t->snd_ptr, t->snd_perm, e->row_ptr, dPs, dPr, BN, E);
+  if (!dw_acc_pair(t, BN, TD, n, TD, dPs, gWs, dPr, gWr)) return lb_fail(LB_ERR_STATE, "dw_acc refused the edge block");
+  return gemm_nt_stack2(t, BN, dPs, (int64_t)BN * TD, Ws, dn);
+}
+
+// floats of partial-sum slots a step needs for BN <= cn nodes and E <= ce edges: the producers of gns_backward, launch by
+// launch (the decoder's narrow dW is counted as a full slot)
+static int64_t gns_red_capacity(const lb_gnt* g, int64_t cn, int64_t ce) {
+  const int L = g->desc.num_mp_steps;
+  const int64_t sn = dw_acc_floats(cn, 128), se = dw_acc_floats(ce, 128);
+  int64_t tot = 0;
+  tot += (int64_t)L * (2 * se + 3 * sn + dw_acc_floats(cn, 256) + ln_bwd_floats(ce) + ln_bwd_floats(cn));  // processor blocks
+  tot += sn + dw_acc_floats(cn, std::max(128, g->kpad)) + ln_bwd_floats(cn);                              // node encoder
+  tot += 2 * se + ln_bwd_floats(ce);                                                                       // edge encoder
+  tot += 2 * sn + colsum_floats(cn);                                                                       // decoder
+  const int64_t mid = g->nlin - 2;                                                                         // middle Linears of every block
+  tot += mid * ((int64_t)L * (se + sn) + 2 * sn + se);
+  return tot + 4096;
+}
+static int gns_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
+  return train_ensure(t, BN, E, [t](int64_t cn, int64_t ce, int64_t cm) -> int {
+    lb_gnt* g = t->gn;
+    const int L = g->desc.num_mp_steps;
+    const size_t nh = (size_t)(g->nlin - 1);   // hidden activations kept per block
+    g->hs_n = cn * TD;
+    g->hs_e = ce * TD;
+    LB_TRY(t->mem.get(&g->xnode, (size_t)cn * g->kpad));
+    LB_TRY(t->mem.get(&g->a_en, nh * cn * TD));
+    LB_TRY(t->mem.get(&g->z_en, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&g->a_ee, nh * ce * TD));
+    LB_TRY(t->mem.get(&g->z_ee, (size_t)ce * TD));
+    for (int k = 0; k <= L; ++k) {
+      LB_TRY(t->mem.get(&g->nlat[k], (size_t)cn * TD));
+      LB_TRY(t->mem.get(&g->elat[k], (size_t)ce * TD));
+    }
+    for (int k = 0; k < L; ++k) {
+      LB_TRY(t->mem.get(&g->ae[k], nh * ce * TD));
+      LB_TRY(t->mem.get(&g->ze[k], (size_t)ce * TD));
+      LB_TRY(t->mem.get(&g->xn[k], (size_t)cn * 2 * TD));
+      LB_TRY(t->mem.get(&g->an[k], nh * cn * TD));
+      LB_TRY(t->mem.get(&g->zn[k], (size_t)cn * TD));
+    }
+    LB_TRY(t->mem.get(&g->a_d, nh * cn * TD));
+    LB_TRY(t->mem.get(&t->pred, (size_t)cn * 4));
+    LB_TRY(t->mem.get(&g->dn, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&g->de, (size_t)ce * TD));
+    LB_TRY(t->mem.get(&t->dy, (size_t)cm * TD));
+    LB_TRY(t->mem.get(&g->dz, (size_t)cm * TD));
+    LB_TRY(t->mem.get(&g->da, (size_t)cm * TD));
+    if (g->nlin > 2) LB_TRY(t->mem.get(&g->da2, (size_t)cm * TD));
+    LB_TRY(t->mem.get(&g->dx, (size_t)cn * std::max(3 * TD, g->kpad)));
+    LB_TRY(t->mem.get(&g->dagg, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&g->agg, (size_t)cn * TD));
+    LB_TRY(t->mem.get(&g->proj, (size_t)cn * 2 * TD));
+    LB_TRY(t->mem.get(&g->dxe, (size_t)ce * 8));
+    t->red_cap = gns_red_capacity(g, cn, ce);
+    return LB_OK;
+  });
+}
+
+// The layout of a GNS training handle's blobs for description d (no HIP call): the offsets of every MLP in the device
+// blob, its float count (t->n_floats), the caller blob's (t->n_compact) and the index map between them (t->cmap)
+static void gns_train_layout(lb_gns_train* t, lb_gnt* g, const lb_gns_desc* d) {
+  const int L = d->num_mp_steps;
+  const bool has_emb = d->num_particle_types > 1;
+  const int emb = has_emb ? d->embedding_size : 0;
+  g->desc = *d;
+  g->nlin = d->blocks_per_step;
+  const int nmid = g->nlin - 2;
+  g->nin = d->node_in + emb;
+  g->kpad = (g->nin + 31) / 32 * 32;
+  int64_t o = 0;
+  g->off_embed = 0;
+  if (has_emb) o += (int64_t)d->num_particle_types * emb;
+  auto mlp = [&](int in, int outw, bool ln) {
+    lb_train_mlp p{};
+    p.in = in;
+    p.out = outw;
+    p.ln = ln;
+    p.w0 = o; o += (int64_t)in * TD;
+    p.b0 = o; o += TD;
+    for (int m = 0; m < nmid; ++m) {   // GNS.flatten order: linear_0, linear_1, ..., LayerNorm
+      p.wm.push_back(o); o += (int64_t)TD * TD;
+      p.bm.push_back(o); o += TD;
+    }
+    p.w1 = o; o += (int64_t)TD * outw;
+    p.b1 = o; o += outw;
+    if (ln) {
+      p.lns = o; o += outw;
+      p.lno = o; o += outw;
+    }
+    return p;
+  };
+  g->enc_node = mlp(g->nin, TD, true);
+  g->enc_edge = mlp(d->edge_in, TD, true);
+  for (int k = 0; k < L; ++k) {
+    g->pe.push_back(mlp(3 * TD, TD, true));
+    g->pn.push_back(mlp(2 * TD, TD, true));
+  }
+  g->dec = mlp(TD, d->out_dim, false);
+  // Latents narrower than 128 (round 4; GNS-5-64 of docs/pages/baselines.rst): the device blobs keep the 128-wide layout with
+  // zeros in the padded rows / columns - they stay zero under the step (a padded hidden unit is relu(0) = 0, so its weight
+  // gradients vanish; padded LayerNorm columns are masked in k_ln_bwd2; AdamW of (w, g, m, v) = 0 is 0) - and the caller's
+  // blob (GNS.flatten with the model's latent size) is scattered into / gathered from it through an index map.
+  const int lat = d->latent_size;
+  g->lat = lat;
+  int64_t oc = has_emb ? (int64_t)d->num_particle_types * emb : 0;
+  if (lat != TD) t->cmap.reserve((size_t)o);
+  for (int64_t i = 0; i < oc && lat != TD; ++i) t->cmap.push_back(i);  // embedding table: as is
+  auto map_mlp = [&](const lb_train_mlp& p, int in_c, int nblk, int out_c) {
+    // in_c caller rows of w0: nblk blocks of `lat` latent rows (row j of block q -> device row 128 q + j), or plain rows (nblk 0)
+    if (lat != TD) {
+      for (int r = 0; r < in_c; ++r) {
+        const int rp = nblk ? (r / lat) * TD + (r % lat) : r;
+        for (int c = 0; c < lat; ++c) t->cmap.push_back(p.w0 + (int64_t)rp * TD + c);
+      }
+      for (int c = 0; c < lat; ++c) t->cmap.push_back(p.b0 + c);
+      for (size_t m = 0; m < p.wm.size(); ++m) {
+        for (int r = 0; r < lat; ++r)
+          for (int c = 0; c < lat; ++c) t->cmap.push_back(p.wm[m] + (int64_t)r * TD + c);
+        for (int c = 0; c < lat; ++c) t->cmap.push_back(p.bm[m] + c);
+      }
+      for (int r = 0; r < lat; ++r)
+        for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.w1 + (int64_t)r * p.out + c);
+      for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.b1 + c);
+      if (p.ln) {
+        for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.lns + c);
+        for (int c = 0; c < out_c; ++c) t->cmap.push_back(p.lno + c);
+      }
+    }
+    oc += (int64_t)in_c * lat + lat + (int64_t)p.wm.size() * ((int64_t)lat * lat + lat) + (int64_t)lat * out_c + out_c +
+          (p.ln ? 2 * out_c : 0);
+  };
+  map_mlp(g->enc_node, g->nin, 0, lat);
+  map_mlp(g->enc_edge, d->edge_in, 0, lat);
+  for (int k = 0; k < L; ++k) {
+    map_mlp(g->pe[k], 3 * lat, 3, lat);
+    map_mlp(g->pn[k], 2 * lat, 2, lat);
+  }
+  map_mlp(g->dec, lat, 1, d->out_dim);
+  t->n_floats = o;
+  t->n_compact = oc;
+}
+int lb_gns_train_padded_map(const lb_gns_desc* d, std::vector<int64_t>* cmap, int64_t* n_dev, int64_t* n_compact) {
+  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
+    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
+  lb_gns_train t;
+  lb_gnt g;
+  gns_train_layout(&t, &g, d);
+  cmap->swap(t.cmap);
+  *n_dev = t.n_floats;
+  *n_compact = t.n_compact;
+  return LB_OK;
+}
+
+// Forward: features, the network with saved activations -> t->pred
+static int gns_forward(lb_gns_train* t, const float**) {
+  lb_engine* e = t->eng;
+  lb_gnt* g = t->gn;
+  hipStream_t s = e->stream;
+  const int64_t E = t->fwd_E, BN = t->fwd_BN;
+  const int L = g->desc.num_mp_steps;
+  const bool has_emb = g->desc.num_particle_types > 1;
+  const int emb = has_emb ? g->desc.embedding_size : 0;
   // ---- features (engine kernels): node row [features | embedding | 0-pad], edge features from the neighbor build
   const int kpad_saved = e->g.kpad;
-  e->g.kpad = t->kpad;
-  int rc = lbk_node_features(e, t->xnode, has_emb ? t->w + t->off_embed : nullptr, emb, t->desc.num_particle_types, nullptr,
+  e->g.kpad = g->kpad;
+  int rc = lbk_node_features(e, g->xnode, has_emb ? t->w + g->off_embed : nullptr, emb, g->desc.num_particle_types, nullptr,
                              nullptr, nullptr, nullptr);
   e->g.kpad = kpad_saved;
   if (rc) return rc;
   // ---- forward
-  LB_TRY(mlp_fwd(t, t->enc_node, BN, t->xnode, t->kpad, t->a_en, t->z_en, nullptr, t->nlat[0], t->hs_n));
-  LB_TRY(mlp_fwd(t, t->enc_edge, E, e->efeat, 8, t->a_ee, t->z_ee, nullptr, t->elat[0], t->hs_e));
+  LB_TRY(mlp_fwd(t, g->enc_node, BN, g->xnode, g->kpad, g->a_en, g->z_en, nullptr, g->nlat[0], g->hs_n));
+  LB_TRY(mlp_fwd(t, g->enc_edge, E, e->efeat, 8, g->a_ee, g->z_ee, nullptr, g->elat[0], g->hs_e));
   for (int k = 0; k < L; ++k) {
     // e' = LN(MLP([n_s | n_r | e])) is both the message and (plus e) the next edge latent: keep e' in dy, then residual
-    LB_TRY(edge_fwd(t, t->pe[k], E, BN, t->nlat[k], t->elat[k], t->ae[k], t->ze[k], t->dy, t->elat[k + 1]));
-    hipLaunchKernelGGL(k_seg_sum, GRID1(BN * 32), 0, s, e->row_ptr, t->dy, t->agg, BN, E, t->nlat[k], t->xn[k]);
-    LB_TRY(mlp_fwd(t, t->pn[k], BN, t->xn[k], 2 * TD, t->an[k], t->zn[k], t->nlat[k], t->nlat[k + 1], t->hs_n));
+    LB_TRY(edge_fwd(t, g->pe[k], E, BN, g->nlat[k], g->elat[k], g->ae[k], g->ze[k], t->dy, g->elat[k + 1]));
+    hipLaunchKernelGGL(k_seg_sum, GRID1(BN * 32), 0, s, e->row_ptr, t->dy, g->agg, BN, E, g->nlat[k], g->xn[k]);
+    LB_TRY(mlp_fwd(t, g->pn[k], BN, g->xn[k], 2 * TD, g->an[k], g->zn[k], g->nlat[k], g->nlat[k + 1], g->hs_n));
   }
-  LB_TRY(mlp_fwd(t, t->dec, BN, t->nlat[L], TD, t->a_d, nullptr, nullptr, t->pred, t->hs_n));
-  if (pred_out_dev) LB_HIP(hipMemcpyAsync(pred_out_dev, t->pred, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
-  return LB_OK;
+  return mlp_fwd(t, g->dec, BN, g->nlat[L], TD, g->a_d, nullptr, nullptr, t->pred, g->hs_n);
 }
 static int feat_bwd(lb_gns_train* t, double* dpos_out_dev);
-// Backward part: the sender-sorted view of this step's edge list, the hand-written backward from t->dy, the frame's end.
+// Backward: the sender-sorted view of this step's edge list, the hand-written backward from t->dy.
 // dpos_out_dev != null: also d loss / d window through the feature builder (k_feat_bwd)
-static int gns_backward_part(lb_gns_train* t, double* dpos_out_dev) {
+static int gns_backward(lb_gns_train* t, double* dpos_out_dev) {
   lb_engine* e = t->eng;
+  lb_gnt* g = t->gn;
   hipStream_t s = e->stream;
   const int64_t E = t->fwd_E, BN = t->fwd_BN;
-  const int L = t->desc.num_mp_steps;
-  const bool has_emb = t->desc.num_particle_types > 1;
-  const int emb = has_emb ? t->desc.embedding_size : 0;
+  const int L = g->desc.num_mp_steps;
+  const bool has_emb = g->desc.num_particle_types > 1;
+  const int emb = has_emb ? g->desc.embedding_size : 0;
   const bool want_dx = dpos_out_dev != nullptr;
   LB_TRY(train_sender_sort(t, E, BN));
   // ---- backward
-  LB_TRY(mlp_bwd(t, t->dec, BN, t->nlat[L], TD, t->a_d, nullptr, t->dy, t->dn, t->hs_n));  // dn = d loss / d n_L
-  LB_HIP(hipMemsetAsync(t->de, 0, sizeof(float) * std::max<int64_t>(E, 1) * TD, s));  // e_L has no reader
+  LB_TRY(mlp_bwd(t, g->dec, BN, g->nlat[L], TD, g->a_d, nullptr, t->dy, g->dn, g->hs_n));  // dn = d loss / d n_L
+  LB_HIP(hipMemsetAsync(g->de, 0, sizeof(float) * std::max<int64_t>(E, 1) * TD, s));  // e_L has no reader
   for (int k = L - 1; k >= 0; --k) {
     // node block: n_{k+1} = n_k + LN(MLP([n_k | agg_k])): dy = dn (also flows to n_k through the residual)
     // d [n_k | agg_k] = da W0^T lands where it is used: the n_k half is added to dn, the agg_k half is dagg (round 4 wrote
     // the 256-wide product and split it in a pass of its own).  dn was consumed (LayerNorm backward) before it is updated.
-    LB_TRY(mlp_bwd(t, t->pn[k], BN, t->xn[k], 2 * TD, t->an[k], t->zn[k], t->dn, nullptr, t->hs_n));
-    LB_TRY(gemm_nt_pair(t, BN, t->da, t->w + t->pn[k].w0, t->dn, 1.f, t->w + t->pn[k].w0 + (size_t)TD * TD, t->dagg, 0.f));
-    LB_TRY(edge_bwd(t, t->pe[k], E, BN, t->nlat[k], t->elat[k], t->ae[k], t->ze[k], t->dagg, t->de, t->dn));
+    LB_TRY(mlp_bwd(t, g->pn[k], BN, g->xn[k], 2 * TD, g->an[k], g->zn[k], g->dn, nullptr, g->hs_n));
+    LB_TRY(gemm_nt_pair(t, BN, g->da, t->w + g->pn[k].w0, g->dn, 1.f, t->w + g->pn[k].w0 + (size_t)TD * TD, g->dagg, 0.f));
+    LB_TRY(edge_bwd(t, g->pe[k], E, BN, g->nlat[k], g->elat[k], g->ae[k], g->ze[k], g->dagg, g->de, g->dn));
   }
   // (d efeat: [E][8] like efeat, rel_disp in the first dim columns, rel_dist in column dim - a 128 x (dim + 1) operand)
-  LB_TRY(mlp_bwd(t, t->enc_edge, E, e->efeat, 8, t->a_ee, t->z_ee, t->de, want_dx ? t->dxe : nullptr, t->hs_e));
-  LB_TRY(mlp_bwd(t, t->enc_node, BN, t->xnode, t->kpad, t->a_en, t->z_en, t->dn, has_emb || want_dx ? t->dx : nullptr, t->hs_n));
-  if (has_emb) embed_grad_acc(t, t->dx, t->kpad, t->desc.node_in, emb, e->ptype, t->desc.num_particle_types, BN, t->g + t->off_embed);
-  if (want_dx) LB_TRY(feat_bwd(t, dpos_out_dev));
-  return train_step_end(t);
+  LB_TRY(mlp_bwd(t, g->enc_edge, E, e->efeat, 8, g->a_ee, g->z_ee, g->de, want_dx ? g->dxe : nullptr, g->hs_e));
+  LB_TRY(mlp_bwd(t, g->enc_node, BN, g->xnode, g->kpad, g->a_en, g->z_en, g->dn, has_emb || want_dx ? g->dx : nullptr, g->hs_n));
+  if (has_emb) embed_grad_acc(t, g->dx, g->kpad, g->desc.node_in, emb, e->ptype, g->desc.num_particle_types, BN, t->g + g->off_embed);
+  return want_dx ? feat_bwd(t, dpos_out_dev) : LB_OK;
 }
 // ---- the transpose of the feature builder (features.py:47-126; lb_features.h, the edge features of the neighbor build):
 // d loss / d window (B, N, isl, dim) fp64 from d loss / d xnode (t->dx, row stride kpad) and d loss / d efeat (t->dxe,
@@ -2001,13 +2027,14 @@ __global__ void __launch_bounds__(256) k_feat_bwd(lb_feat_bwd_args a) {
 }
 static int feat_bwd(lb_gns_train* t, double* dpos_out_dev) {
   lb_engine* e = t->eng;
+  const lb_gnt* g = t->gn;
   lb_feat_bwd_args a{};
   a.BN = t->fwd_BN; a.E = t->fwd_E;
-  a.dim = e->g.dim; a.isl = e->g.isl; a.kpad = t->kpad; a.has_mag = e->g.has_vel_mag; a.has_bound = e->g.has_bound;
+  a.dim = e->g.dim; a.isl = e->g.isl; a.kpad = g->kpad; a.has_mag = e->g.has_vel_mag; a.has_bound = e->g.has_bound;
   a.rc = e->g.rc;
   for (int d = 0; d < 3; ++d) a.inv_std[d] = 1.0 / e->g.vel_std[d];
   a.ptype = e->ptype; a.row_ptr = e->row_ptr; a.snd_ptr = t->snd_ptr; a.snd_perm = t->snd_perm;
-  a.xnode = t->xnode; a.dx = t->dx; a.efeat = e->efeat; a.dxe = t->dxe; a.dpos = dpos_out_dev;
+  a.xnode = g->xnode; a.dx = g->dx; a.efeat = e->efeat; a.dxe = g->dxe; a.dpos = dpos_out_dev;
   if (a.E == 0) {   // no edges: no sender view was built; with row_ptr (all zero) in its place the loops over it are empty
     a.snd_ptr = e->row_ptr;
     a.snd_perm = e->row_ptr;
@@ -2018,25 +2045,59 @@ static int feat_bwd(lb_gns_train* t, double* dpos_out_dev) {
   LB_HIP(hipGetLastError());
   return LB_OK;
 }
-static int linear_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                  float* pred_out_dev);
-static int painn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                 float* pred_out_dev);
-static int gns_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
-  LB_TRY(gns_forward_part(t, "lb_gns_train_loss_grad", pred_out_dev));
-  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));   // loss and d loss / d pred
-  return gns_backward_part(t, nullptr);
+static void gnt_free(lb_gns_train* t) {
+  delete t->gn;  // (its buffers are the handle arena's)
+  t->gn = nullptr;
 }
+static const lb_train_model gns_model = {"GNS", "lb_gns_train_loss_grad", true, true, true, gnt_free, gns_ensure, gns_forward,
+                                         gns_backward, nullptr};
+
+extern "C" int lb_gns_train_create(lb_engine* e, const lb_gns_desc* d, const float* w, int64_t n_floats,
+                                   lb_gns_train** out) {
+  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
+  if (d->latent_size < 4 || d->latent_size > TD || d->blocks_per_step < 2 || d->blocks_per_step > 8)
+    return lb_fail(LB_ERR_UNSUPPORTED, "training path: latent_size <= 128 and 2 <= num_mlp_layers <= 8 are built");
+  if (d->out_dim != e->g.dim || d->node_in != e->g.node_in || d->edge_in != e->g.dim + 1)
+    return lb_fail(LB_ERR_ARG, "model widths do not match the case");
+  lb_gns_train* t = new lb_gns_train();
+  lb_gnt* g = new lb_gnt();
+  t->model = &gns_model;
+  t->gn = g;
+  t->eng = e;
+  gns_train_layout(t, g, d);
+  const int L = d->num_mp_steps;
+  g->nlat.assign(L + 1, nullptr);
+  g->elat.assign(L + 1, nullptr);
+  g->ae.assign(L, nullptr); g->ze.assign(L, nullptr);
+  g->xn.assign(L, nullptr); g->an.assign(L, nullptr); g->zn.assign(L, nullptr);
+  return train_create_finish(t, train_handle_init(t, "weight blob", w, n_floats), out);
+}
+
+// The inference images of m re-made on the device from this handle's current weights (lb_gns_repack.hip)
+extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* m) {
+  if (!t || !m) return lb_fail(LB_ERR_ARG, "null argument");
+  if (!t->model) return blob_refuse("lb_gns_train_sync_model");
+  if (t->model != &gns_model) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
+  if (m->eng != t->eng) return lb_fail(LB_ERR_ARG, "the model was created for another engine");
+  const lb_gns_desc &a = t->gn->desc, &b = m->desc;
+  if (a.latent_size != b.latent_size || a.blocks_per_step != b.blocks_per_step || a.num_mp_steps != b.num_mp_steps ||
+      a.embedding_size != b.embedding_size || a.num_particle_types != b.num_particle_types || a.node_in != b.node_in ||
+      a.edge_in != b.edge_in || a.out_dim != b.out_dim)
+    return lb_fail(LB_ERR_ARG, "the model's description differs from the training handle's (latent %d vs %d)", b.latent_size,
+                   a.latent_size);
+  return lbk_gns_repack(t->eng, m, t->w, t->cmap, t->n_compact, t->n_floats);
+}
+
+// ------------------------------------------------------------------------------------------------ C ABI, every model
+// train_loss_grad on any handle whose model trains on the (B*N, dim) acceleration target
 extern "C" int lb_gns_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                       float* pred_out_dev) {
   if (!t || !target_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->blob) return blob_refuse("lb_gns_train_loss_grad");
-  if (t->eg) return lb_fail(LB_ERR_ARG, "an EGNN training handle: its loss needs the pos / vel / acc targets (lb_egnn_train_loss_grad)");
-  if (t->sg) return lb_segnn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
-  if (t->ln) return linear_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
-  if (t->pa) return painn_train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
-  t->fwd_live = false;
-  return train_loss_grad_guarded(t, loss_out, [&] { return gns_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
+  if (!t->model) return blob_refuse("lb_gns_train_loss_grad");
+  if (!t->model->acc_loss)
+    return lb_fail(LB_ERR_ARG, "an %s training handle: its loss needs the pos / vel / acc targets (%s)", t->model->name,
+                   t->model->loss_entry);
+  return train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
 }
 
 extern "C" int lb_gns_train_zero_grad(lb_gns_train* t) {
@@ -2122,20 +2183,8 @@ extern "C" int lb_gns_train_write(lb_gns_train* t, int32_t which, const float* i
   return LB_OK;
 }
 
-// The inference images of g re-made on the device from this handle's current weights (lb_gns_repack.hip)
-extern "C" int lb_gns_train_sync_model(lb_gns_train* t, lb_gns* g) {
-  if (!t || !g) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->blob) return blob_refuse("lb_gns_train_sync_model");
-  if (t->sg || t->eg || t->ln || t->pa) return lb_fail(LB_ERR_ARG, "not a GNS training handle");
-  if (g->eng != t->eng) return lb_fail(LB_ERR_ARG, "the model was created for another engine");
-  const lb_gns_desc &a = t->desc, &b = g->desc;
-  if (a.latent_size != b.latent_size || a.blocks_per_step != b.blocks_per_step || a.num_mp_steps != b.num_mp_steps ||
-      a.embedding_size != b.embedding_size || a.num_particle_types != b.num_particle_types || a.node_in != b.node_in ||
-      a.edge_in != b.edge_in || a.out_dim != b.out_dim)
-    return lb_fail(LB_ERR_ARG, "the model's description differs from the training handle's (latent %d vs %d)", b.latent_size,
-                   a.latent_size);
-  return lbk_gns_repack(t->eng, g, t->w, t->cmap, t->n_compact, t->n_floats);
-}
+// (for a model's dpred_load; defined with lb_train_backward below)
+__global__ void k_dpred_spread(const float* __restrict__ dsave, int64_t BN, int dim, int ld, float* __restrict__ dst);
 
 // ------------------------------------------------------------------------------------------------ SEGNN
 #include "lb_train_segnn.h"
@@ -2176,21 +2225,14 @@ extern "C" int lb_train_exact_math(lb_gns_train* t, int32_t exact) {
   if (!t) return lb_fail(LB_ERR_ARG, "null argument");
   // (a live forward stays live: saved activations do not depend on the arithmetic that reads them, so a forward in exact
   // products may be followed by a backward in the default ones)
-  t->f16x2 = !exact && !t->eg && !t->ln && !t->pa && !t->blob && lb_train_f16x2_default();
+  t->f16x2 = !exact && t->model && t->model->f16x2 && lb_train_f16x2_default();
   return LB_OK;
-}
-static int train_forward_part(lb_gns_train* t, float* pred_out_dev) {
-  if (t->eg) return egnn_forward_part(t, "lb_train_forward", pred_out_dev);
-  if (t->sg) return segnn_forward_part(t, "lb_train_forward", pred_out_dev);
-  if (t->ln) return linear_forward_part(t, "lb_train_forward", pred_out_dev);
-  if (t->pa) return painn_forward_part(t, "lb_train_forward", pred_out_dev);
-  return gns_forward_part(t, "lb_train_forward", pred_out_dev);
 }
 extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
   if (!t || !pred_out_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->blob) return blob_refuse("lb_train_forward");
+  if (!t->model) return blob_refuse("lb_train_forward");
   t->fwd_live = false;
-  LB_TRY(train_forward_part(t, pred_out_dev));
+  LB_TRY(train_forward_part(t, "lb_train_forward", pred_out_dev));
   LB_HIP(hipGetLastError());
   t->fwd_f16x2 = t->f16x2;
   t->fwd_live = true;
@@ -2198,13 +2240,13 @@ extern "C" int lb_train_forward(lb_gns_train* t, float* pred_out_dev) {
 }
 extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double* dpos_out_dev) {
   if (!t || !dpred_dev) return lb_fail(LB_ERR_ARG, "null argument");
-  if (t->blob) return blob_refuse("lb_train_backward");
+  if (!t->model) return blob_refuse("lb_train_backward");
   if (!t->fwd_live)
     return lb_fail(LB_ERR_STATE, "lb_train_backward needs a live forward: call lb_train_forward first (any other call on the "
                    "handle but lb_gns_train_zero_grad ends it)");
-  if (dpos_out_dev && (t->sg || t->eg || t->ln || t->pa))
+  if (dpos_out_dev && !t->model->window_grad)
     return lb_fail(LB_ERR_UNSUPPORTED, "lb_train_backward: the gradient with respect to the window is built for GNS only, "
-                   "not for %s handles", t->sg ? "SEGNN" : t->eg ? "EGNN" : t->ln ? "Linear" : "PaiNN");
+                   "not for %s handles", t->model->name);
   t->fwd_live = false;   // the backward consumes the forward's scratch
   lb_engine* e = t->eng;
   hipStream_t s = e->stream;
@@ -2219,18 +2261,13 @@ extern "C" int lb_train_backward(lb_gns_train* t, const float* dpred_dev, double
     if (attempt++ > 0) {   // (in the arithmetic of the forward it repeats)
       const bool bwd_f16x2 = t->f16x2;
       t->f16x2 = t->fwd_f16x2;
-      const int rc = train_forward_part(t, nullptr);
+      const int rc = train_forward_part(t, "lb_train_forward", nullptr);
       t->f16x2 = bwd_f16x2;
       if (rc) return rc;
     }
-    if (t->eg) {
-      hipLaunchKernelGGL(k_dpred_spread, GRID1(BN), 0, s, t->dsave, BN, dim, 4, t->eg->dx);
-      return egnn_backward_part(t);
-    }
-    LB_HIP(hipMemcpyAsync(t->dy, t->dsave, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
-    if (t->ln) return linear_backward_part(t);
-    if (t->pa) return painn_backward_part(t);
-    return t->sg ? segnn_backward_part(t) : gns_backward_part(t, dpos_out_dev);
+    if (t->model->dpred_load) LB_TRY(t->model->dpred_load(t));
+    else LB_HIP(hipMemcpyAsync(t->dy, t->dsave, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
+    return train_backward_part(t, dpos_out_dev);
   });
 }
 
@@ -2299,7 +2336,7 @@ extern "C" int lb_train_probe(lb_gns_train* t, int32_t op, lb_train_probe_args* 
   a->guard = a->slot = 0;
   LB_TRY(probe_check(op, a));
   if (!t) return lb_fail(LB_ERR_ARG, "lb_train_probe: null handle");
-  if (!t->blob) return lb_fail(LB_ERR_ARG, "lb_train_probe: a test hook for blob handles (lb_blob_train_create) only");
+  if (t->model) return lb_fail(LB_ERR_ARG, "lb_train_probe: a test hook for blob handles (lb_blob_train_create) only");
   // the destinations inside the gradient blob, the floats of partial sums the call takes
   const int64_t n = t->n_floats;
   auto inside = [&](int64_t off, int64_t len) { return off >= 0 && off + len <= n; };
@@ -2314,7 +2351,7 @@ extern "C" int lb_train_probe(lb_gns_train* t, int32_t op, lb_train_probe_args* 
       break;
     }
     case LB_PROBE_DW_NARROW:
-      need = r64(dw_groups_max(a->rows) * a->K * a->M);
+      need = dw_narrow_floats(a->rows, a->K, a->M);
       ok = inside(a->dst0, (int64_t)a->K * a->M);
       break;
     case LB_PROBE_COLSUM:
@@ -2390,8 +2427,6 @@ extern "C" int lb_train_probe(lb_gns_train* t, int32_t op, lb_train_probe_args* 
   const int rc = run();
   t->f16x2 = f16x2_was;
   t->dw_site.swap(site_was); t->dw_xexp.swap(xexp_was); t->dw_xdyn.swap(xdyn_was);
-  t->red_tab.clear();
-  t->red_off = 0;
-  t->red_blocks = 0;
+  red_reset(t);
   return rc;
 }

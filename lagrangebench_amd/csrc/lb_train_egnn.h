@@ -405,11 +405,10 @@ static int egt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
     LB_TRY(t->mem.get(&g->phi, (size_t)ce));
     LB_TRY(t->mem.get(&g->dphi, (size_t)ce));
     for (float** p : {&g->z0, &g->a, &g->z1, &g->m, &g->zx0, &g->q, &g->de1, &g->de2}) LB_TRY(t->mem.get(p, (size_t)ce * W));
-    // partial-sum slots of the step's reductions (mirrors the backward below)
-    auto slot = [](int64_t rows, int K) { return (dw_groups_max(std::max<int64_t>(rows, 1)) * (K + 1) * 128 + 63) / 64 * 64; };
-    auto narrow = [](int64_t rows) { return (std::min<int64_t>(DW_MAX_G, (rows + 63) / 64 + 1) * 128 + 63) / 64 * 64; };
-    t->red_cap = (int64_t)L * (4 * slot(cn, 128) + slot(cn, 256) + slot(cn, 1) + 2 * slot(ce, 128) + slot(ce, 2) + narrow(cn) +
-                               narrow(ce)) + slot(cn, EGT_XIN) + 4096;
+    // partial-sum slots of the step's reductions: the producers of egnn_backward, per layer and for the embedding
+    t->red_cap = (int64_t)L * (4 * dw_acc_floats(cn, W) + dw_acc_floats(cn, 2 * W) + dw_acc_floats(cn, 1) +
+                               2 * dw_acc_floats(ce, W) + dw_acc_floats(ce, 2) + dw_narrow_floats(cn, W, 1) +
+                               dw_narrow_floats(ce, W, 1)) + dw_acc_floats(cn, EGT_XIN) + 4096;
     return LB_OK;
   });
 }
@@ -419,6 +418,17 @@ static int egt_dw(lb_gns_train* t, int64_t rows, int K, const float* X, int ldx,
   if (rows <= 0) return LB_OK;
   return dw_acc(t, rows, K, X, ldx, dY, dW, db) ? LB_OK : LB_ERR_STATE;
 }
+
+static int egnn_forward(lb_gns_train* t, const float** pred);
+static int egnn_backward(lb_gns_train* t, double* dpos_out_dev);
+// the backward starts from d loss / d x^L in g->dx, rows of 4 floats: k_egt_loss writes it, lb_train_backward spreads into it
+static int egnn_dpred_load(lb_gns_train* t) {
+  const int64_t BN = t->fwd_BN;
+  hipLaunchKernelGGL(k_dpred_spread, GRID1(BN), 0, t->eng->stream, t->dsave, BN, t->eng->g.dim, 4, t->eg->dx);
+  return LB_OK;
+}
+static const lb_train_model egnn_model = {"EGNN", "lb_egnn_train_loss_grad", false, false, false, egt_free, egt_ensure,
+                                          egnn_forward, egnn_backward, egnn_dpred_load};
 
 extern "C" int lb_egnn_train_create(lb_engine* e, const lb_egnn_desc* d, const float* w, int64_t n_floats, lb_gns_train** out) {
   if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
@@ -435,6 +445,7 @@ extern "C" int lb_egnn_train_create(lb_engine* e, const lb_egnn_desc* d, const f
   const int L = d->num_mp_steps, H = d->hidden, W = EGT_W;
   lb_gns_train* t = new lb_gns_train();
   lb_egt* g = new lb_egt();
+  t->model = &egnn_model;
   t->eg = g;
   t->eng = e;
   t->f16x2 = false;   // exact fp32 products throughout (the reference's fp32 policy)
@@ -481,40 +492,28 @@ extern "C" int lb_egnn_train_create(lb_engine* e, const lb_egnn_desc* d, const f
     vd.hidden = W;
     rc = lbk_egnn_view_create(e, &vd, t->w, &g->view);
   }
-  if (rc) {
-    lb_gns_train_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return LB_OK;
+  return train_create_finish(t, rc, out);
 }
 
 // The inference view of the handle (lbk_egnn_view_create on t->w): lb_egnn_forward / lb_egnn_rollout on it run on the CURRENT
 // weights.  Borrowed: it lives and dies with t.
 extern "C" int lb_egnn_train_model(lb_gns_train* t, lb_egnn** out) {
   if (!t || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  if (!t->eg || !t->eg->view) return lb_fail(LB_ERR_ARG, "not an EGNN training handle");
+  if (t->model != &egnn_model) return lb_fail(LB_ERR_ARG, "not an EGNN training handle");
   *out = t->eg->view;
   return LB_OK;
 }
 
 // The step in three parts, split at d loss / d x^L (g->dx, rows of 4 floats).  Forward part: the inference kernels on the
 // current weights, taps on (returns after checking every edge's transpose: nothing has been accumulated yet when it refuses)
-static int egnn_forward_part(lb_gns_train* t, const char* entry, float* pred_pos_out_dev) {
+// The prediction is the last tap, x^L
+static int egnn_forward(lb_gns_train* t, const float** pred) {
   lb_engine* e = t->eng;
   lb_egt* g = t->eg;
-  hipStream_t s = e->stream;
-  int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, entry, &E, &BN));
-  t->fwd_E = E;
-  t->fwd_BN = BN;
-  const int L = g->desc.num_mp_steps, dim = e->g.dim;
-  LB_TRY(egt_ensure(t, BN, E));
   LB_TRY(lb_egnn_set_tap(g->view, g->tap_h, g->tap_x));
   g->st = lb_egnn_state{};
   LB_TRY(lbk_egnn_train_forward(e, g->view, &g->st));
-  const float* xl = g->tap_x + (size_t)L * BN * dim;
-  if (pred_pos_out_dev) LB_HIP(hipMemcpyAsync(pred_pos_out_dev, xl, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
+  *pred = g->tap_x + (size_t)g->desc.num_mp_steps * t->fwd_BN * e->g.dim;
   return LB_OK;
 }
 // ---- loss and d loss / d x^L
@@ -541,7 +540,7 @@ static int egnn_loss_part(lb_gns_train* t, const double* tgt_pos, const double* 
   hipLaunchKernelGGL(k_loss_finish, dim3(1), dim3(64), 0, s, t->loss_part, (int64_t)((BN + 255) / 256) * 4, t->loss_dev);
   return LB_OK;
 }
-static int egnn_backward_part(lb_gns_train* t) {
+static int egnn_backward(lb_gns_train* t, double*) {
   lb_engine* e = t->eng;
   lb_egt* g = t->eg;
   hipStream_t s = e->stream;
@@ -625,20 +624,14 @@ static int egnn_backward_part(lb_gns_train* t) {
     }
   }
   // embedding: h^0 = xin W_emb + b_emb
-  LB_TRY(egt_dw(t, BN, g->node_in, g->xin, EGT_XIN, g->dh, G + g->w_emb, G + g->b_emb));
-  return train_step_end(t);
+  return egt_dw(t, BN, g->node_in, g->xin, EGT_XIN, g->dh, G + g->w_emb, G + g->b_emb);
 }
-static int egnn_train_loss_grad_once(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
-                                     float w_pos, float w_vel, float w_acc, float* pred_pos_out_dev) {
-  LB_TRY(egnn_forward_part(t, "lb_egnn_train_loss_grad", pred_pos_out_dev));
-  LB_TRY(egnn_loss_part(t, tgt_pos, tgt_vel, tgt_acc, w_pos, w_vel, w_acc));
-  return egnn_backward_part(t);
-}
-// value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h)
+// value_and_grad of _mse for EGNN on the engine's CURRENT window / neighbor list (include/lbhip.h): the frame's two halves
+// around the three-target loss
 extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, const double* tgt_vel, const double* tgt_acc,
                                        float w_pos, float w_vel, float w_acc, double* loss_out, float* pred_pos_out_dev) {
-  if (t && t->blob) return blob_refuse("lb_egnn_train_loss_grad");
-  if (!t || !t->eg) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");
+  if (t && !t->model) return blob_refuse("lb_egnn_train_loss_grad");
+  if (!t || t->model != &egnn_model) return lb_fail(LB_ERR_ARG, "null argument / not an EGNN training handle");
   if ((w_pos != 0.f && !tgt_pos) || (w_vel != 0.f && !tgt_vel) || (w_acc != 0.f && !tgt_acc))
     return lb_fail(LB_ERR_ARG, "egnn training: a target with a non-zero loss weight is null");
   t->fwd_live = false;
@@ -646,6 +639,8 @@ extern "C" int lb_egnn_train_loss_grad(lb_gns_train* t, const double* tgt_pos, c
   // not build a sender view (its sender sums go through rev[] and the orphans), so k_sender_transpose never raises bit 4.
   // The loop is then one attempt and its synchronisation the step's last.
   return train_loss_grad_guarded(t, loss_out, [&] {
-    return egnn_train_loss_grad_once(t, tgt_pos, tgt_vel, tgt_acc, w_pos, w_vel, w_acc, pred_pos_out_dev);
+    LB_TRY(train_forward_part(t, egnn_model.loss_entry, pred_pos_out_dev));
+    LB_TRY(egnn_loss_part(t, tgt_pos, tgt_vel, tgt_acc, w_pos, w_vel, w_acc));
+    return train_backward_part(t, nullptr);
   });
 }

@@ -2,8 +2,8 @@
 //
 // The handle is an lb_gns_train on the common frame (train_step_begin / train_ensure / train_step_end): its device blob is
 // lb_linear_create's, w (F + 1, dim) row-major then b (dim), with no padding (cmap empty).
-//   forward   the inference kernel (lb_linear.hip: k_ln_forward) on t->ln, a view of t->w: the prediction is Linear.apply's
-//             bit for bit; the node rows go to the handle's own t->xnode, the saved activation (a forward or rollout on the
+//   forward   the inference kernel (lb_linear.hip: k_ln_forward) on lb_lnt::view, a view of t->w: the prediction is Linear.apply's
+//             bit for bit; the node rows go to the handle's own lb_lnt::xnode, the saved activation (a forward or rollout on the
 //             view between lb_train_forward and lb_train_backward writes the view's rows, not these)
 //   loss      the masked _mse of every "acc" model (train_loss)
 //   backward  [dW ; db] = [X | type | 1]^T dY, dY only dim columns wide: k_ln_dw forms the partial sums of a contiguous chunk
@@ -31,68 +31,43 @@ __global__ void __launch_bounds__(128) k_ln_dw(const float* __restrict__ X, int 
     if (m < M) part[((int64_t)blockIdx.x * (F + 2) + c) * M + m] = acc[m];
 }
 
+struct lb_lnt {
+  lb_linear_desc desc{};
+  lb_linear* view = nullptr;   // the inference forward on t->w
+  float* xnode = nullptr;      // [cap_n][64]: the node rows of the step's forward
+};
+
 static void lnt_free(lb_gns_train* t) {
-  if (t->ln) lb_linear_destroy(t->ln);
+  lb_lnt* g = t->ln;
+  if (!g) return;
+  if (g->view) lb_linear_destroy(g->view);
+  delete g;  // (its buffers are the handle arena's)
   t->ln = nullptr;
 }
 
-static int lnt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
-  return train_ensure(t, BN, E, [t](int64_t cn, int64_t, int64_t) -> int {
-    LB_TRY(t->mem.get(&t->xnode, (size_t)cn * 64));
+static int lnt_ensure(lb_gns_train* t, int64_t BN, int64_t) {   // (no edge-sized scratch: the model reads no edges)
+  return train_ensure(t, BN, 0, [t](int64_t cn, int64_t, int64_t) -> int {
+    lb_lnt* g = t->ln;
+    LB_TRY(t->mem.get(&g->xnode, (size_t)cn * 64));
     LB_TRY(t->mem.get(&t->pred, (size_t)cn * 4));
     LB_TRY(t->mem.get(&t->dy, (size_t)cn * 4));
-    // one slot: a partial of (F + 2) x dim floats per chunk of >= 64 rows (linear_backward_part)
-    t->red_cap = std::min<int64_t>(DW_MAX_G, (cn + 63) / 64 + 1) * (int64_t)(t->ln_desc.n_in + 1) * t->ln_desc.out_dim + 4096;
+    // one slot: a partial of (F + 2) x dim floats per chunk of >= 64 rows (k_ln_dw in linear_backward, split as dw_narrow's)
+    t->red_cap = dw_groups_max(cn) * (int64_t)(g->desc.n_in + 1) * g->desc.out_dim + 4096;
     return LB_OK;
   });
 }
 
-extern "C" int lb_linear_train_create(lb_engine* e, const lb_linear_desc* d, const float* w, int64_t n_floats, lb_gns_train** out) {
-  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  *out = nullptr;
-  lb_gns_train* t = new lb_gns_train();
-  t->eng = e;
-  t->f16x2 = false;   // exact fp32 throughout (the reference's fp32 policy; there is no tall-skinny product here)
-  t->ln_desc = *d;
-  t->n_floats = t->n_compact = (int64_t)(d->n_in + 1) * d->out_dim;
-  int rc = d->n_in >= 1 && d->out_dim >= 1 ? LB_OK : lb_fail(LB_ERR_ARG, "Linear (%d, %d): bad widths", d->n_in, d->out_dim);
-  if (!rc) rc = train_handle_init(t, "linear weight blob", w, n_floats);
-  if (!rc) rc = lbk_linear_view_create(e, d, t->w, &t->ln);   // (checks the description against the engine)
-  if (rc) {
-    lb_gns_train_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return LB_OK;
+// The model's halves of the step: the inference kernel with the node rows kept -> t->pred ...
+static int linear_forward(lb_gns_train* t, const float**) {
+  lb_lnt* g = t->ln;
+  return lbk_linear_forward(t->eng, g->view, g->xnode, t->pred, g->desc.out_dim);
 }
-
-// The inference view of the handle: lb_linear_forward / lb_linear_rollout on it run on the CURRENT weights.  Borrowed: it
-// lives and dies with t.
-extern "C" int lb_linear_train_model(lb_gns_train* t, lb_linear** out) {
-  if (!t || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  if (!t->ln) return lb_fail(LB_ERR_ARG, "not a Linear training handle");
-  *out = t->ln;
-  return LB_OK;
-}
-
-static int linear_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
+// ... and, from d loss / d pred in t->dy (BN x dim)
+static int linear_backward(lb_gns_train* t, double*) {
   lb_engine* e = t->eng;
-  int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, entry, &E, &BN));
-  t->fwd_E = E;
-  t->fwd_BN = BN;
-  LB_TRY(lnt_ensure(t, BN, 0));   // (no edge-sized scratch: the model reads no edges)
-  const int dim = t->ln_desc.out_dim;
-  LB_TRY(lbk_linear_forward(e, t->ln, t->xnode, t->pred, dim));
-  if (pred_out_dev)
-    LB_HIP(hipMemcpyAsync(pred_out_dev, t->pred, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, e->stream));
-  return LB_OK;
-}
-// from d loss / d pred in t->dy (BN x dim)
-static int linear_backward_part(lb_gns_train* t) {
-  lb_engine* e = t->eng;
+  lb_lnt* g = t->ln;
   const int64_t BN = t->fwd_BN;
-  const int F = t->ln_desc.n_in - 1, dim = t->ln_desc.out_dim;
+  const int F = g->desc.n_in - 1, dim = g->desc.out_dim;
   if (BN > 0) {
     int64_t chunk = (BN + DW_MAX_G - 1) / DW_MAX_G, off = 0;
     if (chunk < 64) chunk = 64;
@@ -100,20 +75,38 @@ static int linear_backward_part(lb_gns_train* t) {
     const int64_t n = (int64_t)(F + 2) * dim;
     float* part = red_slot(t, (int64_t)G * n, &off);
     if (!part) return LB_ERR_STATE;
-    hipLaunchKernelGGL(k_ln_dw, dim3(G), dim3(128), 0, e->stream, t->xnode, 64, F, e->ptype, t->dy, dim, BN, chunk,
+    hipLaunchKernelGGL(k_ln_dw, dim3(G), dim3(128), 0, e->stream, g->xnode, 64, F, e->ptype, t->dy, dim, BN, chunk,
                        part);
     red_push(t, off, G, n, (int)n, 0, 0, t->g, nullptr);
   }
-  return train_step_end(t);
+  return LB_OK;
 }
-static int linear_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
-  LB_TRY(linear_forward_part(t, "lb_gns_train_loss_grad", pred_out_dev));
-  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));
-  return linear_backward_part(t);
+// (lb_gns_train_loss_grad is its loss entry; the guard never fires - no f16x2 product, no sender view: one attempt)
+static const lb_train_model linear_model = {"Linear", "lb_gns_train_loss_grad", false, false, true, lnt_free, lnt_ensure,
+                                            linear_forward, linear_backward, nullptr};
+
+extern "C" int lb_linear_train_create(lb_engine* e, const lb_linear_desc* d, const float* w, int64_t n_floats, lb_gns_train** out) {
+  if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
+  *out = nullptr;
+  lb_gns_train* t = new lb_gns_train();
+  lb_lnt* g = new lb_lnt();
+  t->model = &linear_model;
+  t->ln = g;
+  t->eng = e;
+  t->f16x2 = false;   // exact fp32 throughout (the reference's fp32 policy; there is no tall-skinny product here)
+  g->desc = *d;
+  t->n_floats = t->n_compact = (int64_t)(d->n_in + 1) * d->out_dim;
+  int rc = d->n_in >= 1 && d->out_dim >= 1 ? LB_OK : lb_fail(LB_ERR_ARG, "Linear (%d, %d): bad widths", d->n_in, d->out_dim);
+  if (!rc) rc = train_handle_init(t, "linear weight blob", w, n_floats);
+  if (!rc) rc = lbk_linear_view_create(e, d, t->w, &g->view);   // (checks the description against the engine)
+  return train_create_finish(t, rc, out);
 }
-// lb_gns_train_loss_grad on a Linear handle.  The guard never fires (no f16x2 product, no sender view): one attempt.
-static int linear_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
-                                  float* pred_out_dev) {
-  t->fwd_live = false;
-  return train_loss_grad_guarded(t, loss_out, [&] { return linear_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
+
+// The inference view of the handle: lb_linear_forward / lb_linear_rollout on it run on the CURRENT weights.  Borrowed: it
+// lives and dies with t.
+extern "C" int lb_linear_train_model(lb_gns_train* t, lb_linear** out) {
+  if (!t || !out) return lb_fail(LB_ERR_ARG, "null argument");
+  if (t->model != &linear_model) return lb_fail(LB_ERR_ARG, "not a Linear training handle");
+  *out = t->ln->view;
+  return LB_OK;
 }

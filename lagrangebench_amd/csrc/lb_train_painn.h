@@ -525,10 +525,9 @@ static int pnt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
     LB_TRY(t->mem.get(&g->dphi, (size_t)ce * g->ldp));
     LB_TRY(t->mem.get(&g->dpre, (size_t)ce * 3 * W));
     // partial-sum slots of the largest flush segment (one layer; the readout and the embeddings need less)
-    auto slot = [](int64_t rows, int K) { return (dw_groups_max(std::max<int64_t>(rows, 1)) * (K + 1) * 128 + 63) / 64 * 64; };
     const int64_t cnd = (int64_t)nd;
-    t->red_cap = 8 * slot(cnd, 128) + 2 * slot(cn, 256) + 3 * slot(ce, 64) + 2 * ((ce + 127) / 128 * 128 + 64) +
-                 2 * (DW_MAX_G * 128 * 4) + 64 * 68 * 64 + 4096;
+    t->red_cap = 8 * dw_acc_floats(cnd, 128) + 2 * dw_acc_floats(cn, 256) + 3 * dw_acc_floats(ce, 64) + 2 * colsum_floats(ce) +
+                 2 * (DW_MAX_G * 128 * 4) + 64 * 68 * 64 + 4096;   // (... the readout's two dw_narrow, k_pnt_dw_small)
     return LB_OK;
   });
 }
@@ -561,11 +560,15 @@ static int pnt_flush(lb_gns_train* t) {
                        t->g, t->dw_flag);
     g->red_used += (int)n;
   }
-  t->red_tab.clear();
-  t->red_off = 0;
-  t->red_blocks = 0;
+  red_reset(t);
   return LB_OK;
 }
+
+static int painn_forward(lb_gns_train* t, const float** pred);
+static int painn_backward(lb_gns_train* t, double* dpos_out_dev);
+// (lb_gns_train_loss_grad is its loss entry; the guard never fires - f16x2 off, no sender view: one attempt)
+static const lb_train_model painn_model = {"PaiNN", "lb_gns_train_loss_grad", false, false, true, pnt_free, pnt_ensure,
+                                           painn_forward, painn_backward, nullptr};
 
 extern "C" int lb_painn_train_create(lb_engine* e, const lb_painn_desc* d, const float* w, int64_t n_floats, int32_t rbf_trainable,
                                      lb_gns_train** out) {
@@ -581,6 +584,7 @@ extern "C" int lb_painn_train_create(lb_engine* e, const lb_painn_desc* d, const
   const int L = d->num_mp_steps, H = d->hidden, Hh = H / 2, W = PNT_W, Wh = PNT_WH, R = d->n_rbf;
   lb_gns_train* t = new lb_gns_train();
   lb_pnt* g = new lb_pnt();
+  t->model = &painn_model;
   t->pa = g;
   t->eng = e;
   t->f16x2 = false;   // exact fp32 products throughout (the reference's fp32 policy)
@@ -649,46 +653,34 @@ extern "C" int lb_painn_train_create(lb_engine* e, const lb_painn_desc* d, const
     vd.hidden = W;
     rc = lbk_painn_view_create(e, &vd, t->w, t->n_floats, &g->view);
   }
-  if (rc) {
-    lb_gns_train_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return LB_OK;
+  return train_create_finish(t, rc, out);
 }
 
 // The inference view of the handle (lbk_painn_view_create on t->w): lb_painn_forward / lb_painn_rollout on it run on the
 // CURRENT weights.  Borrowed: it lives and dies with t.
 extern "C" int lb_painn_train_model(lb_gns_train* t, lb_painn** out) {
   if (!t || !out) return lb_fail(LB_ERR_ARG, "null argument");
-  if (!t->pa || !t->pa->view) return lb_fail(LB_ERR_ARG, "not a PaiNN training handle");
+  if (t->model != &painn_model) return lb_fail(LB_ERR_ARG, "not a PaiNN training handle");
   *out = t->pa->view;
   return LB_OK;
 }
 
 // The step in two parts, split at d loss / d pred (t->dy, BN x dim).  Forward part: the inference kernels on the current
 // weights, taps on -> t->pred
-static int painn_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
+static int painn_forward(lb_gns_train* t, const float**) {
   lb_engine* e = t->eng;
   lb_pnt* g = t->pa;
-  int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, entry, &E, &BN));
-  t->fwd_E = E;
-  t->fwd_BN = BN;
+  const int64_t BN = t->fwd_BN;
   g->red_used = 0;
-  LB_TRY(pnt_ensure(t, BN, E));
   LB_TRY(lb_painn_set_tap(g->view, g->tap_s, g->tap_v));
   g->st = lb_painn_state{};
   LB_TRY(lbk_painn_train_forward(e, g->view, &g->st));
-  const int dim = e->g.dim;
-  hipLaunchKernelGGL(k_pnt_pred, GRID1(BN), 0, e->stream, BN, dim, e->acc, t->pred);
-  if (pred_out_dev)
-    LB_HIP(hipMemcpyAsync(pred_out_dev, t->pred, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, e->stream));
+  hipLaunchKernelGGL(k_pnt_pred, GRID1(BN), 0, e->stream, BN, e->g.dim, e->acc, t->pred);
   return LB_OK;
 }
 
 // from d loss / d pred in t->dy
-static int painn_backward_part(lb_gns_train* t) {
+static int painn_backward(lb_gns_train* t, double*) {
   lb_engine* e = t->eng;
   lb_pnt* g = t->pa;
   hipStream_t s = e->stream;
@@ -812,17 +804,5 @@ static int painn_backward_part(lb_gns_train* t) {
     LB_TRY(colsum_add(t, g->dphi, E, R, g->ldp, G + g->widths));
     LB_TRY(colsum_add(t, g->phi, E, R, g->ldp, G + g->offsets));
   }
-  LB_TRY(pnt_flush(t));
-  return train_step_end(t);
-}
-
-static int painn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
-  LB_TRY(painn_forward_part(t, "lb_gns_train_loss_grad", pred_out_dev));
-  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));
-  return painn_backward_part(t);
-}
-// lb_gns_train_loss_grad on a PaiNN handle.  The guard never fires (f16x2 off, no sender view): one attempt.
-static int painn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out, float* pred_out_dev) {
-  t->fwd_live = false;
-  return train_loss_grad_guarded(t, loss_out, [&] { return painn_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
+  return pnt_flush(t);
 }

@@ -268,7 +268,7 @@ static int sgt_ensure(lb_gns_train* t, int64_t BN, int64_t E) {
       const int64_t R = b.edge ? ce : cn;
       LB_TRY(t->mem.get(&b.Z, (size_t)4 * R * b.Kp));
       LB_TRY(t->mem.get(&b.raw, (size_t)4 * R * 128));
-      red += (dw_groups_max(4 * R) * (b.Kp + 1) * 128 + 63) / 64 * 64 + (4 * R + 127) / 128 * 128 + 64;
+      red += dw_acc_floats(4 * R, b.Kp) + colsum_floats(4 * R);   // (sgt_bwd; the column-sum slot is spare)
     }
     t->red_cap = red;
     LB_TRY(t->mem.get(&t->pred, (size_t)cn * 4));
@@ -337,6 +337,11 @@ static lb_sgt_op sgt_op(const float* x, int ns, int nv, float* dx = nullptr, int
   return o;
 }
 
+static int segnn_forward(lb_gns_train* t, const float** pred);
+static int segnn_backward(lb_gns_train* t, double* dpos_out_dev);
+static const lb_train_model segnn_model = {"SEGNN", "lb_segnn_train_loss_grad", true, false, true, sgt_free, sgt_ensure,
+                                           segnn_forward, segnn_backward, nullptr};
+
 extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const float* w, int64_t n_floats, lb_gns_train** out) {
   if (!e || !d || !w || !out) return lb_fail(LB_ERR_ARG, "null argument");
   if (d->hidden < 1 || d->hidden > 32)
@@ -350,6 +355,7 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
   const int C = d->hidden, B = d->blocks_per_step, L = d->num_mp_steps, Kv = e->g.isl - 1;
   lb_gns_train* t = new lb_gns_train();
   lb_sgt* g = new lb_sgt();
+  t->model = &segnn_model;
   t->sg = g;
   t->eng = e;
   g->desc = *d;
@@ -358,10 +364,9 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
   g->node_ns4 = (g->node_ns + 3) & ~3;
   g->node_nv4 = (g->node_nv + 3) & ~3;
   g->node_stride = g->node_ns4 + 3 * g->node_nv4;
-  if (g->node_ns > 32 || g->node_nv > 32) {
-    lb_gns_train_destroy(t);
-    return lb_fail(LB_ERR_UNSUPPORTED, "segnn training: %d scalar / %d vector node features (<= 32 each)", g->node_ns, g->node_nv);
-  }
+  if (g->node_ns > 32 || g->node_nv > 32)
+    return train_create_finish(t, lb_fail(LB_ERR_UNSUPPORTED, "segnn training: %d scalar / %d vector node features (<= 32 each)",
+                                          g->node_ns, g->node_nv), out);
   int64_t o = 0, oc = 0;
   auto add = [&](std::vector<std::pair<int, int>> ops, int Ms, int Mv, int mode, bool edge) {
     lb_sgt_block b{};
@@ -399,32 +404,20 @@ extern "C" int lb_segnn_train_create(lb_engine* e, const lb_segnn_desc* d, const
   for (int i = 0; i < B; ++i) add({{C, C}}, 2 * C, C, SGT_GATE, false);
   add({{C, C}}, 0, 1, SGT_OUTVEC, false);
   for (const lb_sgt_block& b : g->blocks)
-    if (b.K > 256) {
-      lb_gns_train_destroy(t);
-      return lb_fail(LB_ERR_UNSUPPORTED, "segnn training: a tensor product with %d input channels (<= 256)", b.K);
-    }
+    if (b.K > 256)
+      return train_create_finish(t, lb_fail(LB_ERR_UNSUPPORTED, "segnn training: a tensor product with %d input channels (<= 256)", b.K), out);
   t->n_floats = o;
   t->n_compact = oc;
-  const int rc = train_handle_init(t, "segnn weight blob", w, n_floats);
-  if (rc) {
-    lb_gns_train_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return LB_OK;
+  return train_create_finish(t, train_handle_init(t, "segnn weight blob", w, n_floats), out);
 }
 
-// The step in two parts, split at d loss / d pred (t->dy), as gns_forward_part / gns_backward_part
-static int segnn_forward_part(lb_gns_train* t, const char* entry, float* pred_out_dev) {
+// The model's halves of the step, split at d loss / d pred (t->dy), as gns_forward / gns_backward
+static int segnn_forward(lb_gns_train* t, const float**) {
   lb_engine* e = t->eng;
   lb_sgt* g = t->sg;
   hipStream_t s = e->stream;
-  int64_t E = 0, BN = 0;
-  LB_TRY(train_step_begin(t, entry, &E, &BN));
-  t->fwd_E = E;
-  t->fwd_BN = BN;
-  const int B = g->desc.blocks_per_step, L = g->desc.num_mp_steps, C = g->desc.hidden, dim = e->g.dim;
-  LB_TRY(sgt_ensure(t, BN, E));
+  const int64_t E = t->fwd_E, BN = t->fwd_BN;
+  const int B = g->desc.blocks_per_step, L = g->desc.num_mp_steps, C = g->desc.hidden;
   LB_TRY(lbk_sg_prep(e, g->desc.homogeneous, g->desc.velocity_avg, g->node_ns4, g->node_nv4, g->xnode, g->eattr, g->msgsv,
                      g->nodesv, g->nattr, t->cap_e));
   // ---- forward (segnn.py:595-610)
@@ -473,11 +466,10 @@ static int segnn_forward_part(lb_gns_train* t, const char* entry, float* pred_ou
     lb_sgt_op op = sgt_op(ncur, C, C);
     LB_TRY(sgt_fwd(t, g->blocks[bi++], BN, &op, g->nattr, nullptr, t->pred));
   }
-  if (pred_out_dev) LB_HIP(hipMemcpyAsync(pred_out_dev, t->pred, sizeof(float) * BN * dim, hipMemcpyDeviceToDevice, s));
   if (bi != g->blocks.size()) return lb_fail(LB_ERR_STATE, "segnn training: block bookkeeping");
   return LB_OK;
 }
-static int segnn_backward_part(lb_gns_train* t) {
+static int segnn_backward(lb_gns_train* t, double*) {
   lb_engine* e = t->eng;
   lb_sgt* g = t->sg;
   hipStream_t s = e->stream;
@@ -530,18 +522,12 @@ static int segnn_backward_part(lb_gns_train* t) {
     LB_TRY(sgt_bwd(t, g->blocks[--bi], BN, g->df, nullptr, &op, g->nattr));             // embedding: parameters only
   }
   if (bi != 0) return lb_fail(LB_ERR_STATE, "segnn training: block bookkeeping");
-  return train_step_end(t);
-}
-static int segnn_train_loss_grad_once(lb_gns_train* t, const float* target_dev, float loss_weight, float* pred_out_dev) {
-  LB_TRY(segnn_forward_part(t, "lb_segnn_train_loss_grad", pred_out_dev));
-  LB_TRY(train_loss(t, t->pred, target_dev, loss_weight, t->dy));
-  return segnn_backward_part(t);
+  return LB_OK;
 }
 // value_and_grad of _mse for SEGNN on the engine's CURRENT window / neighbor list: same contract as lb_gns_train_loss_grad
 extern "C" int lb_segnn_train_loss_grad(lb_gns_train* t, const float* target_dev, float loss_weight, double* loss_out,
                                         float* pred_out_dev) {
-  if (t && t->blob) return blob_refuse("lb_segnn_train_loss_grad");
-  if (!t || !t->sg || !target_dev) return lb_fail(LB_ERR_ARG, "null argument / not a SEGNN training handle");
-  t->fwd_live = false;
-  return train_loss_grad_guarded(t, loss_out, [&] { return segnn_train_loss_grad_once(t, target_dev, loss_weight, pred_out_dev); });
+  if (t && !t->model) return blob_refuse("lb_segnn_train_loss_grad");
+  if (!t || t->model != &segnn_model || !target_dev) return lb_fail(LB_ERR_ARG, "null argument / not a SEGNN training handle");
+  return train_loss_grad(t, target_dev, loss_weight, loss_out, pred_out_dev);
 }
