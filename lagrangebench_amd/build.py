@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "liblbhip.so")
 SOURCES = ["lb_api.hip", "lb_neighbor.hip", "lb_state.hip", "lb_gns.hip", "lb_gns_weights.hip", "lb_gns_repack.hip", "lb_edge16.hip", "lb_segnn.hip", "lb_segnn_gen.hip", "lb_segnn_msg.hip", "lb_segnn_node.hip", "lb_sinkhorn.hip", "lb_edge16v.hip", "lb_edge16w.hip", "lb_node16s.hip", "lb_gns_generic.hip", "lb_msplit.hip", "lb_train.hip", "lb_egnn.hip", "lb_painn.hip", "lb_train_input.hip", "lb_linear.hip", "lb_graph.hip"]
-HEADERS = ["lb_internal.h", "lb_arena.h", "lb_device.h", "lb_f16x2.h", "lb_segnn_dev.h", "lb_features.h", "lb_msplit.h", "lb_msplit_dev.h", "lb_lin32.h", "lb_train_segnn.h", "lb_train_egnn.h", "lb_train_linear.h", "lb_train_painn.h", "lb_gns_repack.h", "lb_sender_view.h", os.path.join("..", "..", "include", "lbhip.h")]
+HEADERS = ["lb_internal.h", "lb_nl_plan.h", "lb_arena.h","lb_device.h", "lb_f16x2.h", "lb_segnn_dev.h", "lb_features.h", "lb_msplit.h", "lb_msplit_dev.h", "lb_lin32.h", "lb_train_segnn.h", "lb_train_egnn.h", "lb_train_linear.h", "lb_train_painn.h", "lb_gns_repack.h", "lb_sender_view.h", os.path.join("..", "..", "include", "lbhip.h")]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function"]
 # per-file extras.  lb_edge16v.hip: the SLP vectoriser packs the LayerNorm / scan arithmetic into

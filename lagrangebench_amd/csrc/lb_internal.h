@@ -18,6 +18,7 @@
 #define LB_TILE 32                // rows (edges / nodes) per wave tile: the N of the 32x32x2 MFMA
 #define LB_D 128                  // latent width built so far
 #define LB_PAD_TYPE (-1)          // NodeType.PAD_VALUE: a particle of a padded trajectory that is not there (utils.py:17-25)
+#include "lb_nl_plan.h"           // (after the three neighbor limits above, which it takes as it finds them)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -164,17 +165,7 @@ struct lb_engine {
   int64_t cell_slots = 0;      // slots allocated for cell_part / cpos (>= BN)
   bool nl_dense = false;  // sticky: the density exceeded the staged kernel's limits once -> wave-per-receiver kernel
   int32_t row_cap = 0;    // its LDS row buffer (entries per wave), sized from the largest degree seen
-  // what the most recent lbk_nl_build launched (lb_nl_route reads it; host bookkeeping, nothing on the device).  single: 0 none,
-  // 1 k_nl_small, 2 k_nl_mid.  cells: 0 none, 1 strided, 2 cells_small, 3 cells_traj, 4 cells_mid, 5 sort.  search / count:
-  // the kernel of the NL_ROWS or NL_FILL sweep / of the NL_COUNT sweep, -1 none, else lb_nl_kernel_kind (an allocation that
-  // turns dense between the two sweeps counts with one kernel and fills with another).  cand / count_cand: staged capacity
-  // of k_nl (0 otherwise).  rows: NL_ROWS sweep.  finish: 1 compact_scan, 2 rows_small, 3 scan+finish.  compact:
-  // k_nl_compact followed.  reentry: an allocation counted with kernel kind reentry - 1 first, hit the stencil limit and
-  // ran again dense.
-  struct nl_route_rec {
-    int8_t single = 0, cells = 0, search = -1, count = -1, rows = 0, finish = 0, compact = 0, reentry = 0;
-    int16_t cand = 0, count_cand = 0;
-  } nl_route;
+  lb_nl_plan nl_plan;  // what the most recent lbk_nl_build ran (lb_nl_plan.h; lb_nl_route prints it; host integers only)
   int32_t maxd;        // per-node slot count of the single-sweep update path (0 = not sized)
   int32_t* tmp_send;   // [BN][maxd] sorted sender rows before compaction
   float* tmp_feat;     // [BN][maxd][4]

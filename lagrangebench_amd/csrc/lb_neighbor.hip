@@ -16,10 +16,8 @@
 //      k_nlc (wave per cell): keeps the stencil candidates in registers and emits the edges of all the cell's receivers
 //            64 at a time;
 //      k_nl_small / k_nl_mid: one trajectory, the whole build (binning, search, CSR offsets, control block) in ONE launch.
-//      The input alone picks the kernel: one trajectory of <= NLM_N particles on the update path runs k_nl_small / k_nl_mid
-//      (lbk_nl_build); otherwise a cell list outside the dense fall-back in 3D or float32 geometry runs k_nlc, the dense
-//      fall-back or float32 geometry without a cell list runs k_nlw, and everything else (fp64 2D with a cell list, fp64
-//      all-pairs) runs k_nl (lb_nl_kernel_kind).
+//      The input alone picks the binning, the kernel and the finish: lb_nl_make_plan (lb_nl_plan.h, plain C++ that
+//      tools/nl_plan_check.cpp runs without a GPU) holds every routing threshold; lbk_nl_build launches what its plan says.
 //      Every kernel evaluates the cutoff predicate as the reference does (lb_pair_in_cutoff; k_nl_mid writes its arithmetic
 //      out) and writes the edge features with lb_write_edge; a row's hits come from a wavefront ballot + popcount prefix
 //      and are ordered by sender id.
@@ -32,10 +30,11 @@
 // the edge list sorted by (receiver, sender) - deterministic, and directly consumable by the
 // atomic-free segmented aggregation.
 #include "lb_features.h"
+#include "lb_nl_plan.h"
 
-#define SCAN_THREADS 256
-#define SCAN_CHUNK (SCAN_THREADS * 8)
-#define NL_SMALL_MAXC 1024
+static_assert(lb_nl_stencil_cand == LB_MAX_STENCIL_CAND && lb_nl_max_row == LB_MAX_ROW && lb_nl_max_row_dense == LB_MAX_ROW_DENSE,
+              "lb_nl_plan.h states the limits of lb_internal.h");
+
 
 enum { NL_COUNT = 0, NL_FILL = 1, NL_ROWS = 2 };
 
@@ -235,14 +234,9 @@ __device__ __forceinline__ int lb_cell_coord(double p, float inv_cs32, double cs
   if (fr < 1e-3f || fr > 0.999f || !(fabsf(q) < 2000.f)) c = __double2int_rz(lb_r(p / cs, F32));
   return c < 0 ? 0 : (c >= n ? n - 1 : c);
 }
-#define LB_SMALL_N 4096
-#define LB_SMALL_T 1024
 // Round 4: the same kernel serves one mid-size trajectory that the single-launch builds refuse (DAM2D: 5740 particles,
 // 12.6 k cells, 262 mask rows): counts in dynamic LDS (up to LB_CELLS1_NCELL cells), up to LB_CELLS1_PER particles per
 // thread - memset + count + two scan passes + fill (25 us of launches on DAM2D) become one ~8 us launch.
-#define LB_CELLS1_PER 8
-#define LB_CELLS1_N (LB_SMALL_T * LB_CELLS1_PER)
-#define LB_CELLS1_NCELL 32768
 template <int PER>
 __global__ void __launch_bounds__(LB_SMALL_T)
     k_cells_small(lb_geom g, int64_t BN, const double* __restrict__ win, lb_ctrl* __restrict__ ctrl,
@@ -784,7 +778,6 @@ __global__ void __launch_bounds__(NL_THREADS)
 // complement of waves in flight; the search is latency bound (three dependent memory round trips
 // per receiver), and with one workgroup per CELL the staged stencil (28 B x cell_capacity x 3^dim of
 // LDS) capped the occupancy at a handful of waves per CU.  Same predicate, same operand order.
-#define NLW_WAVES 4
 template <int MODE, bool F32>
 __global__ void __launch_bounds__(64 * NLW_WAVES)
     k_nlw(lb_geom g, int64_t BN, lb_ctrl* __restrict__ ctrl, lb_nl_args a) {
@@ -864,7 +857,6 @@ __global__ void __launch_bounds__(64 * NLW_WAVES)
 // edges belong to.  Predicate, features and operand order are k_nlw's: the edge list is bit-identical.  Stencils with more
 // than 128 candidates sweep in 128-candidate chunks per receiver (registers reloaded: dense cells, rare); the list holds
 // NLC_LIST hits and is flushed whenever the next row (<= LB_MAX_ROW hits) might not fit.
-#define NLC_WAVES 4
 #define NLC_LIST 448
 #define NLC_BATCH 128
 #define NLC_S 4   // candidate slots per lane held in registers (stencils of up to 256 particles in one chunk)
@@ -1136,7 +1128,6 @@ __global__ void __launch_bounds__(256)
 // (they were four: two scan passes, finish, compact - ~19 us of a 0.6 ms step on one 8 k-particle trajectory).  Every
 // workgroup adds up the degrees of the nodes before its own 16 itself (<= 64 KiB of L2-resident integers, 16-byte
 // loads); the last workgroup, which thereby knows every total, does k_row_finish's job.
-#define LB_CSCAN_N 16384
 __global__ void __launch_bounds__(256)
     k_nl_compact_scan(lb_geom g, int64_t BN, lb_ctrl* __restrict__ ctrl, const int32_t* __restrict__ deg,
                       int32_t* __restrict__ row_ptr, int32_t maxd, const int32_t* __restrict__ tsend,
@@ -1297,9 +1288,7 @@ __global__ void __launch_bounds__(LB_SMALL_T)
 // only inside a 1e-3 band around an integer - or far outside the grid - is the exact (in f32 mode: float-rounded)
 // quotient evaluated.  Every workgroup of the single-launch builds recomputes ALL N coordinates, and in fp64 that
 // was VALU time (k_nl_mid: 8.5 of 35 us).
-#define NLS_WAVES 16  // at most; the launch uses ceil(N / 256) waves so that every CU gets at most one workgroup
 #define NLS_THREADS (64 * NLS_WAVES)
-#define NLS_CAND 512  // stencil candidates per receiver (row buffer entries; >= LB_MAX_ROW)
 struct lb_nls_args {
   const double* win;
   const int32_t* ptype;
@@ -1545,10 +1534,6 @@ __global__ void __launch_bounds__(NLS_THREADS) k_nl_small(lb_geom g, lb_ctrl* __
 // ..), a wave searches NLM_RPW consecutive receivers one after the other, a workgroup of 16 waves owns 16 NLM_RPW
 // consecutive receivers (contiguous, so the CSR offsets work as in k_nl_small).  Replaces, on one 8 k-particle
 // trajectory, memset + cell count + 2 scan passes + cell fill + k_nlw + scan / finish / compact: 9 launches.
-#define NLM_N 8192
-#define NLM_WAVES 16
-#define NLM_RPW 2
-#define NLM_ROWBUF 1024  // row buffer per wave: the hits of the receivers done (<= 256 each) + 768 candidates
 template <bool F32, int DIM>
 __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* __restrict__ ctrl, lb_nls_args a) {
   extern __shared__ double s_dynd[];
@@ -1754,14 +1739,12 @@ __global__ void __launch_bounds__(64 * NLM_WAVES) k_nl_mid(lb_geom g, lb_ctrl* _
 }
 
 // ----------------------------------------------------------------------------------- host
-// Which search kernel a build uses, from the input alone: 0 = k_nl (workgroup per cell, staged stencil), 1 = k_nlw (wave per
-// receiver), 2 = k_nlc (wave per cell).  Measured (MI355X, B = 8): 3^3-cell stencils favour the per-wave kernels (TGV3D 0.28
-// -> 0.18 -> 0.12 ms per step), 3^2-cell stencils the staged per-cell kernel (DAM2D 0.11 vs 0.15 ms).  The dense fall-back
-// (e->nl_dense, sticky) exceeds the staged kernels' LB_MAX_STENCIL_CAND candidates or LB_MAX_ROW neighbors: k_nlw with a row
-// buffer sized from the largest degree runs (the reference re-allocates for ANY occupancy, rollout.py:134-151).
-static int lb_nl_kernel_kind(const lb_engine* e) {
-  if (e->g.use_cell_list && !e->nl_dense && (e->g.dim == 3 || e->g.f32)) return 2;
-  return e->nl_dense || e->g.f32 ? 1 : 0;
+// The inputs of the routing decision (lb_nl_plan.h) as the engine holds them now.
+static lb_nl_in lb_nl_inputs(const lb_engine* e, bool want_efeat64) {
+  const lb_geom& g = e->g;
+  return {g.B, g.N, g.dim, e->BN, g.f32 != 0, g.use_cell_list != 0, {g.ncell[0], g.ncell[1], g.ncell[2]}, g.ncells, g.nstencil,
+          e->cell_capacity, e->e_cap, e->nl_dense, e->nl_one_off, e->nl_wg_sum != nullptr, e->maxd, e->tmp_send != nullptr,
+          e->tmp_feat64 != nullptr, want_efeat64, lb_fused_launches()};
 }
 
 // Launches kernel K with `lds` bytes of dynamic LDS.  Its dynamic-LDS limit is raised to `limit` ONCE, at its first launch,
@@ -1776,34 +1759,28 @@ static void lb_launch_lds(int limit, dim3 grid, dim3 block, size_t lds, hipStrea
   hipLaunchKernelGGL(K, grid, block, lds, s, args...);
 }
 
-// `small` = staged-candidate capacity of the one-wave k_nl variant to use (a multiple of 128 up to NL_SMALL_MAXC), or 0 for the
-// 256-thread / 2048-candidate variant.  The LDS footprint of the staged stencil (28 B per candidate) sets how many cells a CU
-// keeps in flight - the search is latency bound, so the smallest variant that holds cell_capacity * 3^dim candidates is used.
+// One search sweep of plan p: its kernel kind, staged capacity p.small (lb_nl_plan.h) and grid.
 template <int MODE>
-static void lb_launch_nl(lb_engine* e, int small, const lb_nl_args& a) {
-  const int kind = lb_nl_kernel_kind(e);
-  (MODE == NL_COUNT ? e->nl_route.count : e->nl_route.search) = (int8_t)kind;
-  (MODE == NL_COUNT ? e->nl_route.count_cand : e->nl_route.cand) = (int16_t)(kind ? 0 : small ? small : LB_MAX_STENCIL_CAND);
+static void lb_launch_nl(lb_engine* e, const lb_nl_plan& p, const lb_nl_args& a) {
+  const int kind = MODE == NL_COUNT ? p.count : p.search;
   // NL_ROWS in a rollout step: workgroups behind the search's write the node-feature rows
   const bool ride = MODE == NL_ROWS && e->feat_job.xnode && !a.out.efeat64;
   if (ride) e->feat_done = true;
   lb_nl_args aw = a;
-  // the grid: nb_s search workgroups of `waves` waves, plus the feature workgroups behind them
-  auto grid = [&](int64_t nb_s, int waves) -> dim3 {
-    if (!ride) return dim3((unsigned)nb_s);
+  // the grid: the plan's search workgroups, plus the feature workgroups behind them
+  dim3 nb((unsigned)p.nb_search);
+  if (ride) {
     aw.feat = e->feat_job;
     aw.win = e->win;
-    aw.nb_search = (int)nb_s;
-    return dim3((unsigned)(nb_s + (e->BN + waves * NL_FEAT_ROWS - 1) / (waves * NL_FEAT_ROWS)));
-  };
+    aw.nb_search = (int)p.nb_search;
+    nb = dim3((unsigned)(p.nb_search + (e->BN + p.search_waves * NL_FEAT_ROWS - 1) / (p.search_waves * NL_FEAT_ROWS)));
+  }
   if (kind == 2) {  // round 6: one wave per CELL
-    const dim3 nb = grid((e->g.B * e->g.ncells + NLC_WAVES - 1) / NLC_WAVES, NLC_WAVES);
     const auto k = e->g.f32 ? (e->g.dim == 3 ? k_nlc<MODE, true, 3> : k_nlc<MODE, true, 2>) : k_nlc<MODE, false, 3>;
     hipLaunchKernelGGL(k, nb, dim3(64 * NLC_WAVES), 0, e->stream, e->g, e->BN, e->ctrl, aw);
     return;
   }
   if (kind == 1) {
-    const dim3 nb = grid((e->BN + NLW_WAVES - 1) / NLW_WAVES, NLW_WAVES);
     aw.row_cap = e->row_cap > LB_MAX_ROW ? e->row_cap : LB_MAX_ROW;
     const size_t lds = sizeof(int) * 2 * NLW_WAVES * (size_t)aw.row_cap;
     const auto k = e->g.f32 ? k_nlw<MODE, true> : k_nlw<MODE, false>;  // dtype=float32 geometry: every result rounded to float
@@ -1811,12 +1788,11 @@ static void lb_launch_nl(lb_engine* e, int small, const lb_nl_args& a) {
     hipLaunchKernelGGL(k, nb, dim3(64 * NLW_WAVES), lds, e->stream, e->g, e->BN, e->ctrl, aw);
     return;
   }
-  const dim3 nb = grid(e->g.B * e->g.ncells, small ? 1 : 4);
 #define LB_NL_CASE(C)                                                                                         \
   case C:                                                                                                     \
     hipLaunchKernelGGL((k_nl<MODE, 64, C>), nb, dim3(64), 0, e->stream, e->g, e->BN, e->ctrl, aw);           \
     break;
-  switch (small) {
+  switch (p.small) {
     LB_NL_CASE(128)
     LB_NL_CASE(256)
     LB_NL_CASE(384)
@@ -1854,7 +1830,6 @@ static lb_nls_args lb_nls_setup(lb_engine* e, bool want_efeat64, int npad) {
   return a;
 }
 
-#define LB_NLS_MAX_LDS (150 * 1024)  // dynamic LDS the single-launch builds may use
 template <bool F32, int DIM>
 static void lb_launch_one_traj(lb_engine* e, bool mid, int nb, int threads, size_t lds, const lb_nls_args& a) {
   if (mid)
@@ -1867,75 +1842,39 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
   e->nl_gen += 1;   // (what lb_graph.hip caches per list is stale from here on)
   const lb_geom& g = e->g;
   const int64_t BN = e->BN;
-  const int ncell_tot = g.B * g.ncells;
   hipStream_t s = e->stream;
   const int frozen = e->e_cap > 0;
-  lb_engine::nl_route_rec& route = e->nl_route;
-  route = {};
+  lb_nl_in in = lb_nl_inputs(e, want_efeat64);
+  lb_nl_plan& p = e->nl_plan;
+  p = lb_nl_make_plan(in);
+  const int ncell_tot = p.ncell_tot;
+  const int64_t strided_slots = p.strided_slots;
 
-  // LB_SMALL_FUSED=0: always the multi-launch bookkeeping (lb_fused_launches, lb_internal.h)
-  const bool small_ok = lb_fused_launches();
-  const bool small_rows = small_ok && BN <= LB_SMALL_N;
-  const bool small_cells = small_rows && ncell_tot <= LB_SMALL_N;
-  // one trajectory on the update path: the whole build is ONE launch - k_nl_small up to LB_SMALL_N particles, k_nl_mid with
-  // a cell list whose masks fit LDS up to NLM_N
-  static_assert(NLS_CAND >= LB_MAX_ROW, "k_nl_small's row buffer holds a full row");
-  const bool one_traj = small_ok && frozen && g.B == 1 && !e->nl_dense && !e->nl_one_off && e->nl_wg_sum &&
-                        g.ncell[0] < 2048 && g.ncell[1] < 2048 && g.ncell[2] < 1024;
-  const int npad = (int)((BN + 63) / 64 * 64);
-  const int64_t tab = g.use_cell_list ? (int64_t)(g.ncell[0] + g.ncell[1] + (g.dim == 3 ? g.ncell[2] : 0)) * (npad / 64) : 0;
-  const int nls_waves = (int)std::min<int64_t>(NLS_WAVES, std::max<int64_t>(1, (BN + 255) / 256));
-  const size_t nls_lds = (size_t)npad * (8 * g.dim + 4) + 8 * (size_t)tab + sizeof(int) * ((size_t)nls_waves * NLS_CAND + 32);
-  const bool nls = one_traj && BN <= LB_SMALL_N && nls_lds <= LB_NLS_MAX_LDS &&
-                   (!g.use_cell_list || (int64_t)e->cell_capacity * g.nstencil <= NLS_CAND);
-  const size_t nlm_lds = 8 * (size_t)tab + sizeof(int) * ((size_t)npad + NLM_WAVES * NLM_ROWBUF + 48);
-  const bool nlm = one_traj && BN > LB_SMALL_N && BN <= NLM_N && g.use_cell_list && nlm_lds <= LB_NLS_MAX_LDS &&
-                   (int64_t)e->cell_capacity * g.nstencil <= NLM_ROWBUF - LB_MAX_ROW * (NLM_RPW - 1);
-  if (nls || nlm) {
-    route.single = nls ? 1 : 2;
+  if (p.single) {  // one trajectory on the update path: the whole build is ONE launch
     lb_tic(e, LB_T_NEIGH);
-    const lb_nls_args a = lb_nls_setup(e, want_efeat64, npad);
+    const lb_nls_args a = lb_nls_setup(e, want_efeat64, p.npad);
     const auto launch = g.f32 ? (g.dim == 3 ? lb_launch_one_traj<true, 3> : lb_launch_one_traj<true, 2>)
                               : (g.dim == 3 ? lb_launch_one_traj<false, 3> : lb_launch_one_traj<false, 2>);
-    if (nls)
-      launch(e, false, (int)((BN + nls_waves - 1) / nls_waves), 64 * nls_waves, nls_lds, a);
-    else
-      launch(e, true, (int)((BN + NLM_WAVES * NLM_RPW - 1) / (NLM_WAVES * NLM_RPW)), 64 * NLM_WAVES, nlm_lds, a);
+    launch(e, p.single == 2, p.single_blocks, p.single_threads, p.single_lds, a);
     lb_toc(e);
     LB_HIP(hipGetLastError());
     return LB_OK;
   }
   lb_tic(e, LB_T_CELLS);
-  // (one mid-size trajectory that the single-launch builds above refused, e.g. DAM2D: binning still in one launch)
-  const bool mid_cells = small_ok && frozen && g.B == 1 && BN <= LB_CELLS1_N && ncell_tot <= LB_CELLS1_NCELL;
-  // batches: one workgroup per trajectory, one launch (LB_SMALL_FUSED=0: the five-launch counting sort)
-  // (measured, profiles/r04_ab_cells_traj.txt: 2.5 k particles x 8 23.1 -> 17.5 us, 5.7 k x 8 27.7 -> 22.7 us, 8 k x 8 30.8 -> 32.5 us -
-  // one workgroup per trajectory is bound by its scattered stores from ONE CU; above 6 k particles the five launches stay)
-  const bool traj_cells = small_ok && frozen && !small_cells && g.B > 1 && g.use_cell_list && g.N <= 6144 &&
-                          g.ncells <= LB_CELLS1_NCELL;
-  // frozen capacities + a search kernel that walks CELLS: fixed-stride slots, two launches (k_cell_zero, k_cell_bin)
-  const int64_t strided_slots = (int64_t)ncell_tot * e->cell_capacity;
-#ifdef LB_NO_STRIDED   // (A/B builds: tools/build_variant.sh csr -DLB_NO_STRIDED)
-  const bool strided = false;
-#else
-  const bool strided = small_ok && frozen && g.use_cell_list && e->cell_capacity > 0 && lb_nl_kernel_kind(e) != 1 &&
-                       strided_slots < ((int64_t)1 << 30);
-#endif
-  route.cells = strided ? 1 : small_cells ? 2 : traj_cells ? 3 : mid_cells ? 4 : 5;
-  if (strided) {
+  if (p.cells == LB_CELLS_STRIDED) {
     if (strided_slots > e->cell_slots)   // (first build after an allocation: never inside a graph capture)
       LB_TRY(lb_regrow(s, &e->cell_slots, strided_slots + strided_slots / 4, [&](int64_t n) {
         LB_TRY(e->mem.get(&e->cell_part, (size_t)n));
         return e->mem.get(&e->cpos, (size_t)g.dim * (size_t)n);
       }));
     e->cells_traj_ready = false;   // (cell_count is rewritten: k_cells_traj's occupancy slots must be zeroed again after this)
-    hipLaunchKernelGGL(k_cell_zero, dim3((ncell_tot + 255) / 256), dim3(256), 0, s, e->ctrl, e->cell_count, ncell_tot);
-    hipLaunchKernelGGL(k_cell_bin, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
+    hipLaunchKernelGGL(k_cell_zero, dim3(p.nb_cells), dim3(256), 0, s, e->ctrl, e->cell_count, ncell_tot);
+    hipLaunchKernelGGL(k_cell_bin, dim3((unsigned)p.nb_nodes), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
                        e->cell_of, e->cell_count, e->cell_part, e->cpos, e->cell_capacity, strided_slots);
-  } else if (small_cells) {
+  } else if (p.cells == LB_CELLS_SMALL) {
     hipLaunchKernelGGL((k_cells_small<LB_SMALL_N / LB_SMALL_T>), dim3(1), dim3(LB_SMALL_T), sizeof(int) * (size_t)ncell_tot, s, g,
                        BN, e->win, e->ctrl, e->ptype, e->deg, e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
-  } else if (traj_cells) {
+  } else if (p.cells == LB_CELLS_TRAJ) {
     if (!e->cells_traj_ready) {  // occ[0 .. B] (max occupancy per trajectory, arrival ticket) live in the unused cell_count
       LB_HIP(hipMemsetAsync(e->cell_count, 0, sizeof(int32_t) * (size_t)(g.B + 1), s));
       e->cells_traj_ready = true;
@@ -1944,59 +1883,47 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
                                                sizeof(int) * (size_t)g.ncells, s, g, BN, e->win, e->ctrl, e->ptype,
                                                e->live_cnt, e->deg, e->cell_of, e->cell_start, e->cell_part, e->cpos,
                                                e->cell_count);
-  } else if (mid_cells) {
+  } else if (p.cells == LB_CELLS_MID) {
     lb_launch_lds<k_cells_small<LB_CELLS1_PER>>(sizeof(int) * LB_CELLS1_NCELL, dim3(1), dim3(LB_SMALL_T),
                                                 sizeof(int) * (size_t)ncell_tot, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
                                                 e->cell_of, e->cell_start, e->cell_part, e->cpos, ncell_tot);
-  } else {
+  } else {  // LB_CELLS_SORT
     e->cells_traj_ready = false;  // (the counting sort uses cell_count: k_cells_traj's occ[] must be zeroed again after it)
     LB_HIP(hipMemsetAsync(e->cell_count, 0, sizeof(int32_t) * 2 * (size_t)ncell_tot, s));
     // (max_cell_occ, max_deg, row_overflow are reset by k_cell_count)
-    const int nb = (int)((BN + 255) / 256);
-    hipLaunchKernelGGL(k_cell_count, dim3(nb), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
+    hipLaunchKernelGGL(k_cell_count, dim3(p.nb_nodes), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->ptype, e->deg,
                        e->cell_of, e->cell_count);
-    const int nsb_c = (ncell_tot + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    hipLaunchKernelGGL(k_scan_partials, dim3(nsb_c), dim3(SCAN_THREADS), 0, s, e->cell_count, ncell_tot,
+    hipLaunchKernelGGL(k_scan_partials, dim3(p.nsb_cells), dim3(SCAN_THREADS), 0, s, e->cell_count, ncell_tot,
                        e->scan_part, e->ctrl, &e->ctrl->max_cell_occ);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nsb_c), dim3(SCAN_THREADS), 0, s, e->cell_count,
+    hipLaunchKernelGGL(k_scan_apply, dim3(p.nsb_cells), dim3(SCAN_THREADS), 0, s, e->cell_count,
                        e->cell_start, ncell_tot, e->scan_part, e->ctrl);
-    hipLaunchKernelGGL(k_cell_fill, dim3(nb), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->cell_of,
+    hipLaunchKernelGGL(k_cell_fill, dim3(p.nb_nodes), dim3(256), 0, s, g, BN, e->win, e->ctrl, e->cell_of,
                        e->cell_start, e->cell_fill, e->cell_part, e->cpos);
   }
   lb_toc(e);
 
   lb_tic(e, LB_T_NEIGH);
-  // one wave per cell when the frozen cell capacity bounds the stencil (a cell holding more than
-  // cell_capacity particles flags overflow anyway); the 256-thread / 2048-candidate variant otherwise
-  // (the LDS footprint of the staged stencil sets how many cells a CU keeps in flight)
-  const int64_t cand_cap = (int64_t)e->cell_capacity * g.nstencil;
-  const int small = (frozen && g.use_cell_list && cand_cap <= NL_SMALL_MAXC)
-                        ? (int)std::max<int64_t>(128, (cand_cap + 127) / 128 * 128) : 0;
-  const bool rows = frozen && e->maxd > 0 && e->tmp_send && (!want_efeat64 || e->tmp_feat64);
   lb_nl_args a{};
   a.cell_of = e->cell_of;
   a.cell_start = e->cell_start;
   a.cell_part = e->cell_part;
   a.cpos = e->cpos;
   a.cell_cnt = e->cell_count;
-  a.cell_cap = strided ? e->cell_capacity : 0;
-  a.cstride = strided ? strided_slots : BN;
+  a.cell_cap = p.strided ? e->cell_capacity : 0;
+  a.cstride = p.strided ? strided_slots : BN;
   a.deg = e->deg;
   a.row_ptr = e->row_ptr;
   a.e_alloc = e->e_alloc;
   a.maxd = e->maxd;
   const lb_cell_bins bins{e->cell_count, e->cell_start, a.cell_cap};
-  route.rows = rows;
-  if (rows) {
+  if (p.rows) {
     a.out = {e->tmp_send, nullptr, e->tmp_feat, want_efeat64 ? e->tmp_feat64 : nullptr};
-    lb_launch_nl<NL_ROWS>(e, small, a);
+    lb_launch_nl<NL_ROWS>(e, p, a);
   } else {
-    lb_launch_nl<NL_COUNT>(e, small, a);
+    lb_launch_nl<NL_COUNT>(e, p, a);
   }
-  // update path of a small batch: scan + finish + compaction in one launch (LB_SMALL_FUSED=0: the separate launches)
-  if (rows && small_ok && BN <= LB_CSCAN_N && g.B <= 64) {
-    route.finish = 1;
-    hipLaunchKernelGGL(k_nl_compact_scan, dim3((int)((BN + 15) / 16)), dim3(256), 0, s, g, BN, e->ctrl, e->deg, e->row_ptr,
+  if (p.finish == LB_FINISH_COMPACT_SCAN) {  // update path of a small batch: scan + finish + compaction in one launch
+    hipLaunchKernelGGL(k_nl_compact_scan, dim3(p.nb_rows16), dim3(256), 0, s, g, BN, e->ctrl, e->deg, e->row_ptr,
                        e->maxd, e->tmp_send, e->tmp_feat, want_efeat64 ? e->tmp_feat64 : (const double*)nullptr,
                        e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : (double*)nullptr, e->e_alloc,
                        e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->host_flag_dev, bins);
@@ -2004,24 +1931,21 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
     LB_HIP(hipGetLastError());
     return LB_OK;
   }
-  route.finish = small_rows ? 2 : 3;
-  if (small_rows) {
+  if (p.finish == LB_FINISH_ROWS_SMALL) {
     hipLaunchKernelGGL(k_rows_small, dim3(1), dim3(LB_SMALL_T), 0, s, g, e->deg, e->row_ptr, (int)BN, e->ctrl,
                        e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->e_alloc, frozen,
                        e->host_flag_dev, bins);
   } else {
-    const int nsb_r = (int)((BN + SCAN_CHUNK - 1) / SCAN_CHUNK);
-    hipLaunchKernelGGL(k_scan_partials, dim3(nsb_r), dim3(SCAN_THREADS), 0, s, e->deg, (int)BN,
+    hipLaunchKernelGGL(k_scan_partials, dim3(p.nsb_rows), dim3(SCAN_THREADS), 0, s, e->deg, (int)BN,
                        e->scan_part, e->ctrl, &e->ctrl->max_deg);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nsb_r), dim3(SCAN_THREADS), 0, s, e->deg, e->row_ptr, (int)BN,
+    hipLaunchKernelGGL(k_scan_apply, dim3(p.nsb_rows), dim3(SCAN_THREADS), 0, s, e->deg, e->row_ptr, (int)BN,
                        e->scan_part, e->ctrl);
     hipLaunchKernelGGL(k_row_finish, dim3(1), dim3(256), 0, s, g, e->row_ptr, (int)BN, e->ctrl,
                        e->overflow, e->nedges_b, e->cell_capacity, e->e_cap, e->e_alloc, frozen,
                        e->host_flag_dev, bins);
   }
-  if (rows) {
-    route.compact = 1;
-    hipLaunchKernelGGL(k_nl_compact, dim3((int)((BN + 15) / 16)), dim3(256), 0, s, BN, e->ctrl, e->deg,
+  if (p.compact) {
+    hipLaunchKernelGGL(k_nl_compact, dim3(p.nb_rows16), dim3(256), 0, s, BN, e->ctrl, e->deg,
                        e->row_ptr, e->maxd, e->tmp_send, e->tmp_feat,
                        want_efeat64 ? e->tmp_feat64 : (const double*)nullptr, e->senders, e->receivers,
                        e->efeat, want_efeat64 ? e->efeat64 : (double*)nullptr, e->e_alloc);
@@ -2041,9 +1965,9 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
       e->nl_dense = true;
       e->ctrl_host->density_error = 0;
       LB_HIP(hipMemcpyAsync(&e->ctrl->density_error, &e->ctrl_host->density_error, sizeof(int32_t), hipMemcpyHostToDevice, s));
-      const int8_t first = (int8_t)(route.count + 1);
+      const int8_t first = (int8_t)(p.count + 1);
       const int rc = lbk_nl_build(e, want_efeat64);  // count again with the kernel that has no candidate limit
-      route.reentry = first;
+      p.reentry = first;   // (p is the engine's plan, which the call above has made anew)
       return rc;
     }
     if (e->ctrl_host->max_deg > LB_MAX_ROW) e->nl_dense = true;
@@ -2066,9 +1990,11 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
     LB_HIP(hipMemcpyAsync(&e->ctrl->n_edges_total, &e->ctrl_host->n_edges_total, sizeof(int32_t),
                           hipMemcpyHostToDevice, s));
     a.e_alloc = e->e_alloc;
+    in.nl_dense = e->nl_dense;
+    lb_nl_plan_sweep(p, in, false);   // the fill sweep's kernel, now that the count has said whether the build is dense
   }
   a.out = {e->senders, e->receivers, e->efeat, want_efeat64 ? e->efeat64 : nullptr};
-  lb_launch_nl<NL_FILL>(e, small, a);
+  lb_launch_nl<NL_FILL>(e, p, a);
   lb_toc(e);
   LB_HIP(hipGetLastError());
   return LB_OK;
@@ -2076,17 +2002,7 @@ int lbk_nl_build(lb_engine* e, bool want_efeat64) {
 
 extern "C" int lb_nl_route(lb_engine* e, char* out, int32_t cap) {
   if (!e || !out || cap < 1) return lb_fail(LB_ERR_ARG, "null argument");
-  const lb_engine::nl_route_rec& r = e->nl_route;
-  static const char* const single[] = {"multi", "k_nl_small", "k_nl_mid"};
-  static const char* const cells[] = {"none", "strided", "cells_small", "cells_traj", "cells_mid", "sort"};
-  static const char* const search[] = {"none", "k_nl", "k_nlw", "k_nlc"};
-  static const char* const finish[] = {"none", "compact_scan", "rows_small", "scan+finish"};
-  snprintf(out, (size_t)cap,
-           "build=%s;cells=%s;search=%s;cand=%d;count=%s;count_cand=%d;mode=%s;finish=%s%s;reentry=%s;f32=%d;dim=%d;cell_list=%d;"
-           "dense=%d",
-           single[r.single], cells[r.cells], search[r.search + 1], (int)r.cand, search[r.count + 1], (int)r.count_cand,
-           r.rows ? "rows" : r.count >= 0 ? "count+fill" : "none", finish[r.finish], r.compact ? "+compact" : "",
-           search[r.reentry], (int)e->g.f32, e->g.dim, (int)e->g.use_cell_list, (int)e->nl_dense);
+  lb_nl_route_text(out, (size_t)cap, e->nl_plan, (int)e->g.f32, e->g.dim, (int)e->g.use_cell_list, (int)e->nl_dense);
   return LB_OK;
 }
 
